@@ -13,12 +13,17 @@ per-rank times only) -> "scaling": "weak".  Rank 0 prints ONE JSON line.
 `python bench.py --gpus N` without a torchrun environment starts its own N ranks (torch.distributed.run, 127.0.0.1) and
 relays rank 0's line.
 
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps, writes the last step's outputs if
+`--dump-outputs DIR` is given, and prints the line with the headline and the roofline of its own timed region.  Everything else
+(the events-off re-time, the matcher kernels stand-alone, the second batch point and the secondary legs below) runs with `--full` only.
+
 Extra objects on that line:
   roofline      dominant kernel (picked by a per-kernel HIP-event pre-pass), timed with HIP events on the launch stream over
                 the timed region: achieved = algorithmic bytes per launch / mean launch time; `kernels` = the same figures for
                 EVERY kernel class of the step from the pre-pass (describe and the matcher kernels the north_star's 0.6 bar
                 names included); traffic / valu_issue from the committed PMC passes, only while the kernel sources still
                 hash to what those passes measured
+With --full also:
   latency       one frame at a time through the host-buffer entry points (what tracking_module calls per frame)
   stereo        BASELINE config 4 shape: stereo pairs at 1241x376, both extractions + match::stereo::compute per step
   local_ba      LM iterations/s on config 3 (20 KF / 10k landmarks / ~60k observations), with its own roofline
@@ -84,7 +89,7 @@ def main() -> int:
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--batch", type=int, default=1024, help="frames per GPU per step (the kernels' tails and the latency-bound matcher kernels amortise over a larger batch: 64 -> 256 is +7 %, 256 -> 1024 another +7 %)")
+    ap.add_argument("--batch", type=int, default=1024, help="frames per GPU per step (the kernels' tails and the latency-bound matcher kernels amortise over a larger batch: 64 -> 256 is +7 %%, 256 -> 1024 another +7 %%)")
     ap.add_argument("--batch2", type=int, default=256, help="second batch point printed beside the headline (0 = off)")
     ap.add_argument("--detail", default=os.environ.get("BENCH_DETAIL", os.path.join(ROOT, "bench_detail.json")),
                     help="where the full result object goes (the stdout line is the <= 4 KB summary of it)")
@@ -93,6 +98,10 @@ def main() -> int:
     ap.add_argument("--no-ba-large", action="store_true", help="skip the 9.6 M-observation global-BA leg (about 20 s of scene generation per rank)")
     ap.add_argument("--no-extra", action="store_true", help="skip the latency / stereo legs")
     ap.add_argument("--leg-timeout", type=int, default=420, help="seconds the secondary legs (latency, stereo, BA, CPU baseline) may take before the line is printed without them")
+    ap.add_argument("--full", action="store_true", help="also run what the headline does not need: the events-off re-time, the matcher kernels "
+                    "stand-alone, the second batch point, the secondary legs and the CPU baseline (the --no-* options above apply to these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (rank 0; see dump_outputs)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -130,7 +139,10 @@ def main() -> int:
 
     # ---- synthetic input, resident in HBM before the timed region
     frames_np = synthetic.frame_sequence(B, W, H, seed=0x5EED + 7919 * rank)
-    fe = run_front_end(ctx, L, frames_np, B, args.steps, args.warmup, barrier, world)
+    fe = run_front_end(ctx, L, frames_np, B, args.steps, args.warmup, barrier, world, extra_passes=args.full,
+                       capture=args.dump_outputs is not None and rank == 0)
+    if fe["outputs"] is not None:
+        dump_outputs(fe.pop("outputs"), args.dump_outputs)
     src_hash = csrc_hash()
     kernels, dom = roofline_entries(fe, src_hash, B, world)
 
@@ -154,12 +166,17 @@ def main() -> int:
                    "input_residency": ("the same %d frames (%.0f MB) are re-read every step: %s "
                                       "(no kernel of the step is byte-bound; see roofline.kernels[].traffic)" % (B, B * W * H / 1e6, "they fit the 256 MB Infinity Cache, so level-0 reads need not reach HBM"
                                                                                                        if B * W * H <= 256e6 else "more than the 256 MB Infinity Cache holds, so level-0 reads do reach HBM")),
-                   "per_kernel_timing": "HIP events around EVERY kernel class on its launch stream inside the timed region (svgpu_profile_select \"*\"); "
-                                        "the same steps re-timed with the events off: %.4f ms per step" % fe["ms_per_step_unprofiled"]},
+                   "per_kernel_timing": "HIP events around EVERY kernel class on its launch stream inside the timed region (svgpu_profile_select \"*\")"
+                                        + ("; the same steps re-timed with the events off: %.4f ms per step" % fe["ms_per_step_unprofiled"]
+                                           if fe["ms_per_step_unprofiled"] is not None else "")},
         "roofline": dict(dom, csrc_hash=src_hash, per_kernel_ms_per_step={k["kernel"]: round(k["mean_launch_ms"] * k["launches_per_step"], 4) for k in kernels},
                          kernels=kernels),
     }
     del fe
+    if not args.full:
+        if rank == 0:
+            emit(result, args.detail)
+        return finish(world)
     # the operating point of rounds 1-3 (256 frames per step) beside the headline's, so that rounds stay comparable
     if args.batch2 and args.batch2 != B:
         B2 = min(args.batch2, B)
@@ -240,13 +257,47 @@ def main() -> int:
     watchdog.cancel()
     if rank == 0:
         emit(result, args.detail)
+    return finish(world)
+
+
+def finish(world) -> int:
     if world > 1:
+        import threading
+        import torch.distributed as dist
         closer = threading.Timer(60, lambda: os._exit(0))  # the line is out: a stuck teardown must not keep the launcher waiting
         closer.daemon = True
         closer.start()
         dist.barrier()
         dist.destroy_process_group()
     return 0
+
+
+# --dump-outputs: the keypoints / descriptors / match lists of DUMP_FRAMES frames drawn once with a fixed seed (every frame's counts in full),
+# sized so that the files stay under DUMP_BUDGET bytes whatever the keypoint capacity per frame
+DUMP_FRAMES, DUMP_SEED, DUMP_BUDGET = 64, 0x5EED, 56 << 20
+KEYPOINT_FIELDS = ("x", "y", "size", "angle", "response", "octave", "class_id")
+
+
+def dump_sample(B, cap):
+    per_frame = cap * (len(KEYPOINT_FIELDS) + 32 + 1) * 4  # float32 keypoint fields + descriptor bytes + match index per keypoint slot
+    n = max(1, min(B, DUMP_FRAMES, DUMP_BUDGET // per_frame))
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(B, n, replace=False))
+
+
+def dump_outputs(out, directory):
+    """What a caller of the timed path holds after its last step, as float32 / float64 .npy files:
+      keypoint_counts  (B, 1 + levels) f64  [total, per level] of every frame of the last extraction (total may exceed the capacity)
+      match_counts     (B,) f64             matches of pair t = (frame (t + 1) % B, keyframe t) of the last matcher pass
+      sample_frames    (S,) f64             the frames t drawn for the arrays below (fixed seed, ascending)
+      keypoints        (N, 7) f32           x, y, size, angle, response, octave, class_id of the sampled frames' keypoints, frame after frame
+      descriptors      (N, 32) f32          their rBRIEF bytes
+      matches          (M,) f32             for each sampled t: the keyframe-t index matched to every keypoint of frame (t + 1) % B, or -1
+    N and M follow from keypoint_counts (each frame's total clamped to the capacity).  The matcher of a step works on the batch
+    extracted one step earlier; every step extracts the same frames, so the two sets of counts agree."""
+    os.makedirs(directory, exist_ok=True)
+    for name, arr in out.items():
+        assert arr.dtype in (np.float32, np.float64), (name, arr.dtype)
+        np.save(os.path.join(directory, name + ".npy"), arr)
 
 
 def _pick(d, keys):
@@ -373,14 +424,15 @@ def matcher_stream():
     return _MATCHER_STREAM
 
 
-def run_front_end(ctx, L, frames_np, B, steps, warmup, barrier, world, profile=True, h2d=False):
+def run_front_end(ctx, L, frames_np, B, steps, warmup, barrier, world, profile=True, h2d=False, extra_passes=True, capture=False):
     """The step of this bench on one rank: ORB extraction of the B resident frames + brute-force match of each against the previous one
     (ring of B pairs).  Two HIP streams: extraction of step t+1 (stream A = the context's) overlaps the matcher of step t (stream B),
     which leaves most CUs idle during its sort / greedy-replay kernels.  Two output buffer sets alternate; events order
     extract(t) -> match(t) and match(t) -> extract(t+2) (the next writer of that set).
     The timed region (barrier + synchronize on both sides, MAX over ranks) runs with HIP events around EVERY kernel class, so the
-    per-kernel figures are those of the kernels inside this very pipeline; the same number of steps is then re-timed with the events
-    off to show what the bracketing costs."""
+    per-kernel figures are those of the kernels inside this very pipeline; with `extra_passes` the same number of steps is then re-timed
+    with the events off to show what the bracketing costs, and the matcher kernels are timed alone.  `capture`: the outputs of the last
+    timed step, copied to the host before anything else runs (dump_outputs)."""
     import torch
     from stella_vslam_amd import feature
     from stella_vslam_amd.distributed import max_over_ranks
@@ -455,6 +507,7 @@ def run_front_end(ctx, L, frames_np, B, steps, warmup, barrier, world, profile=T
         ctx.check(L.svgpu_orb_extract_batch_device_angles(ctx.handle, C.c_void_p(src.data_ptr()), B, C.c_size_t(Wf * Hf), Wf, None,
                                                           C.c_size_t(0), 0, C.c_void_p(kps.data_ptr()), C.c_void_p(desc.data_ptr()),
                                                           cap, C.c_void_p(counts.data_ptr()), C.c_void_p(bf["angles"].data_ptr()) if PACKED_ANGLES else None, None), "extract_batch")
+        state["last_ext"] = bf
         bf["ev_ext"].record(stream)
         if up is not None:
             up["ev_free"][j].record(stream)
@@ -476,7 +529,26 @@ def run_front_end(ctx, L, frames_np, B, steps, warmup, barrier, world, profile=T
             C.c_void_p(counts.data_ptr()), cap, nc, None,
             C.c_float(LOWE), CHECK_ORI, C.c_void_p(bf["matched"].data_ptr()), C.c_void_p(bf["nmatch"].data_ptr()),
             C.c_void_p(stream_b.cuda_stream)), "match_batch")
+        state["last_match"] = bf
         bf["ev_match"].record(stream_b)
+
+    def last_step_outputs():
+        """dump_outputs' arrays from the buffer sets the last step's extraction and matcher wrote (the streams are idle)."""
+        ext, mat = state["last_ext"], state["last_match"]
+        sel = dump_sample(B, cap)
+        idx = torch.from_numpy(sel).cuda()
+        cnt = ext["counts"].view(B, nc).cpu().numpy()
+        n_ext = np.minimum(cnt[sel, 0], cap)
+        n_mat = np.minimum(mat["counts"].view(B, nc)[:, 0].cpu().numpy(), cap)
+        k = ext["kps"].view(B, cap * 28).index_select(0, idx).cpu().numpy().view(feature.KEYPOINT_DTYPE).reshape(len(sel), cap)
+        d = ext["desc"].view(B, cap, 32).index_select(0, idx).cpu().numpy()
+        m = mat["matched"].view(B, cap).index_select(0, idx).cpu().numpy()
+        return {"keypoint_counts": cnt.astype(np.float64),
+                "match_counts": mat["nmatch"].cpu().numpy().astype(np.float64),
+                "sample_frames": sel.astype(np.float64),
+                "keypoints": np.concatenate([np.stack([k[i, :n][f].astype(np.float32) for f in KEYPOINT_FIELDS], 1) for i, n in enumerate(n_ext)]),
+                "descriptors": np.concatenate([d[i, :n] for i, n in enumerate(n_ext)]).astype(np.float32),
+                "matches": np.concatenate([m[i, :n_mat[(t + 1) % B]] for i, t in enumerate(sel)]).astype(np.float32)}
 
     def sync_all():
         ctx.synchronize()
@@ -500,6 +572,7 @@ def run_front_end(ctx, L, frames_np, B, steps, warmup, barrier, world, profile=T
     n_match = bufs[0]["nmatch"].float().mean().item()
     # ---- timed region: exactly K steps between barrier + synchronize, every kernel class bracketed by HIP events on its stream
     per_kernel, ops, alone = {}, C.c_ulonglong(), {}
+    dt_plain = None
     if profile:
         L.svgpu_profile_select(ctx.handle, b"*")
         dt = max_over_ranks(timed(steps))  # MAX over ranks (RCCL when world > 1)
@@ -509,6 +582,10 @@ def run_front_end(ctx, L, frames_np, B, steps, warmup, barrier, world, profile=T
             per_kernel[name] = (ms.value, n.value)
         L.svgpu_profile_mfma_ops(ctx.handle, C.byref(ops))
         L.svgpu_profile_select(ctx.handle, None)
+    else:
+        dt = dt_plain = max_over_ranks(timed(steps))
+    outputs = last_step_outputs() if capture else None
+    if profile and extra_passes:
         dt_plain = max_over_ranks(timed(steps))
         # the matcher kernels ALONE (outside the timed region, on the buffers of the last batch): inside the pipeline they run on the issue slots the
         # extraction stream leaves, so their elapsed time there is 2 - 3 x their own; both figures are reported
@@ -527,11 +604,10 @@ def run_front_end(ctx, L, frames_np, B, steps, warmup, barrier, world, profile=T
             if n.value:
                 alone[name] = ms.value / n.value
         L.svgpu_profile_select(ctx.handle, None)
-    else:
-        dt = dt_plain = max_over_ranks(timed(steps))
     del bufs, frames
-    return {"dt": dt, "ms_per_step_unprofiled": dt_plain / steps * 1e3, "per_kernel": per_kernel, "mfma_ops": ops.value, "steps": steps, "matcher_alone_ms": alone,
-            "n_kp": n_kp, "n_match": n_match, "alg": algorithmic_bytes(level_px, n_kp, B), "level_px": level_px}
+    return {"dt": dt, "ms_per_step_unprofiled": None if dt_plain is None else dt_plain / steps * 1e3, "per_kernel": per_kernel, "mfma_ops": ops.value,
+            "steps": steps, "matcher_alone_ms": alone, "n_kp": n_kp, "n_match": n_match, "alg": algorithmic_bytes(level_px, n_kp, B), "level_px": level_px,
+            "outputs": outputs}
 
 
 def roofline_entries(fe, src_hash, B, world):

@@ -4,6 +4,9 @@ import json
 import os
 import sys
 
+import numpy as np
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
@@ -74,3 +77,24 @@ def test_emit_prints_the_line_last(tmp_path, capsys):
     assert json.loads(lines[0])["value"] == full["value"]
     assert json.load(open(tmp_path / "bench_detail.json")) == full
     assert json.loads(cap.err.strip().split("\n")[-1]) == full
+
+
+def test_dump_sample_is_fixed_and_within_budget():
+    """--dump-outputs: the same frames on every run, and the sampled arrays stay under 64 MB whatever the keypoint capacity."""
+    for B, cap in ((1024, 2500), (1024, 20000), (8, 2500), (1, 100)):
+        a, b = bench.dump_sample(B, cap), bench.dump_sample(B, cap)
+        assert np.array_equal(a, b) and len(a) >= 1 and len(np.unique(a)) == len(a) and a.min() >= 0 and a.max() < B
+        assert np.array_equal(a, np.sort(a))
+        per_frame = cap * (len(bench.KEYPOINT_FIELDS) + 32 + 1) * 4
+        assert len(a) * per_frame + B * 16 * 8 <= 64 << 20
+    assert len(bench.dump_sample(8, 2500)) == 8
+
+
+def test_dump_outputs_writes_float_arrays(tmp_path):
+    out = {"keypoints": np.zeros((3, 7), np.float32), "match_counts": np.arange(4, dtype=np.float64)}
+    bench.dump_outputs(out, str(tmp_path / "d"))
+    for name, arr in out.items():
+        back = np.load(tmp_path / "d" / (name + ".npy"))
+        assert back.dtype == arr.dtype and np.array_equal(back, arr)
+    with pytest.raises(AssertionError):
+        bench.dump_outputs({"bad": np.zeros(3, np.int32)}, str(tmp_path / "e"))

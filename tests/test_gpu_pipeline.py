@@ -101,3 +101,45 @@ def test_opt_in_paths_keep_parity_in_a_fresh_process():
                            cwd=root, env=env, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, (extra, r.stdout[-2000:], r.stderr[-1000:])
         assert "1 passed" in r.stdout, r.stdout[-500:]
+
+
+def test_bench_plain_run_dumps_the_last_step_equal_to_oracle(tmp_path):
+    """`bench.py --dump-outputs DIR` (a plain run: headline only): the arrays it writes are the oracle's extraction of the sampled frames and
+    its robust::brute_force_match of each against the previous frame; the line carries the timed step count and ms_per_step."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    B, steps = 8, 3
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1", "--batch", str(B),
+                        "--dump-outputs", str(out), "--detail", str(tmp_path / "detail.json")],
+                       cwd=root, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
+    line = json.loads(r.stdout.strip().split("\n")[-1])
+    assert line["steps"] == steps and line["ms_per_step"] > 0 and line["value"] > 0
+    for leg in ("cpu_baseline", "local_ba", "global_ba", "second_batch_point", "with_h2d", "tracked_frame"):
+        assert leg not in line, leg
+    d = {n: np.load(out / (n + ".npy")) for n in ("keypoint_counts", "match_counts", "sample_frames", "keypoints", "descriptors", "matches")}
+    for n, a in d.items():
+        assert a.dtype in (np.float32, np.float64), n
+    frames_np = S.frame_sequence(B, 640, 480, seed=0x5EED)
+    ref = [O.orb_extract(frames_np[t]) for t in range(B)]
+    sel = d["sample_frames"].astype(int)
+    assert list(sel) == list(range(B))  # a batch this small is dumped whole
+    cnt = d["keypoint_counts"].astype(int)
+    assert cnt.shape[0] == B and d["match_counts"].shape == (B,)
+    ko, kd, m = 0, 0, 0
+    for t in range(B):
+        k_ref, d_ref, lv = ref[t]
+        n = len(k_ref)
+        assert cnt[t, 0] == n and np.array_equal(cnt[t, 1:], lv)
+        exp_k = np.stack([k_ref[f].astype(np.float32) for f in ("x", "y", "size", "angle", "response", "octave", "class_id")], 1)
+        assert np.array_equal(d["keypoints"][ko:ko + n], exp_k), t
+        assert np.array_equal(d["descriptors"][kd:kd + n], d_ref.astype(np.float32)), t
+        ko, kd = ko + n, kd + n
+    for t in sel:
+        f = (t + 1) % B
+        exp = O.brute_force_match(ref[f][1], ref[f][0]["angle"], ref[t][1], ref[t][0]["angle"], None, 0.8, True)
+        assert np.array_equal(d["matches"][m:m + len(exp)], exp.astype(np.float32)), t
+        assert d["match_counts"][t] == (exp >= 0).sum(), t
+        m += len(exp)
+    assert ko == len(d["keypoints"]) and m == len(d["matches"])

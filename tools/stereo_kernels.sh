@@ -1,5 +1,5 @@
 R=$PWD; cd /tmp; export TMPDIR=/tmp
-timeout 300 rocprofv3 --kernel-trace --stats --truncate-kernels -d /tmp/stp -o k --output-format csv -- python $R/bench.py --steps 3 --warmup 1 --no-ba --no-cpu-baseline > /dev/null 2>&1
+timeout 300 rocprofv3 --kernel-trace --stats --truncate-kernels -d /tmp/stp -o k --output-format csv -- python $R/bench.py --full --steps 3 --warmup 1 --no-ba --no-cpu-baseline > /dev/null 2>&1
 python3 - <<PY
 import csv,glob
 f=glob.glob("/tmp/stp/**/k_kernel_stats.csv",recursive=True)[0]
