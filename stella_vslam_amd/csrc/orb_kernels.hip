@@ -817,12 +817,13 @@ __global__ __launch_bounds__(256) void k_fast(const OrbLevel* __restrict__ L, in
             const int A = a[0];
             if (A <= t) continue;
             const int s = A - 1;
-            // s > (n > t ? n - 1 : 0) for all 8 neighbours  <=>  every neighbour's A is below this one's (A > t >= 1 makes the
-            // "n <= t" branch always true and n <= t < A)
+            // s > (n > t ? n - 1 : 0) for all 8 neighbours  <=>  A > 1 and every neighbour's A is below this one's (a neighbour with
+            // n <= t < A scores 0, which s = A - 1 beats iff A > 1).  A > t >= 1 implies A > 1; at t = 0 a corner of A = 1 scores 0, like
+            // a non-corner, and cv::FAST's strict NMS drops it whatever its neighbours.
             const int n0 = max(max((int)a[-FP - 1], (int)a[-FP]), (int)a[-FP + 1]);
             const int n1 = max(max((int)a[-1], (int)a[1]), (int)a[FP - 1]);
             const int n2 = max(max((int)a[FP], (int)a[FP + 1]), n0);
-            const bool keep = max(n1, n2) < A;
+            const bool keep = A > 1 && max(n1, n2) < A;
             if (!keep) continue;
             ++found;
             const int x_level = cell.min_x + qx, y_level = cell.min_y + ly;

@@ -7,6 +7,7 @@ import pytest
 
 from oracle import oracle as O
 from stella_vslam_amd import synthetic as S
+from tests import orb_images as OI
 
 
 # ---- reference test/stella_vslam/feature/orb_params.cc:27-70 (EXPECT_FLOAT_EQ = 4 ulp)
@@ -61,7 +62,7 @@ _CIRCLE = [(0, 3), (1, 3), (2, 2), (3, 1), (3, 0), (3, -1), (2, -2), (1, -3), (0
            (-3, 0), (-3, 1), (-2, 2), (-1, 3)]
 
 
-def fast_definition(img, thr):
+def _arc_scores(img):
     h, w = img.shape
     I = img.astype(np.int32)
     A = np.zeros((h, w), np.int32)  # max over 9-arcs of min signed difference, both signs
@@ -73,6 +74,12 @@ def fast_definition(img, thr):
         best = np.maximum(best, d[idx].min(0))
         best = np.maximum(best, (-d[idx]).min(0))
     A[3:h - 3, 3:w - 3] = best
+    return A
+
+
+def fast_definition(img, thr):
+    h, w = img.shape
+    A = _arc_scores(img)
     score = np.where(A > thr, A - 1, 0)
     out = []
     for y in range(3, h - 3):
@@ -87,13 +94,19 @@ def fast_definition(img, thr):
     return np.array(out, np.int32).reshape(-1, 3)
 
 
-@pytest.mark.parametrize("seed,thr", [(0, 20), (1, 7), (2, 20), (3, 1), (4, 40)])
+# threshold 0 (tests/orb_images.py): a corner of arc score 1 gets the NMS score 0, a non-corner's, and never survives the strict NMS
+@pytest.mark.parametrize("seed,thr", [(0, 20), (1, 7), (2, 20), (3, 1), (4, 40), ("low_contrast", 0), ("spots", 0), ("spots", 1)])
 def test_fast_matches_closed_form_definition(seed, thr):
-    img = S.frame(96, 80, seed=seed + 11)
+    img = S.frame(96, 80, seed=seed + 11) if isinstance(seed, int) else OI.make(seed, 96, 80, 12)
     got = O.fast9_16(img, thr)
     exp = fast_definition(img, thr)
     assert len(got) > 0
     assert np.array_equal(got, exp)
+    if thr == 0:  # the case is live: isolated corners of arc score 1 exist, and the oracle drops them
+        A = _arc_scores(img)
+        nb = np.max([np.roll(np.roll(A, dy, 0), dx, 1) for dy in (-1, 0, 1) for dx in (-1, 0, 1) if dy or dx], 0)
+        lone = (A == 1) & (nb == 0)
+        assert lone.sum() > 5 and not lone[got[:, 1], got[:, 0]].any()
 
 
 def test_fast_on_roi_only_reads_roi():

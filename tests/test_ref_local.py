@@ -128,6 +128,36 @@ def test_extractor_equals_the_reference_code(ref, w, h, seed, kw):
         assert np.array_equal(a, b)
 
 
+@pytest.mark.parametrize("name,kw", [("low_contrast", {}), ("half_low_contrast", {}), ("checker_d7", {}), ("checker_d8", {}), ("checker_d20", {}),
+                                     ("checker_d21", {}), ("low_contrast", dict(ini_thr=20, min_thr=0)), ("spots", dict(ini_thr=20, min_thr=0)),
+                                     ("low_contrast", dict(ini_thr=20, min_thr=1)), ("spots", dict(ini_thr=20, min_thr=1)),
+                                     ("low_contrast", dict(ini_thr=12, min_thr=12)), ("half_low_contrast", dict(ini_thr=12, min_thr=12))])
+def test_extractor_on_retry_and_threshold_edges_equals_the_reference_code(ref, name, kw):
+    """The reference's cell loop where the min_thr retry decides (tests/orb_images.py: low-contrast cells, checkerboards whose level-0
+    arc scores sit on either side of the thresholds, thresholds 0 and 1, a retry at the first pass's own threshold)."""
+    from tests import orb_images as OI
+    img = OI.CLASSES[name]()
+    rk, rd, rp = _ref_extract(ref, img, **kw)
+    k, d, _, pyr = O.orb_extract(img, want_pyramid=True, **kw)
+    assert (len(k) == 0) if name == "checker_d7" else (len(k) > 0)
+    _same(rk, rd, k, d)
+    for a, b in zip(rp, pyr[1:]):
+        assert np.array_equal(a, b)
+
+
+def test_mask_after_the_retry_decision_equals_the_reference_code(ref):
+    """Cells whose every ini_thr corner lies in a masked hole, their own corners unmasked: the reference decides on the retry before it
+    masks (orb_extractor.cc:228-256) and those cells yield nothing."""
+    from tests import orb_images as OI
+    img = OI.low_contrast(640, 480, 1)
+    mask, cells = OI.mask_retry_holes(img, O.fast9_16)
+    assert len(cells) >= 3
+    rk, rd, _ = _ref_extract(ref, img, mask=mask)
+    k, d, _ = O.orb_extract(img, mask=mask)
+    assert len(k) > 0
+    _same(rk, rd, k, d)
+
+
 def test_extractor_with_masks_equals_the_reference_code(ref):
     img = S.frame_sequence(1, 640, 480, seed=9)[0]
     yy, xx = np.mgrid[0:480, 0:640]
