@@ -338,7 +338,8 @@ struct MfShared {
     uint32_t list[MF_QB][MF_SLOTS];
     int cnt[MF_QB];
     uint32_t rowmax[MF_QB];          // largest key of a FULL row once it has been scanned (else all-ones): cheap reject of far candidates
-    float qa[MF_QB];                 // query angle, or -1000 for rows that must never match (past n2, !valid2)
+    float qa[MF_QB];                 // query angle, any float (NaN or out of range: the gate decides as the reference does)
+    uint8_t live[MF_QB];             // 0 for rows that must never match (past n2, !valid2): liveness is never coded into an angle
     uint32_t wq[4][MF_WQ];           // (query row of the wave << 16 | target column of the chunk): the drain recomputes the distance
 #ifdef SV_MF_PAD
     uint32_t pad[SV_MF_PAD];
@@ -370,9 +371,8 @@ __device__ __forceinline__ void mf_drain(MfShared& S, const uint32_t* __restrict
             const uint32_t dist = __popc(q0.x ^ S.raw[0][col]) + __popc(q0.y ^ S.raw[1][col]) + __popc(q0.z ^ S.raw[2][col]) + __popc(q0.w ^ S.raw[3][col])
                                   + __popc(q1.x ^ S.raw[4][col]) + __popc(q1.y ^ S.raw[5][col]) + __popc(q1.z ^ S.raw[6][col]) + __popc(q1.w ^ S.raw[7][col]);
             key = (dist << 16) | (uint32_t)S.ridx[col];
-            const float qa = S.qa[ql];
-            live = qa > -500.f;
-            if (ori) live = live && !(fabsf(angle_diff(S.rang[col], qa)) > 30.0f);
+            live = S.live[ql] != 0;
+            if (ori) live = live && !(fabsf(angle_diff(S.rang[col], S.qa[ql])) > 30.0f);
             if (live) slot = atomicAdd(&S.cnt[ql], 1);  // several lanes may hold hits of the same row
             if (live && slot < MF_SLOTS) S.list[ql][slot] = key;
         }
@@ -428,7 +428,8 @@ __global__ __launch_bounds__(256, 3) void k_bf_mfma(BfProblem P) {
             my_j = I2[q];
             live = !P.valid2 || P.valid2[(size_t)pair * P.cap2 + my_j];
         }
-        S.qa[tid] = live ? A2[q] : -1000.f;
+        S.qa[tid] = q < n2c ? A2[q] : 0.f;
+        S.live[tid] = live ? 1 : 0;
     }
     // ---- A fragments: rows = sorted queries q0 + 32a + (lane & 31), k-step s, lane half h -> bits [32s + 16h, +16); step 8 = the popcount step
     const int h = lane >> 5;

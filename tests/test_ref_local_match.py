@@ -67,6 +67,21 @@ def test_brute_force_match(ref, sc, ratio, ori):
         assert num == (exp >= 0).sum() > 100 and np.array_equal(out, exp)
 
 
+def test_brute_force_match_on_planted_boundaries(ref):
+    """The boundary semantics of tests/bf_problems.py (best 50 / 51, fp32 ratio equality, the +-30 degree gate with wrap-around, NaN and
+    out-of-range angles, degenerate ratios, ties, claim chains, valid2 masks) pinned to robust.cc itself, not only to the oracle."""
+    from tests import bf_problems as BP
+    for name, cases in BP.all_classes().items():
+        for case in cases:
+            exp = case.oracle()
+            d1, d2, a1, a2 = _c(case.d1, np.uint8), _c(case.d2, np.uint8), _c(case.a1, np.float32), _c(case.a2, np.float32)
+            valid = _c(case.valid2, np.uint8)
+            out = np.full(len(d1), -1, np.int32)
+            num = ref.svref_brute_force_match(_p(d1), _p(a1), len(d1), _p(d2), _p(a2), _p(valid), len(d2), C.c_float(case.ratio), int(case.check),
+                                              _p(out))
+            assert num == (exp >= 0).sum() and np.array_equal(out, exp), (name, case.name)
+
+
 @pytest.mark.parametrize("keyframes", [0, 1])
 def test_robust_wrappers(ref, sc, keyframes):
     """robust::match_frame_and_keyframe (match/robust.cc:194-230) and robust::match_keyframes (:148-192): brute force, then the essential-matrix
