@@ -563,6 +563,64 @@ int svgpu_match_for_triangulation(svgpu_ctx* ctx, const uint8_t* desc1, const fl
                                   int num_levels, float residual_rad_thr, float lowe_ratio, int check_orientation, int32_t* matched_2_in_1,
                                   int* num_matches);
 
+/* module::two_view_triangulator::triangulate (module/two_view_triangulator.cc:19-96, .h:89-110) for a list of keypoint matches between
+ * keyframe 1 and keyframe 2: the step between svgpu_match_for_triangulation and the landmark refresh in
+ * mapping_module::triangulate_with_two_keyframes (mapping_module.cc:343-375).  One lane per match, fp64 except where the reference
+ * computes in float.  Per match (idx1[m], idx2[m]):
+ *   is_stereo_k = 0 <= xright_k[idx_k]; world rays and cos_rays_parallax; cos_stereo_parallax_k = cos(2 atan2(true_baseline_k / 2, depth_k))
+ *   or 2.0 (:33-42); the three-way choice of :46-67 with its strict comparisons: solve::triangulator::triangulate(bearing_1, bearing_2,
+ *   cam_pose_1w, cam_pose_2w) (solve/triangulator.h:76-88: null vector of the 4 x 4 A, here by a one-sided Jacobi on its columns), else
+ *   data::triangulate_stereo of keyframe 1, else of keyframe 2 (data/common.cc:192-261, unproj_x / unproj_y rounded to float), else reject;
+ *   check_depth_is_positive (always true for equirectangular); check_reprojection_error with camera::*::reproject_to_image and
+ *   chi_sq_2D = 5.99146f / chi_sq_3D = 7.81473f times level_sigma_sq[octave] (:98-129); check_scale_factors with
+ *   ratio_factor = 2.0f * max(scale_factor_1, scale_factor_2) (.h:94-110, .cc:16).
+ *   pose_kw          12 doubles: rows 0..2 of cam_pose_kw, row-major ([rot_kw | trans_kw]); the camera centre is derived as
+ *                    keyframe::set_pose_cw does (data/keyframe.cc:365-376)
+ *   true_baseline_k  camera::base::true_baseline_ (svgpu_camera does not carry it)
+ *   xy / octave / bearings   undist_keypts_[i].pt (n x 2 floats), .octave, bearings_ (n x 3 doubles)
+ *   xright / depth   stereo_x_right_ / depths_, nullable = empty (-1 for every keypoint)
+ *   scale_factors / level_sigma_sq   orb_params tables of num_levels floats; scale_factor_k = orb_params::scale_factor_
+ *   idx2 == NULL     idx1 is matched_2_in_1 of length num_matches = n1, the output of svgpu_match_for_triangulation: entry i pairs keypoint i
+ *                    of keyframe 1 with keypoint idx1[i] of keyframe 2; -1 = no match, status SVGPU_TRI_SKIPPED
+ *   pos_w            num_matches x 3; meaningful where status is SVGPU_TRI_ACCEPTED (else the rejected candidate, or zeros)
+ *   status           num_matches bytes: which gate rejected the match (the reference returns only a bool)
+ *   num_accepted     nullable
+ * An index or octave out of range, or a stereo keypoint of an equirectangular camera (the reference throws, data/common.cc:239-241),
+ * is SVGPU_ERR_INVALID before anything is launched; num_matches == 0 is a success that launches nothing.  Host in/out, synchronous. */
+#define SVGPU_TRI_ACCEPTED 0
+#define SVGPU_TRI_NO_MODE 1       /* neither enough parallax for two cameras nor a usable stereo keypoint (:65-67) */
+#define SVGPU_TRI_DEPTH 2         /* check_depth_is_positive (:70-73) */
+#define SVGPU_TRI_REPROJECTION 3  /* check_reprojection_error (:76-82) */
+#define SVGPU_TRI_SCALE 4         /* check_scale_factors (:85-90) */
+#define SVGPU_TRI_SKIPPED 255     /* matched_2_in_1 form: keypoint without a match */
+int svgpu_triangulate_two_views(svgpu_ctx* ctx, const svgpu_camera* cam1, const double* pose_1w, double true_baseline_1, const float* xy1, const int32_t* octave1,
+                                const double* bearings1, const float* xright1, const float* depth1, int n1, const svgpu_camera* cam2, const double* pose_2w,
+                                double true_baseline_2, const float* xy2, const int32_t* octave2, const double* bearings2, const float* xright2,
+                                const float* depth2, int n2, const float* scale_factors, const float* level_sigma_sq, int num_levels, float scale_factor_1,
+                                float scale_factor_2, float rays_parallax_deg_thr, const int32_t* idx1, const int32_t* idx2, int num_matches, double* pos_w,
+                                uint8_t* status, int* num_accepted);
+
+/* The loop of mapping_module::create_new_landmarks (mapping_module.cc:274-341) in ONE launch: the current keyframe (side 1 of every
+ * match) against num_neighbours covisible keyframes.  A view is one side's arguments of svgpu_triangulate_two_views; the matches of
+ * neighbour k are entries match_off[k] .. match_off[k + 1] of idx1 / idx2 / pos_w / status (match_off[0] = 0, a neighbour may have none).
+ * idx2 == NULL: every non-empty range is a matched_2_in_1 of length view1->n.  num_accepted: nullable, num_neighbours ints.
+ * Results equal num_neighbours single calls bit for bit. */
+typedef struct svgpu_triangulate_view {
+    const svgpu_camera* cam;
+    const double* pose_cw; /* 12 doubles, as pose_kw above */
+    double true_baseline;
+    const float* xy;
+    const int32_t* octave;
+    const double* bearings;
+    const float* xright; /* nullable */
+    const float* depth;  /* nullable */
+    int32_t n;
+    float scale_factor;
+} svgpu_triangulate_view;
+int svgpu_triangulate_two_views_batch(svgpu_ctx* ctx, const svgpu_triangulate_view* view1, const svgpu_triangulate_view* neighbours, int num_neighbours,
+                                      const int32_t* match_off, const float* scale_factors, const float* level_sigma_sq, int num_levels,
+                                      float rays_parallax_deg_thr, const int32_t* idx1, const int32_t* idx2, double* pos_w, uint8_t* status, int* num_accepted);
+
 /* bow_tree::match_frame_and_keyframe (match/bow_tree.cc:169-256) and bow_tree::match_keyframes (:258-366).
  * Side 1 = the keyframe whose landmarks are handed over (queries: valid1 = keypoint holds a live landmark), side 2 = the frame /
  * the other keyframe (valid2 nullable = every keypoint, or "holds a live landmark" for match_keyframes; occupied2 nullable = keypoints

@@ -134,6 +134,29 @@ __device__ inline void frame_obs_one(const svgpu_camera& cam, const svgpu_keypoi
     }
 }
 
+// camera::*::reproject_to_image of the four models (perspective.cc:130-148, fisheye.cc:169-187, radial_division.cc:113-133,
+// equirectangular.cc:59-73) for a point ALREADY in camera coordinates: the image point, the stereo x_right and the function's return
+// value.  A point at or behind the image plane of a pinhole-family model returns false with rx / ry / xr untouched.
+__device__ inline bool project_to_image(const svgpu_camera& c, double X, double Y, double Z, double& rx, double& ry, float& xr) {
+    if (c.model == SVGPU_CAM_EQUIRECTANGULAR) {  // equirectangular.cc:60-75
+        const double nrm = sqrt((X * X + Y * Y) + Z * Z);
+        const double bx = X / nrm, by = Y / nrm, bz = Z / nrm;
+        const double latitude = -asin(by), longitude = atan2(bx, bz);
+        rx = c.cols * (0.5 + longitude / (2.0 * kPi));
+        ry = c.rows * (0.5 - latitude / kPi);
+        return true;
+    }
+    if (Z <= 0.0) return false;
+    // perspective.cc:130-148
+    const double z_inv = 1.0 / Z;
+    rx = c.fx * X * z_inv + c.cx;
+    ry = c.fy * Y * z_inv + c.cy;
+    xr = (float)(rx - c.focal_x_baseline * z_inv);
+    if (c.model == SVGPU_CAM_RADIAL_DIVISION)  // inclusive bounds, radial_division.cc:124-129
+        return !(rx < c.min_x || rx > c.max_x) && !(ry < c.min_y || ry > c.max_y);
+    return c.min_x < rx && rx < c.max_x && c.min_y < ry && ry < c.max_y;
+}
+
 // data::frame::can_observe (data/frame.cc:59-85) and the per-matcher variants (frame_kernels.h) for ONE landmark.  `P` carries the
 // camera, pose and modes; the landmark's own fields come as arguments so that the caller may read them from flat arrays or from a
 // resident landmark table; the pose likewise (kernel argument, or the device copy a previous optimisation left behind).
@@ -156,23 +179,7 @@ __device__ inline void reproject_one(const ReprojProblem& P, const double* __res
         const double X = (R[0] * pw0 + R[1] * pw1 + R[2] * pw2) + trans_cw[0];
         const double Y = (R[3] * pw0 + R[4] * pw1 + R[5] * pw2) + trans_cw[1];
         const double Z = (R[6] * pw0 + R[7] * pw1 + R[8] * pw2) + trans_cw[2];
-        if (c.model == SVGPU_CAM_EQUIRECTANGULAR) {  // equirectangular.cc:60-75
-            const double nrm = sqrt((X * X + Y * Y) + Z * Z);
-            const double bx = X / nrm, by = Y / nrm, bz = Z / nrm;
-            const double latitude = -asin(by), longitude = atan2(bx, bz);
-            rx = c.cols * (0.5 + longitude / (2.0 * kPi));
-            ry = c.rows * (0.5 - latitude / kPi);
-        }
-        else if (Z <= 0.0) vis = false;
-        else {  // perspective.cc:130-148
-            const double z_inv = 1.0 / Z;
-            rx = c.fx * X * z_inv + c.cx;
-            ry = c.fy * Y * z_inv + c.cy;
-            xr = (float)(rx - c.focal_x_baseline * z_inv);
-            if (c.model == SVGPU_CAM_RADIAL_DIVISION)  // inclusive bounds, radial_division.cc:124-129
-                vis = !(rx < c.min_x || rx > c.max_x) && !(ry < c.min_y || ry > c.max_y);
-            else vis = c.min_x < rx && rx < c.max_x && c.min_y < ry && ry < c.max_y;
-        }
+        vis = project_to_image(c, X, Y, Z, rx, ry, xr);
     }
     if (vis && has_q_level) level = q_level;  // match_current_and_last_frames: in-image is the only visibility test
     else if (vis) {  // data/frame.cc:68-84 and the per-matcher variants (frame_kernels.h)

@@ -302,6 +302,64 @@ def match_for_triangulation(ctx, lowe_ratio, check_orientation, desc1, angle1, o
     return out, num.value
 
 
+TRI_ACCEPTED, TRI_NO_MODE, TRI_DEPTH, TRI_REPROJECTION, TRI_SCALE, TRI_SKIPPED = 0, 1, 2, 3, 4, 255  # include/svgpu.h SVGPU_TRI_*
+
+
+class svgpu_triangulate_view(C.Structure):
+    """include/svgpu.h svgpu_triangulate_view."""
+    _fields_ = [("cam", C.c_void_p), ("pose_cw", C.c_void_p), ("true_baseline", C.c_double), ("xy", C.c_void_p), ("octave", C.c_void_p),
+                ("bearings", C.c_void_p), ("xright", C.c_void_p), ("depth", C.c_void_p), ("n", C.c_int32), ("scale_factor", C.c_float)]
+
+
+def _tri_view(view, keep):
+    """One keyframe side of the triangulator as a dict: cam (a camera object or its svgpu_camera), pose_cw (3 x 4 or 4 x 4), true_baseline,
+    xy (n x 2), octave, bearings (n x 3), xright / depth (optional), scale_factor.  `keep` holds the converted arrays alive."""
+    cam = getattr(view["cam"], "c_", view["cam"])
+    pose = np.ascontiguousarray(np.asarray(view["pose_cw"], np.float64)[:3, :4])
+    a = [cam, pose, _c(view["xy"], np.float32), _c(view["octave"], np.int32), _f64(view["bearings"]), _c(view.get("xright"), np.float32),
+         _c(view.get("depth"), np.float32)]
+    keep.append(a)
+    v = svgpu_triangulate_view()
+    v.cam, v.pose_cw, v.true_baseline = C.addressof(cam), pose.ctypes.data, float(view.get("true_baseline", 0.0))
+    v.xy, v.octave, v.bearings = (None if x is None else x.ctypes.data for x in a[2:5])
+    v.xright, v.depth = (None if x is None else x.ctypes.data for x in a[5:7])
+    v.n, v.scale_factor = len(a[3]), float(view["scale_factor"])
+    return v
+
+
+def triangulate_two_views(ctx, view1, view2, scale_factors, level_sigma_sq, idx1, idx2=None, rays_parallax_deg_thr=1.0):
+    """module::two_view_triangulator::triangulate for a list of matches (idx1[m], idx2[m]); idx2 = None: idx1 is matched_2_in_1, the output of
+    match_for_triangulation.  Returns pos_w (M x 3), status (M bytes, TRI_*), num_accepted."""
+    keep = []
+    v1, v2 = _tri_view(view1, keep), _tri_view(view2, keep)
+    sf, sg, i1, i2 = _c(scale_factors, np.float32), _c(level_sigma_sq, np.float32), _c(idx1, np.int32), _c(idx2, np.int32)
+    m = len(i1)
+    pos, st, num = np.zeros((m, 3), np.float64), np.zeros(m, np.uint8), C.c_int(0)
+    ctx.check(lib().svgpu_triangulate_two_views(
+        ctx.handle, C.c_void_p(v1.cam), C.c_void_p(v1.pose_cw), C.c_double(v1.true_baseline), C.c_void_p(v1.xy), C.c_void_p(v1.octave), C.c_void_p(v1.bearings),
+        C.c_void_p(v1.xright), C.c_void_p(v1.depth), v1.n, C.c_void_p(v2.cam), C.c_void_p(v2.pose_cw), C.c_double(v2.true_baseline), C.c_void_p(v2.xy),
+        C.c_void_p(v2.octave), C.c_void_p(v2.bearings), C.c_void_p(v2.xright), C.c_void_p(v2.depth), v2.n, _p(sf), _p(sg), len(sf),
+        C.c_float(v1.scale_factor), C.c_float(v2.scale_factor), C.c_float(rays_parallax_deg_thr), _p(i1), _p(i2), m, _p(pos), _p(st), C.byref(num)),
+        "svgpu_triangulate_two_views")
+    return pos, st, num.value
+
+
+def triangulate_two_views_batch(ctx, view1, neighbours, match_off, scale_factors, level_sigma_sq, idx1, idx2=None, rays_parallax_deg_thr=1.0):
+    """The loop of mapping_module::create_new_landmarks in one launch: `view1` against every view of `neighbours`; the matches of neighbour k
+    are entries match_off[k] .. match_off[k + 1] of idx1 / idx2.  Returns pos_w, status, num_accepted per neighbour."""
+    keep = []
+    v1 = _tri_view(view1, keep)
+    k = len(neighbours)
+    nb = (svgpu_triangulate_view * max(k, 1))(*[_tri_view(v, keep) for v in neighbours])
+    off = _c(match_off, np.int32)
+    sf, sg, i1, i2 = _c(scale_factors, np.float32), _c(level_sigma_sq, np.float32), _c(idx1, np.int32), _c(idx2, np.int32)
+    m = len(i1)
+    pos, st, num = np.zeros((m, 3), np.float64), np.zeros(m, np.uint8), np.zeros(max(k, 1), np.int32)
+    ctx.check(lib().svgpu_triangulate_two_views_batch(ctx.handle, C.byref(v1), nb, k, _p(off), _p(sf), _p(sg), len(sf), C.c_float(rays_parallax_deg_thr),
+                                                      _p(i1), _p(i2), _p(pos), _p(st), _p(num)), "svgpu_triangulate_two_views_batch")
+    return pos, st, num[:k]
+
+
 class bow_tree(base):
     """match/bow_tree.h on flat arrays: side 1 hands its landmarks over (the keyframe), side 2 receives them (frame / other keyframe);
     node ids = bow_feat_vec_ membership of every keypoint (data.bow_vocabulary.descend)."""
