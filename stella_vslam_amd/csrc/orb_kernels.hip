@@ -63,6 +63,18 @@ __device__ __forceinline__ void xcd_frame_map(int per_frame, int batch, int& ite
     }
 }
 
+// one LDS-DMA instruction: lane i copies the 16 bytes at base + voff[i] (any byte address: profiles/r06_ubench_glds.json) to LDS byte
+// lds_dst + 16 i.  M0 carries the LDS address and is written in the statement that reads it (the compiler does not preserve it); the two
+// moves + s_nop 2 are also the five wait states a VMEM instruction needs behind a VALU instruction that produced its scalar base
+// (hipcc does not look for hazards inside an asm statement).
+__device__ __forceinline__ void sv_glds16(unsigned long long base, uint32_t voff, uint32_t lds_dst) {
+    uint32_t keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 2\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(voff), "s"(base), "s"(lds_dst)
+                 : "memory");
+}
+
 // ------------------------------------------------------------------------------------------------ resize
 // OpenCV 8-bit bilinear: horizontal int32 with 11-bit coefficients, vertical
 // ((b0*(r0>>4))>>16) + ((b1*(r1>>4))>>16) + 2) >> 2.  Coefficient tables are built on the host.
@@ -330,8 +342,8 @@ struct BlurRow {  // the 12 source bytes of pixels [x0-4, x0+8) of one row, imag
 // How a thread fetches its rows.  BLUR_INTERIOR: three aligned words.  BLUR_EDGE: the column group touches the left or
 // right image border of an aligned level; the reflected bytes are picked out of the neighbouring aligned words with
 // v_perm_b32 selectors computed once per thread.  BLUR_GATHER: byte gather (caller images with an odd pitch / base,
-// levels narrower than 16 px).
-enum { BLUR_INTERIOR = 0, BLUR_EDGE = 1, BLUR_GATHER = 2 };
+// levels narrower than 16 px).  BLUR_LDS: the band kernel's rows are staged in LDS with the image borders written out (blur_band_lds).
+enum { BLUR_INTERIOR = 0, BLUR_EDGE = 1, BLUR_GATHER = 2, BLUR_LDS = 3 };
 struct BlurEdge {
     bool left, hi_p1;
     uint32_t sel1, sel2;
@@ -414,28 +426,22 @@ __device__ __forceinline__ uint32_t blur_pack(const uint32_t (&acc)[4]) {  // by
     return lo | hi;
 }
 
-// one thread: columns x0..x0+3, rows ys..ye-1 (ys even).  Rows are handled in pairs (ys-4, ys-3), (ys-2, ys-1), ...; four pairs
+// one thread: columns x0..x0+3, rows ys..ye-1.  Rows are handled in pairs (ys-4, ys-3), (ys-2, ys-1), ...; four pairs
 // of horizontal sums stay in registers and every iteration adds one pair and emits two output rows, each as four
-// 2-element dot products (v_dot2_u32_u16) against the vertically paired taps.
-template <int MODE>
-__device__ __forceinline__ void blur_strip(const uint8_t* __restrict__ src, int spitch, int w, int h, uint8_t* __restrict__ dst,
-                                           int dpitch, int x0, int ys, int ye) {
-    auto row_ptr = [&](int y) { return src + __umul24(reflect101(y, h), spitch); };  // < 2^24 each: full-rate multiply, 32-bit offset
-    BlurEdge edge = {};
-    if (MODE == BLUR_EDGE) edge = blur_edge_ctx(x0, w);
-    auto load_pair = [&](int y, BlurRow& a, BlurRow& b) {
-        a = blur_load<MODE>(row_ptr(y), x0, w, edge);
-        b = blur_load<MODE>(row_ptr(y + 1), x0, w, edge);
-    };
+// 2-element dot products (v_dot2_u32_u16) against the vertically paired taps.  load_pair(y, a, b) fetches rows y and y + 1 (row ys - 4
+// carries a zero tap, row ye + 3 is not used when ye - ys is even: both are still fetched).  Dp = the thread's four bytes of output row 0.
+template <int MODE, class LoadPair>
+__device__ __forceinline__ void blur_walk(LoadPair load_pair, uint8_t* __restrict__ Dp, int dpitch, int ys, int ye) {
+    constexpr int AHEAD = MODE == BLUR_LDS ? 0 : 2;  // global memory: one pair of rows of loads stays in flight ahead of the arithmetic
     u16x2 A[4], B[4], C[4], D[4], E[4];
-    BlurRow n0, n1;
+    BlurRow n0 = {}, n1 = {};
     {
         // the ten rows the first output pair needs: all loads issued before the first use (the empty asm ties every loaded word
         // to one point, so the compiler cannot wait for one row pair before requesting the next)
         BlurRow r[8];
 #pragma unroll
         for (int k = 0; k < 4; ++k) load_pair(ys - 4 + 2 * k, r[2 * k], r[2 * k + 1]);
-        load_pair(ys + 4, n0, n1);
+        if (AHEAD) load_pair(ys + 4, n0, n1);
         if (MODE == BLUR_INTERIOR) {
 #pragma unroll
             for (int k = 0; k < 8; ++k) asm volatile("" : "+v"(r[k].w0), "+v"(r[k].w1), "+v"(r[k].w2));
@@ -446,11 +452,11 @@ __device__ __forceinline__ void blur_strip(const uint8_t* __restrict__ src, int 
         blur_hpair(r[4], r[5], C);
         blur_hpair(r[6], r[7], D);
     }
-    uint8_t* Dp = dst + x0;
     for (int y = ys; y < ye; y += 2) {
         const BlurRow c0 = n0, c1 = n1;
-        load_pair(y + 6, n0, n1);  // one pair of rows of loads stays in flight ahead of the arithmetic
-        blur_hpair(c0, c1, E);
+        load_pair(y + 4 + AHEAD, n0, n1);
+        if (AHEAD) blur_hpair(c0, c1, E);
+        else blur_hpair(n0, n1, E);
         uint32_t acc[4];
         // row y: taps 18 34 48 56 48 34 18 over rows y-3 .. y+3 = A.hi | B | C | D
 #pragma unroll
@@ -472,6 +478,18 @@ __device__ __forceinline__ void blur_strip(const uint8_t* __restrict__ src, int 
         }
     }
 }
+// the walk over rows in global memory (ys even)
+template <int MODE>
+__device__ __forceinline__ void blur_strip(const uint8_t* __restrict__ src, int spitch, int w, int h, uint8_t* __restrict__ dst,
+                                           int dpitch, int x0, int ys, int ye) {
+    auto row_ptr = [&](int y) { return src + __umul24(reflect101(y, h), spitch); };  // < 2^24 each: full-rate multiply, 32-bit offset
+    BlurEdge edge = {};
+    if (MODE == BLUR_EDGE) edge = blur_edge_ctx(x0, w);
+    blur_walk<MODE>([&](int y, BlurRow& a, BlurRow& b) {
+        a = blur_load<MODE>(row_ptr(y), x0, w, edge);
+        b = blur_load<MODE>(row_ptr(y + 1), x0, w, edge);
+    }, dst + x0, dpitch, ys, ye);
+}
 
 // Tiles [0, btiles_x*btiles_y) of a level are interior tiles (aligned 12-byte windows, branch-free); the remaining tiles
 // of the level are EDGE tiles whose threads do the column groups that touch the left/right image border.  Keeping the
@@ -480,10 +498,11 @@ __device__ __forceinline__ void blur_strip(const uint8_t* __restrict__ src, int 
 __device__ __forceinline__ void blur_locate(const OrbLevel* __restrict__ L, int num_levels, const uint8_t* __restrict__ img0,
                                             size_t img0_frame_stride, int img0_pitch, const uint8_t* __restrict__ pyr,
                                             size_t pyr_frame_bytes, uint8_t* __restrict__ blur, size_t blur_frame_bytes, OrbLevel& lev,
-                                            int& tile, const uint8_t*& src, int& spitch, uint8_t*& dst) {
+                                            int& tile, const uint8_t*& src, int& spitch, uint8_t*& dst,
+                                            int OrbLevel::*first = &OrbLevel::btile_first) {
     int b, item;
     xcd_frame_map(gridDim.x, gridDim.y, item, b);
-    const int lv = find_level(L, num_levels, item, &OrbLevel::btile_first, &tile);
+    const int lv = find_level(L, num_levels, item, first, &tile);
     lev = L[lv];
     if (lv == 0) {
         src = img0 + (size_t)b * img0_frame_stride;
@@ -498,8 +517,8 @@ __device__ __forceinline__ void blur_locate(const OrbLevel* __restrict__ L, int 
 __device__ __forceinline__ bool blur_streamable(const uint8_t* src, int spitch, int w) {
     return ((((size_t)src) | (size_t)spitch) & 3) == 0 && w >= 16;
 }
-template <int ROWS>  // rows a thread walks: 64 for batches (least halo traffic), 16 for a context configured for a few frames (4 x the threads:
-                     // one 640x480 frame is 1 280 strips of 64 rows, a serial walk of 25 us on a chip that holds 500 k threads)
+template <int ROWS>  // rows a thread walks: BLUR_ROWS_SMALL = 16 for a context configured for a few frames (one 640x480 frame in strips of 64 rows
+                     // is 1 280 strips, a serial walk of 25 us on a chip that holds 500 k threads); batches take the specialisation below
 __global__ __launch_bounds__(256) void k_blur(const OrbLevel* __restrict__ L, int num_levels, const uint8_t* __restrict__ img0,
                                               size_t img0_frame_stride, int img0_pitch, const uint8_t* __restrict__ pyr,
                                               size_t pyr_frame_bytes, uint8_t* __restrict__ blur, size_t blur_frame_bytes) {
@@ -519,9 +538,6 @@ __global__ __launch_bounds__(256) void k_blur(const OrbLevel* __restrict__ L, in
         const int rem_groups = tx == lev.btiles_x - 1 ? (min(lev.w - 6, (tx + 1) * BLUR_TW) - tx * BLUR_TW + 3) / 4 : 64;  // groups x0 with x0 + 6 < w
         int g = 64;
         while (g > 1 && (g >> 1) >= rem_groups) g >>= 1;
-#ifdef BLUR_NO_MULTISTRIP
-        g = 64;
-#endif
         if (g <= 32 && rem_groups > 0) {
             const int spw = 64 / g, lane = threadIdx.x & 63;
             if (ty * spw >= lev.btiles_y) return;  // (this tile's strips are carried by an earlier tile's waves)
@@ -550,6 +566,82 @@ __global__ __launch_bounds__(256) void k_blur(const OrbLevel* __restrict__ L, in
         if (ys >= lev.h || x0 < 0 || (which != 0 && (x0 == 0 || x0 + 6 < lev.w))) return;
         blur_strip<BLUR_EDGE>(src, spitch, lev.w, lev.h, dst, lev.pitch, x0, ys, min(ys + BLUR_EDGE_ROWS, lev.h));
     }
+}
+// Batches (contexts with OrbConfig::blur_rows == BLUR_ROWS): the blur from full-width row bands in LDS.  The streaming kernel above lets every
+// lane fetch its own 12-byte window, so a wave's row touches four 128-byte lines for two lines of payload and the line two column tiles share
+// is fetched twice (2.17 x the algorithmic bytes, profiles/r06_traffic.json).  Here a workgroup owns BLUR_ROWS output rows of one column
+// segment (BLUR_SEG px, or what is left of the row) of one level of one frame:
+//   * the band's source rows y0 - 3 .. y0 + rows + 2 (reflect-101 at the top and bottom of the level) go to LDS by LDS-DMA in 16-byte pieces,
+//     each source line requested once; the piece that holds the row's end is copied as dwords (nothing past the row's pitch is read);
+//   * the reflected columns left of pixel 0 and right of pixel w - 1 are then written into the LDS rows, so that every column group runs
+//     the one branch-free code path: no edge workgroups, no selectors;
+//   * thread = (chunk of consecutive rows, column group), as in k_pyramid_lds: 320 px are 80 groups, three chunks fill 240 of 256 threads.
+//     A chunk pays six rows of horizontal sums as warm-up.  The walk is blur_walk; the 12-byte window is three aligned LDS dwords.
+// LDS map: row k (pitch BLUR_LP) holds source row y0 - 4 + k, pixel x of the level at byte 16 + x - xs.  Rows 0 and BLUR_ROWS + 7 are never
+// staged: blur_walk reads them (first and last row pair) and gives them zero weight / does not use them.
+#define BLUR_LP (16 + BLUR_SEG + 16)                 // 16 bytes left of the segment (pieces stay 16-byte aligned), 4 + padding right of it
+#define BLUR_LDS_ROWS (BLUR_ROWS + 8)
+static_assert(BLUR_SEG % 16 == 0 && BLUR_BAND_THREADS % 64 == 0 && BLUR_SEG / 4 <= BLUR_BAND_THREADS && BLUR_ROWS % 2 == 0, "blur band geometry");
+static_assert(BLUR_LDS_ROWS * BLUR_LP <= 64 * 1024, "blur band exceeds the static LDS limit");
+template <>
+__global__ __launch_bounds__(BLUR_BAND_THREADS) void k_blur<BLUR_ROWS>(const OrbLevel* __restrict__ L, int num_levels, const uint8_t* __restrict__ img0,
+                                                                       size_t img0_frame_stride, int img0_pitch, const uint8_t* __restrict__ pyr,
+                                                                       size_t pyr_frame_bytes, uint8_t* __restrict__ blur, size_t blur_frame_bytes) {
+    __shared__ __attribute__((aligned(16))) uint8_t s_rows[BLUR_LDS_ROWS * BLUR_LP];
+    OrbLevel lev;
+    int item, spitch;
+    const uint8_t* src;
+    uint8_t* dst;
+    blur_locate(L, num_levels, img0, img0_frame_stride, img0_pitch, pyr, pyr_frame_bytes, blur, blur_frame_bytes, lev, item, src, spitch, dst,
+                &OrbLevel::bband_first);
+    if (!blur_streamable(src, spitch, lev.w)) return;  // k_blur_gather's level
+    const int tid = threadIdx.x, w = lev.w, h = lev.h;
+    const int seg = item % lev.bband_segs, xs = seg * BLUR_SEG, sw = min(BLUR_SEG, w - xs);
+    const int y0 = (item / lev.bband_segs) * BLUR_ROWS, rows = min(BLUR_ROWS, h - y0);
+    const int groups = (sw + 3) >> 2, xend = xs + 4 * groups + 4;  // the last group's window ends at pixel xend - 1
+    // ---- stage: piece q = k * CPR + c (k = 0 .. rows + 5 <-> LDS row k + 1) covers pixels [xs - 16 + 16 c, + 16)
+    {
+        constexpr int CPR = BLUR_LP / 16;
+        const int total = (rows + 6) * CPR;
+        const unsigned long long base = (unsigned long long)(uintptr_t)src;
+        const uint32_t lds0 = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(const __attribute__((address_space(3))) uint8_t*)s_rows) + BLUR_LP;
+        for (int q0 = __builtin_amdgcn_readfirstlane(tid & ~63); q0 < total; q0 += BLUR_BAND_THREADS) {  // one instruction: 64 consecutive pieces
+            const int q = q0 + (tid & 63), k = q / CPR, x = xs - 16 + 16 * (q - k * CPR);
+            if (q < total && x >= 0 && x < min(w, xend)) {
+                const uint32_t off = __umul24(reflect101(y0 - 3 + k, h), spitch) + (uint32_t)x;
+                if (x + 16 <= w) sv_glds16(base, off, lds0 + 16u * (uint32_t)q0);
+                else
+#pragma clang loop vectorize(disable)
+                    for (int d = 0; x + 4 * d < w; ++d)
+                        *reinterpret_cast<uint32_t*>(s_rows + BLUR_LP + 16 * q + 4 * d) = *reinterpret_cast<const uint32_t*>(src + off + 4 * d);
+            }
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the wave's own DMA pieces have landed; the barrier publishes them to the other waves
+    }
+    __syncthreads();
+    // ---- reflect-101 columns: pixels -4 .. -1 = pixels 4, 3, 2, 1; pixels w .. xend - 1 = pixels w - 2, w - 3, ... (xend <= w + 7)
+    for (int i = tid; i < (rows + 6) * 8; i += BLUR_BAND_THREADS) {
+        uint8_t* row = s_rows + ((i >> 3) + 1) * BLUR_LP + 16 - xs;  // pixel x of the level at row[x]
+        const int j = i & 7;
+        if (j == 0 && xs == 0) {
+            const uint32_t* p = reinterpret_cast<const uint32_t*>(row);
+            reinterpret_cast<uint32_t*>(row)[-1] = __builtin_amdgcn_perm(p[1], p[0], 0x01020304u);
+        }
+        const int x = w - 1 + j;
+        if (j > 0 && x < xend) row[x] = row[2 * (w - 1) - x];
+    }
+    __syncthreads();
+    // ---- thread -> (chunk of consecutive rows, column group)
+    const int chunks = max(min(BLUR_BAND_THREADS / groups, rows >> 1), 1), rc = ((rows + chunks - 1) / chunks + 1) & ~1;
+    const int c = (int)(((float)tid + 0.5f) * (1.0f / (float)groups)), g = tid - __mul24(c, groups);
+    const int r0 = __mul24(c, rc), r1 = min(r0 + rc, rows);
+    if (r0 >= r1) return;
+    const uint32_t* S = reinterpret_cast<const uint32_t*>(s_rows + 12 + 4 * g);  // window [x0 - 4, x0 + 8) of LDS row 0
+    blur_walk<BLUR_LDS>([&](int y, BlurRow& a, BlurRow& b) {  // output row y of the band reads LDS rows y + 1 .. y + 7
+        const uint32_t* p = S + __mul24(y + 4, BLUR_LP / 4);
+        a = BlurRow{p[0], p[1], p[2]};
+        b = BlurRow{p[BLUR_LP / 4], p[BLUR_LP / 4 + 1], p[BLUR_LP / 4 + 2]};
+    }, dst + __umul24(y0, lev.pitch) + xs + 4 * g, lev.pitch, r0, r1);
 }
 template <int ROWS>
 __global__ __launch_bounds__(256) void k_blur_gather(const OrbLevel* __restrict__ L, int num_levels, const uint8_t* __restrict__ img0,
@@ -596,18 +688,6 @@ __device__ __forceinline__ int arc_score16(int v, const int (&p)[16]) {
         best = __builtin_elementwise_max(best, __builtin_elementwise_min(m8, __builtin_elementwise_max(e[2 * j], e[(2 * j + 9) & 15])));
     }
     return max(max((int)best.x - v, v + 1 + (int)best.y), 0);
-}
-
-// one LDS-DMA instruction: lane i copies the 16 bytes at base + voff[i] (any byte address: profiles/r06_ubench_glds.json) to LDS byte
-// lds_dst + 16 i.  M0 carries the LDS address and is written in the statement that reads it (the compiler does not preserve it); the two
-// moves + s_nop 2 are also the five wait states a VMEM instruction needs behind a VALU instruction that produced its scalar base
-// (hipcc does not look for hazards inside an asm statement).
-__device__ __forceinline__ void sv_glds16(unsigned long long base, uint32_t voff, uint32_t lds_dst) {
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 2\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(voff), "s"(base), "s"(lds_dst)
-                 : "memory");
 }
 
 #define FAST_KT 12  // selection-grid cells per dimension cached in LDS (a 70-px ROI spans at most ~10 at the coarsest level)
@@ -1436,7 +1516,7 @@ void sv_launch_pyramid(hipStream_t s, const OrbLevel* levels, int num_levels, co
                        img0_pitch, pyr, pyr_frame_bytes, xofs, xa, yofs, yb);
 }
 
-void sv_launch_blur(hipStream_t s, const OrbLevel* levels, int num_levels, int total_tiles, const uint8_t* img0,
+void sv_launch_blur(hipStream_t s, const OrbLevel* levels, int num_levels, int total_tiles, int total_bands, const uint8_t* img0,
                     size_t img0_frame_stride, int img0_pitch, const uint8_t* pyr, size_t pyr_frame_bytes, uint8_t* blur,
                     size_t blur_frame_bytes, int batch, bool need_gather, int rows) {
     const dim3 grid(total_tiles, batch), block(256);
@@ -1445,8 +1525,9 @@ void sv_launch_blur(hipStream_t s, const OrbLevel* levels, int num_levels, int t
         if (need_gather)
             hipLaunchKernelGGL(k_blur_gather<BLUR_ROWS_SMALL>, grid, block, 0, s, levels, num_levels, img0, img0_frame_stride, img0_pitch, pyr, pyr_frame_bytes, blur, blur_frame_bytes);
     }
-    else {
-        hipLaunchKernelGGL(k_blur<BLUR_ROWS>, grid, block, 0, s, levels, num_levels, img0, img0_frame_stride, img0_pitch, pyr, pyr_frame_bytes, blur, blur_frame_bytes);
+    else {  // row bands in LDS, one workgroup per (level, band, column segment)
+        hipLaunchKernelGGL(k_blur<BLUR_ROWS>, dim3(total_bands, batch), dim3(BLUR_BAND_THREADS), 0, s, levels, num_levels, img0, img0_frame_stride, img0_pitch, pyr,
+                           pyr_frame_bytes, blur, blur_frame_bytes);
         if (need_gather)
             hipLaunchKernelGGL(k_blur_gather<BLUR_ROWS>, grid, block, 0, s, levels, num_levels, img0, img0_frame_stride, img0_pitch, pyr, pyr_frame_bytes, blur, blur_frame_bytes);
     }

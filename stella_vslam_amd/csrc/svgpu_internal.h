@@ -17,11 +17,22 @@
 #define SV_CELL 64          // orb_extractor.cc:173 cell_size
 #define SV_OVERLAP 6        // orb_extractor.cc:172 overlap
 #define SV_ROI_MAX 70       // SV_CELL + SV_OVERLAP
-// k_blur tiling (shared by the kernel and the host-side tile count): a thread walks BLUR_ROWS rows of 4 columns
+// k_blur tiling (shared by the kernels and the host-side work-item counts).
+// Batches: a workgroup of BLUR_BAND_THREADS threads blurs BLUR_ROWS output rows of one column segment of a level from LDS (k_blur<BLUR_ROWS>).
+// The three values were picked together by measurement in the pipeline: LDS per workgroup, and with it the number of
+// workgroups that stage and compute side by side on a CU, weighs more than halo rows or the six warm-up rows of a chunk.
 #ifndef BLUR_ROWS
-#define BLUR_ROWS 64
+#define BLUR_ROWS 48                // output rows of a band: the band stages BLUR_ROWS + 6 source rows, (R + 6) / R of the level's bytes
 #endif
-#define BLUR_ROWS_SMALL 16          // contexts configured for at most BLUR_SMALL_BATCH frames: latency, not halo traffic, is what counts
+#ifndef BLUR_SEG
+#define BLUR_SEG 320                // widest column segment of a band, a multiple of 16: wider levels are split, each segment re-reading
+#endif                              // 16 bytes per row on either side.  LDS per workgroup: (BLUR_ROWS + 8) x (BLUR_SEG + 32) bytes = 19 712
+#ifndef BLUR_BAND_THREADS
+#define BLUR_BAND_THREADS 256       // thread = (chunk of rows, group of 4 columns): 320 px = 80 groups x 3 chunks of 16 rows
+#endif
+// Contexts configured for at most BLUR_SMALL_BATCH frames: latency, not traffic, is what counts -- the streaming kernel, a thread walks
+// BLUR_ROWS_SMALL rows of 4 columns straight from global memory.  k_blur_gather uses the same tiles with OrbConfig::blur_rows rows.
+#define BLUR_ROWS_SMALL 16
 #define BLUR_SMALL_BATCH 4
 #define BLUR_TW 256                 // tile width  = 64 threads x 4 px; tile height = 4 strips of OrbConfig::blur_rows rows
 
@@ -39,6 +50,7 @@ struct OrbLevel {
     int grid_x, grid_y, grid_first; // selection grid (distribute_keypoints) and its offset in the key array
     int gtab_x_off, gtab_y_off;     // region coordinate -> grid index lookup tables
     int btile_first, btiles_x, btiles_y;  // blur tiles
+    int bband_first, bband_segs;          // blur bands of k_blur<BLUR_ROWS>: first work item, column segments per band (BLUR_SEG px each)
     float scale;            // scale_factors_[level]
     float kp_size;          // (float)(unsigned)(31 * scale)
 };
@@ -68,8 +80,8 @@ struct OrbConfig {
     OrbLevel levels[SV_MAX_LEVELS];
     std::vector<FastCell> cells;
     int total_grid = 0;    // sum of grid cells over levels = max keypoints per frame
-    int total_btiles = 0;
-    int blur_rows = BLUR_ROWS;  // rows per k_blur thread (BLUR_ROWS, or BLUR_ROWS_SMALL for a context of a few frames)
+    int total_btiles = 0, total_bbands = 0;
+    int blur_rows = BLUR_ROWS;  // BLUR_ROWS: the band kernel; BLUR_ROWS_SMALL: the streaming kernel (a context of a few frames)
     size_t pyr_frame_bytes = 0, blur_frame_bytes = 0;
     std::vector<DescBand> dbands;  // empty: the configuration does not fit the band kernel, k_describe takes it
     size_t dband_lds_bytes = 0;    // dynamic LDS of k_describe_bands
@@ -270,7 +282,7 @@ hipError_t sv_pyramid_prepare();
 void sv_launch_pyramid(hipStream_t s, const OrbLevel* levels, int num_levels, const int2* band_rows, int bands, const uint8_t* img0,
                        size_t img0_frame_stride, int img0_pitch, uint8_t* pyr, size_t pyr_frame_bytes, const short* xofs,
                        const short2* xa, const short2* yofs, const short2* yb, const uint32_t* xg, const short4* yrow, int batch, size_t lds_bytes);
-void sv_launch_blur(hipStream_t s, const OrbLevel* levels, int num_levels, int total_tiles, const uint8_t* img0,
+void sv_launch_blur(hipStream_t s, const OrbLevel* levels, int num_levels, int total_tiles, int total_bands, const uint8_t* img0,
                     size_t img0_frame_stride, int img0_pitch, const uint8_t* pyr, size_t pyr_frame_bytes, uint8_t* blur,
                     size_t blur_frame_bytes, int batch, bool need_gather, int rows);
 void sv_launch_fast(hipStream_t s, const OrbLevel* levels, int num_levels, const FastCell* cells, int num_cells,

@@ -119,7 +119,7 @@ int svgpu_orb_configure(svgpu_ctx* ctx, int width, int height, int max_batch, fl
     std::vector<short4> yrow;
     bool xg_ok = true;          // false: a level shrinks by more than 3x, the byte windows of the records do not fit
     size_t pyr_off = 0, blur_off = 0;
-    int grid_first = 0, btile_first = 0;
+    int grid_first = 0, btile_first = 0, bband_first = 0;
     std::vector<std::pair<int, int>> grid_rows[SV_MAX_LEVELS];  // per level and selection-grid row: first / last level row its keypoints can lie on
     for (int l = 0; l < num_levels; ++l) {
         OrbLevel& L = C.levels[l];
@@ -211,6 +211,9 @@ int svgpu_orb_configure(svgpu_ctx* ctx, int width, int height, int max_batch, fl
         L.btiles_x = (L.w + BLUR_TW - 1) / BLUR_TW;
         L.btiles_y = (L.h + 4 * C.blur_rows - 1) / (4 * C.blur_rows);
         btile_first += L.btiles_x * L.btiles_y + ((L.h + 7) / 8 + 63) / 64;  // + edge tiles (64 strips of BLUR_EDGE_ROWS rows each)
+        L.bband_first = bband_first;
+        L.bband_segs = (L.w + BLUR_SEG - 1) / BLUR_SEG;
+        bband_first += L.bband_segs * ((L.h + BLUR_ROWS - 1) / BLUR_ROWS);
         // ---- FAST cell lattice and selection grid
         L.cell_first = (int)C.cells.size();
         L.grid_first = grid_first;
@@ -270,6 +273,7 @@ int svgpu_orb_configure(svgpu_ctx* ctx, int width, int height, int max_batch, fl
     }
     C.total_grid = grid_first;
     C.total_btiles = btile_first;
+    C.total_bbands = bband_first;
     // ---- bands of k_describe_bands: as many consecutive selection-grid rows of a level as fit the LDS budget (and DB_MAX_KP = 128 keypoints).
     //      A keypoint of grid row g lies on level rows [first(g), last(g)]; its patches need rows y - 15 .. y + 16 (un-blurred; row y + 16 carries
     //      zero weights but is read) and y - 18 .. y + 18 (blurred).  LDS pitch: the level width rounded up to 16-byte pieces, then to 32 mod 64
@@ -491,10 +495,10 @@ int svgpu_orb_extract_batch_device_angles(svgpu_ctx* ctx, const uint8_t* imgs_de
     }
     {
         SvProfScope ps(ctx, sb, "k_blur");
-        // levels the streaming kernel cannot take (caller image not 4-byte aligned, level narrower than 16 px) -> gather kernel
+        // levels the band / streaming kernel cannot take (caller image not 4-byte aligned, level narrower than 16 px) -> gather kernel
         bool need_gather = (((size_t)imgs_dev | (size_t)frame_stride | (size_t)row_stride) & 3) != 0;
         for (int l = 0; l < Lc; ++l) need_gather = need_gather || C.levels[l].w < 16;
-        sv_launch_blur(sb, ctx->d_levels, Lc, C.total_btiles, imgs_dev, frame_stride, row_stride, ctx->d_pyr, C.pyr_frame_bytes,
+        sv_launch_blur(sb, ctx->d_levels, Lc, C.total_btiles, C.total_bbands, imgs_dev, frame_stride, row_stride, ctx->d_pyr, C.pyr_frame_bytes,
                        ctx->d_blur, C.blur_frame_bytes, batch, need_gather, C.blur_rows);
     }
     if (sb != s) SV_HIP(ctx, hipEventRecord(ctx->ev_join, sb));
