@@ -462,6 +462,50 @@ int svgpu_tracker_counters(const svgpu_tracker* tracker, long long* launches, lo
 /* debug (SVGPU_TRACK_STAMPS set): 100 MHz wall-clock stamps of the last optimisation kernel's phases, [0] = how many follow; else NULL / zeros */
 const unsigned long long* svgpu_tracker_debug_stamps(const svgpu_tracker* tracker);
 
+/* ------------------------------------------------------------------------------------------------ image ingest
+ * Stands behind what system::create_monocular_frame / create_stereo_frame / create_RGBD_frame do to an image before the extractor sees it:
+ *   util::convert_to_grayscale(img, color_order)        (util/image_converter.cc:8-39)   cv::cvtColor COLOR_{RGB,BGR,RGBA,BGRA}2GRAY
+ *   util::convert_to_true_depth(img, depthmap_factor)   (util/image_converter.cc:41-43)  img.convertTo(img, CV_32F, 1.0 / factor)
+ *   util::stereo_rectifier::rectify                     (util/stereo_rectifier.cc:62-66) cv::remap(.., INTER_LINEAR), constant border 0
+ * in OpenCV's 8-bit fixed-point arithmetic (tests/ingest_problems.py states it; DESIGN.md section 11: PARITY UNPINNED).  With maps the
+ * order is the reference's: remap the image as read, per channel, then convert to grey.  The rectified colour image is never stored.
+ * util::equalize_histogram and the construction of the maps (cv::initUndistortRectifyMap, once per session) stay with the caller. */
+typedef struct svgpu_ingest svgpu_ingest;
+typedef enum svgpu_color_order { SVGPU_COLOR_GRAY = 0, SVGPU_COLOR_RGB = 1, SVGPU_COLOR_BGR = 2 } svgpu_color_order; /* camera::color_order_t */
+typedef enum svgpu_depth_type { SVGPU_DEPTH_NONE = 0, SVGPU_DEPTH_U16 = 1, SVGPU_DEPTH_F32 = 2 } svgpu_depth_type;   /* CV_16U / CV_32F */
+/* One ingest per camera: `width` x `height` frames of `channels` interleaved 8-bit channels (1, 3 or 4; 4 = alpha last, ignored) in
+ * `color_order` (Gray with 3 or 4 channels is refused).  map_x / map_y: both NULL (no rectification) or both set: CV_32FC1 maps of
+ * width x height entries (the rectified image has the size of the image as read, as in the reference), rows `map_stride` BYTES apart,
+ * host memory.  The float maps are compiled once, on the device, into 8 bytes per pixel (clamped integer source position + the two 5-bit
+ * fractions); no frame reads a float again.  Map VALUES are never an error: outside, non-finite and huge entries give 0.  Synchronous. */
+int svgpu_ingest_create(svgpu_ctx* ctx, int width, int height, int channels, int color_order, const float* map_x, const float* map_y,
+                        int map_stride, svgpu_ingest** out);
+void svgpu_ingest_destroy(svgpu_ingest* ingest);
+/* One frame, host in / host out, synchronous (the counterpart of svgpu_orb_extract): src rows `src_stride` bytes apart
+ * (>= width * channels), dst 8UC1 rows `dst_stride` bytes apart (>= width). */
+int svgpu_ingest_gray(svgpu_ctx* ctx, const svgpu_ingest* ingest, const uint8_t* src, int src_stride, uint8_t* dst, int dst_stride);
+/* Throughput path: `batch` raw frames resident in HBM -> `batch` grey frames in HBM, asynchronous, one launch.  The output layout
+ * (frame b at dst_dev + b * dst_frame_stride, rows dst_row_stride apart) is what svgpu_orb_extract_batch_device takes as imgs_dev. */
+int svgpu_ingest_gray_batch_device(svgpu_ctx* ctx, const svgpu_ingest* ingest, const uint8_t* src_dev, int batch, size_t src_frame_stride,
+                                   int src_row_stride, uint8_t* dst_dev, size_t dst_frame_stride, int dst_row_stride, void* stream);
+/* convert_to_true_depth: dst[y][x] = (float)src[y][x] * (float)(1.0 / depthmap_factor).  src_type: svgpu_depth_type (U16 or F32);
+ * strides in BYTES; depthmap_factor must be finite and non-zero.  Host in / host out, synchronous ... */
+int svgpu_ingest_depth(svgpu_ctx* ctx, const void* src, int src_type, int src_stride, int width, int height, double depthmap_factor, float* dst,
+                       int dst_stride);
+/* ... and device in / device out on a stream, asynchronous */
+int svgpu_ingest_depth_device(svgpu_ctx* ctx, const void* src_dev, int src_type, int src_stride, int width, int height, double depthmap_factor,
+                              float* dst_dev, int dst_stride, void* stream);
+/* Switches the tracker's fused extraction to RAW frames.  Afterwards `img` / `img_left` of svgpu_track_motion / _stereo / _rgbd is a frame
+ * in ingest_left's input format and `img_right` one in ingest_right's, `stride` in bytes of the raw row; with depth_type != 0 the `depth`
+ * argument of svgpu_track_motion_rgbd points to raw CV_16U / CV_32F rows, `depth_stride` BYTES apart, and is multiplied by
+ * (float)(1.0 / depthmap_factor) on the device.  The raw frames go down in the submission's own copies, the ingest kernels run on the
+ * submission's own streams between the upload and the extraction (the right image's on the right context's stream): still one submission
+ * and one synchronisation, one more launch per ingested image and one for the depth.  Every argument is nullable / 0 = that input stays
+ * as before; all off restores the grey path.  The ingests' output size must be the configured extractor's (checked per call, before any
+ * launch); a pair of ingests must agree on it.  The ingests must outlive the tracker or be switched off first. */
+int svgpu_tracker_set_ingest(svgpu_tracker* tracker, const svgpu_ingest* ingest_left, const svgpu_ingest* ingest_right, int depth_type,
+                             double depthmap_factor);
+
 /* ------------------------------------------------------------------------------ function-specific matchers
  * One entry point per reference method: candidate generation (reprojection + grid cells, or BoW buckets), the method's own pair
  * gates and the exact sequential bookkeeping all run on the device; the adaptor classes of stella_vslam_amd/host/ flatten the

@@ -178,6 +178,14 @@ struct SvMapReadScope {
     SvMapReadScope& operator=(const SvMapReadScope&) = delete;
 };
 
+// Image ingest of one camera (include/svgpu.h svgpu_ingest_*): the raw frame format and, for a rectified camera, the compiled map.
+struct svgpu_ingest {
+    int device = 0;
+    int width = 0, height = 0, channels = 0, color_order = 0;
+    uint2* d_map = nullptr;  // height x map_pitch compiled entries (ingest_kernels.h); null: no rectification
+    int map_pitch = 0;
+};
+
 struct svgpu_ctx {
     int device = 0;
     hipStream_t stream = nullptr;

@@ -72,6 +72,14 @@ struct svgpu_tracker {
     int32_t* r_counts = nullptr;
     int r_cap = 0;
     hipEvent_t ev_right = nullptr;
+    // image ingest (svgpu_tracker_set_ingest): the images / the depth map arrive raw; grey level 0 and the metric depth are made on the device
+    const svgpu_ingest *ing_l = nullptr, *ing_r = nullptr;
+    int depth_type = 0;
+    double depth_factor = 1.0;
+    uint8_t *d_gray = nullptr, *d_gray_r = nullptr;  // what the ingest kernels write and the extractors read
+    size_t gray_bytes = 0, gray_r_bytes = 0;
+    float* d_depth = nullptr;
+    size_t depth_bytes = 0;
 };
 
 namespace {
@@ -100,6 +108,25 @@ int reserve_right(svgpu_tracker* t, size_t img_bytes, int cap) {
     SV_HIP(ctx, hipMalloc((void**)&t->r_counts, (1 + SV_MAX_LEVELS) * 4));
     SV_HIP(ctx, hipEventCreateWithFlags(&t->ev_right, hipEventDisableTiming));
     t->in_r_bytes = pad256(img_bytes), t->r_cap = cap;
+    return SVGPU_OK;
+}
+
+void release_ingest(svgpu_tracker* t) {
+    if (t->d_gray) (void)hipFree(t->d_gray);
+    if (t->d_gray_r) (void)hipFree(t->d_gray_r);
+    if (t->d_depth) (void)hipFree(t->d_depth);
+    t->d_gray = t->d_gray_r = nullptr, t->d_depth = nullptr;
+    t->gray_bytes = t->gray_r_bytes = t->depth_bytes = 0;
+}
+// grow-only outputs of the ingest kernels (zeroed once: the extractor may load the padding of a row, never uses it)
+int reserve_ingest_buffer(svgpu_tracker* t, void** buf, size_t* have, size_t bytes) {
+    svgpu_ctx* ctx = t->ctx;
+    if (bytes <= *have) return SVGPU_OK;
+    if (*buf) SV_HIP(ctx, hipFree(*buf));
+    *buf = nullptr, *have = 0;
+    SV_HIP(ctx, hipMalloc(buf, pad256(bytes)));
+    SV_HIP(ctx, hipMemset(*buf, 0, pad256(bytes)));
+    *have = pad256(bytes);
     return SVGPU_OK;
 }
 
@@ -325,6 +352,7 @@ void svgpu_tracker_destroy(svgpu_tracker* t) {
     (void)hipSetDevice(t->map_device);
     release(t);
     release_right(t);
+    release_ingest(t);
     delete t;
 }
 
@@ -362,9 +390,16 @@ int track_motion(svgpu_tracker* t, svgpu_ctx* ctx_right, svgpu_frame* cur, const
         return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_track_motion: bad arguments");
     if (cur->device != ctx->device || last->device != ctx->device) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_track_motion: a frame lives on another device");
     const OrbConfig& C = ctx->orb;
-    if (img && (!C.configured || stride < C.width)) return sv_set_error(ctx, SVGPU_ERR_NOT_CONFIGURED, "svgpu_track_motion: fused extraction needs svgpu_orb_configure on the tracker's context");
+    const svgpu_ingest *ing_l = img ? t->ing_l : nullptr, *ing_r = img && img_right ? t->ing_r : nullptr;
+    const int depth_type = img && depth_img ? t->depth_type : 0, depth_es = depth_type == SVGPU_DEPTH_U16 ? 2 : 4;
+    if (ing_l && C.configured && (ing_l->width != C.width || ing_l->height != C.height || ing_l->device != ctx->device || (long long)stride < (long long)C.width * ing_l->channels))
+        return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_track_motion: the ingest's geometry is not the configured extractor's, or the stride is below a raw row");
+    if (ing_r && C.configured && (ing_r->width != C.width || ing_r->height != C.height || ing_r->device != ctx->device || (long long)stride_right < (long long)C.width * ing_r->channels))
+        return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_track_motion_stereo: the right ingest's geometry is not the configured extractor's, or the stride is below a raw row");
+    if (img && (!C.configured || (!ing_l && stride < C.width))) return sv_set_error(ctx, SVGPU_ERR_NOT_CONFIGURED, "svgpu_track_motion: fused extraction needs svgpu_orb_configure on the tracker's context");
     const bool stereo = img && img_right, rgbd = img && depth_img;
-    if (rgbd && (stereo || depth_stride < C.width || t->cfg.is_monocular))
+    if (rgbd && (stereo || (!depth_type && depth_stride < C.width) || t->cfg.is_monocular
+                 || (depth_type && ((long long)depth_stride < (long long)C.width * depth_es || depth_stride % depth_es != 0 || (uintptr_t)depth_img % depth_es != 0))))
         return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_track_motion_rgbd: needs a depth image of the frame's size and a tracker created with is_monocular = 0");
     if (stereo) {
         if (!ctx_right || ctx_right == ctx || ctx_right->device != ctx->device)
@@ -374,7 +409,7 @@ int track_motion(svgpu_tracker* t, svgpu_ctx* ctx_right, svgpu_frame* cur, const
             if (rcc) return sv_set_error(ctx, rcc, "svgpu_track_motion_stereo: configuring the right context failed");
         }
         const OrbConfig& CR = ctx_right->orb;
-        if (!CR.configured || CR.width != C.width || CR.height != C.height || CR.num_levels != C.num_levels || CR.total_grid != C.total_grid || stride_right < C.width)
+        if (!CR.configured || CR.width != C.width || CR.height != C.height || CR.num_levels != C.num_levels || CR.total_grid != C.total_grid || (!ing_r && stride_right < C.width))
             return sv_set_error(ctx, SVGPU_ERR_NOT_CONFIGURED, "svgpu_track_motion_stereo: the right context must be configured like the left one");
         if (t->cfg.is_monocular) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_track_motion_stereo: the tracker was created for a monocular set-up");
     }
@@ -389,11 +424,19 @@ int track_motion(svgpu_tracker* t, svgpu_ctx* ctx_right, svgpu_frame* cur, const
     int rc;
     if (img && (rc = sv_frame_reserve(ctx, cur, nt_cap, ncell))) return rc;
     const int pitch = img ? C.levels[0].pitch : 0;
-    const size_t img_bytes = img ? (size_t)pitch * C.height : 0;
+    const size_t gray_bytes = img ? (size_t)pitch * C.height : 0;
+    // what goes down per image: the grey frame at the extractor's pitch, or the raw frame in dense rows
+    const int row_l = ing_l ? C.width * ing_l->channels : C.width, pitch_l = ing_l ? row_l : pitch;
+    const int row_r = ing_r ? C.width * ing_r->channels : C.width, pitch_r = ing_r ? row_r : pitch;
+    const size_t img_bytes = img ? (size_t)pitch_l * C.height : 0, img_r_bytes = stereo ? (size_t)pitch_r * C.height : 0;
     // what comes back of a fresh observation: the slab's prefix kps_raw | desc | undist | bearings
     const size_t obs_bytes = !img ? 0 : (stereo || rgbd) ? (size_t)((char*)cur->depth - cur->slab) + (size_t)cur->cap * 4 : (size_t)((char*)cur->bearings - cur->slab) + (size_t)cur->cap * 24;
-    const size_t depth_bytes = rgbd ? (size_t)C.width * C.height * sizeof(float) : 0;
-    if ((stereo || rgbd) && (rc = reserve_right(t, std::max(img_bytes, depth_bytes), nt_cap))) return rc;
+    const size_t depth_row = (size_t)C.width * (depth_type ? depth_es : sizeof(float));
+    const size_t depth_bytes = rgbd ? depth_row * C.height : 0;
+    if ((stereo || rgbd) && (rc = reserve_right(t, std::max(img_r_bytes, depth_bytes), nt_cap))) return rc;
+    if (ing_l && (rc = reserve_ingest_buffer(t, (void**)&t->d_gray, &t->gray_bytes, gray_bytes))) return rc;
+    if (ing_r && (rc = reserve_ingest_buffer(t, (void**)&t->d_gray_r, &t->gray_r_bytes, gray_bytes))) return rc;
+    if (depth_type && (rc = reserve_ingest_buffer(t, (void**)&t->d_depth, &t->depth_bytes, (size_t)C.width * C.height * sizeof(float)))) return rc;
     if ((rc = reserve(t, nt_cap, n_last, t->cap_cand, img_bytes, obs_bytes))) return rc;
     // assume_forward / assume_backward (projection.cc:101-116)
     double Rg[9], tg[3], twc[3], tlc[3];
@@ -411,18 +454,28 @@ int track_motion(svgpu_tracker* t, svgpu_ctx* ctx_right, svgpu_frame* cur, const
         // ---- input block: [image] | last frame's landmark ids, one copy
         const size_t o_ids = pad256(t->img_bytes);
         if (extract) {
-            if (stride == pitch) memcpy(t->h_in, img, img_bytes);
+            if (stride == pitch_l) memcpy(t->h_in, img, img_bytes);
             else
-                for (int y = 0; y < C.height; ++y) memcpy(t->h_in + (size_t)y * pitch, img + (size_t)y * stride, C.width);
+                for (int y = 0; y < C.height; ++y) memcpy(t->h_in + (size_t)y * pitch_l, img + (size_t)y * stride, row_l);
         }
         if (n_last > 0) memcpy(t->h_in + o_ids, last_lm_ids, (size_t)n_last * 4);
         if (extract && stereo) {  // the right image: its own copy, its own extraction, on the right context's stream -- beside everything below
-            if (stride_right == pitch) memcpy(t->h_in_r, img_right, img_bytes);
+            if (stride_right == pitch_r) memcpy(t->h_in_r, img_right, img_r_bytes);
             else
-                for (int y = 0; y < C.height; ++y) memcpy(t->h_in_r + (size_t)y * pitch, img_right + (size_t)y * stride_right, C.width);
+                for (int y = 0; y < C.height; ++y) memcpy(t->h_in_r + (size_t)y * pitch_r, img_right + (size_t)y * stride_right, row_r);
             hipStream_t sr = ctx_right->stream;
-            SV_HIP(ctx, hipMemcpyAsync(t->d_in_r, t->h_in_r, img_bytes, hipMemcpyHostToDevice, sr));
-            rc = svgpu_orb_extract_batch_device(ctx_right, (const uint8_t*)t->d_in_r, 1, img_bytes, pitch, nullptr, 0, pitch, t->r_kps, t->r_desc, nt_cap, t->r_counts, sr);
+            SV_HIP(ctx, hipMemcpyAsync(t->d_in_r, t->h_in_r, img_r_bytes, hipMemcpyHostToDevice, sr));
+            const uint8_t* gray_r = (const uint8_t*)t->d_in_r;
+            if (ing_r) {  // raw right frame -> grey, on the right stream between its upload and its extraction
+                rc = svgpu_ingest_gray_batch_device(ctx_right, ing_r, (const uint8_t*)t->d_in_r, 1, img_r_bytes, pitch_r, t->d_gray_r, gray_bytes, pitch, sr);
+                if (rc) {
+                    (void)hipStreamSynchronize(sr);
+                    return sv_set_error(ctx, rc, "svgpu_track_motion_stereo: ingest of the right image failed");
+                }
+                gray_r = t->d_gray_r;
+                t->launches += 1;
+            }
+            rc = svgpu_orb_extract_batch_device(ctx_right, gray_r, 1, gray_bytes, pitch, nullptr, 0, pitch, t->r_kps, t->r_desc, nt_cap, t->r_counts, sr);
             if (rc) {
                 (void)hipStreamSynchronize(sr);
                 return sv_set_error(ctx, rc, "svgpu_track_motion_stereo: extraction of the right image failed");
@@ -431,7 +484,8 @@ int track_motion(svgpu_tracker* t, svgpu_ctx* ctx_right, svgpu_frame* cur, const
             t->launches += 6;
         }
         if (extract && rgbd) {  // the depth image rides down on the main stream behind the colour image (dense rows of C.width floats)
-            for (int y = 0; y < C.height; ++y) memcpy(t->h_in_r + (size_t)y * C.width * 4, depth_img + (size_t)y * depth_stride, (size_t)C.width * 4);
+            const size_t ds = depth_type ? (size_t)depth_stride : (size_t)depth_stride * sizeof(float);  // (raw rows: the stride is in bytes)
+            for (int y = 0; y < C.height; ++y) memcpy(t->h_in_r + (size_t)y * depth_row, (const char*)depth_img + (size_t)y * ds, depth_row);
         }
         std::unique_lock<std::mutex> lock(t->map->mtx);
         if (t->map->cap == 0) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_track_motion: the map is empty");
@@ -445,7 +499,13 @@ int track_motion(svgpu_tracker* t, svgpu_ctx* ctx_right, svgpu_frame* cur, const
         if (img) {
             nt_dev = cur->counts;
             if (extract) {
-                rc = svgpu_orb_extract_batch_device(ctx, (const uint8_t*)t->d_in, 1, img_bytes, pitch, nullptr, 0, pitch, cur->kps_raw, cur->desc, nt_cap, cur->counts, s);
+                const uint8_t* gray_l = (const uint8_t*)t->d_in;
+                if (ing_l) {  // raw frame -> grey, between the upload and the extraction
+                    if ((rc = svgpu_ingest_gray_batch_device(ctx, ing_l, (const uint8_t*)t->d_in, 1, img_bytes, pitch_l, t->d_gray, gray_bytes, pitch, s))) return rc;
+                    gray_l = t->d_gray;
+                    t->launches += 1;
+                }
+                rc = svgpu_orb_extract_batch_device(ctx, gray_l, 1, gray_bytes, pitch, nullptr, 0, pitch, cur->kps_raw, cur->desc, nt_cap, cur->counts, s);
                 if (rc) return rc;
                 cur->grid_cols = t->cfg.grid_cols, cur->grid_rows = t->cfg.grid_rows;
                 cur->min_x = t->cam.min_x, cur->max_x = t->cam.max_x, cur->min_y = t->cam.min_y, cur->max_y = t->cam.max_y;
@@ -477,7 +537,13 @@ int track_motion(svgpu_tracker* t, svgpu_ctx* ctx_right, svgpu_frame* cur, const
                 if (rgbd) {
                     SV_HIP(ctx, hipMemcpyAsync(t->d_in_r, t->h_in_r, depth_bytes, hipMemcpyHostToDevice, s));
                     t->launches += 1;
-                    F.depth_img = (const float*)t->d_in_r, F.depth_pitch = C.width, F.focal_x_baseline = t->cam.focal_x_baseline;
+                    F.depth_img = (const float*)t->d_in_r;
+                    if (depth_type) {  // util::convert_to_true_depth of the raw map (its own streaming kernel; the sampling below reads the result)
+                        if ((rc = svgpu_ingest_depth_device(ctx, t->d_in_r, depth_type, (int)depth_row, C.width, C.height, t->depth_factor, t->d_depth, C.width * 4, s))) return rc;
+                        F.depth_img = t->d_depth;
+                        t->launches += 1;
+                    }
+                    F.depth_pitch = C.width, F.focal_x_baseline = t->cam.focal_x_baseline;
                     F.xright = cur->xright, F.depth_out = cur->depth;
                     cur->has_xright = true;
                 }
@@ -570,6 +636,23 @@ int svgpu_track_motion_rgbd(svgpu_tracker* t, svgpu_frame* cur, const uint8_t* i
     if (!img || !depth) return sv_set_error(t->ctx, SVGPU_ERR_INVALID, "svgpu_track_motion_rgbd: the image and the depth image are required");
     return track_motion(t, nullptr, cur, img, stride, nullptr, 0, depth, depth_stride, last, last_lm_ids, pose_guess_cw, pose_last_cw, margin, check_orientation,
                         nullptr, nullptr, nullptr, nullptr, cap, match_last, outlier, result);
+}
+
+int svgpu_tracker_set_ingest(svgpu_tracker* t, const svgpu_ingest* ingest_left, const svgpu_ingest* ingest_right, int depth_type, double depthmap_factor) {
+    if (!t) return SVGPU_ERR_INVALID;
+    svgpu_ctx* ctx = t->ctx;
+    if (depth_type < SVGPU_DEPTH_NONE || depth_type > SVGPU_DEPTH_F32 || (depth_type && (!std::isfinite(depthmap_factor) || depthmap_factor == 0.0))
+        || (ingest_left && ingest_left->device != ctx->device) || (ingest_right && ingest_right->device != ctx->device))
+        return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_tracker_set_ingest: bad arguments");
+    if (ingest_left && ingest_right && (ingest_left->width != ingest_right->width || ingest_left->height != ingest_right->height))
+        return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_tracker_set_ingest: the two ingests differ in their output geometry");
+    if (ctx->orb.configured)
+        for (const svgpu_ingest* g : {ingest_left, ingest_right})
+            if (g && (g->width != ctx->orb.width || g->height != ctx->orb.height))
+                return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_tracker_set_ingest: the ingest's geometry is not the configured extractor's");
+    t->ing_l = ingest_left, t->ing_r = ingest_right;
+    t->depth_type = depth_type, t->depth_factor = depth_type ? depthmap_factor : 1.0;
+    return SVGPU_OK;
 }
 
 int svgpu_tracker_observation_stereo(const svgpu_tracker* t, const float** x_right, const float** depths) {

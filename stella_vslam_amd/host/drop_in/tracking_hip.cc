@@ -245,12 +245,22 @@ void rebuild_frame(data::frame& frm, data::frame_observation& frm_obs) {
 }
 }  // namespace
 
+void tracked_frame_chain::set_ingest(const svgpu_ingest* left, const svgpu_ingest* right, int depth_type, double depthmap_factor) {
+    check(svgpu_tracker_set_ingest(tracker_, left, right, depth_type, depthmap_factor), "svgpu_tracker_set_ingest");
+    depth_type_ = depth_type;
+}
+
 bool tracked_frame_chain::motion_based_track(data::frame& curr_frm, const data::frame& last_frm, const Mat44_t& velocity, unsigned int num_matches_thr, float margin,
                                              const cv::Mat* img, std::vector<cv::KeyPoint>* keypts, const cv::Mat* img_right, const cv::Mat* img_depth) {
     if (img_right && (!img || !ctx_right_)) throw std::runtime_error("tracked_frame_chain: a stereo frame needs the left image and set_right_context()");
     if (img_depth && (!img || img_right)) throw std::runtime_error("tracked_frame_chain: an RGB-D frame is an image plus its depth map");
     // (svgpu_track_motion_rgbd reads height x width floats behind the pointer: the raw CV_16U map before util::convert_to_true_depth, or a smaller
     //  map, would be read out of bounds -- ADVICE r5)
+    const size_t depth_elem = depth_type_ == SVGPU_DEPTH_U16 ? sizeof(uint16_t) : sizeof(float);
+    if (img_depth && depth_type_ != SVGPU_DEPTH_NONE) {  // a raw map (set_ingest): rows of the image's width in its own element type
+        if (img_depth->rows != img->rows || img_depth->step < (size_t)img->cols * depth_elem) throw std::runtime_error("tracked_frame_chain: the raw depth map must have the image's size");
+    }
+    else
 #ifdef CV_32FC1
     if (img_depth && (img_depth->type() != CV_32FC1 || img_depth->rows != img->rows || img_depth->cols != img->cols))
 #else  // (the stand-in cv::Mat of host/standin/ is untyped bytes: every row must at least hold the image's width in floats)
@@ -293,7 +303,7 @@ bool tracked_frame_chain::motion_based_track(data::frame& curr_frm, const data::
         const bool fused = img && attempt == 0;
         if (fused && img_depth)
             check(svgpu_track_motion_rgbd(tracker_, cur_h.get(), img->ptr(0), (int)img->step, reinterpret_cast<const float*>(img_depth->ptr(0)),
-                                          (int)(img_depth->step / sizeof(float)), last_h.get(), last_ids_.data(), guess12, last12, margin, 1, cap, match_.data(),
+                                          depth_type_ != SVGPU_DEPTH_NONE ? (int)img_depth->step : (int)(img_depth->step / sizeof(float)), last_h.get(), last_ids_.data(), guess12, last12, margin, 1, cap, match_.data(),
                                           outlier_.data(), &last_motion_),
                   "svgpu_track_motion_rgbd");
         else if (fused && img_right)

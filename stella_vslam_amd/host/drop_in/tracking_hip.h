@@ -40,6 +40,10 @@ public:
                             const cv::Mat* img_depth = nullptr);  //!< RGB-D (system.cc:466-526): CV_32F depth in metres instead of a right image
     //! the context of the RIGHT camera's extractor (feature::orb_extractor::context() of extractor_right_; configured like the left one)
     void set_right_context(svgpu_ctx* ctx_right) { ctx_right_ = ctx_right; }
+    //! Switches the chain to RAW frames (svgpu_tracker_set_ingest): afterwards `img` / `img_right` of motion_based_track are the images as read
+    //! (util::stereo_rectifier::rectify and util::convert_to_grayscale run inside the frame's submission) and, with depth_type != 0, `img_depth` is
+    //! the raw CV_16U / CV_32F map (util::convert_to_true_depth likewise).  Ingests: svgpu_ingest_create, or util::hip::stereo_rectifier's.
+    void set_ingest(const svgpu_ingest* left, const svgpu_ingest* right = nullptr, int depth_type = SVGPU_DEPTH_NONE, double depthmap_factor = 1.0);
 
     //! tracking_module::search_local_landmarks (tracking_module.cc:533-608) followed by the optimisation and outlier rejection of
     //! optimize_current_frame_with_local_map (:441-455).  Returns false when no local landmark can be projected ("projection candidate
@@ -80,6 +84,7 @@ private:
     void remember(unsigned int frame_id, const frame_handle& h);
     uint32_t frame_serial_ = 0;
     svgpu_ctx* ctx_right_ = nullptr;
+    int depth_type_ = SVGPU_DEPTH_NONE;    // set_ingest: the depth map arrives raw
     bool device_pose_valid_ = false;       // the tracker's device pose is the pose motion_based_track gave frame device_pose_frame_
     unsigned int device_pose_frame_ = 0;
     std::vector<uint32_t> held_stamp_;  // per landmark id: serial of the frame that holds it (curr_landmark_ids of :536-551 without a hash set)

@@ -118,6 +118,17 @@ class tracker:
         self._h = C.c_void_p()
         ctx.check(lib().svgpu_tracker_create(ctx.handle, table._h, C.byref(camera.c_), C.byref(cfg), C.byref(self._h)), "svgpu_tracker_create")
 
+    def set_ingest(self, ingest_left=None, ingest_right=None, depth_type: int = 0, depthmap_factor: float = 1.0):
+        """svgpu_tracker_set_ingest: afterwards `img` / `img_left` / `img_right` / `depth` of the track_motion* calls are RAW frames in the ingests'
+        input formats (ingest.Ingest; a uint16 / float32 depth map with depth_type = ingest.DEPTH_U16 / DEPTH_F32).  None / 0 = that input stays as it was."""
+        from . import ingest as _ingest
+        L = _ingest._bind()
+        self.ctx.check(L.svgpu_tracker_set_ingest(self._h, ingest_left._h if ingest_left is not None else None, ingest_right._h if ingest_right is not None else None,
+                                                  int(depth_type), float(depthmap_factor)), "svgpu_tracker_set_ingest")
+        self._ingest = (ingest_left, ingest_right)   # (kept alive: the tracker reads them at every call)
+        self._depth_type = int(depth_type)
+        return self
+
     def track_motion(self, cur: resident_frame, last: resident_frame, last_lm_ids, pose_guess_cw, pose_last_cw, margin: float, check_orientation: bool = True,
                      img: np.ndarray | None = None):
         """-> dict(match_last, outlier, result[, keypts, descriptors, undist_keypts, bearings when `img` is given])"""
@@ -167,9 +178,10 @@ class tracker:
         cap = max(int(lib().svgpu_orb_max_keypoints(self.ctx.handle)), 1)
         outl = np.zeros(cap, np.uint8)
         if depth is not None:
-            dm = np.ascontiguousarray(depth, np.float32)
-            assert dm.shape == il.shape
-            self.ctx.check(lib().svgpu_track_motion_rgbd(self._h, cur._h, _p(il), il.strides[0], _p(dm), dm.strides[0] // 4, last._h, _p(ids), _p(guess), _p(plast),
+            raw_depth = getattr(self, "_depth_type", 0)
+            dm = np.ascontiguousarray(depth, (np.uint16 if raw_depth == 1 else np.float32))
+            assert dm.shape == il.shape[:2]
+            self.ctx.check(lib().svgpu_track_motion_rgbd(self._h, cur._h, _p(il), il.strides[0], _p(dm), dm.strides[0] if raw_depth else dm.strides[0] // 4, last._h, _p(ids), _p(guess), _p(plast),
                                                          C.c_float(margin), int(check_orientation), cap, _p(match), _p(outl), C.byref(res)), "svgpu_track_motion_rgbd")
         else:
             ir = np.ascontiguousarray(img_right, np.uint8)
