@@ -141,11 +141,56 @@ __global__ void k_pose_major(const int* __restrict__ pe_idx, const int* __restri
     pm_hub[q] = e_hub[e];
 }
 
-inline size_t pad256(size_t b) { return (b + 255) & ~size_t(255); }
+// Scratch layouts, each described once: the *_scratch_bytes functions measure what the builders below place.
+struct SortScratch {  // double-buffered (key, value) records of sv_sort_pairs + its histograms
+    unsigned* keys[2];
+    unsigned long long* vals[2];
+    int* hist;
+};
+void lay_sort(Arena& A, size_t n, SortScratch& S) {
+    S.keys[0] = A.take<unsigned>(n), S.keys[1] = A.take<unsigned>(n);
+    S.vals[0] = A.take<unsigned long long>(n), S.vals[1] = A.take<unsigned long long>(n);
+    S.hist = A.take<int>(sv_sort_hist_ints(n));
+}
+struct PairScratch {
+    int *cnt, *cnt_scan, *hist;
+    unsigned* keys[2];
+    unsigned long long* vals0;  // (the second value buffer is the caller's pair array)
+};
+void lay_pairs(Arena& A, size_t pair_cap, int E, PairScratch& S) {
+    S.cnt = A.take<int>((size_t)E + 2);
+    S.cnt_scan = A.take<int>(sv_scan_scratch_ints((size_t)E + 1));
+    S.hist = A.take<int>(sv_sort_hist_ints(pair_cap));
+    S.keys[0] = A.take<unsigned>(pair_cap), S.keys[1] = A.take<unsigned>(pair_cap);
+    S.vals0 = A.take<unsigned long long>(pair_cap);
+}
+struct RenumberScratch {
+    SortScratch sort;
+    int* scan_scr;
+};
+void lay_renumber(Arena& A, size_t L, RenumberScratch& S) {
+    lay_sort(A, L, S.sort);
+    S.scan_scr = A.take<int>(sv_scan_scratch_ints(L + 1) + 16);
+}
+struct UnitScratch {
+    int *uid, *scan_scr, *unit_off, *unit_blk;
+    SortScratch sort;
+};
+void lay_units(Arena& A, size_t num_pairs, size_t unit_cap, UnitScratch& S) {
+    S.uid = A.take<int>(num_pairs + 2);
+    S.scan_scr = A.take<int>(sv_scan_scratch_ints(num_pairs + 1) + 16);
+    S.unit_off = A.take<int>(unit_cap + 1);
+    S.unit_blk = A.take<int>(unit_cap);
+    lay_sort(A, unit_cap, S.sort);
+}
 }  // namespace
 
 size_t sv_ba_pairs_scratch_bytes(size_t pair_cap, int E, size_t nb_cap) {  // E: observations (the counts / slots are per observation)
-    return 2 * pad256((size_t)(E + 2) * 4) + pad256(sv_scan_scratch_ints((size_t)E + 1) * 4) + pad256(sv_sort_hist_ints(pair_cap) * 4) + 2 * pad256(pair_cap * 4) + pad256(pair_cap * 8) + pad256((nb_cap + 1) * 4) + 1024;
+    return arena_measure([&](Arena& A) {
+        PairScratch S;
+        lay_pairs(A, pair_cap, E, S);
+        A.take<int>(nb_cap + 1);  // sv_ba_build_pairs: the dense offsets, at the end of the block
+    });
 }
 
 namespace {
@@ -153,19 +198,14 @@ namespace {
 int build_pairs(svgpu_ctx* ctx, hipStream_t s, const BaDev& D, void* scratch, size_t scratch_bytes, size_t pair_cap, int total_host, int2* pairs_out,
                 int* pair_l_out, int* dense_off_dev, bool read_total, int* total_out) {
     const int nb_dense = D.nP * (D.nP + 1) / 2;
-    char* p = (char*)scratch;
-    auto take = [&](size_t bytes) {
-        char* r = p;
-        p += pad256(bytes);
-        return (void*)r;
-    };
     const int E = D.E;
-    int* cnt = (int*)take((size_t)(E + 2) * 4);
-    int* cnt_scan = (int*)take(sv_scan_scratch_ints((size_t)E + 1) * 4);
-    int* hist = (int*)take(sv_sort_hist_ints(pair_cap) * 4);
-    unsigned* keys[2] = {(unsigned*)take(pair_cap * 4), (unsigned*)take(pair_cap * 4)};
-    unsigned long long* vals[2] = {(unsigned long long*)take(pair_cap * 8), reinterpret_cast<unsigned long long*>(pairs_out)};
-    if ((size_t)(p - (char*)scratch) > scratch_bytes) return sv_set_error(ctx, SVGPU_ERR_CAPACITY, "pair-list scratch too small");
+    Arena A(scratch, scratch_bytes);
+    PairScratch S;
+    lay_pairs(A, pair_cap, E, S);
+    if (A.overflow) return sv_set_error(ctx, SVGPU_ERR_CAPACITY, "pair-list scratch too small");
+    int *const cnt = S.cnt, *const cnt_scan = S.cnt_scan, *const hist = S.hist;
+    unsigned* keys[2] = {S.keys[0], S.keys[1]};
+    unsigned long long* vals[2] = {S.vals0, reinterpret_cast<unsigned long long*>(pairs_out)};
     SV_HIP(ctx, hipGetLastError());
     if (E > 0) {
         hipLaunchKernelGGL(k_pair_count, dim3((E + 255) / 256), dim3(256), 0, s, D, cnt);
@@ -206,8 +246,8 @@ int sv_ba_build_pairs(svgpu_ctx* ctx, hipStream_t s, const BaDev& D, void* scrat
     dense_off_host.assign((size_t)nb_dense + 1, 0);
     if (L == 0 || D.nP == 0) return SVGPU_OK;
     // the dense offsets live at the END of the scratch block (behind what build_pairs takes)
-    int* dense_off = (int*)((char*)scratch + scratch_bytes - pad256(((size_t)nb_dense + 1) * 4));
-    const int rc = build_pairs(ctx, s, D, scratch, scratch_bytes - pad256(((size_t)nb_dense + 1) * 4), pair_cap, 0, pairs_out, pair_l_out, dense_off, true, nullptr);
+    int* dense_off = (int*)((char*)scratch + scratch_bytes - pad(((size_t)nb_dense + 1) * 4));
+    const int rc = build_pairs(ctx, s, D, scratch, scratch_bytes - pad(((size_t)nb_dense + 1) * 4), pair_cap, 0, pairs_out, pair_l_out, dense_off, true, nullptr);
     if (rc) return rc;
     SV_HIP(ctx, hipMemcpyAsync(dense_off_host.data(), dense_off, 4 * ((size_t)nb_dense + 1), hipMemcpyDeviceToHost, s));
     SV_HIP(ctx, hipStreamSynchronize(s));
@@ -229,7 +269,12 @@ int sv_ba_build_pairs_async(svgpu_ctx* ctx, hipStream_t s, const BaDev& D, void*
 // Pose -> edge lists (every pose's edges in increasing edge order, whatever their level) and the "has a robust kernel" flags, built on
 // the device from the uploaded observations: a stable radix sort of (pose, edge index) + the offsets of the sorted keys.  The host used to
 // do this with a two-pass counting sort over all observations (0.5 ms of a config-5 call on four threads).
-size_t sv_ba_pose_lists_scratch_bytes(size_t E) { return 2 * pad256(E * 4) + 2 * pad256(E * 8) + pad256(sv_sort_hist_ints(E) * 4) + 1024; }
+size_t sv_ba_pose_lists_scratch_bytes(size_t E) {
+    return arena_measure([&](Arena& A) {
+        SortScratch S;
+        lay_sort(A, E, S);
+    });
+}
 void sv_ba_build_pose_major(hipStream_t s, const int* pe_idx, const int* e_point, const float* e_uvr, const float* e_w, const float* e_hub, int E, int* pm_point,
                             float* pm_uvr, float* pm_w, float* pm_hub) {
     if (E > 0) hipLaunchKernelGGL(k_pose_major, dim3((E + 255) / 256), dim3(256), 0, s, pe_idx, e_point, e_uvr, e_w, e_hub, E, pm_point, pm_uvr, pm_w, pm_hub);
@@ -247,16 +292,13 @@ int sv_ba_prepare_lists(svgpu_ctx* ctx, hipStream_t s, const int* e_pose_dev, in
         SV_HIP(ctx, hipMemsetAsync(pe_off_dev, 0, 4 * ((size_t)P + 1), s));
         return SVGPU_OK;
     }
-    char* p = (char*)scratch;
-    auto take = [&](size_t bytes) {
-        char* r = p;
-        p += pad256(bytes);
-        return (void*)r;
-    };
-    unsigned* keys[2] = {(unsigned*)take((size_t)E * 4), (unsigned*)take((size_t)E * 4)};
-    unsigned long long* vals[2] = {(unsigned long long*)take((size_t)E * 8), (unsigned long long*)take((size_t)E * 8)};
-    int* hist = (int*)take(sv_sort_hist_ints(E) * 4);
-    if ((size_t)(p - (char*)scratch) > scratch_bytes) return sv_set_error(ctx, SVGPU_ERR_CAPACITY, "pose-list scratch too small");
+    Arena A(scratch, scratch_bytes);
+    SortScratch S;
+    lay_sort(A, E, S);
+    if (A.overflow) return sv_set_error(ctx, SVGPU_ERR_CAPACITY, "pose-list scratch too small");
+    unsigned** const keys = S.keys;
+    unsigned long long** const vals = S.vals;
+    int* const hist = S.hist;
     const dim3 g((E + 255) / 256), b(256);
     hipLaunchKernelGGL(k_obs_prepare, g, b, 0, s, e_pose_dev, E, keys[0], vals[0], e_level_dev, e_chi_dev);
     int bits = 1;
@@ -281,16 +323,13 @@ int sv_ba_build_pose_lists(svgpu_ctx* ctx, hipStream_t s, const int* e_pose_dev,
         SV_HIP(ctx, hipMemsetAsync(pe_off_dev, 0, 4 * ((size_t)P + 1), s));
         return SVGPU_OK;
     }
-    char* p = (char*)scratch;
-    auto take = [&](size_t bytes) {
-        char* r = p;
-        p += pad256(bytes);
-        return (void*)r;
-    };
-    unsigned* keys[2] = {(unsigned*)take((size_t)E * 4), (unsigned*)take((size_t)E * 4)};
-    unsigned long long* vals[2] = {(unsigned long long*)take((size_t)E * 8), (unsigned long long*)take((size_t)E * 8)};
-    int* hist = (int*)take(sv_sort_hist_ints(E) * 4);
-    if ((size_t)(p - (char*)scratch) > scratch_bytes) return sv_set_error(ctx, SVGPU_ERR_CAPACITY, "pose-list scratch too small");
+    Arena A(scratch, scratch_bytes);
+    SortScratch S;
+    lay_sort(A, E, S);
+    if (A.overflow) return sv_set_error(ctx, SVGPU_ERR_CAPACITY, "pose-list scratch too small");
+    unsigned** const keys = S.keys;
+    unsigned long long** const vals = S.vals;
+    int* const hist = S.hist;
     const dim3 g((E + 255) / 256), b(256);
     hipLaunchKernelGGL(k_flag_positive, g, b, 0, s, e_huber_dev, E, robust_dev);
     hipLaunchKernelGGL(k_copy_keys, g, b, 0, s, e_pose_dev, E, keys[0]);
@@ -360,22 +399,23 @@ __global__ void k_lm_permute_flags(const int* __restrict__ order, int L, const u
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r < L) new_flags[r] = old_flags[order[r]];
 }
-size_t sv_ba_renumber_scratch_bytes(size_t L) { return 2 * pad256(L * 4) + 2 * pad256(L * 8) + pad256(sv_sort_hist_ints(L) * 4) + pad256(sv_scan_scratch_ints(L + 1) * 4 + 64) + 1024; }
+size_t sv_ba_renumber_scratch_bytes(size_t L) {
+    return arena_measure([&](Arena& A) {
+        RenumberScratch S;
+        lay_renumber(A, L, S);
+    });
+}
 // order_out[r] = caller's index of the landmark at rank r; lm_off_new (L + 1), e_pose_new / e_point_new / src_edge (E) in the new edge order
 int sv_ba_renumber_landmarks(svgpu_ctx* ctx, hipStream_t s, const int* lm_off_old, const int* e_pose_old, int L, int P, int E, void* scratch, size_t scratch_bytes,
                              int* order_out, int* lm_off_new, int* e_pose_new, int* e_point_new, int* src_edge) {
     if (L <= 0 || E <= 0) return SVGPU_OK;
-    char* p = (char*)scratch;
-    auto take = [&](size_t bytes) {
-        char* r = p;
-        p += pad256(bytes);
-        return (void*)r;
-    };
-    unsigned* keys[2] = {(unsigned*)take((size_t)L * 4), (unsigned*)take((size_t)L * 4)};
-    unsigned long long* vals[2] = {(unsigned long long*)take((size_t)L * 8), (unsigned long long*)take((size_t)L * 8)};
-    int* hist = (int*)take(sv_sort_hist_ints(L) * 4);
-    int* scan_scr = (int*)take(sv_scan_scratch_ints((size_t)L + 1) * 4 + 64);
-    if ((size_t)(p - (char*)scratch) > scratch_bytes) return sv_set_error(ctx, SVGPU_ERR_CAPACITY, "landmark renumbering scratch too small");
+    Arena A(scratch, scratch_bytes);
+    RenumberScratch S;
+    lay_renumber(A, L, S);
+    if (A.overflow) return sv_set_error(ctx, SVGPU_ERR_CAPACITY, "landmark renumbering scratch too small");
+    unsigned** const keys = S.sort.keys;
+    unsigned long long** const vals = S.sort.vals;
+    int *const hist = S.sort.hist, *const scan_scr = S.scan_scr;
     const dim3 g((L + 255) / 256), b(256);
     hipLaunchKernelGGL(k_lm_key, g, b, 0, s, lm_off_old, e_pose_old, L, P, keys[0], vals[0]);
     int bits = 1;
@@ -440,28 +480,23 @@ __global__ void k_unit_rec(const unsigned long long* __restrict__ vals, const in
     rec[pos] = make_int4(unit_off[u], unit_off[u + 1], unit_blk[u], u);
 }
 size_t sv_ba_units_scratch_bytes(size_t num_pairs, size_t unit_cap) {
-    return pad256((num_pairs + 2) * 4) + pad256(sv_scan_scratch_ints(num_pairs + 1) * 4 + 64) + pad256((unit_cap + 1) * 4) + pad256(unit_cap * 4) + 2 * pad256(unit_cap * 4) + 2 * pad256(unit_cap * 8)
-           + pad256(sv_sort_hist_ints(unit_cap) * 4) + 2048;
+    return arena_measure([&](Arena& A) {
+        UnitScratch S;
+        lay_units(A, num_pairs, unit_cap, S);
+    });
 }
 // *num_units_out = 0 when the cut would need more than unit_cap units (the caller keeps the arithmetic shares).  One host synchronisation.
 int sv_ba_build_units(svgpu_ctx* ctx, hipStream_t s, const int* blk_off_dev, int NB, const int* pair_l_dev, int num_pairs, int L, int chunk_shift, int unit_cap, void* scratch,
                       size_t scratch_bytes, int4* unit_rec_out, int* blk_unit_off_out, int* num_units_out) {
     *num_units_out = 0;
     if (num_pairs <= 0 || NB <= 0 || unit_cap <= 0) return SVGPU_OK;
-    char* p = (char*)scratch;
-    auto take = [&](size_t bytes) {
-        char* r = p;
-        p += pad256(bytes);
-        return (void*)r;
-    };
-    int* uid = (int*)take(((size_t)num_pairs + 2) * 4);
-    int* scan_scr = (int*)take(sv_scan_scratch_ints((size_t)num_pairs + 1) * 4 + 64);
-    int* unit_off = (int*)take(((size_t)unit_cap + 1) * 4);
-    int* unit_blk = (int*)take((size_t)unit_cap * 4);
-    unsigned* keys[2] = {(unsigned*)take((size_t)unit_cap * 4), (unsigned*)take((size_t)unit_cap * 4)};
-    unsigned long long* vals[2] = {(unsigned long long*)take((size_t)unit_cap * 8), (unsigned long long*)take((size_t)unit_cap * 8)};
-    int* hist = (int*)take(sv_sort_hist_ints((size_t)unit_cap) * 4);
-    if ((size_t)(p - (char*)scratch) > scratch_bytes) return sv_set_error(ctx, SVGPU_ERR_CAPACITY, "unit scratch too small");
+    Arena A(scratch, scratch_bytes);
+    UnitScratch S;
+    lay_units(A, (size_t)num_pairs, (size_t)unit_cap, S);
+    if (A.overflow) return sv_set_error(ctx, SVGPU_ERR_CAPACITY, "unit scratch too small");
+    int *const uid = S.uid, *const scan_scr = S.scan_scr, *const unit_off = S.unit_off, *const unit_blk = S.unit_blk, *const hist = S.sort.hist;
+    unsigned** const keys = S.sort.keys;
+    unsigned long long** const vals = S.sort.vals;
     const dim3 b(256), gq((num_pairs + 255) / 256);
     hipLaunchKernelGGL(k_unit_mark_chunk, gq, b, 0, s, pair_l_dev, num_pairs, chunk_shift, uid);
     hipLaunchKernelGGL(k_unit_mark_blk, dim3((NB + 255) / 256), b, 0, s, blk_off_dev, NB, num_pairs, uid);
@@ -494,21 +529,19 @@ extern "C" int svgpu_selftest_scan_sort(svgpu_ctx* ctx, int n, const int32_t* va
     }
     hipStream_t s = ctx->stream;
     const size_t N = (size_t)n;
-    const size_t bytes = pad256((N + 2) * 4) + pad256(sv_scan_scratch_ints(N + 1) * 4 + 64) + 2 * pad256(N * 4) + 2 * pad256(N * 8) + pad256(sv_sort_hist_ints(N) * 4) + pad256(N * 4) + 4096;
-    int rc = sv_ensure_scratch(ctx, bytes);
-    if (rc) return rc;
-    char* p = (char*)ctx->d_scratch;
-    auto take = [&](size_t b) {
-        char* r = p;
-        p += pad256(b);
-        return (void*)r;
+    int *d_scan, *d_scan_scr, *d_idx;
+    SortScratch S;
+    auto layout = [&](Arena& A) {
+        d_scan = A.take<int>(N + 2);
+        d_scan_scr = A.take<int>(sv_scan_scratch_ints(N + 1) + 16);
+        lay_sort(A, N, S);
+        d_idx = A.take<int>(N);
     };
-    int* d_scan = (int*)take((N + 2) * 4);
-    int* d_scan_scr = (int*)take(sv_scan_scratch_ints(N + 1) * 4 + 64);
-    unsigned* k2[2] = {(unsigned*)take(N * 4), (unsigned*)take(N * 4)};
-    unsigned long long* v2[2] = {(unsigned long long*)take(N * 8), (unsigned long long*)take(N * 8)};
-    int* hist = (int*)take(sv_sort_hist_ints(N) * 4);
-    int* d_idx = (int*)take(N * 4);
+    int rc = sv_scratch_layout(ctx, "svgpu_selftest_scan_sort: internal arena overflow", layout);
+    if (rc) return rc;
+    unsigned** const k2 = S.keys;
+    unsigned long long** const v2 = S.vals;
+    int* const hist = S.hist;
     if (scan_out) {
         SV_HIP(ctx, hipMemcpyAsync(d_scan, values, N * 4, hipMemcpyHostToDevice, s));
         sv_scan_i32(s, d_scan, n, d_scan_scr);

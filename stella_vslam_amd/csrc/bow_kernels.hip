@@ -19,7 +19,6 @@ struct svgpu_vocabulary {
 
 namespace {
 
-inline size_t pad(size_t bytes) { return (bytes + 255) & ~size_t(255); }
 
 __global__ void __launch_bounds__(256) k_bow_descend(int n, const uint32_t* __restrict__ desc, const int32_t* __restrict__ child_off,
                                                      const int32_t* __restrict__ children, const uint32_t* __restrict__ node_desc,
@@ -126,19 +125,21 @@ int svgpu_bow_vocabulary_upload(svgpu_ctx* ctx, int n_nodes, const int32_t* chil
     if (!V) return SVGPU_ERR_INVALID;
     V->device = ctx->device;
     V->n_nodes = n_nodes;
-    const size_t bytes = pad((size_t)(n_nodes + 1) * 4) + pad((size_t)(n_children + 1) * 4) + pad((size_t)n_nodes * 32) + 2 * pad((size_t)n_nodes * 4);
+    auto layout = [&](Arena& A) {  // one allocation; child_off is its base (svgpu_bow_vocabulary_free)
+        V->child_off = A.take<int32_t>(n_nodes + 1);
+        V->children = A.take<int32_t>(n_children + 1);
+        V->node_desc = A.take<uint32_t>((size_t)n_nodes * 8);
+        V->node_weight = A.take<float>(n_nodes);
+        V->word_id = A.take<int32_t>(n_nodes);
+    };
+    const size_t bytes = arena_measure(layout);
     char* base = nullptr;
     if (hipMalloc(&base, bytes) != hipSuccess) {
         delete V;
         return sv_set_error(ctx, SVGPU_ERR_HIP, "svgpu_bow_vocabulary_upload: hipMalloc");
     }
-    size_t off = 0;
-    auto take = [&](size_t b) { char* p = base + off; off += pad(b); return p; };
-    V->child_off = (int32_t*)take((size_t)(n_nodes + 1) * 4);
-    V->children = (int32_t*)take((size_t)(n_children + 1) * 4);
-    V->node_desc = (uint32_t*)take((size_t)n_nodes * 32);
-    V->node_weight = (float*)take((size_t)n_nodes * 4);
-    V->word_id = (int32_t*)take((size_t)n_nodes * 4);
+    Arena A(base, bytes);
+    layout(A);
     hipStream_t s = ctx->stream;
     hipError_t e = hipMemcpyAsync(V->child_off, child_off, (size_t)(n_nodes + 1) * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess && n_children) e = hipMemcpyAsync(V->children, children, (size_t)n_children * 4, hipMemcpyHostToDevice, s);
@@ -180,13 +181,17 @@ static int bow_transform_impl(svgpu_ctx* ctx, const svgpu_vocabulary* vocab, con
     if (n == 0) return SVGPU_OK;
     SV_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    int rc = sv_ensure_scratch(ctx, pad((size_t)n * 32) + 3 * pad((size_t)n * 4) + 256);
+    uint32_t* d_desc;
+    int32_t *d_word, *d_node;
+    float* d_w;
+    auto layout = [&](Arena& A) {
+        d_desc = A.take<uint32_t>((size_t)n * 8);
+        d_word = A.take<int32_t>(n);
+        d_w = A.take<float>(n);
+        d_node = A.take<int32_t>(n);
+    };
+    int rc = sv_scratch_layout(ctx, "svgpu_bow_transform: internal arena overflow", layout);
     if (rc) return rc;
-    char* base = (char*)ctx->d_scratch;
-    uint32_t* d_desc = (uint32_t*)base;
-    int32_t* d_word = (int32_t*)(base + pad((size_t)n * 32));
-    float* d_w = (float*)((char*)d_word + pad((size_t)n * 4));
-    int32_t* d_node = (int32_t*)((char*)d_w + pad((size_t)n * 4));
     SV_HIP(ctx, hipMemcpyAsync(d_desc, desc, (size_t)n * 32, hipMemcpyHostToDevice, s));
     if (fbow_k > 0) {
         int nbits = 0;

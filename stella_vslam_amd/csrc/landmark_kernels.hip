@@ -12,8 +12,6 @@
 
 namespace {
 
-inline size_t pad(size_t bytes) { return (bytes + 255) & ~size_t(255); }
-
 __global__ void __launch_bounds__(256) k_lm_owner(int n, const int32_t* __restrict__ obs_off, int32_t* __restrict__ owner) {
     const int l = blockIdx.x * 256 + threadIdx.x;
     if (l >= n) return;
@@ -94,17 +92,6 @@ __global__ void __launch_bounds__(256) k_lm_geometry(int n, const int32_t* __res
     min_d[l] = mx * inv_sf_last;
 }
 
-struct Bump {
-    char* base;
-    size_t off = 0;
-    template <class T>
-    T* take(size_t n) {
-        T* r = (T*)(base + off);
-        off += pad(n * sizeof(T));
-        return r;
-    }
-};
-
 int check_csr(svgpu_ctx* ctx, const char* who, int n, const int32_t* obs_off, bool need_one) {
     if (!ctx || n < 0 || (n > 0 && !obs_off)) return sv_set_error(ctx, SVGPU_ERR_INVALID, who);
     if (n == 0) return SVGPU_OK;
@@ -126,15 +113,18 @@ int svgpu_landmarks_compute_descriptor(svgpu_ctx* ctx, int n, const int32_t* obs
     const int total = obs_off[n];
     SV_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    rc = sv_ensure_scratch(ctx, pad((size_t)(n + 1) * 4) + pad((size_t)total * 32) + pad((size_t)total * 4) + pad((size_t)total * 2) + pad((size_t)n * 4) + pad((size_t)n * 32) + 256);
-    if (rc) return rc;
-    Bump A{(char*)ctx->d_scratch};
-    int32_t* d_off = A.take<int32_t>(n + 1);
-    uint4* d_desc = A.take<uint4>((size_t)total * 2);
-    int32_t* d_owner = A.take<int32_t>(total);
-    uint16_t* d_med = A.take<uint16_t>(total);
-    int32_t* d_best = A.take<int32_t>(n);
-    uint4* d_out = A.take<uint4>((size_t)n * 2);
+    int32_t *d_off, *d_owner, *d_best;
+    uint4 *d_desc, *d_out;
+    uint16_t* d_med;
+    auto layout = [&](Arena& A) {
+        d_off = A.take<int32_t>(n + 1);
+        d_desc = A.take<uint4>((size_t)total * 2);
+        d_owner = A.take<int32_t>(total);
+        d_med = A.take<uint16_t>(total);
+        d_best = A.take<int32_t>(n);
+        d_out = A.take<uint4>((size_t)n * 2);
+    };
+    if ((rc = sv_scratch_layout(ctx, "svgpu_landmarks_compute_descriptor: internal arena overflow", layout))) return rc;
     SV_HIP(ctx, hipMemcpyAsync(d_off, obs_off, (size_t)(n + 1) * 4, hipMemcpyHostToDevice, s));
     SV_HIP(ctx, hipMemcpyAsync(d_desc, obs_desc, (size_t)total * 32, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_lm_owner, dim3((n + 255) / 256), dim3(256), 0, s, n, d_off, d_owner);
@@ -157,17 +147,20 @@ int svgpu_landmarks_update_geometry(svgpu_ctx* ctx, int n, const int32_t* obs_of
         return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_landmarks_update_geometry: null pointer");
     SV_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    rc = sv_ensure_scratch(ctx, pad((size_t)(n + 1) * 4) + pad((size_t)total * 24 + 8) + 3 * pad((size_t)n * 24) + 3 * pad((size_t)n * 4) + 256);
-    if (rc) return rc;
-    Bump A{(char*)ctx->d_scratch};
-    int32_t* d_off = A.take<int32_t>(n + 1);
-    double* d_c = A.take<double>((size_t)total * 3 + 1);
-    double* d_p = A.take<double>((size_t)n * 3);
-    double* d_r = A.take<double>((size_t)n * 3);
-    double* d_m = A.take<double>((size_t)n * 3);
-    float* d_sf = A.take<float>(n);
-    float* d_mx = A.take<float>(n);
-    float* d_mn = A.take<float>(n);
+    int32_t* d_off;
+    double *d_c, *d_p, *d_r, *d_m;
+    float *d_sf, *d_mx, *d_mn;
+    auto layout = [&](Arena& A) {
+        d_off = A.take<int32_t>(n + 1);
+        d_c = A.take<double>((size_t)total * 3 + 1);
+        d_p = A.take<double>((size_t)n * 3);
+        d_r = A.take<double>((size_t)n * 3);
+        d_m = A.take<double>((size_t)n * 3);
+        d_sf = A.take<float>(n);
+        d_mx = A.take<float>(n);
+        d_mn = A.take<float>(n);
+    };
+    if ((rc = sv_scratch_layout(ctx, "svgpu_landmarks_update_geometry: internal arena overflow", layout))) return rc;
     SV_HIP(ctx, hipMemcpyAsync(d_off, obs_off, (size_t)(n + 1) * 4, hipMemcpyHostToDevice, s));
     if (total > 0) SV_HIP(ctx, hipMemcpyAsync(d_c, obs_trans_wc, (size_t)total * 24, hipMemcpyHostToDevice, s));
     SV_HIP(ctx, hipMemcpyAsync(d_p, pos_w, (size_t)n * 24, hipMemcpyHostToDevice, s));

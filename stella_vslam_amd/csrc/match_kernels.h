@@ -148,7 +148,6 @@ struct StereoProblem {
     int32_t* row_fill;   // pairs x rows
     int32_t* row_items;  // pairs x nr (cap) x rows_per_kp
 };
-size_t sv_stereo_rows_bytes(int pairs, int rows, int nr_cap, int rows_per_kp);  // scratch for the three arrays above
 void sv_launch_stereo(svgpu_ctx* ctx, hipStream_t s, const StereoProblem& P, int pairs = 1);
 void sv_launch_stereo_median(hipStream_t s, const StereoProblem& P, int pairs);  // 2 x median correlation filter (stereo.cc:94-113) on the device
 

@@ -1729,10 +1729,6 @@ __global__ __launch_bounds__(1024) void k_stereo_median(StereoProblem P) {
 
 }  // namespace
 
-size_t sv_stereo_rows_bytes(int pairs, int rows, int nr_cap, int rows_per_kp) {
-    auto pad = [](size_t b) { return (b + 255) & ~size_t(255); };
-    return pad((size_t)pairs * (rows + 1) * 4) + pad((size_t)pairs * rows * 4) + pad((size_t)pairs * nr_cap * rows_per_kp * 4) + 256;
-}
 void sv_launch_stereo(svgpu_ctx* ctx, hipStream_t s, const StereoProblem& P, int pairs) {
     SvProfScope ps(ctx, s, "k_stereo");
     const int nl = P.nl_dev ? P.cap : P.nl, nr = P.nl_dev ? P.cap : P.nr;

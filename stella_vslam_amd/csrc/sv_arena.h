@@ -1,0 +1,35 @@
+// The scratch arena: a bump allocator of 256-byte aligned pieces.  A layout is described ONCE, as a function of an Arena&, and run twice:
+// on a measuring arena (no base) whose `off` is then the byte count to ask sv_ensure_scratch / sv_ensure_stage for, and on the placing
+// arena over the buffer that call returned.  Plain C++ (no HIP): the same header is compiled by the host-only tests.
+#pragma once
+#include <cstddef>
+
+inline size_t pad(size_t bytes) { return (bytes + 255) & ~size_t(255); }
+
+struct Arena {
+    char* base = nullptr;
+    size_t cap = 0, off = 0;
+    bool overflow = false;  // placing: a piece would have ended beyond `cap` (checked once, after the layout)
+    Arena() = default;      // measuring: take() only advances `off`; what it returns is null and must not reach a launch or a copy
+    Arena(void* p, size_t capacity) : base((char*)p), cap(capacity) {}
+    bool measuring() const { return !base; }
+    template <class T>
+    T* take(size_t n) {
+        const size_t o = off;
+        off += pad(n * sizeof(T));
+        if (!base) return nullptr;
+        if (off > cap) {
+            overflow = true;
+            return nullptr;
+        }
+        return (T*)(base + o);
+    }
+};
+
+// bytes a layout takes: the layout run on a measuring arena (A: Arena or a type layered on it)
+template <class A = Arena, class Layout>
+size_t arena_measure(Layout&& layout) {
+    A m;
+    layout(m);
+    return m.off;
+}

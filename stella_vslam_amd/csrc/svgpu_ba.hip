@@ -52,19 +52,6 @@ int sv_ba_build_pose_lists(svgpu_ctx* ctx, hipStream_t s, const int* e_pose_dev,
 
 namespace {
 
-struct Arena {
-    char* base;
-    size_t off = 0;
-    explicit Arena(void* p) : base((char*)p) {}
-    template <class T>
-    T* take(size_t n) {
-        T* r = (T*)(base + off);
-        off += (n * sizeof(T) + 255) & ~size_t(255);
-        return r;
-    }
-};
-inline size_t pad(size_t b) { return (b + 255) & ~size_t(255); }
-
 struct HostStructure {
     std::vector<int> pose_slot, slot_pose;
     std::vector<uint8_t> pt_free;
@@ -240,38 +227,57 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
     //      poses | points | intrinsics | e_pose | e_point | e_uvr | e_w | e_huber | e_robust | lm_off | pe_off | pe_idx.  The observations
     //      are written sorted by landmark (stable; a plain copy when they arrive that way): landmark-major kernels then read
     //      contiguous runs.  pe_* = pose -> edge lists.  Behind it, the output block's host image.
-    struct {
+    // The offsets come from the description that later places the device arrays (lay_in / lay_out, run here on a measuring arena).
+    struct InBlock {
         size_t pose, points, intr, e_pose, e_point, e_uvr, e_w, e_hub, robust, lm_off, pe_off, pe_idx, total;
     } in;
-    {
-        size_t o = 0;
-        auto put = [&](size_t bytes) {
-            const size_t r = o;
-            o += pad(bytes);
-            return r;
-        };
-        in.pose = put(sizeof(double) * 12 * (size_t)P);
-        in.points = put(sizeof(double) * 3 * (size_t)L);
-        in.intr = put(sizeof(double) * 5 * (size_t)P);
-        in.e_pose = put(4 * (size_t)E);
-        in.e_point = put(4 * (size_t)E);
-        in.e_uvr = put(12 * (size_t)E);
-        in.e_w = put(4 * (size_t)E);
-        in.e_hub = put(4 * (size_t)E);
-        in.robust = put(E);
-        in.lm_off = put(4 * (size_t)(L + 1));
-        in.pe_off = put(4 * (size_t)(P + 1));
-        in.pe_idx = put(4 * (size_t)E);
-        in.total = o;
-    }
+    struct OutBlock {  // control block | poses | points | outlier flags
+        size_t ctl, state, outlier, total;
+    } out;
+    double *d_pose0 = nullptr, *d_pt0 = nullptr, *d_intr = nullptr, *d_state_out = nullptr;
+    int *d_e_pose = nullptr, *d_e_point = nullptr, *d_lm_off = nullptr, *d_pe_off = nullptr, *d_pe_idx = nullptr;
+    float *d_e_uvr = nullptr, *d_e_w = nullptr, *d_e_hub = nullptr;
+    uint8_t *d_e_robust = nullptr, *d_outlier = nullptr;
+    BaCtl* d_ctl = nullptr;
+    auto lay_in = [&](Arena& A, InBlock& o) {
+        const size_t o0 = A.off;
+        o.pose = A.off - o0, d_pose0 = A.take<double>(12 * (size_t)P);
+        o.points = A.off - o0, d_pt0 = A.take<double>(3 * (size_t)L);
+        o.intr = A.off - o0, d_intr = A.take<double>(5 * (size_t)P);
+        o.e_pose = A.off - o0, d_e_pose = A.take<int>(E);
+        o.e_point = A.off - o0, d_e_point = A.take<int>(E);
+        o.e_uvr = A.off - o0, d_e_uvr = A.take<float>(3 * (size_t)E);
+        o.e_w = A.off - o0, d_e_w = A.take<float>(E);
+        o.e_hub = A.off - o0, d_e_hub = A.take<float>(E);
+        o.robust = A.off - o0, d_e_robust = A.take<uint8_t>(E);
+        o.lm_off = A.off - o0, d_lm_off = A.take<int>(L + 1);
+        o.pe_off = A.off - o0, d_pe_off = A.take<int>(P + 1);
+        o.pe_idx = A.off - o0, d_pe_idx = A.take<int>(E);
+        o.total = A.off - o0;
+    };
+    auto lay_out = [&](Arena& A, OutBlock& o) {
+        const size_t o0 = A.off;
+        o.ctl = A.off - o0, d_ctl = (BaCtl*)A.take<char>(sizeof(BaCtl));
+        o.state = A.off - o0, d_state_out = A.take<double>(12 * (size_t)P + 3 * (size_t)L);
+        o.outlier = A.off - o0, d_outlier = A.take<uint8_t>(E + 1);
+        o.total = A.off - o0;
+    };
     // structure block (host image only; its pieces go to separate device arrays): pt_free | pose_slot | slot_pose | blk_ab, prow_off, diag | prow_ent
     const size_t nb_cap_h = (size_t)P * (P + 1) / 2;
-    const size_t st_pt_free = 0, st_pose_slot = pad(L), st_pe = st_pose_slot + pad(4 * (size_t)P), st_blk = st_pe + pad(4 * (size_t)P);
-    const size_t st_prow = st_blk + pad(8 * nb_cap_h + 4 * (2 * (size_t)P + 2)), st_total = st_prow + pad(8 * 2 * (nb_cap_h + 1));
-    const size_t out_ctl = 0, out_state = pad(sizeof(BaCtl)), out_outlier = out_state + pad(sizeof(double) * (12 * (size_t)P + 3 * (size_t)L));
-    const size_t out_total = out_outlier + pad((size_t)E + 1);
+    size_t st_pt_free, st_pose_slot, st_pe, st_blk, st_prow;
+    const size_t stage_total = arena_measure([&](Arena& M) {  // the whole host image: input block | output block | structure block
+        lay_in(M, in);
+        lay_out(M, out);
+        const size_t o0 = M.off;
+        st_pt_free = M.off - o0, M.take<char>(L);
+        st_pose_slot = M.off - o0, M.take<char>(4 * (size_t)P);
+        st_pe = M.off - o0, M.take<char>(4 * (size_t)P);
+        st_blk = M.off - o0, M.take<char>(8 * nb_cap_h + 4 * (2 * (size_t)P + 2));
+        st_prow = M.off - o0, M.take<char>(8 * 2 * (nb_cap_h + 1));
+    });
+    const size_t out_ctl = out.ctl, out_state = out.state, out_outlier = out.outlier, out_total = out.total;
     {
-        const int r = sv_ensure_stage(ctx, in.total + out_total + st_total);
+        const int r = sv_ensure_stage(ctx, stage_total);
         if (r) {
             if (team_sized) memcpy(points_out, pr->points, sizeof(double) * 3 * (size_t)L);
             return r;
@@ -551,17 +557,6 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
     const size_t nparts_max = (size_t)(P + 3) / 4 + 1;
     // the dense matrix of the tiled LL^T (ba_dense_tiled.hip): on request, and as a candidate of AUTO for windows of 24 - 256 keyframes on one rank
     const bool want_dense = solver_opt == SV_BA_SOLVER_DENSE || (solver_opt == SV_BA_SOLVER_AUTO && !sharded && P >= 24 && P <= 256 && !std::getenv("SVGPU_BA_NO_DENSE_TILED"));
-    size_t need = 4 * pad(sizeof(double) * 12 * P) + 4 * pad(sizeof(double) * 3 * L) + 2 * pad(4 * (size_t)E) + pad(12 * (size_t)E)
-                  + 2 * pad(4 * (size_t)E) + 2 * pad(E) + pad(8 * (size_t)E) + pad(40 * (size_t)P) + pad(4 * (size_t)P) + pad(L)
-                  + pad(4 * (size_t)(L + 1)) + pad(4 * (size_t)(P + 1)) + pad(4 * (size_t)E) + pad(sizeof(double) * 18 * E)
-                  + pad(sizeof(double) * 27 * 16 * (size_t)P) + pad(sizeof(double) * 36 * sc_part_blocks) + pad(sizeof(double) * 6 * 16 * (size_t)P)
-                  + pad(sizeof(double) * 6 * L) + pad(sizeof(double) * 3 * L) + pad(sizeof(double) * 36 * P)
-                  + pad(sizeof(double) * 6 * P) + pad(sizeof(double) * (36 * nb_cap + 6 * (size_t)P + 8)) + pad(sizeof(double) * nmax)
-                  + (want_dense ? pad(sizeof(double) * ((size_t)(nmax + 1) * nmax + (size_t)(nmax / 48 + 1) * 48 * 48)) : 0)
-                  + pad(sizeof(double) * (nb_chi + nb_lm + nb_pose + 8)) + pad(E + 1) + pad(8 * 42 * (size_t)P)
-                  + pad(8 * (size_t)(64 + world + 1)) + pad(8 * xch_doubles) + pad(sizeof(BaCtl))
-                  + pad(4 * (size_t)(P + 1)) + pad(8 * 2 * (nb_cap + 1)) + pad(4 * (size_t)P) + pad(8 * 36 * (size_t)P) + pad(8 * 6 * (size_t)nmax + 64)
-                  + pad(8 * 2 * (size_t)nmax + 64) + pad(8 * 2 * 4 * nparts_max) + pad(64) + 8192;
     // the solve's own landmark numbering (ba_pairs.hip): one stage, the host team's sizes, observations grouped by landmark
     // (a sharded solve renumbers the landmarks of ITS shard: the numbering is private to the rank's kernels, every landmark-sized exchange
     //  between ranks -- ownership marks, the final positions -- stays in the caller's numbering)
@@ -570,13 +565,6 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
     const size_t unit_cap = chunk_units ? sc_part_blocks : 0;
     const size_t pair_scratch = std::max(std::max(std::max(sv_ba_pairs_scratch_bytes(pair_cap, E, nb_cap), sv_ba_pose_lists_scratch_bytes((size_t)E)), renumber ? sv_ba_renumber_scratch_bytes((size_t)L) : 0),
                                          chunk_units ? sv_ba_units_scratch_bytes(pair_cap, unit_cap) : 0);
-    if (chunk_units) need += pad(16 * unit_cap) + pad(4 * (nb_cap + 2)) + pad(48 * unit_cap) + 1024;
-    if (renumber) need += 3 * pad(4 * (size_t)E) + pad(12 * (size_t)E) + 2 * pad(4 * (size_t)E) + pad(4 * (size_t)(L + 1)) + pad(4 * (size_t)L) + pad(24 * (size_t)L) + pad(L) + 4096;
-    need += pad(4 * (nb_cap + (size_t)P)) + pad(P) + pad(L);  // keyframe-segment exchange: block / slot lists, damping owners
-    need += pad(8 * pair_cap) + pad(8 * nb_cap) + pad(4 * (nb_cap + 1)) + pad(pair_scratch) + in.total + out_total + 3 * pad(4 * (size_t)E) + pad(12 * (size_t)E) + pad(8 * (size_t)nb_lm) + pad(4 * pair_cap) + pad(64 * (size_t)nb_lm);
-    int rc = sv_ensure_scratch(ctx, need);
-    if (rc) return rc;
-    Arena A(ctx->d_scratch);
     BaDev D;
     memset(&D, 0, sizeof(D));
     D.P = P;
@@ -584,74 +572,17 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
     D.E = E;
     D.world = world;
     D.rank = rank;
-    // input block (same layout as the staging buffer)
-    D.pose_buf[0] = A.take<double>(12 * (size_t)P);
-    D.pt_buf[0] = A.take<double>(3 * (size_t)L);
-    double* d_intr = A.take<double>(5 * (size_t)P);
-    int* d_e_pose = A.take<int>(E);
-    int* d_e_point = A.take<int>(E);
-    float* d_e_uvr = A.take<float>(3 * (size_t)E);
-    float* d_e_w = A.take<float>(E);
-    float* d_e_hub = A.take<float>(E);
-    D.e_robust = A.take<uint8_t>(E);
-    int* d_lm_off = A.take<int>(L + 1);
-    int* d_pe_off = A.take<int>(P + 1);
-    int* d_pe_idx = A.take<int>(E);
-    if (A.off != in.total) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_local_ba: internal layout mismatch");
-    // output block: control block | poses | points | outlier flags
-    char* const d_out = A.base + A.off;
-    D.ctl = (BaCtl*)A.take<char>(sizeof(BaCtl));
-    double* d_state_out = A.take<double>(12 * (size_t)P + 3 * (size_t)L);
-    uint8_t* d_outlier = A.take<uint8_t>(E + 1);
-    D.pose_buf[1] = A.take<double>(12 * (size_t)P);
-    D.pt_buf[1] = A.take<double>(3 * (size_t)L);
-    D.e_level = A.take<uint8_t>(E);
-    D.e_chi = A.take<double>(E);
-    int* d_pose_slot = A.take<int>(P);
-    uint8_t* d_pt_free = A.take<uint8_t>(L);
-    int* d_slot_pose = A.take<int>(P);
-    D.W = A.take<double>(18 * (size_t)E);
-    D.lp_part = A.take<double>(27 * 16 * (size_t)P);
-    D.sc_part = A.take<double>(36 * sc_part_blocks);
-    D.rhs_part = A.take<double>(6 * 16 * (size_t)P);
-    D.Hll = A.take<double>(6 * (size_t)L);
-    D.bl = A.take<double>(3 * (size_t)L);
-    D.Hpp = A.take<double>(36 * (size_t)P);
-    D.bp = A.take<double>(6 * (size_t)P);
-    D.Sblk = A.take<double>(36 * nb_cap + 6 * (size_t)P + 8);
-    D.S = want_dense ? A.take<double>((size_t)(nmax + 1) * nmax + (size_t)(nmax / 48 + 1) * 48 * 48) : nullptr;  // (+ the inverted diagonal tiles of ba_dense_tiled.hip)
-    D.dp = A.take<double>(nmax);
-    D.red = A.take<double>(nb_chi + nb_lm + nb_pose + 8);
-    D.lm_max = A.take<double>(nb_lm);  // nb_lm == sv_ba_lm_blocks(L)
     static const bool dbg_stamps = std::getenv("SVGPU_BA_DBG") != nullptr;
     static const bool dbg_schur = dbg_stamps && !strcmp(std::getenv("SVGPU_BA_DBG"), "schur");
     static const bool dbg_chol = dbg_stamps && !strcmp(std::getenv("SVGPU_BA_DBG"), "chol");
     D.dbg_schur_on = dbg_schur ? 1 : (dbg_chol ? 2 : 0);
-    D.dbg = dbg_stamps ? A.take<unsigned long long>(8 * (dbg_schur ? sc_part_blocks + 64 : (size_t)nb_lm)) : nullptr;
-    double* d_HB_full = A.take<double>(42 * (size_t)P + (size_t)std::max(64, world));     // sharded: Hpp | bp summed over ranks | one slot per rank: its landmarks' largest diagonal (computeLambdaInit)
-    double* d_sc = A.take<double>(64 + (size_t)world);            // sharded: [0..3] per-trial sums, [8..8+world) lambda-init slots
-    double* d_xch = A.take<double>(xch_doubles);                  // sharded: pose-activity / block-presence / point exchange
-    int* d_prow_off = A.take<int>(P + 1);
-    int2* d_prow_ent = A.take<int2>(2 * (nb_cap + 1));
-    int* d_diag_blk = A.take<int>(P);
-    D.pcg_Minv = A.take<double>(36 * (size_t)P);
-    D.pcg_rws = A.take<double>(6 * (size_t)nmax + 8);
-    D.pcg_own = A.take<double>(2 * (size_t)nmax + 8);
-    D.pcg_parts = A.take<double>(2 * 4 * nparts_max);
-    D.pcg_scal = A.take<double>(8);
-    int* d_pm_point = A.take<int>(E);
-    float* d_pm_uvr = A.take<float>(3 * (size_t)E);
-    float* d_pm_w = A.take<float>(E);
-    float* d_pm_hub = A.take<float>(E);
-    int2* d_blk_pairs = A.take<int2>(pair_cap);
-    int* d_blk_pair_l = A.take<int>(pair_cap);
-    int2* d_blk_ab = A.take<int2>(nb_cap);
-    int* d_blk_off = A.take<int>(nb_cap + 1);
-    char* d_pair_scratch = A.take<char>(pair_scratch);
-    int* d_xs_idx = A.take<int>(nb_cap + (size_t)P);
-    uint8_t* d_lam_slot = A.take<uint8_t>(P);
-    uint8_t* d_any_owner = A.take<uint8_t>(L);  // sharded: the landmark has observations on some rank
-    D.any_owner = d_any_owner;
+    // ---- the device arena, described once: measured for sv_ensure_scratch, then placed
+    int *d_pose_slot, *d_slot_pose, *d_prow_off, *d_diag_blk, *d_pm_point, *d_blk_pair_l, *d_blk_off, *d_xs_idx;
+    uint8_t *d_pt_free, *d_lam_slot, *d_any_owner;
+    double *d_HB_full, *d_sc, *d_xch;
+    int2 *d_prow_ent, *d_blk_pairs, *d_blk_ab;
+    float *d_pm_uvr, *d_pm_w, *d_pm_hub;
+    char* d_pair_scratch;
     // renumbered solve: the uploaded arrays (caller's order) are the sources, these the arrays the kernels read
     int *rn_e_pose = nullptr, *rn_e_point = nullptr, *rn_src = nullptr, *rn_lm_off = nullptr, *rn_order = nullptr;
     float *rn_uvr = nullptr, *rn_w = nullptr, *rn_hub = nullptr;
@@ -660,19 +591,80 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
     int4* d_unit_rec = nullptr;
     int* d_blk_unit_off = nullptr;
     double* d_rhs_unit = nullptr;
-    if (chunk_units) {
-        d_unit_rec = A.take<int4>(unit_cap);
-        d_blk_unit_off = A.take<int>(nb_cap + 2);
-        d_rhs_unit = A.take<double>(6 * unit_cap);
-    }
-    if (renumber) {
-        rn_e_pose = A.take<int>(E), rn_e_point = A.take<int>(E), rn_src = A.take<int>(E);
-        rn_uvr = A.take<float>(3 * (size_t)E), rn_w = A.take<float>(E), rn_hub = A.take<float>(E);
-        rn_lm_off = A.take<int>(L + 1), rn_order = A.take<int>(L);
-        rn_pts = A.take<double>(3 * (size_t)L);
-        rn_pt_free_in = A.take<uint8_t>(L);
-    }
-    if (A.off > ctx->scratch_bytes) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_local_ba: internal arena overflow");
+    InBlock in_placed;
+    auto layout = [&](Arena& A) {
+        lay_in(A, in_placed);  // input block (same layout as the staging buffer)
+        OutBlock out_placed;
+        lay_out(A, out_placed);  // output block: control block | poses | points | outlier flags
+        D.pose_buf[1] = A.take<double>(12 * (size_t)P);
+        D.pt_buf[1] = A.take<double>(3 * (size_t)L);
+        D.e_level = A.take<uint8_t>(E);
+        D.e_chi = A.take<double>(E);
+        d_pose_slot = A.take<int>(P);
+        d_pt_free = A.take<uint8_t>(L);
+        d_slot_pose = A.take<int>(P);
+        D.W = A.take<double>(18 * (size_t)E);
+        D.lp_part = A.take<double>(27 * 16 * (size_t)P);
+        D.sc_part = A.take<double>(36 * sc_part_blocks);
+        D.rhs_part = A.take<double>(6 * 16 * (size_t)P);
+        D.Hll = A.take<double>(6 * (size_t)L);
+        D.bl = A.take<double>(3 * (size_t)L);
+        D.Hpp = A.take<double>(36 * (size_t)P);
+        D.bp = A.take<double>(6 * (size_t)P);
+        D.Sblk = A.take<double>(36 * nb_cap + 6 * (size_t)P + 8);
+        D.S = want_dense ? A.take<double>((size_t)(nmax + 1) * nmax + (size_t)(nmax / 48 + 1) * 48 * 48) : nullptr;  // (+ the inverted diagonal tiles of ba_dense_tiled.hip)
+        D.dp = A.take<double>(nmax);
+        D.red = A.take<double>(nb_chi + nb_lm + nb_pose + 8);
+        D.lm_max = A.take<double>(nb_lm);  // nb_lm == sv_ba_lm_blocks(L)
+        D.dbg = dbg_stamps ? A.take<unsigned long long>(8 * (dbg_schur ? sc_part_blocks + 64 : (size_t)nb_lm)) : nullptr;
+        d_HB_full = A.take<double>(42 * (size_t)P + (size_t)std::max(64, world));     // sharded: Hpp | bp summed over ranks | one slot per rank: its landmarks' largest diagonal (computeLambdaInit)
+        d_sc = A.take<double>(64 + (size_t)world);            // sharded: [0..3] per-trial sums, [8..8+world) lambda-init slots
+        d_xch = A.take<double>(xch_doubles);                  // sharded: pose-activity / block-presence / point exchange
+        d_prow_off = A.take<int>(P + 1);
+        d_prow_ent = A.take<int2>(2 * (nb_cap + 1));
+        d_diag_blk = A.take<int>(P);
+        D.pcg_Minv = A.take<double>(36 * (size_t)P);
+        D.pcg_rws = A.take<double>(6 * (size_t)nmax + 8);
+        D.pcg_own = A.take<double>(2 * (size_t)nmax + 8);
+        D.pcg_parts = A.take<double>(2 * 4 * nparts_max);
+        D.pcg_scal = A.take<double>(8);
+        d_pm_point = A.take<int>(E);
+        d_pm_uvr = A.take<float>(3 * (size_t)E);
+        d_pm_w = A.take<float>(E);
+        d_pm_hub = A.take<float>(E);
+        d_blk_pairs = A.take<int2>(pair_cap);
+        d_blk_pair_l = A.take<int>(pair_cap);
+        d_blk_ab = A.take<int2>(nb_cap);
+        d_blk_off = A.take<int>(nb_cap + 1);
+        d_pair_scratch = A.take<char>(pair_scratch);
+        d_xs_idx = A.take<int>(nb_cap + (size_t)P);  // keyframe-segment exchange: block / slot lists, damping owners
+        d_lam_slot = A.take<uint8_t>(P);
+        d_any_owner = A.take<uint8_t>(L);  // sharded: the landmark has observations on some rank
+        if (chunk_units) {
+            d_unit_rec = A.take<int4>(unit_cap);
+            d_blk_unit_off = A.take<int>(nb_cap + 2);
+            d_rhs_unit = A.take<double>(6 * unit_cap);
+        }
+        if (renumber) {
+            rn_e_pose = A.take<int>(E), rn_e_point = A.take<int>(E), rn_src = A.take<int>(E);
+            rn_uvr = A.take<float>(3 * (size_t)E), rn_w = A.take<float>(E), rn_hub = A.take<float>(E);
+            rn_lm_off = A.take<int>(L + 1), rn_order = A.take<int>(L);
+            rn_pts = A.take<double>(3 * (size_t)L);
+            rn_pt_free_in = A.take<uint8_t>(L);
+        }
+    };
+    int rc = sv_ensure_scratch(ctx, arena_measure(layout));
+    if (rc) return rc;
+    Arena A(ctx->d_scratch, ctx->scratch_bytes);
+    layout(A);
+    if (in_placed.total != in.total) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_local_ba: internal layout mismatch");
+    if (A.overflow) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_local_ba: internal arena overflow");
+    D.pose_buf[0] = d_pose0;
+    D.pt_buf[0] = d_pt0;
+    D.e_robust = d_e_robust;
+    D.ctl = d_ctl;
+    D.any_owner = d_any_owner;
+    char* const d_out = (char*)d_ctl;
     D.e_pose = d_e_pose;
     D.e_point = d_e_point;
     D.e_uvr = d_e_uvr;
@@ -1430,27 +1422,44 @@ int svgpu_local_ba(svgpu_ctx* ctx, const svgpu_ba_problem* problem, volatile uin
     return local_ba_impl(ctx, problem, false, 0, 1, nullptr, nullptr, stop, pose_out, points_out, outlier_out, stats);
 }
 
-// Shared tail of the two pose-optimizer entry points: inputs already on the device, results come back in ONE copy
-// (pose | result[4] | outlier flags) through the page-locked staging buffer.
-static int pose_optimize_run(svgpu_ctx* ctx, Arena& A, const double* pose_cw, int n, const double* d_pos, const float* d_uvr, const float* d_w,
-                             const float* d_h, const double* intrinsics, int num_trials_robust, int num_trials, int num_each_iter,
-                             int reset_stop_flag_each_round, char* h_out, double* pose_out, uint8_t* outlier_flags, int* num_valid, int* lm_iterations) {
-    PoseOptDev P;
-    memset(&P, 0, sizeof(P));
-    char* const d_out = A.base + A.off;
+// The pose optimizer's arena, described once: with `host_inputs` the input image (pos_w | uvr | inv_sigma_sq | huber, one copy from the
+// page-locked staging buffer, same offsets there), then the output block (pose | result[4] | outlier flags, one copy back), then work flags.
+struct PoseOptLayout {
+    size_t o_pos, o_uvr, o_w, o_h, in_total;           // input image
+    size_t off_result, off_outlier, out_bytes;         // output block, relative to d_out
+    char *d_in, *d_out;
+};
+static void lay_pose_opt(Arena& A, int n, bool host_inputs, PoseOptDev& P, PoseOptLayout& Y) {
+    Y.d_in = nullptr;
+    Y.o_pos = Y.o_uvr = Y.o_w = Y.o_h = Y.in_total = 0;
+    if (host_inputs) {
+        const size_t o0 = A.off;
+        Y.o_pos = 0, P.pos_w = A.take<double>(3 * (size_t)n);
+        Y.o_uvr = A.off - o0, P.uvr = A.take<float>(3 * (size_t)n);
+        Y.o_w = A.off - o0, P.inv_sigma_sq = A.take<float>(n);
+        Y.o_h = A.off - o0, P.huber = A.take<float>(n);
+        Y.in_total = A.off - o0;
+        Y.d_in = (char*)P.pos_w;
+    }
+    const size_t o0 = A.off;
     P.pose_out = A.take<double>(12);
-    P.result = A.take<int>(4);
-    P.outlier = A.take<uint8_t>(n);
-    const size_t out_bytes = (size_t)((A.base + A.off) - d_out), off_result = pad(96), off_outlier = off_result + pad(16);
+    Y.off_result = A.off - o0, P.result = A.take<int>(4);
+    Y.off_outlier = A.off - o0, P.outlier = A.take<uint8_t>(n);
+    Y.out_bytes = A.off - o0;
+    Y.d_out = (char*)P.pose_out;
     P.level = A.take<uint8_t>(n);
     P.robust = A.take<uint8_t>(n);
-    if (A.off > ctx->scratch_bytes) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_pose_optimize: internal arena overflow");
+}
+
+// Shared tail of the two pose-optimizer entry points: arena placed, inputs already on the device (or on their way), results come back in
+// ONE copy (pose | result[4] | outlier flags) through the page-locked staging buffer.
+static int pose_optimize_run(svgpu_ctx* ctx, PoseOptDev& P, const PoseOptLayout& Y, const double* pose_cw, int n, const double* intrinsics, int num_trials_robust,
+                             int num_trials, int num_each_iter, int reset_stop_flag_each_round, char* h_out, double* pose_out, uint8_t* outlier_flags,
+                             int* num_valid, int* lm_iterations) {
+    char* const d_out = Y.d_out;
+    const size_t out_bytes = Y.out_bytes, off_result = Y.off_result, off_outlier = Y.off_outlier;
     hipStream_t s = ctx->stream;
     P.n = n;
-    P.pos_w = d_pos;
-    P.uvr = d_uvr;
-    P.inv_sigma_sq = d_w;
-    P.huber = d_h;
     memcpy(P.intr, intrinsics, sizeof(double) * 5);
     memcpy(P.pose_in, pose_cw, sizeof(double) * 12);
     P.num_trials_robust = num_trials_robust;
@@ -1484,21 +1493,22 @@ int svgpu_pose_optimize(svgpu_ctx* ctx, const double* pose_cw, int n, const doub
     if (n < 5) return SVGPU_OK;  // pose_optimizer_g2o.cc:109-111
     SV_HIP(ctx, hipSetDevice(ctx->device));
     // inputs: one page-locked image in device layout (pos_w | uvr | inv_sigma_sq | huber), one copy
-    const size_t o_uvr = pad(24 * (size_t)n), o_w = o_uvr + pad(12 * (size_t)n), o_h = o_w + pad(4 * (size_t)n), in_total = o_h + pad(4 * (size_t)n);
-    const size_t out_total = pad(96) + pad(16) + pad(n);
-    int rc = sv_ensure_scratch(ctx, in_total + out_total + 2 * pad(n) + 1024);
+    PoseOptDev P;
+    memset(&P, 0, sizeof(P));
+    PoseOptLayout Y;
+    int rc = sv_ensure_scratch(ctx, arena_measure([&](Arena& M) { lay_pose_opt(M, n, true, P, Y); }));
     if (rc) return rc;
-    if ((rc = sv_ensure_stage(ctx, in_total + out_total))) return rc;
+    if ((rc = sv_ensure_stage(ctx, Y.in_total + Y.out_bytes))) return rc;
+    Arena A(ctx->d_scratch, ctx->scratch_bytes);
+    lay_pose_opt(A, n, true, P, Y);
+    if (A.overflow) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_pose_optimize: internal arena overflow");
     char* const hs = ctx->h_stage;
-    memcpy(hs, pos_w, 24 * (size_t)n);
-    memcpy(hs + o_uvr, uvr, 12 * (size_t)n);
-    memcpy(hs + o_w, inv_sigma_sq, 4 * (size_t)n);
-    memcpy(hs + o_h, huber_delta, 4 * (size_t)n);
-    Arena A(ctx->d_scratch);
-    char* const d_in = A.take<char>(in_total);
-    SV_HIP(ctx, hipMemcpyAsync(d_in, hs, in_total, hipMemcpyHostToDevice, ctx->stream));
-    return pose_optimize_run(ctx, A, pose_cw, n, (const double*)d_in, (const float*)(d_in + o_uvr), (const float*)(d_in + o_w), (const float*)(d_in + o_h),
-                             intrinsics, num_trials_robust, num_trials, num_each_iter, reset_stop_flag_each_round, hs + in_total, pose_out,
+    memcpy(hs + Y.o_pos, pos_w, 24 * (size_t)n);
+    memcpy(hs + Y.o_uvr, uvr, 12 * (size_t)n);
+    memcpy(hs + Y.o_w, inv_sigma_sq, 4 * (size_t)n);
+    memcpy(hs + Y.o_h, huber_delta, 4 * (size_t)n);
+    SV_HIP(ctx, hipMemcpyAsync(Y.d_in, hs, Y.in_total, hipMemcpyHostToDevice, ctx->stream));
+    return pose_optimize_run(ctx, P, Y, pose_cw, n, intrinsics, num_trials_robust, num_trials, num_each_iter, reset_stop_flag_each_round, hs + Y.in_total, pose_out,
                              outlier_flags, num_valid, lm_iterations);
 }
 
@@ -1515,13 +1525,18 @@ int svgpu_pose_optimize_device(svgpu_ctx* ctx, const double* pose_cw, int n, con
     for (int i = 0; i < n; ++i) outlier_flags[i] = 0;
     if (n < 5) return SVGPU_OK;
     SV_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t out_total = pad(96) + pad(16) + pad(n);
-    int rc = sv_ensure_scratch(ctx, out_total + 2 * pad(n) + 1024);
+    PoseOptDev P;
+    memset(&P, 0, sizeof(P));
+    PoseOptLayout Y;
+    int rc = sv_ensure_scratch(ctx, arena_measure([&](Arena& M) { lay_pose_opt(M, n, false, P, Y); }));
     if (rc) return rc;
-    if ((rc = sv_ensure_stage(ctx, out_total))) return rc;
-    Arena A(ctx->d_scratch);
-    return pose_optimize_run(ctx, A, pose_cw, n, pos_w_dev, uvr_dev, inv_sigma_sq_dev, huber_delta_dev, intrinsics, num_trials_robust, num_trials,
-                             num_each_iter, reset_stop_flag_each_round, ctx->h_stage, pose_out, outlier_flags, num_valid, lm_iterations);
+    if ((rc = sv_ensure_stage(ctx, Y.out_bytes))) return rc;
+    Arena A(ctx->d_scratch, ctx->scratch_bytes);
+    lay_pose_opt(A, n, false, P, Y);
+    if (A.overflow) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_pose_optimize: internal arena overflow");
+    P.pos_w = pos_w_dev, P.uvr = uvr_dev, P.inv_sigma_sq = inv_sigma_sq_dev, P.huber = huber_delta_dev;
+    return pose_optimize_run(ctx, P, Y, pose_cw, n, intrinsics, num_trials_robust, num_trials, num_each_iter, reset_stop_flag_each_round, ctx->h_stage, pose_out,
+                             outlier_flags, num_valid, lm_iterations);
 }
 
 int svgpu_global_ba(svgpu_ctx* ctx, const svgpu_ba_problem* problem, volatile uint8_t* stop, double* pose_out, double* points_out,

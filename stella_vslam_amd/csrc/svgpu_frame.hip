@@ -9,8 +9,6 @@
 #include "match_kernels.h"
 
 namespace {
-inline size_t pad256(size_t b) { return (b + 255) & ~size_t(255); }
-
 __global__ void k_frame_split(const svgpu_keypoint* __restrict__ k, int n, float* __restrict__ xy, int32_t* __restrict__ octave, float* __restrict__ angle) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -28,29 +26,25 @@ int sv_frame_reserve(svgpu_ctx* ctx, svgpu_frame* f, int n, int ncell) {
         if (f->slab) SV_HIP(ctx, hipFree(f->slab));
         f->slab = nullptr;
         f->cap = 0;
-        size_t off = 0;
-        auto carve = [&](size_t bytes) {
-            const size_t o = off;
-            off += pad256(bytes);
-            return o;
+        auto layout = [&](Arena& A) {
+            f->kps_raw = A.take<svgpu_keypoint>(cap);
+            f->desc = A.take<uint8_t>((size_t)cap * 32);
+            f->undist = A.take<svgpu_keypoint>(cap);
+            f->bearings = A.take<double>((size_t)cap * 3);
+            f->xright = A.take<float>(cap);
+            f->depth = A.take<float>(cap);
+            f->xy = A.take<float>((size_t)cap * 2);
+            f->octave = A.take<int32_t>(cap);
+            f->angle = A.take<float>(cap);
+            f->cell_of = A.take<int32_t>(cap);
+            f->cell_items = A.take<int32_t>(cap);
+            f->counts = A.take<int32_t>(1 + SV_MAX_LEVELS);
         };
-        const size_t o_kps = carve((size_t)cap * sizeof(svgpu_keypoint)), o_desc = carve((size_t)cap * 32), o_und = carve((size_t)cap * sizeof(svgpu_keypoint)),
-                     o_brg = carve((size_t)cap * 24), o_xr = carve((size_t)cap * 4), o_dep = carve((size_t)cap * 4), o_xy = carve((size_t)cap * 8),
-                     o_oct = carve((size_t)cap * 4), o_ang = carve((size_t)cap * 4), o_cof = carve((size_t)cap * 4), o_cit = carve((size_t)cap * 4), o_cnt = carve((1 + SV_MAX_LEVELS) * 4);
-        SV_HIP(ctx, hipMalloc((void**)&f->slab, off));
-        f->slab_bytes = off;
-        f->kps_raw = (svgpu_keypoint*)(f->slab + o_kps);
-        f->desc = (uint8_t*)(f->slab + o_desc);
-        f->undist = (svgpu_keypoint*)(f->slab + o_und);
-        f->bearings = (double*)(f->slab + o_brg);
-        f->xy = (float*)(f->slab + o_xy);
-        f->octave = (int32_t*)(f->slab + o_oct);
-        f->angle = (float*)(f->slab + o_ang);
-        f->xright = (float*)(f->slab + o_xr);
-        f->depth = (float*)(f->slab + o_dep);
-        f->cell_of = (int32_t*)(f->slab + o_cof);
-        f->cell_items = (int32_t*)(f->slab + o_cit);
-        f->counts = (int32_t*)(f->slab + o_cnt);
+        const size_t bytes = arena_measure(layout);
+        SV_HIP(ctx, hipMalloc((void**)&f->slab, bytes));
+        f->slab_bytes = bytes;
+        Arena A(f->slab, bytes);
+        layout(A);
         f->cap = cap;
     }
     if (ncell + 1 > f->cells_cap) {

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "svgpu.h"
+#include "sv_arena.h"
 
 #define SV_MAX_LEVELS 16
 #define SV_PATCH_RADIUS 19  // orb_extractor.h:107 orb_patch_radius_
@@ -270,6 +271,15 @@ struct SvProfScope {  // brackets the launches issued inside its lifetime when `
 int sv_ensure_scratch(svgpu_ctx* ctx, size_t bytes);
 void sv_sky_release(svgpu_ctx* ctx);  // plan + buffers of the envelope Cholesky (ba_skyline.hip)
 int sv_ensure_stage(svgpu_ctx* ctx, size_t bytes);  // grow-only page-locked host buffer (ctx->h_stage)
+// the plain scratch user: measure the layout, grow ctx->d_scratch to it, place it there (`overflow_msg`: the error text of a failed placement)
+template <class Layout>
+int sv_scratch_layout(svgpu_ctx* ctx, const char* overflow_msg, Layout&& layout) {
+    const int rc = sv_ensure_scratch(ctx, arena_measure(layout));
+    if (rc) return rc;
+    Arena A(ctx->d_scratch, ctx->scratch_bytes);
+    layout(A);
+    return A.overflow ? sv_set_error(ctx, SVGPU_ERR_INVALID, overflow_msg) : SVGPU_OK;
+}
 hipError_t sv_allow_dynamic_lds(const void* kernel, size_t bytes);  // per (device, kernel), thread-safe
 void sv_orb_release(svgpu_ctx* ctx);
 int sv_frame_reserve(svgpu_ctx* ctx, svgpu_frame* f, int n, int ncell);  // grow-only slab of a resident frame (svgpu_frame.hip)

@@ -10,7 +10,6 @@
 static_assert(sizeof(svgpu_landmark_record) == 96, "svgpu_landmark_record is a 96-byte record");
 
 namespace {
-inline size_t pad256(size_t b) { return (b + 255) & ~size_t(255); }
 
 // staged = n records behind n ids; one thread per 16-byte piece of a record (6 per record): coalesced reads, 96-byte scattered writes.
 // Entries are applied in order of i within a launch only if no id repeats: the host collapses repeats (last wins) before the upload.
@@ -145,7 +144,7 @@ int svgpu_map_upsert(svgpu_ctx* ctx, svgpu_map* m, int n, const uint32_t* ids, c
     int rc = map_grow(ctx, m, (int)max_id + 1);
     if (rc) return rc;
     // page-locked image: ids | records, with repeated ids collapsed to their LAST entry (the scatter is unordered)
-    const size_t o_rec = pad256((size_t)n * 4), total = o_rec + (size_t)n * sizeof(svgpu_landmark_record);
+    const size_t o_rec = pad((size_t)n * 4), total = o_rec + (size_t)n * sizeof(svgpu_landmark_record);
     if ((rc = sv_ensure_stage(ctx, total))) return rc;
     if ((rc = sv_ensure_scratch(ctx, total))) return rc;
     uint32_t* h_ids = (uint32_t*)ctx->h_stage;
@@ -216,7 +215,7 @@ int svgpu_map_download(svgpu_ctx* ctx, const svgpu_map* cm, int n, const uint32_
     if (n == 0) return SVGPU_OK;
     SV_HIP(ctx, hipSetDevice(ctx->device));
     std::lock_guard<std::mutex> lock(m->mtx);
-    const size_t o_rec = pad256((size_t)n * 4), total = o_rec + (size_t)n * sizeof(svgpu_landmark_record);
+    const size_t o_rec = pad((size_t)n * 4), total = o_rec + (size_t)n * sizeof(svgpu_landmark_record);
     int rc = sv_ensure_stage(ctx, total);
     if (rc) return rc;
     if ((rc = sv_ensure_scratch(ctx, total))) return rc;

@@ -14,12 +14,14 @@ int svgpu_hamming_distance(svgpu_ctx* ctx, const uint8_t* a, const uint8_t* b, i
     if (n == 0) return SVGPU_OK;
     SV_HIP(ctx, hipSetDevice(ctx->device));
     const size_t nb = (size_t)n * 32;
-    int rc = sv_ensure_scratch(ctx, 2 * pad(nb) + pad((size_t)n * 4));
+    uint32_t *da, *db, *dd;
+    auto layout = [&](Arena& A) {
+        da = A.take<uint32_t>((size_t)n * 8);
+        db = A.take<uint32_t>((size_t)n * 8);
+        dd = A.take<uint32_t>(n);
+    };
+    int rc = sv_scratch_layout(ctx, "svgpu_hamming_distance: internal arena overflow", layout);
     if (rc) return rc;
-    Arena A(ctx->d_scratch);
-    uint32_t* da = A.take<uint32_t>((size_t)n * 8);
-    uint32_t* db = A.take<uint32_t>((size_t)n * 8);
-    uint32_t* dd = A.take<uint32_t>(n);
     hipStream_t s = ctx->stream;
     SV_HIP(ctx, hipMemcpyAsync(da, a, nb, hipMemcpyHostToDevice, s));
     SV_HIP(ctx, hipMemcpyAsync(db, b, nb, hipMemcpyHostToDevice, s));
@@ -34,12 +36,15 @@ int svgpu_hamming_matrix(svgpu_ctx* ctx, const uint8_t* desc1, int n1, const uin
     if (n1 == 0 || n2 == 0) return SVGPU_OK;
     if (!desc1 || !desc2 || !out) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_hamming_matrix: null pointer");
     SV_HIP(ctx, hipSetDevice(ctx->device));
-    int rc = sv_ensure_scratch(ctx, pad((size_t)n1 * 32) + pad((size_t)n2 * 32) + pad((size_t)n1 * n2 * 2));
+    uint32_t *d1, *d2;
+    uint16_t* dm;
+    auto layout = [&](Arena& A) {
+        d1 = A.take<uint32_t>((size_t)n1 * 8);
+        d2 = A.take<uint32_t>((size_t)n2 * 8);
+        dm = A.take<uint16_t>((size_t)n1 * n2);
+    };
+    int rc = sv_scratch_layout(ctx, "svgpu_hamming_matrix: internal arena overflow", layout);
     if (rc) return rc;
-    Arena A(ctx->d_scratch);
-    uint32_t* d1 = A.take<uint32_t>((size_t)n1 * 8);
-    uint32_t* d2 = A.take<uint32_t>((size_t)n2 * 8);
-    uint16_t* dm = A.take<uint16_t>((size_t)n1 * n2);
     hipStream_t s = ctx->stream;
     SV_HIP(ctx, hipMemcpyAsync(d1, desc1, (size_t)n1 * 32, hipMemcpyHostToDevice, s));
     SV_HIP(ctx, hipMemcpyAsync(d2, desc2, (size_t)n2 * 32, hipMemcpyHostToDevice, s));
@@ -60,12 +65,17 @@ int bf_batch_device(svgpu_ctx* ctx, int pairs, int ring1, const uint8_t* desc1_d
         || cap1 > 65535 || cap2 > 65535 || !matched_dev || !num_dev)
         return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_match_bruteforce_batch_device: bad arguments");
     SV_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t need = pad((size_t)pairs * cap2 * BF_LIST * 4) + pad((size_t)pairs * cap2 * 4) + pad((size_t)pairs * cap1 * 4)
-                        + pad((size_t)pairs * cap2 * 4) + sort_bytes(pairs, cap1, cap2);
-    int rc = sv_ensure_scratch(ctx, need);
-    if (rc) return rc;
-    Arena A(ctx->d_scratch);
     BfProblem P{};
+    int *g_owner, *g_match;
+    auto layout = [&](Arena& A) {
+        P.topk = A.take<uint32_t>((size_t)pairs * cap2 * BF_LIST);
+        P.cnt = A.take<int32_t>((size_t)pairs * cap2);
+        g_owner = A.take<int>((size_t)pairs * cap1);
+        g_match = A.take<int>((size_t)pairs * cap2);
+        take_sort(A, P, pairs, cap1, cap2);
+    };
+    int rc = sv_scratch_layout(ctx, "svgpu_match_bruteforce_batch_device: internal arena overflow", layout);
+    if (rc) return rc;
     P.desc1 = (const uint32_t*)desc1_dev;
     P.desc2 = (const uint32_t*)desc2_dev;
     if (angles1_dev && angles2_dev) {  // packed copies (svgpu_orb_extract_batch_device_angles): 4 bytes per keypoint instead of a 28-byte stride
@@ -87,11 +97,6 @@ int bf_batch_device(svgpu_ctx* ctx, int pairs, int ring1, const uint8_t* desc1_d
     P.valid2 = valid2_dev;
     P.lowe_ratio = lowe_ratio;
     P.check_orientation = check_orientation;
-    P.topk = A.take<uint32_t>((size_t)pairs * cap2 * BF_LIST);
-    P.cnt = A.take<int32_t>((size_t)pairs * cap2);
-    int* g_owner = A.take<int>((size_t)pairs * cap1);
-    int* g_match = A.take<int>((size_t)pairs * cap2);
-    take_sort(A, P, pairs, cap1, cap2);
     P.matched = matched_dev;
     P.num = num_dev;
     sv_launch_bf(ctx, stream ? (hipStream_t)stream : ctx->stream, P, pairs, g_owner, g_match);
@@ -140,29 +145,34 @@ int svgpu_match_bruteforce(svgpu_ctx* ctx, const uint8_t* desc1, const float* an
     if (!desc1 || !desc2 || (check_orientation && (!angle1 || !angle2)))
         return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_match_bruteforce: null input");
     SV_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t need = pad((size_t)n1 * 32) + pad((size_t)n2 * 32) + pad((size_t)n1 * 4) + pad((size_t)n2 * 4) + pad(n2)
-                        + pad((size_t)n2 * BF_LIST * 4) + pad((size_t)n2 * 4) + 2 * pad((size_t)n1 * 4) + pad((size_t)n2 * 4) + 256
-                        + sort_bytes(1, n1, n2);
+    uint32_t *d1, *d2;
+    float *a1, *a2;
+    uint8_t* v2;
+    int *g_owner, *g_match;
+    BfProblem P{};
+    auto layout = [&](Arena& A) {
+        d1 = A.take<uint32_t>((size_t)n1 * 8);
+        d2 = A.take<uint32_t>((size_t)n2 * 8);
+        a1 = A.take<float>(n1);
+        a2 = A.take<float>(n2);
+        v2 = A.take<uint8_t>(n2);
+        P.topk = A.take<uint32_t>((size_t)n2 * BF_LIST);
+        P.cnt = A.take<int32_t>(n2);
+        P.matched = A.take<int32_t>(n1);
+        g_owner = A.take<int>(n1);
+        g_match = A.take<int>(n2);
+        P.num = A.take<int32_t>(1);
+        take_sort(A, P, 1, n1, n2);
+    };
+    const size_t need = arena_measure(layout);
     int rc = sv_ensure_scratch(ctx, need);
     if (rc) return rc;
-    Arena A(ctx->d_scratch);
-    uint32_t* d1 = A.take<uint32_t>((size_t)n1 * 8);
-    uint32_t* d2 = A.take<uint32_t>((size_t)n2 * 8);
-    float* a1 = A.take<float>(n1);
-    float* a2 = A.take<float>(n2);
-    uint8_t* v2 = A.take<uint8_t>(n2);
-    BfProblem P{};
-    P.topk = A.take<uint32_t>((size_t)n2 * BF_LIST);
-    P.cnt = A.take<int32_t>(n2);
-    P.matched = A.take<int32_t>(n1);
-    int* g_owner = A.take<int>(n1);
-    int* g_match = A.take<int>(n2);
-    P.num = A.take<int32_t>(1);
-    take_sort(A, P, 1, n1, n2);
     hipStream_t s = ctx->stream;
     // inputs through the page-locked mirror of the arena: one copy down (the five arrays are the first takes: one contiguous range), one up
     if ((rc = sv_ensure_stage(ctx, need))) return rc;
-    A.mirror = ctx->h_stage;
+    UploadArena A(ctx, ctx->h_stage);
+    layout(A);
+    if (A.overflow) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_match_bruteforce: internal arena overflow");
     if ((rc = A.upload(ctx, s, d1, desc1, (size_t)n1 * 32))) return rc;
     if ((rc = A.upload(ctx, s, d2, desc2, (size_t)n2 * 32))) return rc;
     if (angle1) rc = A.upload(ctx, s, a1, angle1, (size_t)n1 * 4);
@@ -220,62 +230,47 @@ int svgpu_match_candidates(svgpu_ctx* ctx, const uint8_t* qdesc, int nq, const u
     for (int c = 0; c < nc; ++c)
         if (cand_idx[c] < 0 || cand_idx[c] >= nt) return sv_set_error(ctx, SVGPU_ERR_INVALID, "cand_idx out of range");
     SV_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t need = pad((size_t)nq * 32) + pad((size_t)nt * 32) + 3 * pad((size_t)nt * 4) + pad(nt) + pad((size_t)(nq + 1) * 4)
-                        + pad((size_t)nc * 4) + pad(nc) + pad(nq) + 3 * pad((size_t)nq * 4) + pad((size_t)nc * 4) + 2 * pad((size_t)nq * 4)
-                        + 2 * pad((size_t)nt * 4) + 512;
+    hipStream_t s = ctx->stream;
+    CandProblem P{};
+    int *owner, *match;
+    unsigned* mdist;
+    auto layout = [&](UploadArena& A) -> int {
+        int rc = SVGPU_OK;
+        P.qdesc = (const uint32_t*)A.put(ctx, s, qdesc, (size_t)nq * 32, true, rc);
+        P.tdesc = (const uint32_t*)A.put(ctx, s, tdesc, (size_t)nt * 32, true, rc);
+        P.t_octave = A.put(ctx, s, t_octave, nt, true, rc);
+        P.cand_off = A.put(ctx, s, cand_off, nq + 1, true, rc);
+        P.cand_idx = A.put(ctx, s, cand_idx, nc, true, rc);
+        P.cand_skip = A.put(ctx, s, cand_skip, nc, true, rc);
+        P.q_valid = A.put(ctx, s, q_valid, nq, true, rc);
+        P.occupied = A.put(ctx, s, occupied, nt, true, rc);
+        P.q_angle = A.put(ctx, s, q_angle, nq, true, rc);
+        P.t_angle = A.put(ctx, s, t_angle, nt, true, rc);
+        P.q_xright = A.put(ctx, s, q_xright, nq, true, rc);
+        P.t_xright = A.put(ctx, s, t_xright, nt, true, rc);
+        P.q_xr_tol = A.put(ctx, s, q_xr_tol, nq, true, rc);
+        P.dist = A.take<uint32_t>(nc);
+        P.match_q = A.take<int32_t>(nq);
+        P.num = A.take<int32_t>(1);
+        owner = A.take<int>(nt);
+        match = A.take<int>(nq);
+        mdist = A.take<unsigned>(nt);
+        return rc;
+    };
+    const size_t need = arena_measure<UploadArena>(layout);
     int rc = sv_ensure_scratch(ctx, need);
     if (rc) return rc;
-    Arena A(ctx->d_scratch);
-    hipStream_t s = ctx->stream;
     if ((rc = sv_ensure_stage(ctx, need))) return rc;
-    A.mirror = ctx->h_stage;  // batched upload / read-back (Arena::upload, Downloads)
-    CandProblem P{};
-#define UP(dst, T, src, n)                                                                          \
-    T* dst = nullptr;                                                                               \
-    if (src) {                                                                                      \
-        dst = A.take<T>(n);                                                                         \
-        if ((rc = A.upload(ctx, s, dst, src, (size_t)(n) * sizeof(T)))) return rc;                  \
-    }
-    UP(d_q, uint8_t, qdesc, (size_t)nq * 32)
-    UP(d_t, uint8_t, tdesc, (size_t)nt * 32)
-    UP(d_toct, int32_t, t_octave, nt)
-    UP(d_off, int32_t, cand_off, nq + 1)
-    UP(d_idx, int32_t, cand_idx, nc)
-    UP(d_skip, uint8_t, cand_skip, nc)
-    UP(d_qv, uint8_t, q_valid, nq)
-    UP(d_occ, uint8_t, occupied, nt)
-    UP(d_qa, float, q_angle, nq)
-    UP(d_ta, float, t_angle, nt)
-    UP(d_qx, float, q_xright, nq)
-    UP(d_tx, float, t_xright, nt)
-    UP(d_qtol, float, q_xr_tol, nq)
-#undef UP
+    UploadArena A(ctx, ctx->h_stage);  // batched upload / read-back (UploadArena::upload, Downloads)
+    if ((rc = layout(A))) return rc;
+    if (A.overflow) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_match_candidates: internal arena overflow");
     if ((rc = A.flush(ctx, s))) return rc;
-    P.qdesc = (const uint32_t*)d_q;
-    P.tdesc = (const uint32_t*)d_t;
-    P.t_octave = d_toct;
     P.nq = nq;
     P.nt = nt;
-    P.cand_off = d_off;
-    P.cand_idx = d_idx;
-    P.cand_skip = d_skip;
-    P.q_valid = d_qv;
-    P.occupied = d_occ;
-    P.q_angle = d_qa;
-    P.t_angle = d_ta;
     P.check_orientation = check_orientation;
-    P.q_xright = d_qx;
-    P.t_xright = d_tx;
-    P.q_xr_tol = d_qtol;
     P.thr = thr;
     P.lowe_ratio = lowe_ratio;
     P.mode = mode;
-    P.dist = A.take<uint32_t>(nc);
-    P.match_q = A.take<int32_t>(nq);
-    P.num = A.take<int32_t>(1);
-    int* owner = A.take<int>(nt);
-    int* match = A.take<int>(nq);
-    unsigned* mdist = A.take<unsigned>(nt);
     sv_launch_cand(ctx, s, P, owner, match, mdist);
     SV_HIP(ctx, hipGetLastError());
     int32_t num = 0;
@@ -319,45 +314,24 @@ int svgpu_match_in_cells(svgpu_ctx* ctx, const uint8_t* qdesc, int nq, const flo
         return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_match_in_cells: inconsistent inputs");
     InCellsFrame F{tdesc, t_xy, t_octave, nt, occupied, t_angle, t_xright, min_x, max_x, min_y, max_y, grid_cols, grid_rows};
     F.res = rf;
-    const size_t qbytes = pad((size_t)nq * 32) + pad((size_t)nq * 8) + 6 * pad((size_t)nq * 4) + 2 * pad(nq);
     hipStream_t s = ctx->stream;
     return in_cells_core(
-        ctx, nq, F, qbytes, check_orientation, thr, lowe_ratio, mode,
-        [&](Arena& A, bool fresh, CandProblem& P, GridProblem& G) -> int {
-#define UP(dst, T, src, n)                                                                          \
-    T* dst = nullptr;                                                                               \
-    if (src) {                                                                                      \
-        dst = A.take<T>(n);                                                                         \
-        if (fresh) {                                                                                \
-            const int rcu = A.upload(ctx, s, dst, src, (size_t)(n) * sizeof(T));                    \
-            if (rcu) return rcu;                                                                    \
-        }                                                                                           \
-    }
-            UP(d_q, uint8_t, qdesc, (size_t)nq * 32)
-            UP(d_qxy, float, q_xy, (size_t)nq * 2)
-            UP(d_qm, float, q_margin, nq)
-            UP(d_qlo, int32_t, q_min_level, nq)
-            UP(d_qhi, int32_t, q_max_level, nq)
-            UP(d_qv, uint8_t, q_valid, nq)
-            UP(d_qa, float, q_angle, nq)
-            UP(d_qx, float, q_xright, nq)
-            UP(d_qtol, float, q_xr_tol, nq)
-            UP(d_qb, uint8_t, q_blocks, nq)
-#undef UP
-            G.q_xy = d_qxy;
-            G.q_margin = d_qm;
-            G.q_min_level = d_qlo;
-            G.q_max_level = d_qhi;
-            G.q_valid = d_qv;
-            P.qdesc = (const uint32_t*)d_q;
-            P.q_valid = d_qv;
-            P.q_angle = d_qa;
-            P.q_xright = d_qx;
-            P.q_xr_tol = d_qtol;
-            P.q_blocks = d_qb;
-            return SVGPU_OK;
+        ctx, nq, F, check_orientation, thr, lowe_ratio, mode,
+        [&](UploadArena& A, bool fresh, CandProblem& P, GridProblem& G) -> int {
+            int rc = SVGPU_OK;
+            P.qdesc = (const uint32_t*)A.put(ctx, s, qdesc, (size_t)nq * 32, fresh, rc);
+            G.q_xy = A.put(ctx, s, q_xy, (size_t)nq * 2, fresh, rc);
+            G.q_margin = A.put(ctx, s, q_margin, nq, fresh, rc);
+            G.q_min_level = A.put(ctx, s, q_min_level, nq, fresh, rc);
+            G.q_max_level = A.put(ctx, s, q_max_level, nq, fresh, rc);
+            G.q_valid = P.q_valid = A.put(ctx, s, q_valid, nq, fresh, rc);
+            P.q_angle = A.put(ctx, s, q_angle, nq, fresh, rc);
+            P.q_xright = A.put(ctx, s, q_xright, nq, fresh, rc);
+            P.q_xr_tol = A.put(ctx, s, q_xr_tol, nq, fresh, rc);
+            P.q_blocks = A.put(ctx, s, q_blocks, nq, fresh, rc);
+            return rc;
         },
-        [&](const CandProblem&, const Arena&, Downloads&) -> int { return SVGPU_OK; }, match_q, num_matches);
+        [&](const CandProblem&, const UploadArena&, Downloads&) -> int { return SVGPU_OK; }, match_q, num_matches);
 }
 
 int svgpu_camera_image_bounds(svgpu_ctx* ctx, svgpu_camera* cam) {
@@ -419,24 +393,30 @@ int svgpu_frame_observation(svgpu_ctx* ctx, const svgpu_camera* cam, const svgpu
     }
     SV_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    const size_t need = 2 * pad((size_t)n * 28) + pad((size_t)n * 8) + pad((size_t)n * 24) + 2 * pad((size_t)n * 4) + pad((size_t)(ncell + 1) * 4) + 1024;
-    int rc = sv_ensure_scratch(ctx, need);
-    if (rc) return rc;
-    Arena A(ctx->d_scratch);
     FrameObsProblem P{};
+    GridProblem G{};
+    svgpu_keypoint* d_in;
+    auto layout = [&](Arena& A) {
+        P.kps = d_in = A.take<svgpu_keypoint>(n);
+        P.undist = undist_kps ? A.take<svgpu_keypoint>(n) : nullptr;
+        P.undist_xy = A.take<float>((size_t)n * 2);
+        P.bearings = bearings ? A.take<double>((size_t)n * 3) : nullptr;
+        if (want_grid) {
+            G.cell_of = A.take<int32_t>(n);
+            G.cell_off = A.take<int32_t>(ncell + 1);
+            G.cell_items = A.take<int32_t>(n);
+            G.cand_off = A.take<int32_t>(1);
+        }
+    };
+    int rc = sv_scratch_layout(ctx, "svgpu_frame_observation: internal arena overflow", layout);
+    if (rc) return rc;
     P.cam = *cam;
-    svgpu_keypoint* d_in = A.take<svgpu_keypoint>(n);
-    P.kps = d_in;
     P.n = n;
-    P.undist = undist_kps ? A.take<svgpu_keypoint>(n) : nullptr;
-    P.undist_xy = A.take<float>((size_t)n * 2);
-    P.bearings = bearings ? A.take<double>((size_t)n * 3) : nullptr;
     SV_HIP(ctx, hipMemcpyAsync(d_in, kps, (size_t)n * sizeof(svgpu_keypoint), hipMemcpyHostToDevice, s));
     sv_launch_frame_observation(s, P);
     if (undist_kps) SV_HIP(ctx, hipMemcpyAsync(undist_kps, P.undist, (size_t)n * sizeof(svgpu_keypoint), hipMemcpyDeviceToHost, s));
     if (bearings) SV_HIP(ctx, hipMemcpyAsync(bearings, P.bearings, (size_t)n * 24, hipMemcpyDeviceToHost, s));
     if (want_grid) {
-        GridProblem G{};
         G.t_xy = P.undist_xy;
         G.nt = n;
         G.min_x = cam->min_x;
@@ -445,11 +425,7 @@ int svgpu_frame_observation(svgpu_ctx* ctx, const svgpu_camera* cam, const svgpu
         G.inv_h = (double)grid_rows / (cam->max_y - cam->min_y);
         G.cols = grid_cols;
         G.rows = grid_rows;
-        G.cell_of = A.take<int32_t>(n);
-        G.cell_off = A.take<int32_t>(ncell + 1);
-        G.cell_items = A.take<int32_t>(n);
         G.nq = 0;
-        G.cand_off = A.take<int32_t>(1);
         sv_launch_grid_build(s, G);
         SV_HIP(ctx, hipMemcpyAsync(cell_off, G.cell_off, (size_t)(ncell + 1) * 4, hipMemcpyDeviceToHost, s));
         SV_HIP(ctx, hipStreamSynchronize(s));
@@ -467,16 +443,17 @@ int svgpu_keypoints_to_bearings(svgpu_ctx* ctx, const svgpu_camera* cam, const s
     if (n == 0) return SVGPU_OK;
     SV_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    int rc = sv_ensure_scratch(ctx, pad((size_t)n * 28) + pad((size_t)n * 24) + 256);
-    if (rc) return rc;
-    Arena A(ctx->d_scratch);
     FrameObsProblem P{};
+    svgpu_keypoint* d_in;
+    auto layout = [&](Arena& A) {
+        P.kps = d_in = A.take<svgpu_keypoint>(n);
+        P.bearings = A.take<double>((size_t)n * 3);
+    };
+    int rc = sv_scratch_layout(ctx, "svgpu_keypoints_to_bearings: internal arena overflow", layout);
+    if (rc) return rc;
     P.cam = *cam;
-    svgpu_keypoint* d_in = A.take<svgpu_keypoint>(n);
-    P.kps = d_in;
     P.n = n;
     P.already_undistorted = 1;
-    P.bearings = A.take<double>((size_t)n * 3);
     SV_HIP(ctx, hipMemcpyAsync(d_in, undist_kps, (size_t)n * sizeof(svgpu_keypoint), hipMemcpyHostToDevice, s));
     sv_launch_frame_observation(s, P);
     SV_HIP(ctx, hipGetLastError());
@@ -506,6 +483,19 @@ int fill_reproj(svgpu_ctx* ctx, const char* who, ReprojProblem& R, const svgpu_c
     R.log_scale_factor = log_scale_factor;
     return SVGPU_OK;
 }
+// The landmark side of a reprojection in the arena: inputs (uploaded when `fresh`) and observability outputs.
+void take_reproj(svgpu_ctx* ctx, hipStream_t s, UploadArena& A, bool fresh, ReprojProblem& R, int n, const double* pos_w, const double* mean_normal,
+                 const float* min_valid_dist, const float* max_valid_dist, const uint8_t* skip, int& rc) {
+    R.pos_w = A.put(ctx, s, pos_w, (size_t)n * 3, fresh, rc);
+    R.mean_normal = A.put(ctx, s, mean_normal, (size_t)n * 3, fresh, rc);
+    R.min_valid_dist = A.put(ctx, s, min_valid_dist, n, fresh, rc);
+    R.max_valid_dist = A.put(ctx, s, max_valid_dist, n, fresh, rc);
+    R.skip = A.put(ctx, s, skip, n, fresh, rc);
+    R.visible = A.take<uint8_t>(n);
+    R.reproj = A.take<double>((size_t)n * 2);
+    R.x_right = A.take<float>(n);
+    R.pred_level = A.take<int32_t>(n);
+}
 }  // namespace
 
 extern "C" {
@@ -523,30 +513,19 @@ int svgpu_reproject_landmarks(svgpu_ctx* ctx, const svgpu_camera* cam, const dou
     if (!visible || !reproj || !x_right || !pred_scale_level) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_reproject_landmarks: null output");
     SV_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    const size_t need = 2 * pad((size_t)n * 24) + 4 * pad((size_t)n * 4) + 2 * pad(n) + pad((size_t)n * 16) + 1024;
-    rc = sv_ensure_scratch(ctx, need);
-    if (rc) return rc;
-    Arena A(ctx->d_scratch);
-    double* d_pw = A.take<double>((size_t)n * 3);
-    double* d_nv = A.take<double>((size_t)n * 3);
-    float* d_mn = A.take<float>(n);
-    float* d_mx = A.take<float>(n);
-    uint8_t* d_skip = skip ? A.take<uint8_t>(n) : nullptr;
-    R.visible = A.take<uint8_t>(n);
-    R.reproj = A.take<double>((size_t)n * 2);
-    R.x_right = A.take<float>(n);
-    R.pred_level = A.take<int32_t>(n);
-    // one upload and one read-back through the page-locked mirror of the arena (Arena::upload / Downloads): nine separate copies from / to
-    // pageable memory were nine staging kernels on the stream
+    // one upload and one read-back through the page-locked mirror of the arena (UploadArena::upload / Downloads): nine separate copies
+    // from / to pageable memory were nine staging kernels on the stream
+    auto layout = [&](UploadArena& A) -> int {
+        int ru = SVGPU_OK;
+        take_reproj(ctx, s, A, true, R, n, pos_w, mean_normal, min_valid_dist, max_valid_dist, skip, ru);
+        return ru ? ru : A.flush(ctx, s);
+    };
+    const size_t need = arena_measure<UploadArena>(layout);
+    if ((rc = sv_ensure_scratch(ctx, need))) return rc;
     if ((rc = sv_ensure_stage(ctx, need))) return rc;
-    A.mirror = ctx->h_stage;
-    if ((rc = A.upload(ctx, s, d_pw, pos_w, (size_t)n * 24))) return rc;
-    if ((rc = A.upload(ctx, s, d_nv, mean_normal, (size_t)n * 24))) return rc;
-    if ((rc = A.upload(ctx, s, d_mn, min_valid_dist, (size_t)n * 4))) return rc;
-    if ((rc = A.upload(ctx, s, d_mx, max_valid_dist, (size_t)n * 4))) return rc;
-    if (skip && (rc = A.upload(ctx, s, d_skip, skip, n))) return rc;
-    if ((rc = A.flush(ctx, s))) return rc;
-    R.pos_w = d_pw, R.mean_normal = d_nv, R.min_valid_dist = d_mn, R.max_valid_dist = d_mx, R.skip = d_skip;
+    UploadArena A(ctx, ctx->h_stage);
+    if ((rc = layout(A))) return rc;
+    if (A.overflow) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_reproject_landmarks: internal arena overflow");
     sv_launch_reproject(s, R);
     SV_HIP(ctx, hipGetLastError());
     Downloads D;
@@ -593,33 +572,18 @@ int svgpu_match_frame_and_landmarks(svgpu_ctx* ctx, const svgpu_camera* cam, con
     for (int l = 0; l < num_levels; ++l) R.scale_factors[l] = scale_factors[l];
     InCellsFrame F{tdesc, t_xy, t_octave, nt, occupied, nullptr, t_xright, cam->min_x, cam->max_x, cam->min_y, cam->max_y, grid_cols, grid_rows};
     if (rf) F.min_x = rf->min_x, F.max_x = rf->max_x, F.min_y = rf->min_y, F.max_y = rf->max_y, F.res = rf;
-    const size_t qbytes = pad((size_t)n * 32) + 2 * pad((size_t)n * 24) + 8 * pad((size_t)n * 4) + 2 * pad(n) + pad((size_t)n * 16) + pad((size_t)n * 8);
     hipStream_t s = ctx->stream;
     return in_cells_core(
-        ctx, n, F, qbytes, 0, thr, lowe_ratio, SVGPU_MATCH_RATIO_SAME_OCTAVE,
-        [&](Arena& A, bool fresh, CandProblem& P, GridProblem& G) -> int {
-            uint8_t* d_q = A.take<uint8_t>((size_t)n * 32);
-            double* d_pw = A.take<double>((size_t)n * 3);
-            double* d_nv = A.take<double>((size_t)n * 3);
-            float* d_mn = A.take<float>(n);
-            float* d_mx = A.take<float>(n);
-            uint8_t* d_skip = skip ? A.take<uint8_t>(n) : nullptr;
-            R.visible = A.take<uint8_t>(n);
-            R.reproj = A.take<double>((size_t)n * 2);
-            R.x_right = A.take<float>(n);
-            R.pred_level = A.take<int32_t>(n);
+        ctx, n, F, 0, thr, lowe_ratio, SVGPU_MATCH_RATIO_SAME_OCTAVE,
+        [&](UploadArena& A, bool fresh, CandProblem& P, GridProblem& G) -> int {
+            int ru = SVGPU_OK;
+            uint8_t* d_q = A.put(ctx, s, lm_desc, (size_t)n * 32, fresh, ru);
+            take_reproj(ctx, s, A, fresh, R, n, pos_w, mean_normal, min_valid_dist, max_valid_dist, skip, ru);
             R.q_xy = A.take<float>((size_t)n * 2);
             R.q_margin = A.take<float>(n);
             R.q_min_level = A.take<int32_t>(n);
             R.q_max_level = A.take<int32_t>(n);
-            R.pos_w = d_pw, R.mean_normal = d_nv, R.min_valid_dist = d_mn, R.max_valid_dist = d_mx, R.skip = d_skip;
-            if (fresh) {  // one batched upload (Arena::upload / flush), then the reprojection that consumes it
-                int ru = A.upload(ctx, s, d_q, lm_desc, (size_t)n * 32);
-                if (!ru) ru = A.upload(ctx, s, d_pw, pos_w, (size_t)n * 24);
-                if (!ru) ru = A.upload(ctx, s, d_nv, mean_normal, (size_t)n * 24);
-                if (!ru) ru = A.upload(ctx, s, d_mn, min_valid_dist, (size_t)n * 4);
-                if (!ru) ru = A.upload(ctx, s, d_mx, max_valid_dist, (size_t)n * 4);
-                if (!ru && skip) ru = A.upload(ctx, s, d_skip, skip, n);
+            if (fresh) {  // one batched upload (UploadArena::put / flush), then the reprojection that consumes it
                 if (!ru) ru = A.flush(ctx, s);
                 if (ru) return ru;
                 sv_launch_reproject(s, R);
@@ -637,7 +601,7 @@ int svgpu_match_frame_and_landmarks(svgpu_ctx* ctx, const svgpu_camera* cam, con
             }
             return SVGPU_OK;
         },
-        [&](const CandProblem&, const Arena& A, Downloads& D) -> int {
+        [&](const CandProblem&, const UploadArena& A, Downloads& D) -> int {
             D.add(A, visible, R.visible, n);
             D.add(A, reproj, R.reproj, (size_t)n * 16);
             D.add(A, x_right, R.x_right, (size_t)n * 4);
@@ -674,23 +638,24 @@ int svgpu_stereo_match(svgpu_ctx* ctx_left, svgpu_ctx* ctx_right, const svgpu_ke
     SV_HIP(ctx, hipSetDevice(ctx->device));
     SV_HIP(ctx, hipStreamSynchronize(ctx_right->stream));  // the right pyramid must be complete
     const int rows = CL.levels[0].h, rows_per_kp = 2 * (int)std::ceil(2.0 * std::pow((double)CL.scale_factor, CL.num_levels - 1)) + 3;  // rows of the widest band, one to spare
-    const size_t need = pad((size_t)n_left * 28) + pad((size_t)n_right * 28) + pad((size_t)n_left * 32) + pad((size_t)n_right * 32)
-                        + 3 * pad((size_t)n_left * 4) + sv_stereo_rows_bytes(1, rows, n_right, rows_per_kp) + 256;
-    int rc = sv_ensure_scratch(ctx, need);
-    if (rc) return rc;
-    Arena A(ctx->d_scratch);
     StereoProblem P{};
-    svgpu_keypoint* dkl = A.take<svgpu_keypoint>(n_left);
-    svgpu_keypoint* dkr = A.take<svgpu_keypoint>(n_right);
-    uint32_t* ddl = A.take<uint32_t>((size_t)n_left * 8);
-    uint32_t* ddr = A.take<uint32_t>((size_t)n_right * 8);
-    P.xr = A.take<float>(n_left);
-    P.depth = A.take<float>(n_left);
-    P.corr = A.take<float>(n_left);
+    svgpu_keypoint *dkl, *dkr;
+    uint32_t *ddl, *ddr;
+    auto layout = [&](Arena& A) {
+        dkl = A.take<svgpu_keypoint>(n_left);
+        dkr = A.take<svgpu_keypoint>(n_right);
+        ddl = A.take<uint32_t>((size_t)n_left * 8);
+        ddr = A.take<uint32_t>((size_t)n_right * 8);
+        P.xr = A.take<float>(n_left);
+        P.depth = A.take<float>(n_left);
+        P.corr = A.take<float>(n_left);
+        P.row_off = A.take<int32_t>((size_t)rows + 1);
+        P.row_fill = A.take<int32_t>(rows);
+        P.row_items = A.take<int32_t>((size_t)n_right * rows_per_kp);
+    };
+    int rc = sv_scratch_layout(ctx, "svgpu_stereo_match: internal arena overflow", layout);
+    if (rc) return rc;
     P.rows = rows, P.rows_per_kp = rows_per_kp;
-    P.row_off = A.take<int32_t>((size_t)rows + 1);
-    P.row_fill = A.take<int32_t>(rows);
-    P.row_items = A.take<int32_t>((size_t)n_right * rows_per_kp);
     hipStream_t s = ctx->stream;
     SV_HIP(ctx, hipMemcpyAsync(dkl, kps_left, (size_t)n_left * 28, hipMemcpyHostToDevice, s));
     SV_HIP(ctx, hipMemcpyAsync(dkr, kps_right, (size_t)n_right * 28, hipMemcpyHostToDevice, s));
@@ -754,14 +719,16 @@ int svgpu_stereo_match_batch_device(svgpu_ctx* ctx_left, svgpu_ctx* ctx_right, i
     SV_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
     const int rows = CL.levels[0].h, rows_per_kp = 2 * (int)std::ceil(2.0 * std::pow((double)CL.scale_factor, CL.num_levels - 1)) + 3;  // rows of the widest band, one to spare
-    int rc = sv_ensure_scratch(ctx, pad((size_t)pairs * cap * 4) + sv_stereo_rows_bytes(pairs, rows, cap, rows_per_kp) + 256);
-    if (rc) return rc;
-    Arena A(ctx->d_scratch);
     StereoProblem P{};
+    auto layout = [&](Arena& A) {
+        P.row_off = A.take<int32_t>((size_t)pairs * (rows + 1));
+        P.row_fill = A.take<int32_t>((size_t)pairs * rows);
+        P.row_items = A.take<int32_t>((size_t)pairs * cap * rows_per_kp);
+        P.corr = A.take<float>((size_t)pairs * cap);
+    };
+    int rc = sv_scratch_layout(ctx, "svgpu_stereo_match_batch_device: internal arena overflow", layout);
+    if (rc) return rc;
     P.rows = rows, P.rows_per_kp = rows_per_kp;
-    P.row_off = A.take<int32_t>((size_t)pairs * (rows + 1));
-    P.row_fill = A.take<int32_t>((size_t)pairs * rows);
-    P.row_items = A.take<int32_t>((size_t)pairs * cap * rows_per_kp);
     P.kl = kps_left_dev;
     P.kr = kps_right_dev;
     P.dl = (const uint32_t*)desc_left_dev;
@@ -772,7 +739,6 @@ int svgpu_stereo_match_batch_device(svgpu_ctx* ctx_left, svgpu_ctx* ctx_right, i
     P.cap = cap;
     P.xr = stereo_x_right_dev;
     P.depth = depths_dev;
-    P.corr = A.take<float>((size_t)pairs * cap);
     P.num_levels = CL.num_levels;
     float inv[SV_MAX_LEVELS];
     svgpu_orb_scale_tables(CL.scale_factor, CL.num_levels, P.sf, inv, nullptr, nullptr);

@@ -84,20 +84,20 @@ int proj_match(svgpu_ctx* ctx, const char* who, const svgpu_camera* cam, const d
     }
     InCellsFrame Fq = F;
     if (!O.stereo_gate && !O.chi_gate) Fq.t_xright = nullptr;
-    const size_t qbytes = pad((size_t)n * 32) + 2 * pad((size_t)n * 24) + 10 * pad((size_t)n * 4) + 3 * pad(n) + pad((size_t)n * 16) + pad((size_t)n * 8);
     hipStream_t s = ctx->stream;
     return in_cells_core(
-        ctx, n, Fq, qbytes, O.check_orientation, O.thr, O.lowe_ratio, O.mode,
-        [&](Arena& A, bool fresh, CandProblem& P, GridProblem& G) -> int {
-            uint8_t* d_q = A.take<uint8_t>((size_t)n * 32);
-            double* d_pw = A.take<double>((size_t)n * 3);
-            double* d_nv = Q.mean_normal ? A.take<double>((size_t)n * 3) : nullptr;
-            float* d_mn = Q.min_valid_dist ? A.take<float>(n) : nullptr;
-            float* d_mx = Q.max_valid_dist ? A.take<float>(n) : nullptr;
-            uint8_t* d_skip = Q.valid ? A.take<uint8_t>(n) : nullptr;
-            int32_t* d_lvl = Q.q_level ? A.take<int32_t>(n) : nullptr;
-            float* d_qa = Q.q_angle ? A.take<float>(n) : nullptr;
-            uint8_t* d_qb = Q.q_blocks ? A.take<uint8_t>(n) : nullptr;
+        ctx, n, Fq, O.check_orientation, O.thr, O.lowe_ratio, O.mode,
+        [&](UploadArena& A, bool fresh, CandProblem& P, GridProblem& G) -> int {
+            int ru = SVGPU_OK;
+            P.qdesc = (const uint32_t*)A.put(ctx, s, Q.desc, (size_t)n * 32, fresh, ru);
+            R.pos_w = A.put(ctx, s, Q.pos_w, (size_t)n * 3, fresh, ru);
+            R.mean_normal = A.put(ctx, s, Q.mean_normal, (size_t)n * 3, fresh, ru);
+            R.min_valid_dist = A.put(ctx, s, Q.min_valid_dist, n, fresh, ru);
+            R.max_valid_dist = A.put(ctx, s, Q.max_valid_dist, n, fresh, ru);
+            R.skip = A.put(ctx, s, Q.valid ? skip.data() : nullptr, n, fresh, ru);
+            R.q_level = A.put(ctx, s, Q.q_level, n, fresh, ru);
+            P.q_angle = A.put(ctx, s, Q.q_angle, n, fresh, ru);
+            P.q_blocks = A.put(ctx, s, Q.q_blocks, n, fresh, ru);
             R.visible = A.take<uint8_t>(n);
             R.reproj = A.take<double>((size_t)n * 2);
             R.x_right = A.take<float>(n);
@@ -106,17 +106,7 @@ int proj_match(svgpu_ctx* ctx, const char* who, const svgpu_camera* cam, const d
             R.q_margin = A.take<float>(n);
             R.q_min_level = A.take<int32_t>(n);
             R.q_max_level = A.take<int32_t>(n);
-            R.pos_w = d_pw, R.mean_normal = d_nv, R.min_valid_dist = d_mn, R.max_valid_dist = d_mx, R.skip = d_skip, R.q_level = d_lvl;
-            if (fresh) {  // one batched upload (Arena::upload / flush), then the reprojection that consumes it
-                int ru = A.upload(ctx, s, d_q, Q.desc, (size_t)n * 32);
-                if (!ru) ru = A.upload(ctx, s, d_pw, Q.pos_w, (size_t)n * 24);
-                if (!ru && d_nv) ru = A.upload(ctx, s, d_nv, Q.mean_normal, (size_t)n * 24);
-                if (!ru && d_mn) ru = A.upload(ctx, s, d_mn, Q.min_valid_dist, (size_t)n * 4);
-                if (!ru && d_mx) ru = A.upload(ctx, s, d_mx, Q.max_valid_dist, (size_t)n * 4);
-                if (!ru && d_skip) ru = A.upload(ctx, s, d_skip, skip.data(), n);
-                if (!ru && d_lvl) ru = A.upload(ctx, s, d_lvl, Q.q_level, (size_t)n * 4);
-                if (!ru && d_qa) ru = A.upload(ctx, s, d_qa, Q.q_angle, (size_t)n * 4);
-                if (!ru && d_qb) ru = A.upload(ctx, s, d_qb, Q.q_blocks, n);
+            if (fresh) {  // one batched upload (UploadArena::put / flush), then the reprojection that consumes it
                 if (!ru) ru = A.flush(ctx, s);
                 if (ru) return ru;
                 sv_launch_reproject(s, R);
@@ -126,10 +116,7 @@ int proj_match(svgpu_ctx* ctx, const char* who, const svgpu_camera* cam, const d
             G.q_min_level = R.q_min_level;
             G.q_max_level = R.q_max_level;
             G.q_valid = R.visible;
-            P.qdesc = (const uint32_t*)d_q;
             P.q_valid = R.visible;
-            P.q_angle = d_qa;
-            P.q_blocks = d_qb;
             P.no_claims = O.no_claims;
             if (O.stereo_gate && F.t_xright) {
                 P.q_xright = R.x_right;
@@ -143,7 +130,7 @@ int proj_match(svgpu_ctx* ctx, const char* who, const svgpu_camera* cam, const d
             }
             return SVGPU_OK;
         },
-        [&](const CandProblem&, const Arena& A, Downloads& D) -> int {
+        [&](const CandProblem&, const UploadArena& A, Downloads& D) -> int {
             D.add(A, visible, R.visible, n);
             D.add(A, reproj, R.reproj, (size_t)n * 16);
             D.add(A, x_right, R.x_right, (size_t)n * 4);
@@ -193,71 +180,73 @@ int bucket_match(svgpu_ctx* ctx, const char* who, const BucketSide& S1, const Bu
     SV_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     const size_t sortb = std::max(sv_bucket_sort_bytes(n1), sv_bucket_sort_bytes(n2));
-    const size_t need1 = 2 * pad((size_t)n1 * 32) + pad((size_t)n2 * 32) + 3 * pad((size_t)n1 * 4) + 2 * pad((size_t)n2 * 4) + 2 * pad(n1) + 3 * pad(n2)
-                         + 2 * pad((size_t)n1 * 24) + 2 * pad((size_t)n2 * 24) + 16 * pad((size_t)n1 * 4) + 8 * pad((size_t)n2 * 4) + pad(sortb) + 4096;
-    int total = 0;
-    for (int pass = 0; pass < 2; ++pass) {
-        const size_t need = need1 + (pass ? 2 * pad((size_t)total * 4) : 0);
-        const bool regrow = need > ctx->scratch_bytes;
-        int rc = sv_ensure_scratch(ctx, need);
-        if (rc) return rc;
-        const bool fresh = !pass || regrow;
-        Arena A(ctx->d_scratch);
-        BucketProblem B{};
-#define UP(dst, T, src, cnt)                                                                          \
-    T* dst = nullptr;                                                                                 \
-    if (src) {                                                                                        \
-        dst = A.take<T>(cnt);                                                                         \
-        if (fresh) SV_HIP(ctx, hipMemcpyAsync(dst, src, (size_t)(cnt) * sizeof(T), hipMemcpyHostToDevice, s)); \
-    }
-        UP(d_d1, uint8_t, S1.desc, (size_t)n1 * 32)
-        UP(d_d2, uint8_t, S2.desc, (size_t)n2 * 32)
-        UP(d_a1, float, S1.angle, n1)
-        UP(d_a2, float, S2.angle, n2)
-        UP(d_v1, uint8_t, S1.valid, n1)
-        UP(d_v2, uint8_t, S2.valid, n2)
-        UP(d_n1, int32_t, S1.node, n1)
-        UP(d_n2, int32_t, S2.node, n2)
-        UP(d_o1, int32_t, S1.octave, n1)
-        UP(d_b1, double, S1.bearings, (size_t)n1 * 3)
-        UP(d_b2, double, S2.bearings, (size_t)n2 * 3)
-        UP(d_x1, float, S1.xright, n1)
-        UP(d_x2, float, S2.xright, n2)
-        UP(d_occ, uint8_t, occupied2, n2)
-#undef UP
-        unsigned* key1 = A.take<unsigned>(n1);
-        int* q_idx = A.take<int>(n1);
-        unsigned* key2 = A.take<unsigned>(n2);
-        int* t_sorted = A.take<int>(n2);
+    // The arena of one pass, described once; with `lists`, the candidate lists of `total` entries behind it.
+    struct Pieces {
+        uint8_t *d_d2, *d_occ;
+        int32_t *d_n1, *d_n2, *match_rows, *d_match, *d_num;
+        unsigned *key1, *key2, *mdist;
+        int *q_idx, *t_sorted, *owner, *match;
+        uint32_t* qdesc_rows;
+        float* qangle_rows;
+        void* sort_scratch;
+    };
+    auto layout = [&](UploadArena& A, bool fresh, bool lists, size_t total, Pieces& Y, BucketProblem& B, CandProblem& P) -> int {
+        int rc = SVGPU_OK;
+        B.desc1 = (const uint32_t*)A.put(ctx, s, S1.desc, (size_t)n1 * 32, fresh, rc);
+        B.desc2 = (const uint32_t*)(Y.d_d2 = A.put(ctx, s, S2.desc, (size_t)n2 * 32, fresh, rc));
+        B.angle1 = A.put(ctx, s, S1.angle, n1, fresh, rc);
+        B.angle2 = A.put(ctx, s, S2.angle, n2, fresh, rc);
+        B.valid1 = A.put(ctx, s, S1.valid, n1, fresh, rc);
+        B.valid2 = A.put(ctx, s, S2.valid, n2, fresh, rc);
+        Y.d_n1 = A.put(ctx, s, S1.node, n1, fresh, rc);
+        Y.d_n2 = A.put(ctx, s, S2.node, n2, fresh, rc);
+        B.octave1 = A.put(ctx, s, S1.octave, n1, fresh, rc);
+        B.bearings1 = A.put(ctx, s, S1.bearings, (size_t)n1 * 3, fresh, rc);
+        B.bearings2 = A.put(ctx, s, S2.bearings, (size_t)n2 * 3, fresh, rc);
+        B.xright1 = A.put(ctx, s, S1.xright, n1, fresh, rc);
+        B.xright2 = A.put(ctx, s, S2.xright, n2, fresh, rc);
+        Y.d_occ = A.put(ctx, s, occupied2, n2, fresh, rc);
+        B.key1 = Y.key1 = A.take<unsigned>(n1);
+        B.q_idx = Y.q_idx = A.take<int>(n1);
+        B.key2 = Y.key2 = A.take<unsigned>(n2);
+        B.t_sorted = Y.t_sorted = A.take<int>(n2);
         B.row_lo = A.take<int>(n1);
         B.row_hi = A.take<int>(n1);
         B.q_valid = A.take<uint8_t>(n1);
         B.cand_off = A.take<int32_t>(n1 + 1);
-        uint32_t* qdesc_rows = A.take<uint32_t>((size_t)n1 * 8);
-        float* qangle_rows = A.take<float>(n1);
-        int32_t* match_rows = A.take<int32_t>(n1);
-        int32_t* d_match = A.take<int32_t>(n1);
-        int32_t* d_num = A.take<int32_t>(1);
-        int* owner = A.take<int>(n2);
-        int* match = A.take<int>(n1);
-        unsigned* mdist = A.take<unsigned>(n2);
-        void* sort_scratch = A.take<char>(sortb);
+        Y.qdesc_rows = A.take<uint32_t>((size_t)n1 * 8);
+        Y.qangle_rows = A.take<float>(n1);
+        Y.match_rows = A.take<int32_t>(n1);
+        Y.d_match = A.take<int32_t>(n1);
+        Y.d_num = A.take<int32_t>(1);
+        Y.owner = A.take<int>(n2);
+        Y.match = A.take<int>(n1);
+        Y.mdist = A.take<unsigned>(n2);
+        Y.sort_scratch = A.take<char>(sortb);
+        if (lists) {
+            B.cand_idx = A.take<int32_t>(total);
+            P.dist = A.take<uint32_t>(total);
+        }
+        return rc;
+    };
+    int total = 0;
+    for (int pass = 0; pass < 2; ++pass) {
+        Pieces Y{};
+        BucketProblem B{};
+        CandProblem P{};
+        const size_t need = arena_measure<UploadArena>([&](UploadArena& M) { layout(M, false, pass != 0, (size_t)total, Y, B, P); });
+        const bool regrow = need > ctx->scratch_bytes;
+        int rc = sv_ensure_scratch(ctx, need);
+        if (rc) return rc;
+        const bool fresh = !pass || regrow;
+        UploadArena A(ctx);
+        if ((rc = layout(A, fresh, pass != 0, (size_t)total, Y, B, P))) return rc;
+        if (A.overflow) return sv_set_error(ctx, SVGPU_ERR_INVALID, "bucket matcher: internal arena overflow");
         B.n1 = n1;
         B.n2 = n2;
-        B.desc1 = (const uint32_t*)d_d1;
-        B.desc2 = (const uint32_t*)d_d2;
-        B.angle1 = d_a1;
-        B.angle2 = d_a2;
-        B.valid1 = d_v1;
-        B.valid2 = d_v2;
         B.check_orientation = check_orientation;
         B.tri = tri;
         B.thr = thr;
-        B.octave1 = d_o1;
-        B.bearings1 = d_b1;
-        B.bearings2 = d_b2;
-        B.xright1 = d_x1;
-        B.xright2 = d_x2;
         if (tri) {
             std::memcpy(B.E12, E12, sizeof B.E12);
             std::memcpy(B.epipole, epipole, sizeof B.epipole);
@@ -265,14 +254,10 @@ int bucket_match(svgpu_ctx* ctx, const char* who, const BucketSide& S1, const Bu
             for (int l = 0; l < num_levels; ++l) B.scale_factors[l] = scale_factors[l];
             B.residual_rad_thr = residual_rad_thr;
         }
-        B.key1 = key1;
-        B.q_idx = q_idx;
-        B.key2 = key2;
-        B.t_sorted = t_sorted;
         if (fresh) {
-            rc = sv_bucket_sort(ctx, s, d_n1, n1, sort_scratch, sortb, key1, q_idx);
+            rc = sv_bucket_sort(ctx, s, Y.d_n1, n1, Y.sort_scratch, sortb, Y.key1, Y.q_idx);
             if (rc) return rc;
-            rc = sv_bucket_sort(ctx, s, d_n2, n2, sort_scratch, sortb, key2, t_sorted);
+            rc = sv_bucket_sort(ctx, s, Y.d_n2, n2, Y.sort_scratch, sortb, Y.key2, Y.t_sorted);
             if (rc) return rc;
             sv_bucket_rows(s, B);
             sv_bucket_count(s, B);
@@ -283,33 +268,29 @@ int bucket_match(svgpu_ctx* ctx, const char* who, const BucketSide& S1, const Bu
             if (total == 0) return SVGPU_OK;
             continue;
         }
-        B.cand_idx = A.take<int32_t>(total);
-        if (A.off + pad((size_t)total * 4) > ctx->scratch_bytes) return sv_set_error(ctx, SVGPU_ERR_INVALID, "bucket matcher: internal arena overflow");
         sv_bucket_fill(s, B);
-        sv_bucket_gather_rows(s, B, qdesc_rows, qangle_rows);
-        CandProblem P{};
-        P.qdesc = qdesc_rows;
-        P.tdesc = (const uint32_t*)d_d2;
+        sv_bucket_gather_rows(s, B, Y.qdesc_rows, Y.qangle_rows);
+        P.qdesc = Y.qdesc_rows;
+        P.tdesc = (const uint32_t*)Y.d_d2;
         P.nq = n1;
         P.nt = n2;
         P.cand_off = B.cand_off;
         P.cand_idx = B.cand_idx;
         P.q_valid = B.q_valid;
-        P.occupied = d_occ;
+        P.occupied = Y.d_occ;
         P.check_orientation = 0;  // gated in the scan
         P.thr = thr;
         P.lowe_ratio = lowe_ratio;
         P.mode = mode;
-        P.dist = A.take<uint32_t>(total);
-        P.match_q = match_rows;
-        P.num = d_num;
-        sv_launch_cand(ctx, s, P, owner, match, mdist);
-        SV_HIP(ctx, hipMemsetAsync(d_match, 0xFF, (size_t)n1 * 4, s));
-        sv_bucket_scatter(s, B, match_rows, d_match);
+        P.match_q = Y.match_rows;
+        P.num = Y.d_num;
+        sv_launch_cand(ctx, s, P, Y.owner, Y.match, Y.mdist);
+        SV_HIP(ctx, hipMemsetAsync(Y.d_match, 0xFF, (size_t)n1 * 4, s));
+        sv_bucket_scatter(s, B, Y.match_rows, Y.d_match);
         SV_HIP(ctx, hipGetLastError());
         int32_t num = 0;
-        SV_HIP(ctx, hipMemcpyAsync(match_1to2, d_match, (size_t)n1 * 4, hipMemcpyDeviceToHost, s));
-        SV_HIP(ctx, hipMemcpyAsync(&num, d_num, 4, hipMemcpyDeviceToHost, s));
+        SV_HIP(ctx, hipMemcpyAsync(match_1to2, Y.d_match, (size_t)n1 * 4, hipMemcpyDeviceToHost, s));
+        SV_HIP(ctx, hipMemcpyAsync(&num, Y.d_num, 4, hipMemcpyDeviceToHost, s));
         SV_HIP(ctx, hipStreamSynchronize(s));
         *num_matches = num;
     }

@@ -16,18 +16,18 @@
 
 namespace svm {
 
-// bump allocator over ctx->d_scratch (256-byte aligned pieces)
-struct Arena {
-    char* base;
-    size_t off = 0;
-    // Batched uploads: with a page-locked mirror of the arena (ctx->h_stage) every host array is copied to the mirror at its arena offset and
-    // ONE host-to-device copy of the touched range follows (flush) -- the runtime turns every small copy from pageable memory into a staging
-    // kernel of its own (~5 us each on the stream: ten of them per cell-matcher call were half of what the call waited for).  Device-only
-    // pieces inside the range receive stale bytes, harmlessly: the kernels that produce them run behind the copy.
+// The scratch arena (sv_arena.h) with batched uploads: with a page-locked mirror of the arena (ctx->h_stage) every host array is copied to the
+// mirror at its arena offset and ONE host-to-device copy of the touched range follows (flush) -- the runtime turns every small copy from
+// pageable memory into a staging kernel of its own (~5 us each on the stream: ten of them per cell-matcher call were half of what the call
+// waited for).  Device-only pieces inside the range receive stale bytes, harmlessly: the kernels that produce them run behind the copy.
+// On a measuring arena upload / put / flush do nothing.
+struct UploadArena : Arena {
     char* mirror = nullptr;
     size_t up_lo = ~size_t(0), up_hi = 0;
-    explicit Arena(void* p) : base((char*)p) {}
+    UploadArena() = default;
+    explicit UploadArena(svgpu_ctx* ctx, char* mirror_ = nullptr) : Arena(ctx->d_scratch, ctx->scratch_bytes), mirror(mirror_) {}
     int upload(svgpu_ctx* ctx, hipStream_t s, void* dst, const void* src, size_t bytes) {
+        if (!dst || !bytes) return SVGPU_OK;
         if (!mirror) {
             SV_HIP(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));
             return SVGPU_OK;
@@ -38,19 +38,20 @@ struct Arena {
         up_hi = std::max(up_hi, o + bytes);
         return SVGPU_OK;
     }
+    // take n elements for an optional host array and, when `fresh`, upload it; no source: no piece, null.  The first failure stays in `rc`.
+    template <class T>
+    T* put(svgpu_ctx* ctx, hipStream_t s, const T* src, size_t n, bool fresh, int& rc) {
+        if (!src) return nullptr;
+        T* dst = take<T>(n);
+        if (fresh && !rc) rc = upload(ctx, s, dst, src, n * sizeof(T));
+        return dst;
+    }
     int flush(svgpu_ctx* ctx, hipStream_t s) {
         if (mirror && up_hi > up_lo) SV_HIP(ctx, hipMemcpyAsync(base + up_lo, mirror + up_lo, up_hi - up_lo, hipMemcpyHostToDevice, s));
         up_lo = ~size_t(0), up_hi = 0;
         return SVGPU_OK;
     }
-    template <class T>
-    T* take(size_t n) {
-        T* r = (T*)(base + off);
-        off += (n * sizeof(T) + 255) & ~size_t(255);
-        return r;
-    }
 };
-inline size_t pad(size_t bytes) { return (bytes + 255) & ~size_t(255); }
 
 // Batched read-backs, the counterpart of Arena::upload: results that live in the arena are requested with add(), fetch() copies the
 // range(s) that cover them into the page-locked mirror (requests closer than 32 KB share one copy), and after the stream has been
@@ -61,10 +62,10 @@ struct Downloads {
         size_t off, bytes;
     };
     std::vector<Item> items;
-    void add(const Arena& A, void* dst, const void* src, size_t bytes) {
+    void add(const UploadArena& A, void* dst, const void* src, size_t bytes) {
         if (dst && bytes) items.push_back({dst, (size_t)((const char*)src - A.base), bytes});
     }
-    int fetch(svgpu_ctx* ctx, hipStream_t s, const Arena& A) {
+    int fetch(svgpu_ctx* ctx, hipStream_t s, const UploadArena& A) {
         std::sort(items.begin(), items.end(), [](const Item& a, const Item& b) { return a.off < b.off; });
         size_t k = 0;
         while (k < items.size()) {
@@ -78,16 +79,12 @@ struct Downloads {
         }
         return SVGPU_OK;
     }
-    void scatter(const Arena& A) const {
+    void scatter(const UploadArena& A) const {
         for (const Item& it : items) memcpy(it.dst, A.mirror + it.off, it.bytes);
     }
 };
 
 // scratch for the angle-bin sorted copies of both sides (see k_bf_binsort)
-inline size_t sort_bytes(int pairs, int cap1, int cap2) {
-    const size_t p = (size_t)pairs;
-    return pad(p * cap1 * 32) + pad(p * cap2 * 32) + 2 * pad(p * cap1 * 4) + 2 * pad(p * cap2 * 4) + 2 * pad(p * 362 * 4) + pad(p * 2 * 4);
-}
 inline void take_sort(Arena& A, BfProblem& P, int pairs, int cap1, int cap2) {
     const size_t p = (size_t)pairs;
     P.sd1 = A.take<uint32_t>(p * cap1 * 8);
@@ -128,7 +125,7 @@ inline const svgpu_frame* sv_take_bound_frame(svgpu_ctx* ctx) {
 // Pass 0 builds the grid and the list sizes and reads the total back; the scratch arena may then have to grow for the
 // lists, which discards its contents, so pass 1 repeats the (cheap) staging and the grid build in the final arena.
 template <class Stage, class Finish>
-int in_cells_core(svgpu_ctx* ctx, int nq, const InCellsFrame& F, size_t query_bytes, int check_orientation, unsigned thr, float lowe_ratio,
+int in_cells_core(svgpu_ctx* ctx, int nq, const InCellsFrame& F, int check_orientation, unsigned thr, float lowe_ratio,
                   int mode, Stage&& stage, Finish&& finish, int32_t* match_q, int* num_matches) {
     SV_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
@@ -142,65 +139,28 @@ int in_cells_core(svgpu_ctx* ctx, int nq, const InCellsFrame& F, size_t query_by
         t_prev = t;
     };
     const int nt = F.nt, ncell = F.grid_cols * F.grid_rows;
-    // target side: descriptors, xy, seven nt x 4 arrays (t_octave, t_angle, t_xright, cell_of, cell_items, owner, mdist), occupied;
-    // query side: cand_off, match_q, match; P.num; slack for the alignment of each take
-    const size_t need1 = query_bytes + pad((size_t)nt * 32) + pad((size_t)nt * 8) + 7 * pad((size_t)nt * 4) + pad(nt)
-                         + pad((size_t)(ncell + 1) * 4) + pad((size_t)(nq + 1) * 4) + 2 * pad((size_t)nq * 4) + pad(4) + 2048;
-    int total = 0;
-    // Sizing of the candidate lists.  Exact: pass 0 builds the grid and the list sizes and reads their total back (a synchronisation in the
-    // middle of the call), pass 1 fills and matches.  Speculative (a capacity that sufficed for this context before, ctx->cand_cap_hint):
-    // everything is enqueued in pass 0 against that capacity, the kernels do nothing if the total exceeds it, and the total comes back with
-    // the results -- one synchronisation per call; a miss falls through to the exact pass 1.
-    const size_t guess = std::getenv("SVGPU_MATCH_EXACT_SIZING") ? 0 : ctx->cand_cap_hint;
-    for (int pass = 0; pass < 2; ++pass) {
-        const bool speculative = !pass && guess > 0;
-        const size_t cap = pass ? (size_t)total : guess;
-        const size_t need = need1 + ((pass || speculative) ? 2 * pad(cap * 4) : 0);
-        const bool regrow = need > ctx->scratch_bytes;  // pass 1 without regrowth: the arena of pass 0 is still valid, same layout
-        int rc = sv_ensure_scratch(ctx, need);
+    // The arena of one pass, described once: target side, the caller's query side (`stage`), grid, matcher state and -- with `lists` -- the
+    // candidate lists of capacity `cap`.  Run on a measuring arena (not fresh: nothing is uploaded or launched) it gives the pass's bytes.
+    struct Pieces {
+        uint8_t *d_t, *d_occ;
+        float *d_txy, *d_ta, *d_tx;
+        int32_t* d_toct;
+        int *owner, *match;
+        unsigned* mdist;
+    };
+    auto layout = [&](UploadArena& A, bool fresh, bool lists, size_t cap, Pieces& Y, CandProblem& P, GridProblem& G) -> int {
+        int rc = SVGPU_OK;
+        // (resident frame: the keypoint side is the frame's own device arrays)
+        Y.d_t = F.res ? const_cast<uint8_t*>(F.tdesc) : A.put(ctx, s, F.tdesc, (size_t)nt * 32, fresh, rc);
+        Y.d_txy = F.res ? const_cast<float*>(F.t_xy) : A.put(ctx, s, F.t_xy, (size_t)nt * 2, fresh, rc);
+        Y.d_toct = F.res ? const_cast<int32_t*>(F.t_octave) : A.put(ctx, s, F.t_octave, nt, fresh, rc);
+        Y.d_occ = A.put(ctx, s, F.occupied, nt, fresh, rc);
+        Y.d_ta = F.res ? const_cast<float*>(F.t_angle) : A.put(ctx, s, F.t_angle, nt, fresh, rc);
+        Y.d_tx = F.res ? const_cast<float*>(F.t_xright) : A.put(ctx, s, F.t_xright, nt, fresh, rc);
         if (rc) return rc;
-        const bool fresh = !pass || regrow;
-        Arena A(ctx->d_scratch);
-        rc = sv_ensure_stage(ctx, need);  // page-locked mirror of the arena: batched uploads (fresh passes) and read-backs
-        if (rc) return rc;
-        A.mirror = ctx->h_stage;
-        CandProblem P{};
-        GridProblem G{};
-#define UP(dst, T, src, n)                                                                          \
-    T* dst = nullptr;                                                                               \
-    if (src) {                                                                                      \
-        dst = A.take<T>(n);                                                                         \
-        if (fresh && (rc = A.upload(ctx, s, dst, src, (size_t)(n) * sizeof(T)))) return rc; \
-    }
-#define UPR(dst, T, src, n)                       \
-    T* dst = nullptr;                             \
-    if (F.res) dst = const_cast<T*>(src);         \
-    else if (src) {                               \
-        dst = A.take<T>(n);                       \
-        if (fresh && (rc = A.upload(ctx, s, dst, src, (size_t)(n) * sizeof(T)))) return rc; \
-    }
-        UPR(d_t, uint8_t, F.tdesc, (size_t)nt * 32)
-        UPR(d_txy, float, F.t_xy, (size_t)nt * 2)
-        UPR(d_toct, int32_t, F.t_octave, nt)
-        UP(d_occ, uint8_t, F.occupied, nt)
-        UPR(d_ta, float, F.t_angle, nt)
-        UPR(d_tx, float, F.t_xright, nt)
-#undef UP
-#undef UPR
-        lap(pass ? "target side (pass 1)" : "target side uploads");
         rc = stage(A, fresh, P, G);
         if (rc) return rc;
         if ((rc = A.flush(ctx, s))) return rc;
-        lap(pass ? "stage (pass 1)" : "stage: query uploads");
-        G.t_xy = d_txy;
-        G.t_octave = d_toct;
-        G.nt = nt;
-        G.min_x = F.min_x;
-        G.min_y = F.min_y;
-        G.inv_w = (double)F.grid_cols / (F.max_x - F.min_x);  // float difference, double quotient: data/common.cc:86-87 via camera::base
-        G.inv_h = (double)F.grid_rows / (F.max_y - F.min_y);
-        G.cols = F.grid_cols;
-        G.rows = F.grid_rows;
         if (F.res) {  // binned when the frame was created
             G.cell_of = F.res->cell_of;
             G.cell_off = F.res->cell_off;
@@ -211,13 +171,52 @@ int in_cells_core(svgpu_ctx* ctx, int nq, const InCellsFrame& F, size_t query_by
             G.cell_off = A.take<int32_t>(ncell + 1);
             G.cell_items = A.take<int32_t>(nt);
         }
-        G.nq = nq;
         G.cand_off = A.take<int32_t>(nq + 1);
         P.match_q = A.take<int32_t>(nq);
         P.num = A.take<int32_t>(1);
-        int* owner = A.take<int>(nt);
-        int* match = A.take<int>(nq);
-        unsigned* mdist = A.take<unsigned>(nt);
+        Y.owner = A.take<int>(nt);
+        Y.match = A.take<int>(nq);
+        Y.mdist = A.take<unsigned>(nt);
+        if (lists) {
+            G.cand_idx = A.take<int32_t>(cap);
+            P.dist = A.take<uint32_t>(cap);
+        }
+        return SVGPU_OK;
+    };
+    int total = 0;
+    // Sizing of the candidate lists.  Exact: pass 0 builds the grid and the list sizes and reads their total back (a synchronisation in the
+    // middle of the call), pass 1 fills and matches.  Speculative (a capacity that sufficed for this context before, ctx->cand_cap_hint):
+    // everything is enqueued in pass 0 against that capacity, the kernels do nothing if the total exceeds it, and the total comes back with
+    // the results -- one synchronisation per call; a miss falls through to the exact pass 1.
+    const size_t guess = std::getenv("SVGPU_MATCH_EXACT_SIZING") ? 0 : ctx->cand_cap_hint;
+    for (int pass = 0; pass < 2; ++pass) {
+        const bool speculative = !pass && guess > 0;
+        const size_t cap = pass ? (size_t)total : guess;
+        const bool lists = pass || speculative;
+        Pieces Y{};
+        CandProblem P{};
+        GridProblem G{};
+        const size_t need = arena_measure<UploadArena>([&](UploadArena& M) { layout(M, false, lists, cap, Y, P, G); });
+        const bool regrow = need > ctx->scratch_bytes;  // pass 1 without regrowth: the arena of pass 0 is still valid, same layout
+        int rc = sv_ensure_scratch(ctx, need);
+        if (rc) return rc;
+        const bool fresh = !pass || regrow;
+        rc = sv_ensure_stage(ctx, need);  // page-locked mirror of the arena: batched uploads (fresh passes) and read-backs
+        if (rc) return rc;
+        UploadArena A(ctx, ctx->h_stage);
+        if ((rc = layout(A, fresh, lists, cap, Y, P, G))) return rc;
+        if (A.overflow) return sv_set_error(ctx, SVGPU_ERR_INVALID, "cell matcher: internal arena overflow");
+        lap(pass ? "stage (pass 1)" : "stage: uploads");
+        G.t_xy = Y.d_txy;
+        G.t_octave = Y.d_toct;
+        G.nt = nt;
+        G.min_x = F.min_x;
+        G.min_y = F.min_y;
+        G.inv_w = (double)F.grid_cols / (F.max_x - F.min_x);  // float difference, double quotient: data/common.cc:86-87 via camera::base
+        G.inv_h = (double)F.grid_rows / (F.max_y - F.min_y);
+        G.cols = F.grid_cols;
+        G.rows = F.grid_rows;
+        G.nq = nq;
         if (fresh) {
             if (F.res) sv_launch_grid_queries(s, G);
             else sv_launch_grid_build(s, G);
@@ -238,28 +237,25 @@ int in_cells_core(svgpu_ctx* ctx, int nq, const InCellsFrame& F, size_t query_by
             }
             continue;
         }
-        G.cand_idx = A.take<int32_t>(cap);
-        P.dist = A.take<uint32_t>(cap);
         G.cap = P.cap = speculative ? (int)cap : 0;
-        if (A.off > ctx->scratch_bytes) return sv_set_error(ctx, SVGPU_ERR_INVALID, "cell matcher: internal arena overflow");
         sv_launch_grid_fill(s, G);
-        P.tdesc = (const uint32_t*)d_t;
-        P.t_octave = d_toct;
+        P.tdesc = (const uint32_t*)Y.d_t;
+        P.t_octave = Y.d_toct;
         P.nq = nq;
         P.nt = nt;
         P.cand_off = G.cand_off;
         P.cand_idx = G.cand_idx;
         P.cand_skip = nullptr;
-        P.occupied = d_occ;
-        P.t_angle = d_ta;
+        P.occupied = Y.d_occ;
+        P.t_angle = Y.d_ta;
         P.check_orientation = check_orientation;
-        P.t_xright = P.q_xright ? d_tx : nullptr;
-        P.t_xy = d_txy;
-        P.chi_t_xright = P.chi_gate ? d_tx : nullptr;
+        P.t_xright = P.q_xright ? Y.d_tx : nullptr;
+        P.t_xy = Y.d_txy;
+        P.chi_t_xright = P.chi_gate ? Y.d_tx : nullptr;
         P.thr = thr;
         P.lowe_ratio = lowe_ratio;
         P.mode = mode;
-        sv_launch_cand(ctx, s, P, owner, match, mdist);
+        sv_launch_cand(ctx, s, P, Y.owner, Y.match, Y.mdist);
         SV_HIP(ctx, hipGetLastError());
         int32_t num = 0, total_dev = 0;
         Downloads D;

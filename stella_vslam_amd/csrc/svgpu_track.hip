@@ -83,8 +83,6 @@ struct svgpu_tracker {
 };
 
 namespace {
-inline size_t pad256(size_t b) { return (b + 255) & ~size_t(255); }
-
 void release_right(svgpu_tracker* t) {
     if (t->d_in_r) (void)hipFree(t->d_in_r);
     if (t->h_in_r) (void)hipHostFree(t->h_in_r);
@@ -101,13 +99,13 @@ int reserve_right(svgpu_tracker* t, size_t img_bytes, int cap) {
     svgpu_ctx* ctx = t->ctx;
     if (img_bytes <= t->in_r_bytes && cap <= t->r_cap && t->ev_right) return SVGPU_OK;
     release_right(t);
-    SV_HIP(ctx, hipMalloc((void**)&t->d_in_r, pad256(img_bytes)));
-    SV_HIP(ctx, hipHostMalloc((void**)&t->h_in_r, pad256(img_bytes), hipHostMallocDefault));
+    SV_HIP(ctx, hipMalloc((void**)&t->d_in_r, pad(img_bytes)));
+    SV_HIP(ctx, hipHostMalloc((void**)&t->h_in_r, pad(img_bytes), hipHostMallocDefault));
     SV_HIP(ctx, hipMalloc((void**)&t->r_kps, (size_t)cap * sizeof(svgpu_keypoint)));
     SV_HIP(ctx, hipMalloc((void**)&t->r_desc, (size_t)cap * 32));
     SV_HIP(ctx, hipMalloc((void**)&t->r_counts, (1 + SV_MAX_LEVELS) * 4));
     SV_HIP(ctx, hipEventCreateWithFlags(&t->ev_right, hipEventDisableTiming));
-    t->in_r_bytes = pad256(img_bytes), t->r_cap = cap;
+    t->in_r_bytes = pad(img_bytes), t->r_cap = cap;
     return SVGPU_OK;
 }
 
@@ -124,9 +122,9 @@ int reserve_ingest_buffer(svgpu_tracker* t, void** buf, size_t* have, size_t byt
     if (bytes <= *have) return SVGPU_OK;
     if (*buf) SV_HIP(ctx, hipFree(*buf));
     *buf = nullptr, *have = 0;
-    SV_HIP(ctx, hipMalloc(buf, pad256(bytes)));
-    SV_HIP(ctx, hipMemset(*buf, 0, pad256(bytes)));
-    *have = pad256(bytes);
+    SV_HIP(ctx, hipMalloc(buf, pad(bytes)));
+    SV_HIP(ctx, hipMemset(*buf, 0, pad(bytes)));
+    *have = pad(bytes);
     return SVGPU_OK;
 }
 
@@ -153,45 +151,37 @@ int reserve(svgpu_tracker* t, int kp, int q, size_t cand, size_t img_bytes, size
     if (t->obs_n > 0 && t->h_obs) obs_keep.assign(t->h_obs, t->h_obs + t->h_obs_bytes);
     release(t);
     // input block: image | ids of the frame's keypoints (ckp) | ids of the queries (cq) | pose
-    t->in_bytes = pad256(ib) + pad256((size_t)ckp * 4) + pad256((size_t)cq * 4) + 256;
+    t->in_bytes = pad(ib) + pad((size_t)ckp * 4) + pad((size_t)cq * 4) + 256;
     SV_HIP(ctx, hipMalloc((void**)&t->d_in, t->in_bytes));
     SV_HIP(ctx, hipHostMalloc((void**)&t->h_in, t->in_bytes, hipHostMallocDefault));
     t->h_in_bytes = t->in_bytes;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off += pad256(bytes);
-        return o;
+    auto work = [&](Arena& A) {
+        t->cand_off = A.take<int32_t>(cq + 1), t->cand_cnt = A.take<int32_t>(cq), t->match_q = A.take<int32_t>(cq), t->num = A.take<int32_t>(4);
+        t->who = A.take<int32_t>(ckp), t->kp_of = A.take<int32_t>(ckp), t->pred_level = A.take<int32_t>(cq), t->dist = A.take<uint32_t>((size_t)cq * TRACK_SLOT + cc);
+        t->q_valid = A.take<uint8_t>(cq), t->q_blocks = A.take<uint8_t>(cq), t->occupied = A.take<uint8_t>(ckp), t->visible = A.take<uint8_t>(cq);
+        t->outlier_kp = A.take<uint8_t>(ckp), t->po_outlier = A.take<uint8_t>(ckp), t->po_level = A.take<uint8_t>(ckp), t->po_robust = A.take<uint8_t>(ckp);
+        t->reproj = A.take<double>((size_t)cq * 2), t->po_pos = A.take<double>((size_t)ckp * 3), t->x_right = A.take<float>(cq), t->po_uvr = A.take<float>((size_t)ckp * 3);
+        t->po_w = A.take<float>(ckp), t->po_h = A.take<float>(ckp), t->po_result = A.take<int>(4), t->cur_lm_motion = A.take<int32_t>(ckp);
+        t->d_pose = A.take<double>(12);
+        t->g_owner = A.take<int>(ckp), t->g_match = A.take<int>(cq);
     };
-    const size_t o_off = take((size_t)(cq + 1) * 4), o_cnt = take((size_t)cq * 4), o_mq = take((size_t)cq * 4), o_num = take(16), o_who = take((size_t)ckp * 4),
-                 o_kpof = take((size_t)ckp * 4), o_pl = take((size_t)cq * 4), o_dist = take(((size_t)cq * TRACK_SLOT + cc) * 4), o_qv = take(cq), o_qb = take(cq), o_occ = take(ckp),
-                 o_vis = take(cq), o_okp = take(ckp), o_poo = take(ckp), o_pol = take(ckp), o_por = take(ckp), o_rp = take((size_t)cq * 16),
-                 o_pos = take((size_t)ckp * 24), o_xr = take((size_t)cq * 4), o_uvr = take((size_t)ckp * 12), o_w = take((size_t)ckp * 4), o_h = take((size_t)ckp * 4),
-                 o_res = take(16), o_clm = take((size_t)ckp * 4), o_pose = take(96), o_gown = take((size_t)ckp * 4), o_gmat = take((size_t)cq * 4);
-    t->work_bytes = off;
-    SV_HIP(ctx, hipMalloc((void**)&t->d_work, off));
-    SV_HIP(ctx, hipMemset(t->d_work, 0, off));  // (the list allocation counter starts at zero; every chain leaves it at zero again)
-    char* w = t->d_work;
-    t->cand_off = (int32_t*)(w + o_off), t->cand_cnt = (int32_t*)(w + o_cnt), t->match_q = (int32_t*)(w + o_mq), t->num = (int32_t*)(w + o_num);
-    t->who = (int32_t*)(w + o_who), t->kp_of = (int32_t*)(w + o_kpof), t->pred_level = (int32_t*)(w + o_pl), t->dist = (uint32_t*)(w + o_dist);
-    t->q_valid = (uint8_t*)(w + o_qv), t->q_blocks = (uint8_t*)(w + o_qb), t->occupied = (uint8_t*)(w + o_occ), t->visible = (uint8_t*)(w + o_vis);
-    t->outlier_kp = (uint8_t*)(w + o_okp), t->po_outlier = (uint8_t*)(w + o_poo), t->po_level = (uint8_t*)(w + o_pol), t->po_robust = (uint8_t*)(w + o_por);
-    t->reproj = (double*)(w + o_rp), t->po_pos = (double*)(w + o_pos), t->x_right = (float*)(w + o_xr), t->po_uvr = (float*)(w + o_uvr);
-    t->po_w = (float*)(w + o_w), t->po_h = (float*)(w + o_h), t->po_result = (int*)(w + o_res), t->cur_lm_motion = (int32_t*)(w + o_clm);
-    t->d_pose = (double*)(w + o_pose);
-    t->g_owner = (int*)(w + o_gown), t->g_match = (int*)(w + o_gmat);
+    t->work_bytes = arena_measure(work);
+    SV_HIP(ctx, hipMalloc((void**)&t->d_work, t->work_bytes));
+    SV_HIP(ctx, hipMemset(t->d_work, 0, t->work_bytes));  // (the list allocation counter starts at zero; every chain leaves it at zero again)
+    Arena W(t->d_work, t->work_bytes);
+    work(W);
     if (had_pose) SV_HIP(ctx, hipMemcpy(t->d_pose, pose_keep, sizeof pose_keep, hipMemcpyHostToDevice));
     // host results
-    off = 0;
-    const size_t h_st = take(64 * 8), h_n = take(16), h_num = take(16), h_res = take(16), h_pose = take(96), h_out = take(ckp), h_match = take((size_t)cq * 4), h_vis = take(cq),
-                 h_obs = take(ob);
-    t->h_out_bytes = off;
-    SV_HIP(ctx, hipHostMalloc((void**)&t->h_out, off, hipHostMallocDefault));
-    memset(t->h_out, 0, off);
-    char* h = t->h_out;
-    t->h_stamps = (unsigned long long*)(h + h_st);
-    t->h_n = (int32_t*)(h + h_n), t->h_num = (int32_t*)(h + h_num), t->h_result = (int*)(h + h_res), t->h_pose = (double*)(h + h_pose);
-    t->h_outlier = (uint8_t*)(h + h_out), t->h_match = (int32_t*)(h + h_match), t->h_visible = (uint8_t*)(h + h_vis), t->h_obs = h + h_obs;
+    auto results = [&](Arena& A) {
+        t->h_stamps = A.take<unsigned long long>(64);
+        t->h_n = A.take<int32_t>(4), t->h_num = A.take<int32_t>(4), t->h_result = A.take<int>(4), t->h_pose = A.take<double>(12);
+        t->h_outlier = A.take<uint8_t>(ckp), t->h_match = A.take<int32_t>(cq), t->h_visible = A.take<uint8_t>(cq), t->h_obs = A.take<char>(ob);
+    };
+    t->h_out_bytes = arena_measure(results);
+    SV_HIP(ctx, hipHostMalloc((void**)&t->h_out, t->h_out_bytes, hipHostMallocDefault));
+    memset(t->h_out, 0, t->h_out_bytes);
+    Arena H(t->h_out, t->h_out_bytes);
+    results(H);
     t->h_obs_bytes = ob;
     t->cap_kp = ckp, t->cap_q = cq, t->cap_cand = cc, t->img_bytes = ib;
     t->last_n_local = -1;
@@ -452,7 +442,7 @@ int track_motion(svgpu_tracker* t, svgpu_ctx* ctx_right, svgpu_frame* cur, const
     for (int attempt = 0; attempt < 2; ++attempt) {
         const bool extract = img && attempt == 0;
         // ---- input block: [image] | last frame's landmark ids, one copy
-        const size_t o_ids = pad256(t->img_bytes);
+        const size_t o_ids = pad(t->img_bytes);
         if (extract) {
             if (stride == pitch_l) memcpy(t->h_in, img, img_bytes);
             else
@@ -681,7 +671,7 @@ int svgpu_track_local_map(svgpu_tracker* t, const svgpu_frame* cur, const int32_
     if ((rc = reserve(t, nt, n_local, t->cap_cand, t->img_bytes, t->h_obs_bytes))) return rc;
     for (int attempt = 0; attempt < 2; ++attempt) {
         // ---- input block (behind the image area): the frame's landmark ids | the local landmarks' ids, one copy
-        const size_t o_cur = pad256(t->img_bytes), o_loc = o_cur + pad256((size_t)t->cap_kp * 4);
+        const size_t o_cur = pad(t->img_bytes), o_loc = o_cur + pad((size_t)t->cap_kp * 4);
         if (nt > 0) memcpy(t->h_in + o_cur, cur_lm_ids, (size_t)nt * 4);
         if (n_local > 0) memcpy(t->h_in + o_loc, local_ids, (size_t)n_local * 4);
         std::unique_lock<std::mutex> lock(t->map->mtx);

@@ -14,13 +14,8 @@ bool view_ok(const svgpu_triangulate_view& v) {
            && (v.n == 0 || (v.xy && v.octave && v.bearings));
 }
 
-size_t view_bytes(const svgpu_triangulate_view& v) {
-    const size_t n = (size_t)v.n;
-    return pad(n * 8) + pad(n * 4) + pad(n * 24) + (v.xright ? pad(n * 4) : 0) + (v.depth ? pad(n * 4) : 0);
-}
-
 // camera, pose and derived constants of one side; the keypoint arrays go into the arena
-int stage_view(svgpu_ctx* ctx, hipStream_t s, Arena& A, const svgpu_triangulate_view& v, float scale_factor_1, TriView& T) {
+int stage_view(svgpu_ctx* ctx, hipStream_t s, UploadArena& A, const svgpu_triangulate_view& v, float scale_factor_1, TriView& T) {
     T.cam = *v.cam;
     std::memcpy(T.pose_cw, v.pose_cw, sizeof T.pose_cw);
     const double* P = v.pose_cw;
@@ -32,23 +27,13 @@ int stage_view(svgpu_ctx* ctx, hipStream_t s, Arena& A, const svgpu_triangulate_
     T.ratio_factor = 2.0f * std::max(scale_factor_1, v.scale_factor);
     T.n = v.n;
     const size_t n = (size_t)v.n;
-    int rc;
-#define UPV(field, T_, cnt)                                                    \
-    {                                                                          \
-        T_* d = nullptr;                                                       \
-        if (v.field) {                                                         \
-            d = A.take<T_>(cnt);                                               \
-            if ((cnt) && (rc = A.upload(ctx, s, d, v.field, (cnt) * sizeof(T_)))) return rc; \
-        }                                                                      \
-        T.field = d;                                                           \
-    }
-    UPV(xy, float, n * 2)
-    UPV(octave, int32_t, n)
-    UPV(bearings, double, n * 3)
-    UPV(xright, float, n)
-    UPV(depth, float, n)
-#undef UPV
-    return SVGPU_OK;
+    int rc = SVGPU_OK;
+    T.xy = A.put(ctx, s, v.xy, n * 2, true, rc);
+    T.octave = A.put(ctx, s, v.octave, n, true, rc);
+    T.bearings = A.put(ctx, s, v.bearings, n * 3, true, rc);
+    T.xright = A.put(ctx, s, v.xright, n, true, rc);
+    T.depth = A.put(ctx, s, v.depth, n, true, rc);
+    return rc;
 }
 
 int tri_core(svgpu_ctx* ctx, const char* who, const svgpu_triangulate_view* v1, const svgpu_triangulate_view* nb, int K, const int32_t* off,
@@ -84,32 +69,28 @@ int tri_core(svgpu_ctx* ctx, const char* who, const svgpu_triangulate_view* v1, 
     }
     SV_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    size_t need = view_bytes(*v1) + pad((size_t)K * sizeof(TriView)) + pad((size_t)K * 4) + 3 * pad((size_t)M * 4) + pad((size_t)M * 24) + pad(M) + 4096;
-    for (int k = 0; k < K; ++k) need += view_bytes(nb[k]);
+    TriProblem P{};
+    std::vector<TriView> views(K);
+    auto layout = [&](UploadArena& A) -> int {
+        int rc = stage_view(ctx, s, A, *v1, v1->scale_factor, P.v1);
+        for (int k = 0; k < K && !rc; ++k) rc = stage_view(ctx, s, A, nb[k], v1->scale_factor, views[k]);
+        P.nb = A.put(ctx, s, views.data(), K, true, rc);  // (the views carry device pointers: staged above, copied here)
+        P.nb_first = A.put(ctx, s, nb_first.data(), K, true, rc);
+        P.nb_of_match = A.put(ctx, s, nb_of.data(), M, true, rc);
+        P.idx1 = A.put(ctx, s, idx1, M, true, rc);
+        P.idx2 = A.put(ctx, s, idx2, M, true, rc);
+        if (!rc) rc = A.flush(ctx, s);
+        P.pos_w = A.take<double>((size_t)M * 3);
+        P.status = A.take<uint8_t>(M);
+        return rc;
+    };
+    const size_t need = arena_measure<UploadArena>(layout);
     int rc;
     if ((rc = sv_ensure_scratch(ctx, need))) return rc;
     if ((rc = sv_ensure_stage(ctx, need))) return rc;
-    Arena A(ctx->d_scratch);
-    A.mirror = ctx->h_stage;
-    TriProblem P{};
-    if ((rc = stage_view(ctx, s, A, *v1, v1->scale_factor, P.v1))) return rc;
-    std::vector<TriView> views(K);
-    for (int k = 0; k < K; ++k)
-        if ((rc = stage_view(ctx, s, A, nb[k], v1->scale_factor, views[k]))) return rc;
-    TriView* d_views = A.take<TriView>(K);
-    int32_t* d_first = A.take<int32_t>(K);
-    int32_t* d_nb_of = A.take<int32_t>(M);
-    int32_t* d_idx1 = A.take<int32_t>(M);
-    int32_t* d_idx2 = idx2 ? A.take<int32_t>(M) : nullptr;
-    if ((rc = A.upload(ctx, s, d_views, views.data(), (size_t)K * sizeof(TriView)))) return rc;
-    if ((rc = A.upload(ctx, s, d_first, nb_first.data(), (size_t)K * 4))) return rc;
-    if ((rc = A.upload(ctx, s, d_nb_of, nb_of.data(), (size_t)M * 4))) return rc;
-    if ((rc = A.upload(ctx, s, d_idx1, idx1, (size_t)M * 4))) return rc;
-    if (idx2 && (rc = A.upload(ctx, s, d_idx2, idx2, (size_t)M * 4))) return rc;
-    if ((rc = A.flush(ctx, s))) return rc;
-    P.pos_w = A.take<double>((size_t)M * 3);
-    P.status = A.take<uint8_t>(M);
-    P.nb = d_views, P.nb_first = d_first, P.nb_of_match = d_nb_of, P.idx1 = d_idx1, P.idx2 = d_idx2;
+    UploadArena A(ctx, ctx->h_stage);
+    if ((rc = layout(A))) return rc;
+    if (A.overflow) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_triangulate_two_views: internal arena overflow");
     P.num_matches = M;
     for (int l = 0; l < num_levels; ++l) P.scale_factors[l] = scale_factors[l], P.level_sigma_sq[l] = level_sigma_sq[l];
     P.cos_rays_parallax_thr = (float)std::cos(rays_parallax_deg_thr * M_PI / 180.0);  // two_view_triangulator.cc:17 (a float member)
