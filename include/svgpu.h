@@ -716,6 +716,63 @@ int svgpu_bow_transform(svgpu_ctx* ctx, const svgpu_vocabulary* vocab, const uin
 int svgpu_fbow_transform(svgpu_ctx* ctx, const svgpu_vocabulary* vocab, const uint8_t* desc, int n, int store_level, int k,
                          int32_t* word_id, float* weight, uint32_t* node_code);
 
+/* ------------------------------------------------------------------------------ keyframe BoW database
+ * data::bow_database (data/bow_database.h:20-100, data/bow_database.cc:21-159): the candidates of module::relocalizer::relocalize
+ * (module/relocalizer.cc:58) and module::loop_detector::detect_loop_candidates (module/loop_detector.cc:83-129), resident on the device.
+ * A BoW vector is n_words (word id, weight) pairs with STRICTLY ascending ids (the iteration order of the reference's std::map), weights
+ * as doubles (what compute_bow hands out).  The database keeps a forward index -- per keyframe its ids and weights in two pools, and a slot
+ * table -- and scans it per query; the reference's inverted index keyfrms_in_node_ has no device counterpart, by design.
+ * acquire (data/bow_database.cc:58-96), per query:
+ *   1. common = shared word ids with every live keyframe that is not rejected (compute_num_common_words, :98-129); keyframes with
+ *      common == 0 do not exist for the rest of the query; none at all: empty result, max_common = 0
+ *   2. max_common = the largest count (:72-77); thr = (unsigned)(ratio * max_common), a float product truncated (:78)
+ *   3. survivors: thr < common, strict (:143); each is scored; dropped iff min_score > score (:147), a score equal to min_score stays
+ *   4. the kept keyframes in ASCENDING SLOT order (the reference returns them in unordered_set order, which is unspecified), each with its
+ *      common and score
+ * score(query, keyframe) (data/bow_vocabulary.cc:9-16), chosen at creation like the build switch USE_DBOW2; v = the query's weight of a
+ * shared word, w = the keyframe's, shared words added one after another in ascending word order:
+ *   SVGPU_BOW_SCORE_FBOW_L2   the DEFAULT build, fbow::BoWVector::score: weights rounded to float, s += (double)(v * w) with the product
+ *                             in fp32; score = s >= 1 ? 1 : 1 - sqrt(1 - s) in fp64, returned as float
+ *   SVGPU_BOW_SCORE_DBOW2_L1  USE_DBOW2, DBoW2's L1Scoring::score: s += fabs(v - w) - fabs(v) - fabs(w) in fp64; score = -s / 2 as float
+ * Both forms are restated from the libraries' published sources (neither is in the reference checkout): parity unpinned.
+ * Against a sequential host loop of these definitions the counts, the candidate lists and the scores are equal bit for bit.
+ * Every call is synchronous (one synchronisation at its end); calls on one database are serialised by a mutex, as bow_database::mtx_ does. */
+#define SVGPU_BOW_SCORE_FBOW_L2 0
+#define SVGPU_BOW_SCORE_DBOW2_L1 1
+typedef struct svgpu_bowdb svgpu_bowdb;
+int svgpu_bowdb_create(svgpu_ctx* ctx, int score_form, svgpu_bowdb** db);
+void svgpu_bowdb_destroy(svgpu_bowdb* db);
+/* bow_database::clear (data/bow_database.cc:52-56): every keyframe gone, slot numbers start again at 0 (the allocations are kept) */
+int svgpu_bowdb_clear(svgpu_ctx* ctx, svgpu_bowdb* db);
+/* bow_database::add_keyframe (data/bow_database.cc:21-28).  *slot: the keyframe's number; slots are handed out in increasing order and not
+ * reused before clear, so ascending slot order is insertion order.  Ids that do not ascend strictly: SVGPU_ERR_INVALID. */
+int svgpu_bowdb_add(svgpu_ctx* ctx, svgpu_bowdb* db, int n_words, const uint32_t* words, const double* weights, int32_t* slot);
+/* bow_database::erase_keyframe (data/bow_database.cc:30-50); an erased or unknown slot is ignored, as the reference ignores a keyframe it
+ * does not hold.  Erased spans of the pools are reclaimed by a compaction once they exceed half of what the pools hold. */
+int svgpu_bowdb_erase(svgpu_ctx* ctx, svgpu_bowdb* db, int32_t slot);
+int svgpu_bowdb_size(svgpu_bowdb* db, int* live_keyframes, long long* live_entries);
+/* slots handed out since the last clear, pool capacity / fill in entries, pool growths and compactions since creation (all nullable) */
+int svgpu_bowdb_diagnostics(svgpu_bowdb* db, long long* num_slots, long long* pool_capacity, long long* pool_used, long long* num_growths,
+                            long long* num_compactions);
+/* word ids of a query a workgroup holds in LDS at a time; a longer query is processed in chunks, with the same results */
+int svgpu_bowdb_query_stage_capacity(void);
+/* bow_database::acquire_keyframes (data/bow_database.cc:58-96).  reject_slots: keyfrms_to_reject as slot numbers (unknown or erased ones
+ * are ignored).  out_*: `cap` entries each; when more than cap keyframes pass, the first cap in slot order are written and *n_out is the
+ * full count.  max_common: nullable. */
+int svgpu_bowdb_acquire(svgpu_ctx* ctx, svgpu_bowdb* db, int n_words, const uint32_t* words, const double* weights, float min_score, float ratio,
+                        int n_reject, const int32_t* reject_slots, int cap, int32_t* out_slots, uint32_t* out_common, float* out_score, int32_t* n_out,
+                        uint32_t* max_common);
+/* num_queries queries in one submission (a batch of lost frames; an offline loop search of a whole map): query q is entries
+ * q_off[q] .. q_off[q + 1] of words / weights (q_off[0] = 0) with its own min_score[q]; ratio and the reject list are shared; results of
+ * query q at q * cap, n_out / max_common per query.  Every query's outputs equal the single call's bit for bit. */
+int svgpu_bowdb_acquire_batch(svgpu_ctx* ctx, svgpu_bowdb* db, int num_queries, const int32_t* q_off, const uint32_t* words, const double* weights,
+                              const float* min_score, float ratio, int n_reject, const int32_t* reject_slots, int cap, int32_t* out_slots,
+                              uint32_t* out_common, float* out_score, int32_t* n_out, uint32_t* max_common);
+/* The score of the query against each of n listed slots, whatever they share (loop_detector::compute_min_score_in_covisibilities,
+ * module/loop_detector.cc:278-297); an erased or unknown slot gives -1. */
+int svgpu_bowdb_score(svgpu_ctx* ctx, svgpu_bowdb* db, int n_words, const uint32_t* words, const double* weights, int n, const int32_t* slots,
+                      float* out_score);
+
 /* match::stereo::compute (match/stereo.cc:20-114): for every left keypoint the closest right keypoint in its row band
  * (rows +-2*scale, octave +-1, disparity in [0, focal_x_baseline / true_baseline], Hamming < 75), then the 11x11 L1 patch
  * slide (+-5 px) on the keypoint's pyramid level with parabolic sub-pixel refinement, finally the 2x-median correlation

@@ -208,6 +208,110 @@ class bow_vocabulary:
             pass
 
 
+def bowdb_query_stage_capacity() -> int:
+    """Word ids of a query that k_bowdb_count / k_bowdb_score hold in LDS at a time (a longer query is walked in chunks)."""
+    return int(lib().svgpu_bowdb_query_stage_capacity())
+
+
+def _bow_arrays(bow_vec):
+    """{word: weight} (or a (words, weights) pair) -> ascending uint32 ids and float64 weights, the order of the reference's std::map"""
+    if isinstance(bow_vec, dict):
+        items = sorted(bow_vec.items())
+        return np.array([k for k, _ in items], np.uint32), np.array([v for _, v in items], np.float64)
+    w, v = bow_vec
+    return np.ascontiguousarray(w, np.uint32), np.ascontiguousarray(v, np.float64)
+
+
+class bow_database:
+    """data/bow_database.h on the device (include/svgpu.h svgpu_bowdb_*): keyframes are known by the slot number add_keyframe returns
+    (increasing, not reused before clear).  `framework` selects the score like bow_vocabulary's: "fbow" = fbow::BoWVector::score
+    (the default build), "dbow2" = DBoW2's L1 score (USE_DBOW2); both restated from the published sources: parity unpinned.
+    BoW vectors are the {word: weight} dicts bow_vocabulary.transform returns."""
+
+    def __init__(self, ctx: Context, framework: str = "fbow"):
+        if framework not in ("dbow2", "fbow"):
+            raise ValueError(f"unknown BoW framework {framework!r}")
+        self.ctx, self.framework_ = ctx, framework
+        self._h = C.c_void_p()
+        ctx.check(lib().svgpu_bowdb_create(ctx.handle, 0 if framework == "fbow" else 1, C.byref(self._h)), "svgpu_bowdb_create")
+
+    def add_keyframe(self, bow_vec) -> int:
+        w, v = _bow_arrays(bow_vec)
+        slot = C.c_int32(-1)
+        self.ctx.check(lib().svgpu_bowdb_add(self.ctx.handle, self._h, len(w), _p(w), _p(v), C.byref(slot)), "svgpu_bowdb_add")
+        return slot.value
+
+    def erase_keyframe(self, slot: int):
+        self.ctx.check(lib().svgpu_bowdb_erase(self.ctx.handle, self._h, int(slot)), "svgpu_bowdb_erase")
+
+    def clear(self):
+        self.ctx.check(lib().svgpu_bowdb_clear(self.ctx.handle, self._h), "svgpu_bowdb_clear")
+
+    def size(self):
+        """-> (live keyframes, live entries)"""
+        k, e = C.c_int(0), C.c_longlong(0)
+        lib().svgpu_bowdb_size(self._h, C.byref(k), C.byref(e))
+        return k.value, e.value
+
+    def diagnostics(self) -> dict:
+        v = [C.c_longlong(0) for _ in range(5)]
+        lib().svgpu_bowdb_diagnostics(self._h, *[C.byref(x) for x in v])
+        return dict(zip(("num_slots", "pool_capacity", "pool_used", "num_growths", "num_compactions"), (x.value for x in v)))
+
+    def acquire_keyframes(self, bow_vec, min_score: float = 0.0, num_common_words_thr_ratio: float = 0.8, reject=(), cap: int | None = None,
+                          full: bool = False):
+        """-> (slots, common, score) of the candidates in ascending slot order; `cap` limits what is written (default: every slot).
+        full=True: -> (slots, common, score, n_out, max_common), n_out counting the candidates beyond `cap` as well."""
+        w, v = _bow_arrays(bow_vec)
+        rej = np.ascontiguousarray(list(reject), np.int32)
+        cap = self.diagnostics()["num_slots"] if cap is None else int(cap)
+        slots, common, score = np.zeros(cap, np.int32), np.zeros(cap, np.uint32), np.zeros(cap, np.float32)
+        n, mc = C.c_int32(0), C.c_uint32(0)
+        self.ctx.check(lib().svgpu_bowdb_acquire(self.ctx.handle, self._h, len(w), _p(w), _p(v), C.c_float(min_score), C.c_float(num_common_words_thr_ratio),
+                                                 len(rej), _p(rej), cap, _p(slots), _p(common), _p(score), C.byref(n), C.byref(mc)), "svgpu_bowdb_acquire")
+        k = min(n.value, cap)
+        r = (slots[:k], common[:k], score[:k])
+        return r + (n.value, mc.value) if full else r
+
+    def acquire_keyframes_batch(self, bow_vecs, min_scores=0.0, num_common_words_thr_ratio: float = 0.8, reject=(), cap: int | None = None):
+        """One submission for len(bow_vecs) queries -> a list of (slots, common, score, n_out, max_common), one per query."""
+        arrs = [_bow_arrays(b) for b in bow_vecs]
+        q = len(arrs)
+        if q == 0:
+            return []
+        off = np.zeros(q + 1, np.int32)
+        off[1:] = np.cumsum([len(w) for w, _ in arrs])
+        w = np.ascontiguousarray(np.concatenate([a for a, _ in arrs]), np.uint32)
+        v = np.ascontiguousarray(np.concatenate([a for _, a in arrs]), np.float64)
+        ms = np.ascontiguousarray(np.broadcast_to(np.asarray(min_scores, np.float32), (q,)))
+        rej = np.ascontiguousarray(list(reject), np.int32)
+        cap = self.diagnostics()["num_slots"] if cap is None else int(cap)
+        slots, common, score = np.zeros((q, cap), np.int32), np.zeros((q, cap), np.uint32), np.zeros((q, cap), np.float32)
+        n, mc = np.zeros(q, np.int32), np.zeros(q, np.uint32)
+        self.ctx.check(lib().svgpu_bowdb_acquire_batch(self.ctx.handle, self._h, q, _p(off), _p(w), _p(v), _p(ms), C.c_float(num_common_words_thr_ratio),
+                                                       len(rej), _p(rej), cap, _p(slots), _p(common), _p(score), _p(n), _p(mc)), "svgpu_bowdb_acquire_batch")
+        return [(slots[i, :min(n[i], cap)], common[i, :min(n[i], cap)], score[i, :min(n[i], cap)], int(n[i]), int(mc[i])) for i in range(q)]
+
+    def score(self, bow_vec, slots) -> np.ndarray:
+        """bow_vocabulary_util::score of the query against each listed slot (-1 for an erased or unknown one)."""
+        w, v = _bow_arrays(bow_vec)
+        sl = np.ascontiguousarray(slots, np.int32)
+        out = np.zeros(len(sl), np.float32)
+        self.ctx.check(lib().svgpu_bowdb_score(self.ctx.handle, self._h, len(w), _p(w), _p(v), len(sl), _p(sl), _p(out)), "svgpu_bowdb_score")
+        return out
+
+    def close(self):
+        if self._h:
+            lib().svgpu_bowdb_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # ------------------------------------------------------------------------------------------- .fbow vocabulary files
 # data::bow_vocabulary_util::load (data/bow_vocabulary.cc:26-47) hands the path to fbow::Vocabulary::readFromFile in the default
 # (FBoW) build.  FBoW is an un-vendored submodule (3rd/FBoW is empty in the checkout studied; the reference pins stella-cv/FBoW),

@@ -187,6 +187,7 @@ struct frame_observation {
     unsigned int num_grid_cols_ = 64, num_grid_rows_ = 48;
 };
 using bow_feature_vector = std::map<unsigned int, std::vector<unsigned int>>;  // data/bow_vocabulary_fwd.h (fbow::BoWFeatVector)
+using bow_vector = std::map<unsigned int, double>;  // data/bow_vocabulary_fwd.h (fbow::BoWVector / DBoW2::BowVector): word id -> weight, as compute_bow hands it out
 
 template <class T>
 struct id_less {  // type.h: ordering of the weak_ptr keys of landmark::observations_t by id (T = std::weak_ptr<keyframe>)
@@ -342,6 +343,7 @@ public:
     camera::base* camera_;
     const feature::orb_params* orb_params_;
     frame_observation frm_obs_;
+    bow_vector bow_vec_;
     bow_feature_vector bow_feat_vec_;
     std::unique_ptr<graph_node> graph_node_;
     std::vector<std::shared_ptr<landmark>> landmarks_;

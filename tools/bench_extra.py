@@ -144,4 +144,7 @@ out["local_ba_config3_ms"] = {"gpu": round(g, 3), "lm_iterations": int(r["stats"
 sc5 = S.ba_scene(num_kf=100, num_lm=40000, obs_per_lm=6, num_fixed=1, seed=9, loop=True)
 g, r = timeit(lambda: ba.optimize_global_flat(sc5, num_iter=10), 3, 1)
 out["global_ba_100kf_40k_landmarks_ms"] = {"gpu": round(g, 3), "observations": int(len(sc5["obs_pose"])), "lm_iterations": int(r["stats"]["iters_stage1"])}
+# ---- keyframe BoW database: loop / relocalisation candidates (HIP events; tools/bench_bowdb.py)
+import bench_bowdb
+out["bow_database_acquire"] = bench_bowdb.run(ctx)
 print(json.dumps(out))
