@@ -787,6 +787,7 @@ int svgpu_stereo_match(svgpu_ctx* ctx_left, svgpu_ctx* ctx_right, const svgpu_ke
  * descriptors / counts are the outputs of svgpu_orb_extract_batch_device on ctx_left and ctx_right (pair p at p * cap records,
  * count at n_*_dev[p * n_stride]), the pyramids those calls left in the two contexts.  The 2 x median correlation filter runs on the
  * device as well (rank-size/2 value by bisection).  stereo_x_right_dev / depths_dev: pairs * cap floats (-1 = no match).
+ * Only the first min(n_left, cap) entries of a pair are written; the entries behind a pair's left count keep what the buffers held.
  * Asynchronous on `stream` (NULL = ctx_left's); the caller orders it behind both extractions. */
 int svgpu_stereo_match_batch_device(svgpu_ctx* ctx_left, svgpu_ctx* ctx_right, int pairs, const svgpu_keypoint* kps_left_dev, const uint8_t* desc_left_dev,
                                     const int32_t* n_left_dev, const svgpu_keypoint* kps_right_dev, const uint8_t* desc_right_dev,
