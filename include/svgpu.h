@@ -665,6 +665,56 @@ int svgpu_triangulate_two_views_batch(svgpu_ctx* ctx, const svgpu_triangulate_vi
                                       const int32_t* match_off, const float* scale_factors, const float* level_sigma_sq, int num_levels,
                                       float rays_parallax_deg_thr, const int32_t* idx1, const int32_t* idx2, double* pos_w, uint8_t* status, int* num_accepted);
 
+/* ------------------------------------------------------------------------------ PnP pose from 2D-3D matches (EPnP + RANSAC)
+ * solve::pnp_solver (solve/pnp_solver.cc): the pose step of module::relocalizer::relocalize_by_pnp_solver (module/relocalizer.cc:134-209)
+ * and of module::loop_detector (module/loop_detector.cc:423-446), for every candidate keyframe in one call.  fp64, one wavefront per
+ * correspondence set or RANSAC hypothesis; Eigen's JacobiSVD is replaced by Jacobi iterations of the project's own, so singular vectors
+ * may differ from Eigen's in sign and, inside a null space, in basis.
+ *
+ * svgpu_pnp_compute_pose: pnp_solver::compute_pose (:155-206) for num_sets correspondence sets; set s is entries set_off[s] ..
+ * set_off[s + 1] of bearings / pos_w (n x 3 doubles each; set_off[0] = 0, every set holds at least 4 correspondences).
+ *   choose_control_points (:208-238), compute_barycentric_coordinates with the D(i) > 1e-6 pseudo-inverse rule (:240-275), M^T M and its
+ *   singular vectors 11 - j, compute_L_6x10 / compute_rho (:502-548), find_initial_betas_2 / _3 / _4 with every sign rule (:386-500),
+ *   gauss_newton with gauss_newton_num_iter Householder-QR steps (:550-579), compute_ccs / compute_pcs with the z-sign flip (:303-334),
+ *   estimate_R_and_t with the det < 0 repair (:350-384), reprojection_error (:336-348) and the strict `<` choice over N = 2, 3, 4.
+ *   pose_cw        num_sets x 12: rows 0..2 of [rot_cw | trans_cw], row-major (as svgpu_triangulate_view::pose_cw); NaN when no N
+ *                  gave a comparable error (the reference leaves its outputs untouched)
+ *   reproj_error   num_sets: the value compute_pose returns
+ * Non-monotone offsets or a set of fewer than 4 are SVGPU_ERR_INVALID before anything is launched; num_sets == 0 is a success. */
+int svgpu_pnp_compute_pose(svgpu_ctx* ctx, int num_sets, const int32_t* set_off, const double* bearings, const double* pos_w,
+                           int gauss_newton_num_iter, double* pose_cw, double* reproj_error);
+
+/* pnp_solver::find_via_ransac (:44-124) for num_problems problems (candidate keyframes) at once; problem p is entries match_off[p] ..
+ * match_off[p + 1] of bearings / pos_w / octaves / is_inlier (match_off[0] = 0, a problem may be empty).
+ *   scale_factors / num_levels   orb_params::scale_factors_; max_cos_errors_ is computed here, on the host, as the constructor does
+ *                  (:27-32): util::cos(scale_factors[octave] * pi / 180), a float
+ *   samples        num_problems x num_iter x 4 indices local to their problem: what util::create_random_array(4, 0, n - 1, engine)
+ *                  (util/random_array.cc:26-63) returned for every iteration (:73).  The table is an input: the engine is host state,
+ *                  and with the draws made elsewhere the device is deterministic.  Entries of a problem that does not run are not read.
+ *   per hypothesis compute_pose of the four sampled correspondences, check_inliers (:126-153: max_cos_error < cos_angle, strict; the cost
+ *                  adds 1 - cos_angle for an inlier and 1 - max_cos_error for an outlier)
+ *   selection      in iteration order, num_inliers > min_num_inliers && min_cost > cost, both strict (:95): the first of equal costs
+ *                  stays, a NaN cost never wins; valid = min_cost < DBL_MAX (:103)
+ *   recompute      != 0: compute_pose over the winner's inliers, in ascending index order, replaces the pose of a valid problem (:109-123)
+ *                  -- unless no N gave it a comparable error: the pose then stays the winning hypothesis', as the reference leaves it
+ *   valid / pose_cw / best_iter   per problem; best_iter is the winning iteration or -1, pose_cw is zero when invalid
+ *   is_inlier      one byte per match: the winner's flags, zero when invalid
+ *   hyp_pose / hyp_num_inliers / hyp_cost   nullable diagnostics, num_problems x num_iter (x 12): what every hypothesis gave (zero for a
+ *                  problem that did not run)
+ * A problem with fewer than 4 or fewer than min_num_inliers matches is valid = 0 and launches nothing for itself (:49-52).
+ * SVGPU_ERR_INVALID before anything is launched: an octave outside [0, num_levels), a sample index outside its problem, an index repeated
+ * within one sample, non-monotone offsets.  num_problems == 0 is a success.  Host in/out, synchronous, one synchronisation per call. */
+int svgpu_pnp_ransac_batch(svgpu_ctx* ctx, int num_problems, const int32_t* match_off, const double* bearings, const double* pos_w,
+                           const int32_t* octaves, const float* scale_factors, int num_levels, int min_num_inliers, int num_iter,
+                           const uint32_t* samples, int recompute, int gauss_newton_num_iter, uint8_t* valid, double* pose_cw,
+                           uint8_t* is_inlier, int32_t* best_iter, double* hyp_pose, int32_t* hyp_num_inliers, double* hyp_cost);
+
+/* One problem: the batch of one, bit for bit. */
+int svgpu_pnp_ransac(svgpu_ctx* ctx, const double* bearings, const double* pos_w, const int32_t* octaves, int num_matches,
+                     const float* scale_factors, int num_levels, int min_num_inliers, int num_iter, const uint32_t* samples, int recompute,
+                     int gauss_newton_num_iter, uint8_t* valid, double* pose_cw, uint8_t* is_inlier, int32_t* best_iter, double* hyp_pose,
+                     int32_t* hyp_num_inliers, double* hyp_cost);
+
 /* bow_tree::match_frame_and_keyframe (match/bow_tree.cc:169-256) and bow_tree::match_keyframes (:258-366).
  * Side 1 = the keyframe whose landmarks are handed over (queries: valid1 = keypoint holds a live landmark), side 2 = the frame /
  * the other keyframe (valid2 nullable = every keypoint, or "holds a live landmark" for match_keyframes; occupied2 nullable = keypoints

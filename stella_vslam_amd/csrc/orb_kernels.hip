@@ -9,6 +9,7 @@
 // All integer stages are bit-exact by construction; the fp32 stages replicate the reference's
 // operation order with contraction disabled (-ffp-contract=off, checked in the disassembly).
 #include "svgpu_internal.h"
+#include "sv_trig.h"
 #include <cstdlib>
 #include <utility>
 
@@ -1010,28 +1011,9 @@ __device__ __forceinline__ float dev_fast_atan2(float y, float x) {  // cv::fast
     return a;
 }
 
-__device__ __forceinline__ float dev_cos_poly(float v) {  // util/trigonometric.h:17-24
-    const float c1 = 0.99940307f, c2 = -0.49558072f, c3 = 0.03679168f;
-    const float v2 = v * v;
-    return c1 + v2 * (c2 + c3 * v2);
-}
-__device__ __forceinline__ float dev_util_cos(float v) {  // util/trigonometric.h:26-42
-    constexpr float PI_ = 3.14159265358979f;
-    constexpr float PI_2 = PI_ / 2.0f;
-    constexpr float TWO_PI = 2.0f * PI_;
-    constexpr float INV_TWO_PI = 1.0f / TWO_PI;
-    constexpr float THREE_PI_2 = 3.0f * PI_2;
-    v = v - (float)(int)floorf(v * INV_TWO_PI) * TWO_PI;
-    v = (0.0f < v) ? v : -v;
-    if (v < PI_2) return dev_cos_poly(v);
-    else if (v < PI_) return -dev_cos_poly(PI_ - v);
-    else if (v < THREE_PI_2) return -dev_cos_poly(v - PI_);
-    else return dev_cos_poly(TWO_PI - v);
-}
-__device__ __forceinline__ float dev_util_sin(float v) {
-    constexpr float PI_2 = 3.14159265358979f / 2.0f;
-    return dev_util_cos(PI_2 - v);
-}
+// util::cos / util::sin (util/trigonometric.h): the restatement shared with the host lives in sv_trig.h
+__device__ __forceinline__ float dev_util_cos(float v) { return sv_util_cos(v); }
+__device__ __forceinline__ float dev_util_sin(float v) { return sv_util_sin(v); }
 
 __device__ __forceinline__ int wave_sum(int v) {
     // row scans with DPP adds (one VALU instruction each, no LDS round trip), then the row totals across rows; the wave total
