@@ -400,26 +400,35 @@ __device__ __forceinline__ BlurRow blur_load(const uint8_t* __restrict__ row, in
     }
     return r;
 }
-// Horizontal 7-tap sums of the 4 owned columns for TWO image rows at once: pixel k of row a and of row b travel as the
-// two 16-bit halves of one register (v_perm_b32 gathers them), so every packed multiply-add serves both rows.
-// 256 * 255 = 65280 fits 16 bits exactly.
+// Horizontal 7-tap sums of the 4 owned columns for TWO image rows at once.  Pixels and taps are bytes: the sum of owned pixel j is the
+// byte dot product (v_dot4_u32_u8) of the 12-byte window with the taps shifted to window bytes j + 1 .. j + 7 -- no unpacking.  Window
+// byte i is pixel x0 - 4 + i, tap t of pixel j multiplies pixel x0 + j - 3 + t: byte i carries tap i - j - 1.  Two of the twelve tap
+// words are empty (pixel 0 never reaches w2, pixel 3 never reaches w0): ten dot products per row.  The sums of row a and row b then share
+// one register as its 16-bit halves (v_lshl_or_b32), which is what the vertical v_dot2_u32_u16 takes.  256 * 255 = 65280 fits 16 bits exactly.
+constexpr uint32_t BLUR_TAPS[7] = {18, 34, 48, 56, 48, 34, 18};
+constexpr uint32_t blur_tap_word(int j, int word) {  // the taps of owned pixel j that fall on window word `word`, tap of byte k at bits 8 k
+    uint32_t t = 0;
+    for (int k = 0; k < 4; ++k) {
+        const int i = 4 * word + k - j - 1;
+        if (i >= 0 && i < 7) t |= BLUR_TAPS[i] << (8 * k);
+    }
+    return t;
+}
+static_assert(blur_tap_word(0, 0) == 0x30221200u && blur_tap_word(0, 1) == 0x12223038u && blur_tap_word(0, 2) == 0u && blur_tap_word(3, 0) == 0u &&
+              blur_tap_word(3, 1) == 0x38302212u && blur_tap_word(3, 2) == 0x00122230u, "blur tap words");
+template <int J>
+__device__ __forceinline__ uint32_t blur_hsum(const BlurRow& r) {
+    constexpr uint32_t t0 = blur_tap_word(J, 0), t1 = blur_tap_word(J, 1), t2 = blur_tap_word(J, 2);
+    uint32_t s = __builtin_amdgcn_udot4(r.w1, t1, 0u, false);
+    if (t0) s = __builtin_amdgcn_udot4(r.w0, t0, s, false);
+    if (t2) s = __builtin_amdgcn_udot4(r.w2, t2, s, false);
+    return s;
+}
 __device__ __forceinline__ void blur_hpair(const BlurRow& a, const BlurRow& b, u16x2 (&hp)[4]) {
-    u16x2 q[10];  // pixels x0-3 .. x0+6
-#define SV_PK(WA, WB, K) as_u16x2(__builtin_amdgcn_perm(WB, WA, 0x0c000c00u | ((4u + K) << 16) | K))
-    q[0] = SV_PK(a.w0, b.w0, 1u);
-    q[1] = SV_PK(a.w0, b.w0, 2u);
-    q[2] = SV_PK(a.w0, b.w0, 3u);
-    q[3] = SV_PK(a.w1, b.w1, 0u);
-    q[4] = SV_PK(a.w1, b.w1, 1u);
-    q[5] = SV_PK(a.w1, b.w1, 2u);
-    q[6] = SV_PK(a.w1, b.w1, 3u);
-    q[7] = SV_PK(a.w2, b.w2, 0u);
-    q[8] = SV_PK(a.w2, b.w2, 1u);
-    q[9] = SV_PK(a.w2, b.w2, 2u);
-#undef SV_PK
-    const u16x2 t18 = {18, 18}, t34 = {34, 34}, t48 = {48, 48}, t56 = {56, 56};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) hp[j] = t18 * (q[j] + q[j + 6]) + t34 * (q[j + 1] + q[j + 5]) + t48 * (q[j + 2] + q[j + 4]) + t56 * q[j + 3];
+    hp[0] = as_u16x2(blur_hsum<0>(a) | (blur_hsum<0>(b) << 16));
+    hp[1] = as_u16x2(blur_hsum<1>(a) | (blur_hsum<1>(b) << 16));
+    hp[2] = as_u16x2(blur_hsum<2>(a) | (blur_hsum<2>(b) << 16));
+    hp[3] = as_u16x2(blur_hsum<3>(a) | (blur_hsum<3>(b) << 16));
 }
 __device__ __forceinline__ uint32_t blur_dot(u16x2 h, uint32_t taps, uint32_t acc) { return __builtin_amdgcn_udot2(h, as_u16x2(taps), acc, false); }
 __device__ __forceinline__ uint32_t blur_pack(const uint32_t (&acc)[4]) {  // byte 2 of each accumulator = (acc >> 16) & 255
@@ -431,7 +440,9 @@ __device__ __forceinline__ uint32_t blur_pack(const uint32_t (&acc)[4]) {  // by
 // of horizontal sums stay in registers and every iteration adds one pair and emits two output rows, each as four
 // 2-element dot products (v_dot2_u32_u16) against the vertically paired taps.  load_pair(y, a, b) fetches rows y and y + 1 (row ys - 4
 // carries a zero tap, row ye + 3 is not used when ye - ys is even: both are still fetched).  Dp = the thread's four bytes of output row 0.
-template <int MODE, class LoadPair>
+// PAIRS > 0: ye - ys == 2 * PAIRS is known when the kernel is compiled and the loop is unrolled in full, so the five register sets are
+// names and the rotation A = B, B = C, ... moves nothing; PAIRS == 0: any ye, the sets rotate through copies.
+template <int MODE, int PAIRS = 0, class LoadPair>
 __device__ __forceinline__ void blur_walk(LoadPair load_pair, uint8_t* __restrict__ Dp, int dpitch, int ys, int ye) {
     constexpr int AHEAD = MODE == BLUR_LDS ? 0 : 2;  // global memory: one pair of rows of loads stays in flight ahead of the arithmetic
     u16x2 A[4], B[4], C[4], D[4], E[4];
@@ -453,7 +464,7 @@ __device__ __forceinline__ void blur_walk(LoadPair load_pair, uint8_t* __restric
         blur_hpair(r[4], r[5], C);
         blur_hpair(r[6], r[7], D);
     }
-    for (int y = ys; y < ye; y += 2) {
+    auto step = [&](int y, bool second) {
         const BlurRow c0 = n0, c1 = n1;
         load_pair(y + 4 + AHEAD, n0, n1);
         if (AHEAD) blur_hpair(c0, c1, E);
@@ -464,7 +475,7 @@ __device__ __forceinline__ void blur_walk(LoadPair load_pair, uint8_t* __restric
         for (int j = 0; j < 4; ++j)
             acc[j] = blur_dot(D[j], 34u | (18u << 16), blur_dot(C[j], 56u | (48u << 16), blur_dot(B[j], 34u | (48u << 16), blur_dot(A[j], 18u << 16, 32768u))));
         *reinterpret_cast<uint32_t*>(Dp + __umul24(y, dpitch)) = blur_pack(acc);
-        if (y + 1 < ye) {  // row y+1: rows y-2 .. y+4 = B | C | D | E.lo
+        if (second) {  // row y+1: rows y-2 .. y+4 = B | C | D | E.lo
 #pragma unroll
             for (int j = 0; j < 4; ++j)
                 acc[j] = blur_dot(E[j], 18u, blur_dot(D[j], 48u | (34u << 16), blur_dot(C[j], 48u | (56u << 16), blur_dot(B[j], 18u | (34u << 16), 32768u))));
@@ -477,7 +488,13 @@ __device__ __forceinline__ void blur_walk(LoadPair load_pair, uint8_t* __restric
             C[j] = D[j];
             D[j] = E[j];
         }
+    };
+    if constexpr (PAIRS > 0) {
+#pragma unroll
+        for (int i = 0; i < PAIRS; ++i) step(ys + 2 * i, true);
     }
+    else
+        for (int y = ys; y < ye; y += 2) step(y, y + 1 < ye);
 }
 // the walk over rows in global memory (ys even)
 template <int MODE>
@@ -584,6 +601,14 @@ __global__ __launch_bounds__(256) void k_blur(const OrbLevel* __restrict__ L, in
 #define BLUR_LDS_ROWS (BLUR_ROWS + 8)
 static_assert(BLUR_SEG % 16 == 0 && BLUR_BAND_THREADS % 64 == 0 && BLUR_SEG / 4 <= BLUR_BAND_THREADS && BLUR_ROWS % 2 == 0, "blur band geometry");
 static_assert(BLUR_LDS_ROWS * BLUR_LP <= 64 * 1024, "blur band exceeds the static LDS limit");
+// rows of a chunk (even) when `rows` rows of `groups` column groups are split over the workgroup's threads, and that figure for a full band of
+// a full segment: the one chunk length compiled with a constant trip count
+constexpr int blur_chunks(int groups, int rows) {
+    const int fit = BLUR_BAND_THREADS / groups, pairs = rows >> 1, c = fit < pairs ? fit : pairs;
+    return c > 1 ? c : 1;
+}
+constexpr int blur_chunk_rows(int groups, int rows) { return ((rows + blur_chunks(groups, rows) - 1) / blur_chunks(groups, rows) + 1) & ~1; }
+constexpr int BLUR_FULL_RC = blur_chunk_rows(BLUR_SEG / 4, BLUR_ROWS);
 template <>
 __global__ __launch_bounds__(BLUR_BAND_THREADS) void k_blur<BLUR_ROWS>(const OrbLevel* __restrict__ L, int num_levels, const uint8_t* __restrict__ img0,
                                                                        size_t img0_frame_stride, int img0_pitch, const uint8_t* __restrict__ pyr,
@@ -633,16 +658,21 @@ __global__ __launch_bounds__(BLUR_BAND_THREADS) void k_blur<BLUR_ROWS>(const Orb
     }
     __syncthreads();
     // ---- thread -> (chunk of consecutive rows, column group)
-    const int chunks = max(min(BLUR_BAND_THREADS / groups, rows >> 1), 1), rc = ((rows + chunks - 1) / chunks + 1) & ~1;
+    const int chunks = blur_chunks(groups, rows), rc = blur_chunk_rows(groups, rows);
     const int c = (int)(((float)tid + 0.5f) * (1.0f / (float)groups)), g = tid - __mul24(c, groups);
     const int r0 = __mul24(c, rc), r1 = min(r0 + rc, rows);
     if (r0 >= r1) return;
     const uint32_t* S = reinterpret_cast<const uint32_t*>(s_rows + 12 + 4 * g);  // window [x0 - 4, x0 + 8) of LDS row 0
-    blur_walk<BLUR_LDS>([&](int y, BlurRow& a, BlurRow& b) {  // output row y of the band reads LDS rows y + 1 .. y + 7
+    auto load_pair = [&](int y, BlurRow& a, BlurRow& b) {  // output row y of the band reads LDS rows y + 1 .. y + 7
         const uint32_t* p = S + __mul24(y + 4, BLUR_LP / 4);
         a = BlurRow{p[0], p[1], p[2]};
         b = BlurRow{p[BLUR_LP / 4], p[BLUR_LP / 4 + 1], p[BLUR_LP / 4 + 2]};
-    }, dst + __umul24(y0, lev.pitch) + xs + 4 * g, lev.pitch, r0, r1);
+    };
+    uint8_t* const Dp = dst + __umul24(y0, lev.pitch) + xs + 4 * g;
+    // A full band whose chunks are all BLUR_FULL_RC rows (the full segment's split; at 640 x 480 also the 309- and 257-px levels) takes the
+    // unrolled walk.  `rows`, `chunks` and `rc` are the same for the whole workgroup: one code path per workgroup.
+    if (rc == BLUR_FULL_RC && chunks * rc == rows) blur_walk<BLUR_LDS, BLUR_FULL_RC / 2>(load_pair, Dp, lev.pitch, r0, r1);
+    else blur_walk<BLUR_LDS>(load_pair, Dp, lev.pitch, r0, r1);
 }
 template <int ROWS>
 __global__ __launch_bounds__(256) void k_blur_gather(const OrbLevel* __restrict__ L, int num_levels, const uint8_t* __restrict__ img0,
