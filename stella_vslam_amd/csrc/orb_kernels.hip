@@ -1,5 +1,6 @@
 // HIP kernels of the ORB front end for gfx950 (wave64).  One kernel per reference routine:
-//   k_resize    <- cv::resize INTER_LINEAR chain       (feature/orb_extractor.cc:153-162)
+//   k_pyramid_lds / k_pyramid
+//               <- cv::resize INTER_LINEAR chain       (feature/orb_extractor.cc:153-162), every level in one launch
 //   k_blur      <- cv::GaussianBlur 7x7 sigma 2        (feature/orb_extractor.cc:103)
 //   k_fast      <- per-cell cv::FAST + NMS + retry + selection-grid arg-max
 //                                                      (feature/orb_extractor.cc:164-287, 289-329)
@@ -10,7 +11,6 @@
 // operation order with contraction disabled (-ffp-contract=off, checked in the disassembly).
 #include "svgpu_internal.h"
 #include "sv_trig.h"
-#include <cstdlib>
 #include <utility>
 
 #pragma clang fp contract(off)
@@ -76,39 +76,9 @@ __device__ __forceinline__ void sv_glds16(unsigned long long base, uint32_t voff
                  : "memory");
 }
 
-// ------------------------------------------------------------------------------------------------ resize
+// ------------------------------------------------------------------------------------------------ pyramid
 // OpenCV 8-bit bilinear: horizontal int32 with 11-bit coefficients, vertical
-// ((b0*(r0>>4))>>16) + ((b1*(r1>>4))>>16) + 2) >> 2.  Coefficient tables are built on the host.
-__global__ __launch_bounds__(256) void k_resize(const uint8_t* __restrict__ src, size_t src_frame_stride, int src_pitch,
-                                                int sw, uint8_t* __restrict__ dst, size_t dst_frame_stride, int dst_pitch,
-                                                int dw, int dh, const short* __restrict__ xofs,
-                                                const short2* __restrict__ xa, const short2* __restrict__ yofs,
-                                                const short2* __restrict__ yb) {
-    const int dy = blockIdx.y * 4 + threadIdx.y;
-    const int dx0 = (blockIdx.x * 64 + threadIdx.x) * 4;
-    if (dy >= dh || dx0 >= dw) return;
-    const uint8_t* S = src + (size_t)blockIdx.z * src_frame_stride;
-    const short2 yo = yofs[dy];
-    const short2 bb = yb[dy];
-    const uint8_t* S0 = S + (size_t)yo.x * src_pitch;
-    const uint8_t* S1 = S + (size_t)yo.y * src_pitch;
-    uint32_t packed = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int dx = dx0 + i;
-        if (dx < dw) {
-            const int sx = xofs[dx];
-            const short2 a = xa[dx];
-            const int sx1 = min(sx + 1, sw - 1);
-            const int r0 = S0[sx] * a.x + S0[sx1] * a.y;
-            const int r1 = S1[sx] * a.x + S1[sx1] * a.y;
-            const int v = ((((int)bb.x * (r0 >> 4)) >> 16) + (((int)bb.y * (r1 >> 4)) >> 16) + 2) >> 2;
-            packed |= (uint32_t)(v & 255) << (8 * i);
-        }
-    }
-    uint8_t* D = dst + (size_t)blockIdx.z * dst_frame_stride + (size_t)dy * dst_pitch + dx0;
-    *reinterpret_cast<uint32_t*>(D) = packed;  // pitch is a multiple of 64: in-bounds and aligned
-}
+// ((b0*(r0>>4))>>16) + ((b1*(r1>>4))>>16) + 2) >> 2.  Coefficient tables are built on the host (orb_plan.h).
 
 // Whole pyramid in ONE launch.  A workgroup owns a horizontal band of one frame through all levels: for level
 // l = 1..L-1 it computes the rows of that level it owns plus the few halo rows its own next level reads
@@ -190,7 +160,7 @@ __global__ __launch_bounds__(PYR_THREADS) void k_pyramid(const OrbLevel* __restr
 //   halves, one v_dot2_u32_u16 forms H.  Vertical: ((b0 * (H0 >> 4)) >> 16) + ((b1 * (H1 >> 4)) >> 16) as two v_mul_hi_u32_u24 of
 //   (b << 12) and (H & ~15): (b * 2^12) * ((H >> 4) * 2^4) >> 32 == (b * (H >> 4)) >> 16, both factors below 2^24.
 // LDS map (dynamic): [rows of the odd levels (one region, reused)][rows of the even levels, level 0 included (one region, reused)], pitch = w
-// rounded up to 4, [8-byte row records of the band's rows].  The host picks the band count so that two workgroups fit a CU (svgpu_orb_configure).
+// rounded up to 4, [8-byte row records of the band's rows].  The host picks the band count so that two workgroups fit a CU (orb_plan.h).
 __device__ __forceinline__ uint32_t mul_hi_u24(uint32_t a, uint32_t b) {  // (a * b) >> 32 for a, b < 2^24: full-rate v_mul_hi_u32_u24
     uint32_t d;
     asm("v_mul_hi_u32_u24 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
@@ -512,7 +482,7 @@ __device__ __forceinline__ void blur_strip(const uint8_t* __restrict__ src, int 
 // Tiles [0, btiles_x*btiles_y) of a level are interior tiles (aligned 12-byte windows, branch-free); the remaining tiles
 // of the level are EDGE tiles whose threads do the column groups that touch the left/right image border.  Keeping the
 // two roles in different workgroups keeps every wave on a single code path.  Sources that are not 4-byte aligned
-// (caller images) or narrower than 16 px go through k_blur_gather instead (host decision, sv_launch_blur).
+// (caller images) or narrower than 16 px go through k_blur_gather instead (host decision, orb_launch_plan).
 __device__ __forceinline__ void blur_locate(const OrbLevel* __restrict__ L, int num_levels, const uint8_t* __restrict__ img0,
                                             size_t img0_frame_stride, int img0_pitch, const uint8_t* __restrict__ pyr,
                                             size_t pyr_frame_bytes, uint8_t* __restrict__ blur, size_t blur_frame_bytes, OrbLevel& lev,
@@ -1282,7 +1252,7 @@ __global__ __launch_bounds__(256) void k_describe(const OrbLevel* __restrict__ L
 // patch row pulls a whole 128-byte line from L2 (4.5 cycles each): 300 cycles per keypoint per CU, of which the arithmetic is 110.
 // LDS-DMA per patch (global_load_lds_dwordx4 into a per-wave ring, built and measured: 1.39 ms against 1.20) does not change that count.
 // So the image goes to LDS in full rows instead, once per group of neighbouring keypoints:
-//   * a BAND = a few consecutive rows of the selection grid of one level (svgpu_orb.hip builds the table); its keypoints are one
+//   * a BAND = a few consecutive rows of the selection grid of one level (orb_plan.h builds the table); its keypoints are one
 //     contiguous run of the selection order (k_select writes every cell's position), its pixels the level's rows
 //     [y_min - 18, y_max + 18], full width: one workgroup of 8 waves copies them with 1 KB `global_load_lds_dwordx4` instructions
 //     (lane-linear: LDS pitch = 16 x pieces per row, chosen = 32 mod 64 so that eight rows of dword reads hit 64 different banks);
@@ -1295,7 +1265,7 @@ __global__ __launch_bounds__(256) void k_describe(const OrbLevel* __restrict__ L
 #define DB_THREADS 512
 #endif
 #define DB_WAVES (DB_THREADS / 64)
-#define DB_MAX_KP 128  // keypoints per band (svgpu_orb.hip keeps bands below it): phase A gives each keypoint one thread of waves 0-1
+#define DB_MAX_KP 128  // keypoints per band (orb_plan.h keeps bands below it): phase A gives each keypoint one thread of waves 0-1
 struct IcWeights3 {
     uint32_t w1[256], wu[256], wv[256];  // per (row, dword) item: disc mask bytes, (u + 15) x mask, (v + 15) x mask
 };
@@ -1504,83 +1474,65 @@ __global__ __launch_bounds__(DB_THREADS) void k_describe_bands(const OrbLevel* _
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------ launchers
-void sv_launch_resize(hipStream_t s, const uint8_t* src, size_t src_frame_stride, int src_pitch, int sw, int sh,
-                      uint8_t* dst, size_t dst_frame_stride, int dst_pitch, int dw, int dh, const short* xofs,
-                      const short2* xa, const short2* yofs, const short2* yb, int batch) {
-    (void)sh;
-    dim3 block(64, 4), grid((dw + 255) / 256, (dh + 3) / 4, batch);
-    hipLaunchKernelGGL(k_resize, grid, block, 0, s, src, src_frame_stride, src_pitch, sw, dst, dst_frame_stride, dst_pitch, dw,
-                       dh, xofs, xa, yofs, yb);
-}
-
+// What to launch is decided by orb_launch_plan (orb_plan.h); the launchers expand OrbFrames into the kernels' parameter lists.
 hipError_t sv_pyramid_prepare() {  // once per device: allow the LDS-resident pyramid its large dynamic allocation
     return sv_allow_dynamic_lds(reinterpret_cast<const void*>(k_pyramid_lds), SV_PYR_LDS_MAX);
 }
-void sv_launch_pyramid(hipStream_t s, const OrbLevel* levels, int num_levels, const int2* band_rows, int bands, const uint8_t* img0,
-                       size_t img0_frame_stride, int img0_pitch, uint8_t* pyr, size_t pyr_frame_bytes, const short* xofs,
-                       const short2* xa, const short2* yofs, const short2* yb, const uint32_t* xg, const short4* yrow, int batch, size_t lds_bytes) {
-    if (lds_bytes > 0) {
-        hipLaunchKernelGGL(k_pyramid_lds, dim3(bands, batch), dim3(PYR_THREADS), lds_bytes, s, levels, num_levels, band_rows, bands, img0,
-                           img0_frame_stride, img0_pitch, pyr, pyr_frame_bytes, xg, yrow);
-        return;
-    }
-    hipLaunchKernelGGL(k_pyramid, dim3(bands, batch), dim3(PYR_THREADS), 0, s, levels, num_levels, band_rows, img0, img0_frame_stride,
-                       img0_pitch, pyr, pyr_frame_bytes, xofs, xa, yofs, yb);
+void sv_launch_pyramid(hipStream_t s, const OrbFrames& F, const OrbLaunch& plan, const int2* band_rows, int bands, size_t lds_bytes, const short* xofs,
+                       const short2* xa, const short2* yofs, const short2* yb, const uint32_t* xg, const short4* yrow) {
+    if (plan.pyramid_lds)
+        hipLaunchKernelGGL(k_pyramid_lds, dim3(bands, F.batch), dim3(PYR_THREADS), lds_bytes, s, F.levels, F.num_levels, band_rows, bands, F.img0,
+                           F.img0_frame_stride, F.img0_pitch, F.pyr, F.pyr_frame_bytes, xg, yrow);
+    else
+        hipLaunchKernelGGL(k_pyramid, dim3(bands, F.batch), dim3(PYR_THREADS), 0, s, F.levels, F.num_levels, band_rows, F.img0, F.img0_frame_stride,
+                           F.img0_pitch, F.pyr, F.pyr_frame_bytes, xofs, xa, yofs, yb);
 }
 
-void sv_launch_blur(hipStream_t s, const OrbLevel* levels, int num_levels, int total_tiles, int total_bands, const uint8_t* img0,
-                    size_t img0_frame_stride, int img0_pitch, const uint8_t* pyr, size_t pyr_frame_bytes, uint8_t* blur,
-                    size_t blur_frame_bytes, int batch, bool need_gather, int rows) {
-    const dim3 grid(total_tiles, batch), block(256);
-    if (rows == BLUR_ROWS_SMALL) {
-        hipLaunchKernelGGL(k_blur<BLUR_ROWS_SMALL>, grid, block, 0, s, levels, num_levels, img0, img0_frame_stride, img0_pitch, pyr, pyr_frame_bytes, blur, blur_frame_bytes);
-        if (need_gather)
-            hipLaunchKernelGGL(k_blur_gather<BLUR_ROWS_SMALL>, grid, block, 0, s, levels, num_levels, img0, img0_frame_stride, img0_pitch, pyr, pyr_frame_bytes, blur, blur_frame_bytes);
+void sv_launch_blur(hipStream_t s, const OrbFrames& F, const OrbLaunch& plan, int total_tiles, int total_bands) {
+    const dim3 grid(total_tiles, F.batch), block(256);
+    if (!plan.blur_bands) {  // streaming: a thread walks BLUR_ROWS_SMALL rows of 4 columns
+        hipLaunchKernelGGL(k_blur<BLUR_ROWS_SMALL>, grid, block, 0, s, F.levels, F.num_levels, F.img0, F.img0_frame_stride, F.img0_pitch, F.pyr,
+                           F.pyr_frame_bytes, F.blur, F.blur_frame_bytes);
+        if (plan.need_gather)
+            hipLaunchKernelGGL(k_blur_gather<BLUR_ROWS_SMALL>, grid, block, 0, s, F.levels, F.num_levels, F.img0, F.img0_frame_stride, F.img0_pitch, F.pyr,
+                               F.pyr_frame_bytes, F.blur, F.blur_frame_bytes);
     }
     else {  // row bands in LDS, one workgroup per (level, band, column segment)
-        hipLaunchKernelGGL(k_blur<BLUR_ROWS>, dim3(total_bands, batch), dim3(BLUR_BAND_THREADS), 0, s, levels, num_levels, img0, img0_frame_stride, img0_pitch, pyr,
-                           pyr_frame_bytes, blur, blur_frame_bytes);
-        if (need_gather)
-            hipLaunchKernelGGL(k_blur_gather<BLUR_ROWS>, grid, block, 0, s, levels, num_levels, img0, img0_frame_stride, img0_pitch, pyr, pyr_frame_bytes, blur, blur_frame_bytes);
+        hipLaunchKernelGGL(k_blur<BLUR_ROWS>, dim3(total_bands, F.batch), dim3(BLUR_BAND_THREADS), 0, s, F.levels, F.num_levels, F.img0, F.img0_frame_stride,
+                           F.img0_pitch, F.pyr, F.pyr_frame_bytes, F.blur, F.blur_frame_bytes);
+        if (plan.need_gather)
+            hipLaunchKernelGGL(k_blur_gather<BLUR_ROWS>, grid, block, 0, s, F.levels, F.num_levels, F.img0, F.img0_frame_stride, F.img0_pitch, F.pyr,
+                               F.pyr_frame_bytes, F.blur, F.blur_frame_bytes);
     }
 }
 
-void sv_launch_fast(hipStream_t s, const OrbLevel* levels, int num_levels, const FastCell* cells, int num_cells,
-                    const uint8_t* img0, size_t img0_frame_stride, int img0_pitch, const uint8_t* pyr,
-                    size_t pyr_frame_bytes, const unsigned short* gtab, unsigned long long* keys, int total_grid,
-                    int ini_thr, int min_thr, const uint8_t* mask, size_t mask_frame_stride, int mask_pitch, int mask_w,
-                    int mask_h, int batch) {
+void sv_launch_fast(hipStream_t s, const OrbFrames& F, int cpw, const FastCell* cells, int num_cells, const unsigned short* gtab,
+                    unsigned long long* keys, int total_grid, int ini_thr, int min_thr, const uint8_t* mask, size_t mask_frame_stride,
+                    int mask_pitch, int mask_w, int mask_h) {
     if (num_cells == 0) return;
-    // cells per workgroup: four once the batch alone fills the chip many times over, one for a few frames (latency: more workgroups)
-    int cpw = (long long)num_cells * batch >= 16384 ? 4 : 1;
-    if (const char* e = getenv("SVGPU_FAST_CPW")) cpw = std::max(1, atoi(e));
-    hipLaunchKernelGGL(k_fast, dim3((num_cells + cpw - 1) / cpw, batch), dim3(256), 0, s, levels, num_levels, cells, num_cells, cpw, img0, img0_frame_stride,
-                       img0_pitch, pyr, pyr_frame_bytes, gtab, keys, total_grid, ini_thr, min_thr, mask, mask_frame_stride,
+    hipLaunchKernelGGL(k_fast, dim3((num_cells + cpw - 1) / cpw, F.batch), dim3(256), 0, s, F.levels, F.num_levels, cells, num_cells, cpw, F.img0,
+                       F.img0_frame_stride, F.img0_pitch, F.pyr, F.pyr_frame_bytes, gtab, keys, total_grid, ini_thr, min_thr, mask, mask_frame_stride,
                        mask_pitch, mask_w, mask_h);
 }
 
-void sv_launch_select(hipStream_t s, const OrbLevel* levels, int num_levels, unsigned long long* keys, int total_grid,
-                      int4* sel, int32_t* counts, int32_t* cellpos, int batch) {
-    hipLaunchKernelGGL(k_select, dim3(batch), dim3(1024), 0, s, levels, num_levels, keys, total_grid, sel, counts, cellpos);
+void sv_launch_select(hipStream_t s, const OrbFrames& F, unsigned long long* keys, int total_grid, int4* sel, int32_t* counts, int32_t* cellpos) {
+    hipLaunchKernelGGL(k_select, dim3(F.batch), dim3(1024), 0, s, F.levels, F.num_levels, keys, total_grid, sel, counts, cellpos);
 }
 
-void sv_launch_describe(hipStream_t s, const OrbLevel* levels, int num_levels, const int4* sel, int total_grid,
-                        const int32_t* counts, const uint8_t* img0, size_t img0_frame_stride, int img0_pitch,
-                        const uint8_t* pyr, size_t pyr_frame_bytes, const uint8_t* blur, size_t blur_frame_bytes,
-                        svgpu_keypoint* kps, uint8_t* desc, int cap, int batch, float* angles) {
+void sv_launch_describe(hipStream_t s, const OrbFrames& F, const int4* sel, int total_grid, const int32_t* counts, svgpu_keypoint* kps,
+                        uint8_t* desc, int cap, float* angles) {
     if (total_grid == 0) return;
-    hipLaunchKernelGGL(k_describe, dim3((total_grid + 4 * DESC_KPW - 1) / (4 * DESC_KPW), batch), dim3(256), 0, s, levels, num_levels, sel, total_grid,
-                       counts, img0, img0_frame_stride, img0_pitch, pyr, pyr_frame_bytes, blur, blur_frame_bytes, kps, desc, cap, angles);
+    hipLaunchKernelGGL(k_describe, dim3((total_grid + 4 * DESC_KPW - 1) / (4 * DESC_KPW), F.batch), dim3(256), 0, s, F.levels, F.num_levels, sel, total_grid,
+                       counts, F.img0, F.img0_frame_stride, F.img0_pitch, F.pyr, F.pyr_frame_bytes, F.blur, F.blur_frame_bytes, kps, desc, cap, angles);
 }
 
 hipError_t sv_describe_bands_prepare(size_t lds_bytes) {  // once per device: allow the band kernel its dynamic LDS
     return sv_allow_dynamic_lds(reinterpret_cast<const void*>(k_describe_bands), lds_bytes);
 }
-void sv_launch_describe_bands(hipStream_t s, const OrbLevel* levels, int num_levels, const DescBand* bands, int num_bands, size_t lds_bytes,
-                              const int4* sel, int total_grid, const int32_t* cellpos, const int32_t* counts, const uint8_t* img0,
-                              size_t img0_frame_stride, int img0_pitch, const uint8_t* pyr, size_t pyr_frame_bytes, const uint8_t* blur,
-                              size_t blur_frame_bytes, svgpu_keypoint* kps, uint8_t* desc, int cap, int batch, float* angles) {
+void sv_launch_describe_bands(hipStream_t s, const OrbFrames& F, const DescBand* bands, int num_bands, size_t lds_bytes, const int4* sel,
+                              int total_grid, const int32_t* cellpos, const int32_t* counts, svgpu_keypoint* kps, uint8_t* desc, int cap,
+                              float* angles) {
     if (num_bands == 0) return;
-    hipLaunchKernelGGL(k_describe_bands, dim3(num_bands, batch), dim3(DB_THREADS), lds_bytes, s, levels, num_levels, bands, num_bands, sel, total_grid,
-                       cellpos, counts, img0, img0_frame_stride, img0_pitch, pyr, pyr_frame_bytes, blur, blur_frame_bytes, kps, desc, cap, angles);
+    hipLaunchKernelGGL(k_describe_bands, dim3(num_bands, F.batch), dim3(DB_THREADS), lds_bytes, s, F.levels, F.num_levels, bands, num_bands, sel, total_grid,
+                       cellpos, counts, F.img0, F.img0_frame_stride, F.img0_pitch, F.pyr, F.pyr_frame_bytes, F.blur, F.blur_frame_bytes, kps, desc, cap, angles);
 }

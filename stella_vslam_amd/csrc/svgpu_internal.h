@@ -12,82 +12,7 @@
 
 #include "svgpu.h"
 #include "sv_arena.h"
-
-#define SV_MAX_LEVELS 16
-#define SV_PATCH_RADIUS 19  // orb_extractor.h:107 orb_patch_radius_
-#define SV_CELL 64          // orb_extractor.cc:173 cell_size
-#define SV_OVERLAP 6        // orb_extractor.cc:172 overlap
-#define SV_ROI_MAX 70       // SV_CELL + SV_OVERLAP
-// k_blur tiling (shared by the kernels and the host-side work-item counts).
-// Batches: a workgroup of BLUR_BAND_THREADS threads blurs BLUR_ROWS output rows of one column segment of a level from LDS (k_blur<BLUR_ROWS>).
-// The three values were picked together by measurement in the pipeline: LDS per workgroup, and with it the number of
-// workgroups that stage and compute side by side on a CU, weighs more than halo rows or the six warm-up rows of a chunk.
-#ifndef BLUR_ROWS
-#define BLUR_ROWS 48                // output rows of a band: the band stages BLUR_ROWS + 6 source rows, (R + 6) / R of the level's bytes
-#endif
-#ifndef BLUR_SEG
-#define BLUR_SEG 320                // widest column segment of a band, a multiple of 16: wider levels are split, each segment re-reading
-#endif                              // 16 bytes per row on either side.  LDS per workgroup: (BLUR_ROWS + 8) x (BLUR_SEG + 32) bytes = 19 712
-#ifndef BLUR_BAND_THREADS
-#define BLUR_BAND_THREADS 256       // thread = (chunk of rows, group of 4 columns): 320 px = 80 groups x 3 chunks of 16 rows
-#endif
-// Contexts configured for at most BLUR_SMALL_BATCH frames: latency, not traffic, is what counts -- the streaming kernel, a thread walks
-// BLUR_ROWS_SMALL rows of 4 columns straight from global memory.  k_blur_gather uses the same tiles with OrbConfig::blur_rows rows.
-#define BLUR_ROWS_SMALL 16
-#define BLUR_SMALL_BATCH 4
-#define BLUR_TW 256                 // tile width  = 64 threads x 4 px; tile height = 4 strips of OrbConfig::blur_rows rows
-
-// ---- per-level geometry, read by every ORB kernel (lives in device memory, one array per context)
-struct OrbLevel {
-    int w, h;               // level size in pixels
-    int pitch;              // row pitch (bytes) of the stored pyramid / blurred level
-    int has_cells;          // 0 if the level is too small for a 19-px border
-    long long pyr_off;      // byte offset of this level inside one frame's pyramid block (levels >= 1)
-    long long blur_off;     // byte offset inside one frame's blurred block (all levels)
-    int xtab_off, ytab_off; // resize coefficient tables (level produced from level-1)
-    int xg_off;             // first 32-byte column-group record of this level in the packed table of k_pyramid_lds
-    int cell_first, cell_count;     // FAST cells of this level in the cell table
-    int cells_x;                    // num_cols of the FAST cell lattice (orb_extractor.cc:186)
-    int grid_x, grid_y, grid_first; // selection grid (distribute_keypoints) and its offset in the key array
-    int gtab_x_off, gtab_y_off;     // region coordinate -> grid index lookup tables
-    int btile_first, btiles_x, btiles_y;  // blur tiles
-    int bband_first, bband_segs;          // blur bands of k_blur<BLUR_ROWS>: first work item, column segments per band (BLUR_SEG px each)
-    float scale;            // scale_factors_[level]
-    float kp_size;          // (float)(unsigned)(31 * scale)
-};
-
-struct FastCell {
-    short min_x, min_y;  // ROI origin in level coordinates
-    short w, h;          // ROI size (<= 70)
-    short lv, cj;        // pyramid level; cell column (j in orb_extractor.cc:199-217)
-    int order_base;      // (ci * num_cols + cj) << 14 : emission order prefix
-};
-
-// k_describe_bands: a band = consecutive rows of one level's selection grid whose pixels one workgroup stages in LDS (orb_kernels.hip)
-struct DescBand {
-    int cell0, cell1;  // selection-grid cells [cell0, cell1) (indices into the per-frame key / position arrays)
-    int img_bytes;     // LDS bytes of the staged rows (the larger of the two phases), a multiple of 16
-    short lv, lp;      // level; LDS row pitch (multiple of 16, = 32 mod 64)
-    short yu0, nru;    // un-blurred rows [yu0, yu0 + nru)  (every keypoint's y - 15 .. y + 16)
-    short yb0, nrb;    // blurred rows    [yb0, yb0 + nrb)  (every keypoint's y - 18 .. y + 18)
-};
-
-struct OrbConfig {
-    int width = 0, height = 0, max_batch = 0, num_levels = 0;
-    float scale_factor = 0;
-    int ini_thr = 0, min_thr = 0;
-    unsigned min_area_sqrt = 0;
-    float scale_factors[SV_MAX_LEVELS];
-    OrbLevel levels[SV_MAX_LEVELS];
-    std::vector<FastCell> cells;
-    int total_grid = 0;    // sum of grid cells over levels = max keypoints per frame
-    int total_btiles = 0, total_bbands = 0;
-    int blur_rows = BLUR_ROWS;  // BLUR_ROWS: the band kernel; BLUR_ROWS_SMALL: the streaming kernel (a context of a few frames)
-    size_t pyr_frame_bytes = 0, blur_frame_bytes = 0;
-    std::vector<DescBand> dbands;  // empty: the configuration does not fit the band kernel, k_describe takes it
-    size_t dband_lds_bytes = 0;    // dynamic LDS of k_describe_bands
-    bool configured = false;
-};
+#include "orb_plan.h"  // ORB constants, OrbLevel / FastCell / DescBand / OrbConfig, the host planner
 
 // Optional per-kernel timing with HIP events on the launch stream (svgpu_profile_select / _read / _read_class).
 // One accumulator per kernel class; the selection "*" brackets EVERY class, so that one timed region yields the mean launch time of
@@ -204,11 +129,9 @@ struct svgpu_ctx {
     short2* d_xa = nullptr;         // (a0, a1) 11-bit coefficients
     short2* d_yofs = nullptr;       // (row0, row1) clamped
     short2* d_yb = nullptr;         // (b0, b1)
-    uint32_t* d_xg = nullptr;       // k_pyramid_lds: 8 words per group of 4 output columns (see build in svgpu_orb.hip)
+    uint32_t* d_xg = nullptr;       // k_pyramid_lds: 8 words per group of 4 output columns (orb_plan.h orb_plan_pyramid_records)
     short4* d_yrow = nullptr;       // k_pyramid_lds: (row0, row1, b0, b1) per output row
     int2* d_band_rows = nullptr;    // [bands][levels]: rows of each level a pyramid band computes
-    int pyr_bands = 0;
-    size_t pyr_lds_bytes = 0;       // dynamic LDS of k_pyramid_lds for this configuration; 0 = use the global-memory variant
     unsigned short* d_gtab = nullptr;
     uint8_t* d_pyr = nullptr;       // max_batch * pyr_frame_bytes
     uint8_t* d_blur = nullptr;      // max_batch * blur_frame_bytes
@@ -291,31 +214,30 @@ int sv_frame_reserve(svgpu_ctx* ctx, svgpu_frame* f, int n, int ncell);  // grow
     } while (0)
 
 // ---- kernel launchers (orb_kernels.hip)
-void sv_launch_resize(hipStream_t s, const uint8_t* src, size_t src_frame_stride, int src_pitch, int sw, int sh,
-                      uint8_t* dst, size_t dst_frame_stride, int dst_pitch, int dw, int dh, const short* xofs,
-                      const short2* xa, const short2* yofs, const short2* yb, int batch);
-#define SV_PYR_LDS_MAX (156 * 1024)  // dynamic LDS budget of k_pyramid_lds (160 KB per CU minus its static tables)
-#define SV_PYR_LDS_HALF (78 * 1024)  // ... of which two fit a CU
+// The images of one extract call, as every ORB kernel takes them: the launchers expand it into the kernels' parameter lists.
+struct OrbFrames {
+    const OrbLevel* levels;
+    int num_levels;
+    const uint8_t* img0;  // level 0: the caller's frames
+    size_t img0_frame_stride;
+    int img0_pitch;
+    uint8_t* pyr;         // levels >= 1
+    size_t pyr_frame_bytes;
+    uint8_t* blur;        // blurred copy of every level
+    size_t blur_frame_bytes;
+    int batch;
+};
 hipError_t sv_pyramid_prepare();
-void sv_launch_pyramid(hipStream_t s, const OrbLevel* levels, int num_levels, const int2* band_rows, int bands, const uint8_t* img0,
-                       size_t img0_frame_stride, int img0_pitch, uint8_t* pyr, size_t pyr_frame_bytes, const short* xofs,
-                       const short2* xa, const short2* yofs, const short2* yb, const uint32_t* xg, const short4* yrow, int batch, size_t lds_bytes);
-void sv_launch_blur(hipStream_t s, const OrbLevel* levels, int num_levels, int total_tiles, int total_bands, const uint8_t* img0,
-                    size_t img0_frame_stride, int img0_pitch, const uint8_t* pyr, size_t pyr_frame_bytes, uint8_t* blur,
-                    size_t blur_frame_bytes, int batch, bool need_gather, int rows);
-void sv_launch_fast(hipStream_t s, const OrbLevel* levels, int num_levels, const FastCell* cells, int num_cells,
-                    const uint8_t* img0, size_t img0_frame_stride, int img0_pitch, const uint8_t* pyr,
-                    size_t pyr_frame_bytes, const unsigned short* gtab, unsigned long long* keys, int total_grid,
-                    int ini_thr, int min_thr, const uint8_t* mask, size_t mask_frame_stride, int mask_pitch, int mask_w,
-                    int mask_h, int batch);
-void sv_launch_select(hipStream_t s, const OrbLevel* levels, int num_levels, unsigned long long* keys, int total_grid,
-                      int4* sel, int32_t* counts, int32_t* cellpos, int batch);
+void sv_launch_pyramid(hipStream_t s, const OrbFrames& F, const OrbLaunch& plan, const int2* band_rows, int bands, size_t lds_bytes, const short* xofs,
+                       const short2* xa, const short2* yofs, const short2* yb, const uint32_t* xg, const short4* yrow);
+void sv_launch_blur(hipStream_t s, const OrbFrames& F, const OrbLaunch& plan, int total_tiles, int total_bands);
+void sv_launch_fast(hipStream_t s, const OrbFrames& F, int cpw, const FastCell* cells, int num_cells, const unsigned short* gtab,
+                    unsigned long long* keys, int total_grid, int ini_thr, int min_thr, const uint8_t* mask, size_t mask_frame_stride,
+                    int mask_pitch, int mask_w, int mask_h);
+void sv_launch_select(hipStream_t s, const OrbFrames& F, unsigned long long* keys, int total_grid, int4* sel, int32_t* counts, int32_t* cellpos);
 hipError_t sv_describe_bands_prepare(size_t lds_bytes);
-void sv_launch_describe_bands(hipStream_t s, const OrbLevel* levels, int num_levels, const DescBand* bands, int num_bands, size_t lds_bytes,
-                              const int4* sel, int total_grid, const int32_t* cellpos, const int32_t* counts, const uint8_t* img0,
-                              size_t img0_frame_stride, int img0_pitch, const uint8_t* pyr, size_t pyr_frame_bytes, const uint8_t* blur,
-                              size_t blur_frame_bytes, svgpu_keypoint* kps, uint8_t* desc, int cap, int batch, float* angles);
-void sv_launch_describe(hipStream_t s, const OrbLevel* levels, int num_levels, const int4* sel, int total_grid,
-                        const int32_t* counts, const uint8_t* img0, size_t img0_frame_stride, int img0_pitch,
-                        const uint8_t* pyr, size_t pyr_frame_bytes, const uint8_t* blur, size_t blur_frame_bytes,
-                        svgpu_keypoint* kps, uint8_t* desc, int cap, int batch, float* angles);
+void sv_launch_describe_bands(hipStream_t s, const OrbFrames& F, const DescBand* bands, int num_bands, size_t lds_bytes, const int4* sel,
+                              int total_grid, const int32_t* cellpos, const int32_t* counts, svgpu_keypoint* kps, uint8_t* desc, int cap,
+                              float* angles);
+void sv_launch_describe(hipStream_t s, const OrbFrames& F, const int4* sel, int total_grid, const int32_t* counts, svgpu_keypoint* kps,
+                        uint8_t* desc, int cap, float* angles);

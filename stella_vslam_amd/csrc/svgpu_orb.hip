@@ -1,37 +1,46 @@
-// Host side of the ORB front end: geometry / coefficient tables (bit-identical to the reference's
-// host arithmetic), device workspace layout, launch sequence.
-//   orb_params scale tables        feature/orb_params.cc:41-71
-//   level sizes                    feature/orb_extractor.cc:157-159
-//   cv::resize coefficient tables  OpenCV 4.x imgproc/src/resize.cpp (8-bit fixed point, 11-bit coefficients)
-//   FAST cell lattice              feature/orb_extractor.cc:179-217
-//   selection grid                 feature/orb_extractor.cc:292-305
-#include <algorithm>
-#include <cmath>
+// Host side of the ORB front end: environment switches, device workspace (uploads what the planner of orb_plan.h returns), launch sequence.
 #include <cstdlib>
 
 #include "svgpu_internal.h"
 
-#pragma clang fp contract(off)
-#pragma STDC FP_CONTRACT OFF
-
 namespace {
 
-inline int cv_floor_f(float v) {
-    int i = (int)v;
-    return i - (i > v);
+// The ORB environment switches, all read here (a switch that takes a number: at least 1):
+//   name                    takes effect at      meaning
+//   SVGPU_DESCRIBE_LEGACY   configure            no band table: the per-keypoint kernel k_describe serves every batch
+//   SVGPU_DESC_BAND_KB      configure            LDS budget of a band of k_describe_bands in KB (default 48)
+//   SVGPU_PYR_BANDS         configure            pyramid bands per frame, taken as given (no search for the count that fits half a CU's LDS)
+//   SVGPU_DESCRIBE_BANDS    every extract call   k_describe_bands for any batch, where the configuration has a band table
+//   SVGPU_FAST_CPW          every extract call   FAST cells per workgroup of k_fast
+//   SVGPU_FORK_BLUR         once per process     the blur runs on the auxiliary stream beside FAST and selection (opt-in)
+// svgpu_orb_configure and every extract call read them afresh; each uses only its own rows of the table.
+OrbEnv orb_env() {
+    auto number = [](const char* name) {
+        const char* e = getenv(name);
+        return e ? std::max(1, atoi(e)) : 0;
+    };
+    static const bool fork_blur = getenv("SVGPU_FORK_BLUR") != nullptr;
+    OrbEnv E;
+    E.describe_legacy = getenv("SVGPU_DESCRIBE_LEGACY") != nullptr;
+    E.desc_band_kb = number("SVGPU_DESC_BAND_KB");
+    E.pyr_bands = number("SVGPU_PYR_BANDS");
+    E.describe_bands = getenv("SVGPU_DESCRIBE_BANDS") != nullptr;
+    E.fast_cpw = number("SVGPU_FAST_CPW");
+    E.fork_blur = fork_blur;
+    return E;
 }
-inline int cv_round_f(float v) { return (int)lrintf(v); }  // round half to even (default rounding mode)
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-template <class T>
-int upload(svgpu_ctx* ctx, T** dptr, const std::vector<T>& v) {
+// D: the element type the kernels read; H: the planner's plain twin of it
+template <class D, class H>
+int upload(svgpu_ctx* ctx, D** dptr, const std::vector<H>& v) {
+    static_assert(sizeof(D) == sizeof(H) && alignof(D) == alignof(H), "a planner table element must be layout-equal to what the kernels read");
     if (*dptr) {
         SV_HIP(ctx, hipFree(*dptr));
         *dptr = nullptr;
     }
     const size_t n = v.empty() ? 1 : v.size();
-    SV_HIP(ctx, hipMalloc((void**)dptr, n * sizeof(T)));
-    if (!v.empty()) SV_HIP(ctx, hipMemcpy(*dptr, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    SV_HIP(ctx, hipMalloc((void**)dptr, n * sizeof(D)));
+    if (!v.empty()) SV_HIP(ctx, hipMemcpy(*dptr, v.data(), v.size() * sizeof(D), hipMemcpyHostToDevice));
     return SVGPU_OK;
 }
 
@@ -75,18 +84,7 @@ extern "C" {
 int svgpu_orb_scale_tables(float scale_factor, int num_levels, float* scale_factors, float* inv_scale_factors,
                            float* level_sigma_sq, float* inv_level_sigma_sq) {
     if (num_levels < 1) return SVGPU_ERR_INVALID;
-    // orb_params.cc:41-71 -- four independent fp32 recurrences
-    float s = 1.0f, inv = 1.0f;
-    for (int l = 0; l < num_levels; ++l) {
-        if (l > 0) {
-            s = scale_factor * s;
-            inv = (1.0f / scale_factor) * inv;
-        }
-        if (scale_factors) scale_factors[l] = s;
-        if (inv_scale_factors) inv_scale_factors[l] = inv;
-        if (level_sigma_sq) level_sigma_sq[l] = l == 0 ? 1.0f : s * s;
-        if (inv_level_sigma_sq) inv_level_sigma_sq[l] = l == 0 ? 1.0f : 1.0f / (s * s);
-    }
+    orb_plan_scale_tables(scale_factor, num_levels, scale_factors, inv_scale_factors, level_sigma_sq, inv_level_sigma_sq);
     return SVGPU_OK;
 }
 
@@ -99,333 +97,25 @@ int svgpu_orb_configure(svgpu_ctx* ctx, int width, int height, int max_batch, fl
     SV_HIP(ctx, hipSetDevice(ctx->device));
     SV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     sv_orb_release(ctx);
+    OrbPlan plan;
+    if (const char* err = orb_plan_build(width, height, max_batch, scale_factor, num_levels, ini_fast_thr, min_fast_thr, min_area, orb_env(), plan))
+        return sv_set_error(ctx, SVGPU_ERR_INVALID, err);
     OrbConfig& C = ctx->orb;
-    C = OrbConfig();
-    C.width = width;
-    C.height = height;
-    C.max_batch = max_batch;
-    C.blur_rows = max_batch <= BLUR_SMALL_BATCH ? BLUR_ROWS_SMALL : BLUR_ROWS;
-    C.num_levels = num_levels;
-    C.scale_factor = scale_factor;
-    C.ini_thr = ini_fast_thr < 0 ? 0 : (ini_fast_thr > 255 ? 255 : ini_fast_thr);  // cv::FAST clamps (fast.cpp)
-    C.min_thr = min_fast_thr < 0 ? 0 : (min_fast_thr > 255 ? 255 : min_fast_thr);
-    C.min_area_sqrt = (unsigned)std::sqrt((double)min_area);  // orb_extractor.cc:20 (unsigned member)
-    svgpu_orb_scale_tables(scale_factor, num_levels, C.scale_factors, nullptr, nullptr, nullptr);
-
-    std::vector<short> xofs;
-    std::vector<short2> xa, yofs, yb;
-    std::vector<unsigned short> gtab;
-    std::vector<uint32_t> xg;   // packed column-group records of k_pyramid_lds
-    std::vector<short4> yrow;
-    bool xg_ok = true;          // false: a level shrinks by more than 3x, the byte windows of the records do not fit
-    size_t pyr_off = 0, blur_off = 0;
-    int grid_first = 0, btile_first = 0, bband_first = 0;
-    std::vector<std::pair<int, int>> grid_rows[SV_MAX_LEVELS];  // per level and selection-grid row: first / last level row its keypoints can lie on
-    for (int l = 0; l < num_levels; ++l) {
-        OrbLevel& L = C.levels[l];
-        memset(&L, 0, sizeof(L));
-        const float s = C.scale_factors[l];
-        if (l == 0) {
-            L.w = width;
-            L.h = height;
-        }
-        else {  // orb_extractor.cc:157-159
-            const double scale = (double)s;
-            L.w = (int)std::round(width * 1.0 / scale);
-            L.h = (int)std::round(height * 1.0 / scale);
-        }
-        if (L.w < 2 || L.h < 2) return sv_set_error(ctx, SVGPU_ERR_INVALID, "pyramid level smaller than 2 px");
-        L.pitch = (int)align_up(L.w, 64);
-        L.scale = s;
-        L.kp_size = (float)(unsigned)(31u * s);  // orb_extractor.cc:274
-        L.blur_off = (long long)blur_off;
-        blur_off += align_up((size_t)L.pitch * L.h, 256);
-        if (l > 0) {
-            L.pyr_off = (long long)pyr_off;
-            pyr_off += align_up((size_t)L.pitch * L.h, 256);
-            // ---- resize tables (level l from level l-1)
-            const OrbLevel& P = C.levels[l - 1];
-            const double inv_scale_x = (double)L.w / P.w, inv_scale_y = (double)L.h / P.h;
-            const double scale_x = 1. / inv_scale_x, scale_y = 1. / inv_scale_y;
-            L.xtab_off = (int)xofs.size();
-            L.ytab_off = (int)yofs.size();
-            for (int dx = 0; dx < L.w; ++dx) {
-                float fx = (float)((dx + 0.5) * scale_x - 0.5);
-                int sx = cv_floor_f(fx);
-                fx -= sx;
-                if (sx < 0) {
-                    fx = 0;
-                    sx = 0;
-                }
-                if (sx >= P.w - 1) {
-                    fx = 0;
-                    sx = P.w - 1;
-                }
-                xofs.push_back((short)sx);
-                short2 a;
-                a.x = (short)cv_round_f((1.f - fx) * 2048);
-                a.y = (short)cv_round_f(fx * 2048);
-                xa.push_back(a);
-            }
-            for (int dy = 0; dy < L.h; ++dy) {
-                float fy = (float)((dy + 0.5) * scale_y - 0.5);
-                int sy = cv_floor_f(fy);
-                fy -= sy;
-                short2 o, bb;
-                o.x = (short)(sy < 0 ? 0 : (sy > P.h - 1 ? P.h - 1 : sy));
-                o.y = (short)(sy + 1 < 0 ? 0 : (sy + 1 > P.h - 1 ? P.h - 1 : sy + 1));
-                bb.x = (short)cv_round_f((1.f - fy) * 2048);
-                bb.y = (short)cv_round_f(fy * 2048);
-                yofs.push_back(o);
-                yb.push_back(bb);
-            }
-            // ---- packed records for k_pyramid_lds.  One record per 4 output columns c..c+3 (columns past w-1 repeat w-1):
-            //      w0 = dword index of sx[c] | dword index of sx[c+2] << 16 (two 8-byte windows per source row),
-            //      w1 = byte index inside its window of sx[c], sx[c+1] (window 0), sx[c+2], sx[c+3] (window 1),
-            //      w2..w5 = (a0 | a1 << 16) of the four columns.  sx+1 is always the next byte (its weight is 0 when clamped).
-            L.xg_off = (int)(xg.size() / 8);
-            for (int c = 0; c < L.w; c += 4) {
-                int sxs[4];
-                for (int i = 0; i < 4; ++i) sxs[i] = xofs[L.xtab_off + std::min(c + i, L.w - 1)];
-                const int base0 = sxs[0] >> 2, base2 = sxs[2] >> 2;
-                const int k[4] = {sxs[0] - 4 * base0, sxs[1] - 4 * base0, sxs[2] - 4 * base2, sxs[3] - 4 * base2};
-                for (int i = 0; i < 4; ++i) xg_ok = xg_ok && k[i] >= 0 && k[i] <= 6;
-                xg.push_back((uint32_t)base0 | ((uint32_t)base2 << 16));
-                xg.push_back((uint32_t)(k[0] & 255) | ((uint32_t)(k[1] & 255) << 8) | ((uint32_t)(k[2] & 255) << 16) | ((uint32_t)(k[3] & 255) << 24));
-                for (int i = 0; i < 4; ++i) {
-                    const short2 a = xa[L.xtab_off + std::min(c + i, L.w - 1)];
-                    xg_ok = xg_ok && a.x >= 0 && a.y >= 0;
-                    xg.push_back((uint32_t)(unsigned short)a.x | ((uint32_t)(unsigned short)a.y << 16));
-                }
-                xg.push_back(0);
-                xg.push_back(0);
-            }
-            for (int dy = 0; dy < L.h; ++dy) {
-                const short2 o = yofs[L.ytab_off + dy], c = yb[L.ytab_off + dy];
-                xg_ok = xg_ok && c.x >= 0 && c.y >= 0;
-                yrow.push_back(make_short4(o.x, o.y, c.x, c.y));
-            }
-        }
-        // ---- blur tiles
-        L.btile_first = btile_first;
-        L.btiles_x = (L.w + BLUR_TW - 1) / BLUR_TW;
-        L.btiles_y = (L.h + 4 * C.blur_rows - 1) / (4 * C.blur_rows);
-        btile_first += L.btiles_x * L.btiles_y + ((L.h + 7) / 8 + 63) / 64;  // + edge tiles (64 strips of BLUR_EDGE_ROWS rows each)
-        L.bband_first = bband_first;
-        L.bband_segs = (L.w + BLUR_SEG - 1) / BLUR_SEG;
-        bband_first += L.bband_segs * ((L.h + BLUR_ROWS - 1) / BLUR_ROWS);
-        // ---- FAST cell lattice and selection grid
-        L.cell_first = (int)C.cells.size();
-        L.grid_first = grid_first;
-        L.gtab_x_off = L.gtab_y_off = (int)gtab.size();
-        if (L.w > 2 * SV_PATCH_RADIUS && L.h > 2 * SV_PATCH_RADIUS) {
-            L.has_cells = 1;
-            const unsigned min_bx = SV_PATCH_RADIUS, min_by = SV_PATCH_RADIUS;
-            const unsigned max_bx = L.w - SV_PATCH_RADIUS, max_by = L.h - SV_PATCH_RADIUS;
-            const unsigned rw = max_bx - min_bx, rh = max_by - min_by;
-            const unsigned num_cols = rw / SV_CELL + 1, num_rows = rh / SV_CELL + 1;
-            L.cells_x = (int)num_cols;
-            for (unsigned i = 0; i < num_rows; ++i) {
-                const unsigned min_y = min_by + i * SV_CELL;
-                if (max_by - SV_OVERLAP <= min_y) continue;
-                unsigned max_y = min_y + SV_CELL + SV_OVERLAP;
-                if (max_by < max_y) max_y = max_by;
-                for (unsigned j = 0; j < num_cols; ++j) {
-                    const unsigned min_x = min_bx + j * SV_CELL;
-                    if (max_bx - SV_OVERLAP <= min_x) continue;
-                    unsigned max_x = min_x + SV_CELL + SV_OVERLAP;
-                    if (max_bx < max_x) max_x = max_bx;
-                    FastCell c;
-                    c.min_x = (short)min_x;
-                    c.min_y = (short)min_y;
-                    c.w = (short)(max_x - min_x);
-                    c.h = (short)(max_y - min_y);
-                    c.lv = (short)l;
-                    c.cj = (short)j;
-                    c.order_base = (int)((i * num_cols + j) << 14);
-                    C.cells.push_back(c);
-                }
-            }
-            // distribute_keypoints (:292-305)
-            const double scaled_min_area_sqrt = C.min_area_sqrt / s;  // fp32 division, widened
-            const unsigned gx = (unsigned)std::ceil((int)rw / scaled_min_area_sqrt);
-            const unsigned gy = (unsigned)std::ceil((int)rh / scaled_min_area_sqrt);
-            const double delta_x = (double)(int)rw / gx, delta_y = (double)(int)rh / gy;
-            L.grid_x = (int)gx;
-            L.grid_y = (int)gy;
-            L.gtab_x_off = (int)gtab.size();
-            for (unsigned x = 0; x < rw; ++x) {
-                unsigned ix = (unsigned)((float)x / delta_x);
-                gtab.push_back((unsigned short)(ix < gx ? ix : gx - 1));
-            }
-            L.gtab_y_off = (int)gtab.size();
-            grid_rows[l].assign(gy, std::make_pair(1 << 30, -1));
-            for (unsigned y = 0; y < rh; ++y) {
-                unsigned iy = (unsigned)((float)y / delta_y);
-                iy = iy < gy ? iy : gy - 1;
-                gtab.push_back((unsigned short)iy);
-                grid_rows[l][iy].first = std::min(grid_rows[l][iy].first, (int)(min_by + y));
-                grid_rows[l][iy].second = std::max(grid_rows[l][iy].second, (int)(min_by + y));
-            }
-            grid_first += (int)(gx * gy);
-        }
-        L.cell_count = (int)C.cells.size() - L.cell_first;
-    }
-    C.total_grid = grid_first;
-    C.total_btiles = btile_first;
-    C.total_bbands = bband_first;
-    // ---- bands of k_describe_bands: as many consecutive selection-grid rows of a level as fit the LDS budget (and DB_MAX_KP = 128 keypoints).
-    //      A keypoint of grid row g lies on level rows [first(g), last(g)]; its patches need rows y - 15 .. y + 16 (un-blurred; row y + 16 carries
-    //      zero weights but is read) and y - 18 .. y + 18 (blurred).  LDS pitch: the level width rounded up to 16-byte pieces, then to 32 mod 64
-    //      (eight rows of dword reads then fall into 64 different banks); pieces beyond the level's own pitch read the next row's first bytes.
-    {
-        C.dbands.clear();
-        C.dband_lds_bytes = 0;
-        size_t budget = 48 * 1024;  // three 512-thread workgroups per CU
-        if (const char* e = getenv("SVGPU_DESC_BAND_KB")) budget = (size_t)std::max(1, atoi(e)) * 1024;
-        const size_t hard_limit = 80 * 1024;  // two workgroups per CU; wider images than that take k_describe
-        bool ok = C.total_grid > 0 && getenv("SVGPU_DESCRIBE_LEGACY") == nullptr;
-        for (int l = 0; l < num_levels && ok; ++l) {
-            const OrbLevel& L = C.levels[l];
-            if (!L.has_cells) continue;
-            int lp = (L.w + 15) / 16 * 16;
-            while (lp % 64 != 32) lp += 16;
-            if (lp > 32000) ok = false;
-            const int gy = L.grid_y, gx = L.grid_x;
-            auto band_bytes = [&](int g0, int g1, DescBand* out) {  // rows of grid rows [g0, g1)
-                int y0 = 1 << 30, y1 = -1;
-                for (int g = g0; g < g1; ++g)
-                    if (grid_rows[l][g].second >= 0) {
-                        y0 = std::min(y0, grid_rows[l][g].first);
-                        y1 = std::max(y1, grid_rows[l][g].second);
-                    }
-                if (y1 < 0) y0 = y1 = SV_PATCH_RADIUS;  // (grid rows no level row maps to: no keypoints either)
-                const int nru = y1 - y0 + 32, nrb = y1 - y0 + 37;
-                const int rpi = std::max(1, 64 / (lp / 16));  // a staging instruction carries whole groups of rpi rows: room for the last group
-                const size_t bytes = (size_t)((std::max(nru, nrb) + rpi - 1) / rpi * rpi) * lp;
-                if (out) {
-                    out->lv = (short)l;
-                    out->lp = (short)lp;
-                    out->yu0 = (short)(y0 - 15);
-                    out->nru = (short)nru;
-                    out->yb0 = (short)(y0 - 18);
-                    out->nrb = (short)nrb;
-                    out->img_bytes = (int)bytes;
-                    out->cell0 = L.grid_first + g0 * gx;
-                    out->cell1 = L.grid_first + g1 * gx;
-                }
-                return bytes;
-            };
-            if (gx > 128) ok = false;
-            for (int g0 = 0; g0 < gy && ok;) {
-                int g1 = g0 + 1;
-                if (band_bytes(g0, g1, nullptr) > hard_limit) ok = false;
-                while (g1 < gy && (g1 + 1 - g0) * gx <= 128 && band_bytes(g0, g1 + 1, nullptr) <= budget) ++g1;
-                DescBand bd;
-                C.dband_lds_bytes = std::max(C.dband_lds_bytes, band_bytes(g0, g1, &bd));
-                C.dbands.push_back(bd);
-                g0 = g1;
-            }
-        }
-        if (!ok) C.dbands.clear();
-        // heaviest bands first (level 0 stages the most bytes per keypoint): the tail of the launch is made of the light ones
-        std::stable_sort(C.dbands.begin(), C.dbands.end(), [](const DescBand& a, const DescBand& b) { return a.img_bytes > b.img_bytes; });
-        if (!C.dbands.empty()) C.dband_lds_bytes += 2 * 128 * sizeof(int2);  // + the per-keypoint arrays (DB_MAX_KP)
-    }
-    C.pyr_frame_bytes = pyr_off ? pyr_off : 256;
-    C.blur_frame_bytes = blur_off;
-
-    // ---- pyramid bands: band k owns rows [k*h/K, (k+1)*h/K) of every level; bottom-up it also needs the source rows
-    //      of everything it computes at the next level (two taps per output row, clamped -- the yofs table).
-    //      K is the smallest count (>= 16) whose per-band LDS footprint fits k_pyramid_lds; none fits -> global variant.
-    auto make_bands = [&](int bands, std::vector<int2>& band_rows) -> size_t {
-        band_rows.assign((size_t)bands * num_levels, int2{0, 0});
-        size_t worst = 0;
-        for (int k = 0; k < bands; ++k) {
-            int need_lo = 0, need_hi = 0;
-            for (int l = num_levels - 1; l >= 1; --l) {
-                const OrbLevel& Lv = C.levels[l];
-                int lo = (int)((long long)k * Lv.h / bands), hi = (int)((long long)(k + 1) * Lv.h / bands);
-                if (l < num_levels - 1 && need_hi > need_lo) {
-                    lo = std::min(lo, need_lo);
-                    hi = std::max(hi, need_hi);
-                }
-                band_rows[(size_t)k * num_levels + l] = int2{lo, hi};
-                // rows of level l-1 read by rows [lo, hi) of level l
-                need_lo = 1 << 30;
-                need_hi = 0;
-                for (int dy = lo; dy < hi; ++dy) {
-                    const short2 o = yofs[Lv.ytab_off + dy];
-                    need_lo = std::min(need_lo, (int)o.x);
-                    need_hi = std::max(need_hi, (int)o.y + 1);
-                }
-            }
-            if (need_hi > need_lo) band_rows[(size_t)k * num_levels] = int2{need_lo, need_hi};  // level-0 rows the band reads
-            size_t size_a = 0, size_b = 0;  // must mirror the LDS map of k_pyramid_lds: odd / even levels (level 0 included) alternate in two regions
-            for (int l = 0; l < num_levels; ++l) {
-                const int2 r = band_rows[(size_t)k * num_levels + l];
-                const size_t b = (size_t)(r.y - r.x) * (size_t)((C.levels[l].w + 3) & ~3);
-                if (l & 1) size_a = std::max(size_a, b);
-                else size_b = std::max(size_b, b);
-            }
-            size_a = (size_a + 15) & ~(size_t)15;
-            size_b = (size_b + 15) & ~(size_t)15;
-            size_t bytes = size_a + size_b;
-            for (int l = 1; l < num_levels; ++l) {
-                const int2 r = band_rows[(size_t)k * num_levels + l];
-                bytes += (size_t)(r.y - r.x) * 8;
-            }
-            worst = std::max(worst, bytes);
-        }
-        return worst;
-    };
-    std::vector<int2> band_rows;
-    // few, tall bands recompute the fewest halo rows; small batches need more bands to fill the 256 CUs.  A footprint of at most half the
-    // CU's LDS lets two workgroups share a CU (one computes while the other waits at a level barrier): preferred while <= 32 bands reach it.
-    int bands = std::max(8, std::min(32, (512 + max_batch - 1) / std::max(max_batch, 1)));
-    bool forced = false;
-    if (const char* e = getenv("SVGPU_PYR_BANDS")) {
-        bands = std::max(1, atoi(e));
-        forced = true;
-    }
-    xg_ok = xg_ok && (num_levels < 2 || C.levels[1].w <= 4 * 1024);  // one thread per column group of a level: at most 1024 groups
-    size_t lds = 0;
-    if (!forced && xg_ok) {
-        std::vector<int2> trial;
-        for (int k = bands; k <= 32; k += 2)
-            if (make_bands(k, trial) <= SV_PYR_LDS_HALF) {
-                bands = k;
-                break;
-            }
-    }
-    for (;; bands += 2) {
-        lds = make_bands(bands, band_rows);
-        if (lds <= SV_PYR_LDS_MAX && xg_ok) break;
-        if (bands >= 256 || !xg_ok) {  // very wide images: chain the levels through global memory instead (k_pyramid)
-            bands = 16;
-            make_bands(bands, band_rows);
-            lds = 0;
-            break;
-        }
-    }
-    ctx->pyr_bands = bands;
-    ctx->pyr_lds_bytes = lds;
-    if (lds) SV_HIP(ctx, sv_pyramid_prepare());
-    {
-        int rcb;
-        if ((rcb = upload(ctx, &ctx->d_band_rows, band_rows))) return rcb;
-    }
-    std::vector<OrbLevel> lv(C.levels, C.levels + num_levels);
+    C = std::move(plan.config);
+    const OrbTables& T = plan.tables;
+    const std::vector<OrbLevel> lv(C.levels, C.levels + num_levels);
     int rc;
+    if ((rc = upload(ctx, &ctx->d_band_rows, T.band_rows))) return rc;  // int2 <- OrbInt2
     if ((rc = upload(ctx, &ctx->d_levels, lv))) return rc;
     if ((rc = upload(ctx, &ctx->d_cells, C.cells))) return rc;
-    if ((rc = upload(ctx, &ctx->d_xofs, xofs))) return rc;
-    if ((rc = upload(ctx, &ctx->d_xa, xa))) return rc;
-    if ((rc = upload(ctx, &ctx->d_yofs, yofs))) return rc;
-    if ((rc = upload(ctx, &ctx->d_yb, yb))) return rc;
-    if ((rc = upload(ctx, &ctx->d_xg, xg))) return rc;
-    if ((rc = upload(ctx, &ctx->d_yrow, yrow))) return rc;
-    if ((rc = upload(ctx, &ctx->d_gtab, gtab))) return rc;
+    if ((rc = upload(ctx, &ctx->d_xofs, T.xofs))) return rc;
+    if ((rc = upload(ctx, &ctx->d_xa, T.xa))) return rc;      // short2 <- OrbShort2
+    if ((rc = upload(ctx, &ctx->d_yofs, T.yofs))) return rc;  // short2 <- OrbShort2
+    if ((rc = upload(ctx, &ctx->d_yb, T.yb))) return rc;      // short2 <- OrbShort2
+    if ((rc = upload(ctx, &ctx->d_xg, T.xg))) return rc;
+    if ((rc = upload(ctx, &ctx->d_yrow, T.yrow))) return rc;  // short4 <- OrbShort4
+    if ((rc = upload(ctx, &ctx->d_gtab, T.gtab))) return rc;
+    if (C.pyr_lds_bytes) SV_HIP(ctx, sv_pyramid_prepare());
     if (!C.dbands.empty()) {
         if ((rc = upload(ctx, &ctx->d_dbands, C.dbands))) return rc;
         SV_HIP(ctx, sv_describe_bands_prepare(C.dband_lds_bytes));
@@ -478,58 +168,50 @@ int svgpu_orb_extract_batch_device_angles(svgpu_ctx* ctx, const uint8_t* imgs_de
     SV_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
     ctx->last_extract_n = -1;  // whatever the last svgpu_orb_extract left behind is stale from here on (it sets the count again after its own call)
-    const int Lc = C.num_levels;
+    // 0. plan: which kernels this call takes, and the images every one of them reads
+    const OrbEnv env = orb_env();
+    const bool aligned = (((size_t)imgs_dev | (size_t)frame_stride | (size_t)row_stride) & 3) == 0;
+    const OrbLaunch plan = orb_launch_plan(C, batch, aligned, env);
+    const OrbFrames F{ctx->d_levels, C.num_levels, imgs_dev, frame_stride, row_stride, ctx->d_pyr, C.pyr_frame_bytes, ctx->d_blur, C.blur_frame_bytes, batch};
     // 1. pyramid: chained bilinear resize (level l from level l-1), all levels in one launch (banded, see k_pyramid)
-    if (Lc > 1) {
+    if (C.num_levels > 1) {
         SvProfScope ps(ctx, s, "k_resize");
-        sv_launch_pyramid(s, ctx->d_levels, Lc, ctx->d_band_rows, ctx->pyr_bands, imgs_dev, frame_stride, row_stride, ctx->d_pyr,
-                          C.pyr_frame_bytes, ctx->d_xofs, ctx->d_xa, ctx->d_yofs, ctx->d_yb, ctx->d_xg, ctx->d_yrow, batch, ctx->pyr_lds_bytes);
+        sv_launch_pyramid(s, F, plan, ctx->d_band_rows, C.pyr_bands, C.pyr_lds_bytes, ctx->d_xofs, ctx->d_xa, ctx->d_yofs, ctx->d_yb, ctx->d_xg, ctx->d_yrow);
     }
     // 2. blurred copy of every level -- on the auxiliary stream, beside steps 3-4: the blur waits on memory where FAST is bound by
     //    instruction issue, so the two share the CUs well; step 5 joins them
-    static const bool fork_blur = getenv("SVGPU_FORK_BLUR") != nullptr;  // opt-in, see DESIGN.md section 6
-    hipStream_t sb = (ctx->stream_aux && fork_blur) ? ctx->stream_aux : s;
+    hipStream_t sb = (ctx->stream_aux && env.fork_blur) ? ctx->stream_aux : s;
     if (sb != s) {
         SV_HIP(ctx, hipEventRecord(ctx->ev_fork, s));
         SV_HIP(ctx, hipStreamWaitEvent(sb, ctx->ev_fork, 0));
     }
     {
         SvProfScope ps(ctx, sb, "k_blur");
-        // levels the band / streaming kernel cannot take (caller image not 4-byte aligned, level narrower than 16 px) -> gather kernel
-        bool need_gather = (((size_t)imgs_dev | (size_t)frame_stride | (size_t)row_stride) & 3) != 0;
-        for (int l = 0; l < Lc; ++l) need_gather = need_gather || C.levels[l].w < 16;
-        sv_launch_blur(sb, ctx->d_levels, Lc, C.total_btiles, C.total_bbands, imgs_dev, frame_stride, row_stride, ctx->d_pyr, C.pyr_frame_bytes,
-                       ctx->d_blur, C.blur_frame_bytes, batch, need_gather, C.blur_rows);
+        sv_launch_blur(sb, F, plan, C.total_btiles, C.total_bbands);
     }
     if (sb != s) SV_HIP(ctx, hipEventRecord(ctx->ev_join, sb));
     // 3. FAST per cell + selection-grid arg-max
     SV_HIP(ctx, hipEventRecord(ctx->ev_stage[0], s));
     {
         SvProfScope ps(ctx, s, "k_fast");
-        sv_launch_fast(s, ctx->d_levels, Lc, ctx->d_cells, (int)C.cells.size(), imgs_dev, frame_stride, row_stride, ctx->d_pyr,
-                   C.pyr_frame_bytes, ctx->d_gtab, ctx->d_keys, C.total_grid, C.ini_thr, C.min_thr, mask_dev,
-                       mask_frame_stride, mask_row_stride, C.width, C.height, batch);
+        sv_launch_fast(s, F, plan.fast_cpw, ctx->d_cells, (int)C.cells.size(), ctx->d_gtab, ctx->d_keys, C.total_grid, C.ini_thr, C.min_thr, mask_dev,
+                       mask_frame_stride, mask_row_stride, C.width, C.height);
     }
     // 4. ordered compaction (+ key reset for the next call)
     {
         SvProfScope ps(ctx, s, "k_select");
-        sv_launch_select(s, ctx->d_levels, Lc, ctx->d_keys, C.total_grid, ctx->d_sel, counts_dev, C.dbands.empty() ? nullptr : ctx->d_cellpos, batch);
+        sv_launch_select(s, F, ctx->d_keys, C.total_grid, ctx->d_sel, counts_dev, C.dbands.empty() ? nullptr : ctx->d_cellpos);
     }
     // 5. orientation, descriptor, scale correction
     if (sb != s) SV_HIP(ctx, hipStreamWaitEvent(s, ctx->ev_join, 0));
     SV_HIP(ctx, hipEventRecord(ctx->ev_stage[1], s));
     ctx->stage_recorded = true;
     SvProfScope ps(ctx, s, "k_describe");
-    // bands when the batch alone fills the chip (they are bound by throughput: 0.80 against 1.20 ms per 1 024 frames); for a few frames the
-    // per-keypoint kernel's many short workgroups finish sooner (one frame: 11 against 17 us, break-even near 16 frames of 2 400 keypoints)
-    const bool bands = !C.dbands.empty() && ((long long)batch * C.total_grid >= 32768 || getenv("SVGPU_DESCRIBE_BANDS") != nullptr);
-    if (bands)
-        sv_launch_describe_bands(s, ctx->d_levels, Lc, ctx->d_dbands, (int)C.dbands.size(), C.dband_lds_bytes, ctx->d_sel, C.total_grid, ctx->d_cellpos,
-                                 counts_dev, imgs_dev, frame_stride, row_stride, ctx->d_pyr, C.pyr_frame_bytes, ctx->d_blur, C.blur_frame_bytes,
-                                 kps_dev, desc_dev, cap, batch, angles_dev);
+    if (plan.describe_bands)
+        sv_launch_describe_bands(s, F, ctx->d_dbands, (int)C.dbands.size(), C.dband_lds_bytes, ctx->d_sel, C.total_grid, ctx->d_cellpos, counts_dev, kps_dev,
+                                 desc_dev, cap, angles_dev);
     else
-        sv_launch_describe(s, ctx->d_levels, Lc, ctx->d_sel, C.total_grid, counts_dev, imgs_dev, frame_stride, row_stride,
-                           ctx->d_pyr, C.pyr_frame_bytes, ctx->d_blur, C.blur_frame_bytes, kps_dev, desc_dev, cap, batch, angles_dev);
+        sv_launch_describe(s, F, ctx->d_sel, C.total_grid, counts_dev, kps_dev, desc_dev, cap, angles_dev);
     SV_HIP(ctx, hipGetLastError());
     ctx->last_batch = batch;
     ctx->last_imgs = imgs_dev;

@@ -16,7 +16,7 @@ from stella_vslam_amd import synthetic as S
 
 pytestmark = pytest.mark.gpu
 
-# mirrors of stella_vslam_amd/csrc/svgpu_internal.h (test_constants_mirror_the_header reads the header)
+# mirrors of stella_vslam_amd/csrc/orb_plan.h (test_constants_mirror_the_header reads the header)
 BLUR_ROWS = 48        # output rows of a band
 BLUR_SMALL_BATCH = 4  # contexts of at most this many frames keep the streaming kernel
 MAX_BATCH = BLUR_SMALL_BATCH + 1
@@ -43,7 +43,7 @@ def _assert_blur_matches(ext, what):
 
 
 def test_constants_mirror_the_header():
-    hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "stella_vslam_amd", "csrc", "svgpu_internal.h")).read()
+    hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "stella_vslam_amd", "csrc", "orb_plan.h")).read()
     assert int(re.search(r"^#define BLUR_ROWS (\d+)", hdr, flags=re.M).group(1)) == BLUR_ROWS
     assert int(re.search(r"^#define BLUR_SMALL_BATCH (\d+)", hdr, flags=re.M).group(1)) == BLUR_SMALL_BATCH
 

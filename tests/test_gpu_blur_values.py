@@ -15,7 +15,7 @@ import pytest
 from oracle import oracle as O
 
 TAPS = (18, 34, 48, 56, 48, 34, 18)
-BLUR_SMALL_BATCH = 4  # stella_vslam_amd/csrc/svgpu_internal.h (tests/test_gpu_blur_bands.py checks the mirror against the header)
+BLUR_SMALL_BATCH = 4  # stella_vslam_amd/csrc/orb_plan.h (tests/test_gpu_blur_bands.py checks the mirror against the header)
 SIZES = [(96, 64), (331, 250)]  # one band, one segment; all four w % 4 classes over the levels, a segment boundary at 320, a ragged last band
 
 # The one place the tap dwords live on the Python side: TAP_DWORDS[j] = (x w0, x w1, x w2) for owned pixel j of the window w0 | w1 | w2, where

@@ -44,6 +44,22 @@ def test_extract_bit_exact(F, w, h, seed, bands, monkeypatch):
     _assert_same(kg, dg, ko, do)
 
 
+def test_extract_bit_exact_wide_image_global_pyramid(F):
+    """Level 1 of a 4920 x 48 frame is 4100 px wide: more than the 4096 px of the LDS-resident pyramid kernel's column groups, so the
+    configuration takes k_pyramid, the variant that chains the levels through global memory (and k_describe: a band of level 0 does not fit LDS)."""
+    img = S.frame(4920, 48, 12)
+    ext = F.orb_extractor(F.orb_params("wide", 1.2, 2, 20, 7))
+    kg, dg = ext.extract(img)
+    ko, do, counts, pyr = O.orb_extract(img, num_levels=2, want_pyramid=True)
+    assert len(ko) > 50 and pyr[1].shape == (40, 4100)
+    for l, (a, b) in enumerate(zip(ext.image_pyramid_, pyr)):
+        assert np.array_equal(a, b), f"pyramid level {l}"
+    for l, a in enumerate(ext.blurred_pyramid()):
+        assert np.array_equal(a, O.gaussian_blur7(pyr[l])), f"blurred level {l}"
+    assert np.array_equal(ext.level_counts_, counts)
+    _assert_same(kg, dg, ko, do)
+
+
 def test_extract_params_and_strided_input(F):
     big = S.frame(700, 500, 3)
     view = big[10:490, 30:670]  # non-contiguous rows (stride 700)
