@@ -715,6 +715,44 @@ int svgpu_pnp_ransac(svgpu_ctx* ctx, const double* bearings, const double* pos_w
                      int gauss_newton_num_iter, uint8_t* valid, double* pose_cw, uint8_t* is_inlier, int32_t* best_iter, double* hyp_pose,
                      int32_t* hyp_num_inliers, double* hyp_cost);
 
+/* ------------------------------------------------------------------------------ Sim3 pose-graph optimisation (loop correction)
+ * optimize::graph_optimizer::optimize (optimize/graph_optimizer.cc:26-303), the step module::global_optimization_module::correct_loop runs
+ * between loop validation and the global bundle adjustment.  Every vertex is a Sim3 (8 doubles: qx qy qz qw tx ty tz s, g2o's unit
+ * quaternion, translation, scale), every edge the 7-vector log(Sim3_21 * v1 * v2^-1) with identity information and g2o's numeric Jacobian
+ * (central differences, delta 1e-9, through exp(update) * estimate; with fix_scale coordinate 6 of every update is zero).  Levenberg-
+ * Marquardt as svgpu_global_ba runs it (lambda0 = 1e-5 max diag H, at most 10 damping trials per iteration) with terminate_action on the
+ * relative chi2 gain; no robust kernel.  The damped 7x7-block system is solved by block-Jacobi PCG to a relative residual of 1e-14, capped
+ * at 10 iterations per unknown.  fp64 throughout, sums in a fixed order, no atomics: two calls on the same input are bit-equal.
+ *   sim3 / fixed      num_vertices x 8 doubles, num_vertices bytes (non-zero: the vertex is fixed and comes back bit-equal)
+ *   edge_v1 / edge_v2 / edge_sim3_21   num_edges vertex indices each, num_edges x 8 doubles.  Duplicate edges between one pair are allowed;
+ *                     an edge between two fixed vertices contributes to chi2 only
+ *   sim3_out          num_vertices x 8; pose_cw_out (nullable) num_vertices x 12: rows 0..2 of [R | t / s] as the reference writes the
+ *                     pose back (:272-278, the scale rounded to a float first)
+ * SVGPU_ERR_INVALID before anything is launched: num_vertices or num_edges < 1, max_iterations < 0, an index out of range, a self-edge, a
+ * quaternion whose squared norm is further than 1e-9 from 1, a scale that is not positive and finite, a free vertex without an edge, no
+ * fixed vertex.  Host in/out, synchronous: one upload, the launches on the context's stream, one read-back; the damping decisions are
+ * taken on the device and the host only polls for the end of the run between batches of enqueued trials. */
+typedef struct svgpu_pose_graph_stats {
+    int32_t lm_iterations;    /* LM iterations run */
+    int32_t lm_trials;        /* damping trials = linear solves */
+    int32_t pcg_iterations;   /* PCG iterations over all solves */
+    int32_t pcg_capped;       /* solves that ended at the iteration cap */
+    int32_t stopped_by_gain;  /* terminate_action raised the stop flag */
+    int32_t num_free;         /* free vertices */
+    double initial_chi2;
+    double final_chi2;
+    double lambda;            /* damping after the last trial */
+} svgpu_pose_graph_stats;
+int svgpu_pose_graph_optimize(svgpu_ctx* ctx, int num_vertices, const double* sim3, const uint8_t* fixed, int num_edges, const int32_t* edge_v1,
+                              const int32_t* edge_v2, const double* edge_sim3_21, int fix_scale, int max_iterations, double gain_threshold,
+                              double* sim3_out, double* pose_cw_out, svgpu_pose_graph_stats* stats);
+
+/* Step 5 of the same function (:284-301): pos_out = sim3_after[ref]^-1 .map( sim3_before[ref] .map(pos_w) ) for num_landmarks landmarks,
+ * ref_vertex being the landmark's reference vertex.  The output feeds svgpu_landmarks_update_geometry.  SVGPU_ERR_INVALID for a
+ * reference out of range; num_landmarks == 0 is a success. */
+int svgpu_pose_graph_correct_landmarks(svgpu_ctx* ctx, int num_vertices, const double* sim3_before, const double* sim3_after, int num_landmarks,
+                                       const int32_t* ref_vertex, const double* pos_w, double* pos_w_out);
+
 /* bow_tree::match_frame_and_keyframe (match/bow_tree.cc:169-256) and bow_tree::match_keyframes (:258-366).
  * Side 1 = the keyframe whose landmarks are handed over (queries: valid1 = keypoint holds a live landmark), side 2 = the frame /
  * the other keyframe (valid2 nullable = every keypoint, or "holds a live landmark" for match_keyframes; occupied2 nullable = keypoints

@@ -43,6 +43,11 @@ def lib() -> C.CDLL:
         _LIB.svgpu_last_error.restype = C.c_char_p
         _LIB.svgpu_status_string.restype = C.c_char_p
         _LIB.svgpu_stream.restype = C.c_void_p
+        vp, i32 = C.c_void_p, C.c_int
+        _LIB.svgpu_pose_graph_optimize.restype = C.c_int
+        _LIB.svgpu_pose_graph_optimize.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, i32, i32, C.c_double, vp, vp, vp]
+        _LIB.svgpu_pose_graph_correct_landmarks.restype = C.c_int
+        _LIB.svgpu_pose_graph_correct_landmarks.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp]
         if _LIB.svgpu_abi_version() != 1:
             raise ImportError("libsvgpu.so ABI version mismatch")
     return _LIB

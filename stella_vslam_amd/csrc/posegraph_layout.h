@@ -1,0 +1,71 @@
+// The scratch-arena layouts of the pose-graph entry points (svgpu_posegraph.hip), as functions of an arena: run on a measuring arena they
+// give the bytes the call asks for, run on the placing arena they hand out the pieces.  Plain C++ (no HIP):
+// tests/posegraph_arena_check.cpp compiles this header with sv_arena.h alone.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+#include "sv_arena.h"
+
+#define PG_LAYOUT_REC 162     // doubles per edge record (PG_REC of posegraph_kernels.h; svgpu_posegraph.hip asserts they agree)
+#define PG_LAYOUT_CTL 128     // bytes reserved for the control block (>= sizeof(PgCtl), asserted there too)
+
+struct PgPieces {
+    // uploaded
+    char* ctl;
+    double* est0;  // the estimate buffer the input goes to
+    uint8_t* fixed;
+    int32_t *slot, *e_i, *e_j;
+    double* meas;
+    int32_t *v_off, *v_ent;
+    // device only
+    double* est1;
+    double *rec, *chi_trial, *Hd, *b, *maxd, *Minv, *x, *r, *z, *p, *Ap, *scale_part;
+    // results
+    double *out_sim3, *out_pose;
+};
+// svgpu_pose_graph_optimize: N vertices of which nfree are free, E edges, `incident` entries in the free vertices' edge lists (<= 2 E)
+template <class A>
+void pg_optimize_layout(A& arena, size_t N, size_t E, size_t nfree, size_t incident, PgPieces& Y) {
+    const size_t n = 7 * nfree;
+    Y.ctl = arena.template take<char>(PG_LAYOUT_CTL);
+    Y.est0 = arena.template take<double>(8 * N);
+    Y.fixed = arena.template take<uint8_t>(N);
+    Y.slot = arena.template take<int32_t>(N);
+    Y.e_i = arena.template take<int32_t>(E);
+    Y.e_j = arena.template take<int32_t>(E);
+    Y.meas = arena.template take<double>(8 * E);
+    Y.v_off = arena.template take<int32_t>(nfree + 1);
+    Y.v_ent = arena.template take<int32_t>(incident);
+    Y.est1 = arena.template take<double>(8 * N);
+    Y.rec = arena.template take<double>(PG_LAYOUT_REC * E);
+    Y.chi_trial = arena.template take<double>(E);
+    Y.Hd = arena.template take<double>(49 * nfree);
+    Y.b = arena.template take<double>(n);
+    Y.maxd = arena.template take<double>(nfree);
+    Y.Minv = arena.template take<double>(49 * nfree);
+    Y.x = arena.template take<double>(n);
+    Y.r = arena.template take<double>(n);
+    Y.z = arena.template take<double>(n);
+    Y.p = arena.template take<double>(n);
+    Y.Ap = arena.template take<double>(n);
+    Y.scale_part = arena.template take<double>(nfree);
+    Y.out_sim3 = arena.template take<double>(8 * N);
+    Y.out_pose = arena.template take<double>(12 * N);
+}
+
+struct PgLandmarkPieces {
+    double *before, *after;  // uploaded
+    int32_t* ref;
+    double* pos_in;
+    double* pos_out;         // result
+};
+// svgpu_pose_graph_correct_landmarks: N vertices, L landmarks
+template <class A>
+void pg_landmarks_layout(A& arena, size_t N, size_t L, PgLandmarkPieces& Y) {
+    Y.before = arena.template take<double>(8 * N);
+    Y.after = arena.template take<double>(8 * N);
+    Y.ref = arena.template take<int32_t>(L);
+    Y.pos_in = arena.template take<double>(3 * L);
+    Y.pos_out = arena.template take<double>(3 * L);
+}

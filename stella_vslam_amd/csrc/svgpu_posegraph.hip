@@ -1,0 +1,209 @@
+// svgpu_pose_graph_optimize / svgpu_pose_graph_correct_landmarks: host glue of the pose-graph kernels (posegraph_kernels.hip).  Host arrays
+// in and out, synchronous: one upload, the launches on the context's stream, one read-back.  The Levenberg-Marquardt decisions are taken
+// on the device (PgCtl); the host enqueues batches of damping trials and reads the control block between batches only to learn whether the
+// run has ended.
+#include <cmath>
+
+#include "svgpu_match_common.h"
+#include "posegraph_kernels.h"
+#include "posegraph_layout.h"
+
+using namespace svm;
+
+static_assert(PG_LAYOUT_REC == PG_REC, "posegraph_layout.h and posegraph_kernels.h disagree on the edge record");
+static_assert(sizeof(PgCtl) <= PG_LAYOUT_CTL, "posegraph_layout.h reserves too little for PgCtl");
+
+namespace {
+
+bool sim3_ok(const double* p) {
+    double n2 = 0.0;
+    for (int k = 0; k < 8; ++k)
+        if (!std::isfinite(p[k])) return false;
+    for (int k = 0; k < 4; ++k) n2 += p[k] * p[k];
+    return std::fabs(n2 - 1.0) <= 1e-9 && p[7] > 0.0;
+}
+
+// one damping trial; the kernels of a step that has nothing to do (PgCtl::phase) return at once
+void enqueue_step(svgpu_ctx* ctx, hipStream_t s, const PgDev& D) {
+    {
+        SvProfScope prof(ctx, s, "k_pg_linearize");
+        sv_pg_linearize(s, D);
+    }
+    {
+        SvProfScope prof(ctx, s, "k_pg_assemble");
+        sv_pg_assemble(s, D);
+    }
+    sv_pg_prepare(s, D);
+    {
+        SvProfScope prof(ctx, s, "k_pg_solve");
+        sv_pg_precond(s, D);
+        sv_pg_solve(s, D);
+    }
+    {
+        SvProfScope prof(ctx, s, "k_pg_trial");
+        sv_pg_update(s, D);
+        sv_pg_chi2(s, D);
+        sv_pg_decide(s, D);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int svgpu_pose_graph_optimize(svgpu_ctx* ctx, int num_vertices, const double* sim3, const uint8_t* fixed, int num_edges, const int32_t* edge_v1,
+                              const int32_t* edge_v2, const double* edge_sim3_21, int fix_scale, int max_iterations, double gain_threshold,
+                              double* sim3_out, double* pose_cw_out, svgpu_pose_graph_stats* stats) {
+    const char* who = "svgpu_pose_graph_optimize: bad arguments";
+    if (!ctx || num_vertices < 1 || num_edges < 1 || max_iterations < 0 || !sim3 || !fixed || !edge_v1 || !edge_v2 || !edge_sim3_21 || !sim3_out)
+        return sv_set_error(ctx, SVGPU_ERR_INVALID, who);
+    const int N = num_vertices, E = num_edges;
+    // ---- validation and structure: nothing is launched before all of it has passed
+    std::vector<int32_t> slot(N);
+    int nfree = 0;
+    for (int v = 0; v < N; ++v) {
+        if (!sim3_ok(sim3 + 8 * (size_t)v)) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_pose_graph_optimize: a vertex is not a Sim3 (unit quaternion, positive scale)");
+        slot[v] = fixed[v] ? -1 : nfree++;
+    }
+    if (nfree == N) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_pose_graph_optimize: no fixed vertex");
+    std::vector<int32_t> v_off((size_t)nfree + 1, 0);
+    for (int e = 0; e < E; ++e) {
+        const int a = edge_v1[e], b = edge_v2[e];
+        if (a < 0 || a >= N || b < 0 || b >= N) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_pose_graph_optimize: vertex index out of range");
+        if (a == b) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_pose_graph_optimize: an edge from a vertex to itself");
+        if (!sim3_ok(edge_sim3_21 + 8 * (size_t)e)) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_pose_graph_optimize: a measurement is not a Sim3");
+        if (slot[a] >= 0) ++v_off[slot[a] + 1];
+        if (slot[b] >= 0) ++v_off[slot[b] + 1];
+    }
+    for (int k = 0; k < nfree; ++k) {
+        if (v_off[k + 1] == 0) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_pose_graph_optimize: a free vertex without an edge");
+        v_off[k + 1] += v_off[k];
+    }
+    // the free vertices' edge lists, in ascending edge order (built once: the structure does not change between iterations)
+    const size_t incident = (size_t)v_off[nfree];
+    std::vector<int32_t> v_ent(incident), fill(v_off.begin(), v_off.end() - 1);
+    for (int e = 0; e < E; ++e) {
+        const int sa = slot[edge_v1[e]], sb = slot[edge_v2[e]];
+        if (sa >= 0) v_ent[fill[sa]++] = e << 1;
+        if (sb >= 0) v_ent[fill[sb]++] = e << 1 | 1;
+    }
+
+    SV_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    PgPieces Y{};
+    const auto layout = [&](UploadArena& A) { pg_optimize_layout(A, (size_t)N, (size_t)E, (size_t)nfree, incident, Y); };
+    const size_t need = arena_measure<UploadArena>(layout);
+    int rc;
+    if ((rc = sv_ensure_scratch(ctx, need))) return rc;
+    if ((rc = sv_ensure_stage(ctx, need))) return rc;
+    UploadArena A(ctx, ctx->h_stage);
+    layout(A);
+    if (A.overflow) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_pose_graph_optimize: internal arena overflow");
+    PgCtl c0{};
+    c0.ni = 2.0;
+    c0.gain_thr = gain_threshold;
+    c0.it_max = max_iterations;
+    c0.ok = 1;
+    if ((rc = A.upload(ctx, s, Y.ctl, &c0, sizeof c0))) return rc;
+    if ((rc = A.upload(ctx, s, Y.est0, sim3, (size_t)N * 64))) return rc;
+    if ((rc = A.upload(ctx, s, Y.fixed, fixed, (size_t)N))) return rc;
+    if ((rc = A.upload(ctx, s, Y.slot, slot.data(), (size_t)N * 4))) return rc;
+    if ((rc = A.upload(ctx, s, Y.e_i, edge_v1, (size_t)E * 4))) return rc;
+    if ((rc = A.upload(ctx, s, Y.e_j, edge_v2, (size_t)E * 4))) return rc;
+    if ((rc = A.upload(ctx, s, Y.meas, edge_sim3_21, (size_t)E * 64))) return rc;
+    if ((rc = A.upload(ctx, s, Y.v_off, v_off.data(), ((size_t)nfree + 1) * 4))) return rc;
+    if ((rc = A.upload(ctx, s, Y.v_ent, v_ent.data(), incident * 4))) return rc;
+    if ((rc = A.flush(ctx, s))) return rc;
+
+    PgDev D{};
+    D.N = N, D.E = E, D.nfree = nfree, D.n = 7 * nfree, D.fix_scale = fix_scale != 0;
+    D.ctl = (PgCtl*)Y.ctl;
+    D.est[0] = Y.est0, D.est[1] = Y.est1;
+    D.fixed = Y.fixed, D.slot = Y.slot, D.e_i = Y.e_i, D.e_j = Y.e_j, D.meas = Y.meas, D.v_off = Y.v_off, D.v_ent = Y.v_ent;
+    D.rec = Y.rec, D.chi_trial = Y.chi_trial, D.Hd = Y.Hd, D.b = Y.b, D.maxd = Y.maxd, D.Minv = Y.Minv;
+    D.x = Y.x, D.r = Y.r, D.z = Y.z, D.p = Y.p, D.Ap = Y.Ap, D.scale_part = Y.scale_part;
+    D.out_sim3 = Y.out_sim3, D.out_pose = Y.out_pose;
+
+    // at most 10 trials per iteration; the first step also serves max_iterations == 0 (chi2 of the input, then phase 2)
+    const long max_steps = std::max(1L, 10L * max_iterations);
+    PgCtl* c_host = (PgCtl*)(A.mirror + (Y.ctl - A.base));
+    long done = 0;
+    int batch = 8;
+    for (;;) {
+        const long count = std::min<long>(batch, max_steps - done);
+        for (long k = 0; k < count; ++k) enqueue_step(ctx, s, D);
+        done += count;
+        SV_HIP(ctx, hipGetLastError());
+        SV_HIP(ctx, hipMemcpyAsync(c_host, Y.ctl, sizeof(PgCtl), hipMemcpyDeviceToHost, s));
+        SV_HIP(ctx, hipStreamSynchronize(s));
+        if (c_host->phase == 2 || done >= max_steps) break;
+        batch = 16;
+    }
+    const PgCtl c = *c_host;
+    sv_pg_output(s, D);
+    SV_HIP(ctx, hipGetLastError());
+    Downloads Dl;
+    Dl.add(A, sim3_out, Y.out_sim3, (size_t)N * 64);
+    Dl.add(A, pose_cw_out, Y.out_pose, (size_t)N * 96);
+    if ((rc = Dl.fetch(ctx, s, A))) return rc;
+    SV_HIP(ctx, hipStreamSynchronize(s));
+    Dl.scatter(A);
+    if (stats) {
+        stats->lm_iterations = c.it;
+        stats->lm_trials = c.lm_trials;
+        stats->pcg_iterations = c.pcg_total_it;
+        stats->pcg_capped = c.pcg_capped;
+        stats->stopped_by_gain = c.stopped_by_gain;
+        stats->num_free = nfree;
+        stats->initial_chi2 = c.chi_begin;
+        stats->final_chi2 = c.current_chi;
+        stats->lambda = c.lambda;
+    }
+    return SVGPU_OK;
+}
+
+int svgpu_pose_graph_correct_landmarks(svgpu_ctx* ctx, int num_vertices, const double* sim3_before, const double* sim3_after, int num_landmarks,
+                                       const int32_t* ref_vertex, const double* pos_w, double* pos_w_out) {
+    const char* who = "svgpu_pose_graph_correct_landmarks: bad arguments";
+    if (!ctx || num_vertices < 1 || num_landmarks < 0 || !sim3_before || !sim3_after) return sv_set_error(ctx, SVGPU_ERR_INVALID, who);
+    if (num_landmarks == 0) return SVGPU_OK;
+    if (!ref_vertex || !pos_w || !pos_w_out) return sv_set_error(ctx, SVGPU_ERR_INVALID, who);
+    const size_t N = (size_t)num_vertices, L = (size_t)num_landmarks;
+    for (size_t l = 0; l < L; ++l)
+        if (ref_vertex[l] < 0 || ref_vertex[l] >= num_vertices)
+            return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_pose_graph_correct_landmarks: reference vertex out of range");
+    for (size_t v = 0; v < N; ++v)
+        if (!sim3_ok(sim3_before + 8 * v) || !sim3_ok(sim3_after + 8 * v))
+            return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_pose_graph_correct_landmarks: a vertex is not a Sim3");
+    SV_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    PgLandmarkPieces Y{};
+    const auto layout = [&](UploadArena& A) { pg_landmarks_layout(A, N, L, Y); };
+    const size_t need = arena_measure<UploadArena>(layout);
+    int rc;
+    if ((rc = sv_ensure_scratch(ctx, need))) return rc;
+    if ((rc = sv_ensure_stage(ctx, need))) return rc;
+    UploadArena A(ctx, ctx->h_stage);
+    layout(A);
+    if (A.overflow) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_pose_graph_correct_landmarks: internal arena overflow");
+    if ((rc = A.upload(ctx, s, Y.before, sim3_before, N * 64))) return rc;
+    if ((rc = A.upload(ctx, s, Y.after, sim3_after, N * 64))) return rc;
+    if ((rc = A.upload(ctx, s, Y.ref, ref_vertex, L * 4))) return rc;
+    if ((rc = A.upload(ctx, s, Y.pos_in, pos_w, L * 24))) return rc;
+    if ((rc = A.flush(ctx, s))) return rc;
+    PgLandmarks P{};
+    P.L = num_landmarks, P.N = num_vertices, P.sim3_before = Y.before, P.sim3_after = Y.after, P.ref = Y.ref, P.pos_in = Y.pos_in, P.pos_out = Y.pos_out;
+    {
+        SvProfScope prof(ctx, s, "k_pg_correct_landmarks");
+        sv_pg_correct_landmarks(s, P);
+    }
+    SV_HIP(ctx, hipGetLastError());
+    Downloads Dl;
+    Dl.add(A, pos_w_out, Y.pos_out, L * 24);
+    if ((rc = Dl.fetch(ctx, s, A))) return rc;
+    SV_HIP(ctx, hipStreamSynchronize(s));
+    Dl.scatter(A);
+    return SVGPU_OK;
+}
+
+}  // extern "C"

@@ -70,6 +70,8 @@ template <>
 inline std::string Value::as<std::string>(const std::string& def) const { return s ? *s : def; }
 template <>
 inline bool Value::as<bool>(const bool& def) const { return s ? (*s == "true" || *s == "1") : def; }
+template <>
+inline unsigned int Value::as<unsigned int>(const unsigned int& def) const { return s ? (unsigned int)std::stoul(*s) : def; }
 struct Node {
     std::map<std::string, std::string> kv;
     Value operator[](const std::string& k) const {
@@ -200,6 +202,20 @@ public:
     bool is_spanning_root() const { return spanning_root_; }
     std::vector<std::shared_ptr<keyframe>> covisibilities_;
     bool spanning_root_ = false;
+    // ---- what optimize::hip::graph_optimizer reads (data/graph_node.h:33-140); defined behind keyframe.  `covisibilities_` is the
+    //      ordered list (descending weight), `num_shared_lms_` its weights in the same order (ordered_num_shared_lms_)
+    std::vector<std::shared_ptr<keyframe>> get_covisibilities_over_min_num_shared_lms(const unsigned int min_num_shared_lms) const;  // graph_node.cc:224-258
+    unsigned int get_num_shared_landmarks(const std::shared_ptr<keyframe>& keyfrm) const;                                         // :260-268
+    std::shared_ptr<keyframe> get_spanning_parent() const { return spanning_parent_.lock(); }
+    std::vector<std::shared_ptr<keyframe>> get_spanning_children() const;  // in ascending id, as the reference's id-ordered set iterates
+    bool has_spanning_child(const std::shared_ptr<keyframe>& keyfrm) const;
+    std::set<std::shared_ptr<keyframe>> get_loop_edges() const { return loop_edges_; }
+    std::shared_ptr<keyframe> get_spanning_root();
+    std::vector<std::shared_ptr<keyframe>> get_keyframes_from_root();      // :435-449: breadth first over the spanning children
+    std::vector<unsigned int> num_shared_lms_;
+    std::weak_ptr<keyframe> owner_keyfrm_, spanning_parent_;
+    std::vector<std::weak_ptr<keyframe>> spanning_children_;
+    std::set<std::shared_ptr<keyframe>> loop_edges_;
 };
 
 class map_database {  // data/map_database.h:52, 270
@@ -359,6 +375,41 @@ bool id_less<T>::operator()(const T& a, const T& b) const {
     return (pa ? (long long)pa->id_ : -1) < (pb ? (long long)pb->id_ : -1);
 }
 
+inline std::vector<std::shared_ptr<keyframe>> graph_node::get_covisibilities_over_min_num_shared_lms(const unsigned int min_num_shared_lms) const {
+    std::vector<std::shared_ptr<keyframe>> out;
+    for (size_t k = 0; k < covisibilities_.size() && k < num_shared_lms_.size() && num_shared_lms_[k] >= min_num_shared_lms; ++k) out.push_back(covisibilities_[k]);
+    return out;
+}
+inline unsigned int graph_node::get_num_shared_landmarks(const std::shared_ptr<keyframe>& keyfrm) const {
+    for (size_t k = 0; k < covisibilities_.size() && k < num_shared_lms_.size(); ++k)
+        if (covisibilities_[k] == keyfrm) return num_shared_lms_[k];
+    return 0;
+}
+inline std::vector<std::shared_ptr<keyframe>> graph_node::get_spanning_children() const {
+    std::vector<std::shared_ptr<keyframe>> out;
+    for (const auto& w : spanning_children_)
+        if (auto c = w.lock()) out.push_back(c);
+    std::sort(out.begin(), out.end(), [](const std::shared_ptr<keyframe>& a, const std::shared_ptr<keyframe>& b) { return a->id_ < b->id_; });
+    return out;
+}
+inline bool graph_node::has_spanning_child(const std::shared_ptr<keyframe>& keyfrm) const {
+    for (const auto& w : spanning_children_)
+        if (w.lock() == keyfrm) return true;
+    return false;
+}
+inline std::shared_ptr<keyframe> graph_node::get_spanning_root() {
+    auto k = owner_keyfrm_.lock();
+    while (k && !k->graph_node_->spanning_root_ && k->graph_node_->get_spanning_parent()) k = k->graph_node_->get_spanning_parent();
+    return k;
+}
+inline std::vector<std::shared_ptr<keyframe>> graph_node::get_keyframes_from_root() {
+    std::vector<std::shared_ptr<keyframe>> keyfrms;
+    if (auto root = get_spanning_root()) keyfrms.push_back(root);
+    for (size_t k = 0; k < keyfrms.size(); ++k)
+        for (const auto& child : keyfrms[k]->graph_node_->get_spanning_children()) keyfrms.push_back(child);
+    return keyfrms;
+}
+
 inline void landmark::compute_descriptor() {  // median-of-distances representative (data/landmark.cc:199-254)
     std::vector<const uint8_t*> descs;
     for (const auto& obs : observations_)
@@ -460,3 +511,17 @@ private:
 namespace YAML {
 using Node = stella_vslam::yaml_standin::Node;
 }
+
+// g2o::Sim3 as far as optimize::hip::graph_optimizer reads it (g2o/types/sim3/sim3.h): rotation as a quaternion x y z w, translation, scale
+namespace g2o {
+struct Sim3 {
+    double q[4] = {0, 0, 0, 1}, t[3] = {0, 0, 0}, s = 1.0;
+    Sim3() = default;
+    explicit Sim3(const double* p8) : q{p8[0], p8[1], p8[2], p8[3]}, t{p8[4], p8[5], p8[6]}, s(p8[7]) {}
+};
+}  // namespace g2o
+namespace stella_vslam {
+namespace module {
+using keyframe_Sim3_pairs_t = std::map<std::shared_ptr<data::keyframe>, g2o::Sim3>;  // module/type.h:17-21
+}
+}  // namespace stella_vslam

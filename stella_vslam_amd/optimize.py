@@ -186,3 +186,43 @@ class pose_optimizer:
                                                         int(self.reset_stop_flag_each_round_), p(out), p(outl), C.byref(nv), C.byref(it)),
                        "svgpu_pose_optimize_device")
         return nv.value, out, outl[:n].copy(), it.value
+
+
+# ------------------------------------------------------------------------------------------------ Sim3 pose graph (loop correction)
+class _PoseGraphStats(C.Structure):
+    _fields_ = [("lm_iterations", C.c_int32), ("lm_trials", C.c_int32), ("pcg_iterations", C.c_int32), ("pcg_capped", C.c_int32),
+                ("stopped_by_gain", C.c_int32), ("num_free", C.c_int32), ("initial_chi2", C.c_double), ("final_chi2", C.c_double),
+                ("lambda_final", C.c_double)]
+
+
+def _vp(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def pose_graph_optimize(ctx: Context, sim3, fixed, edge_v1, edge_v2, edge_sim3_21, fix_scale=False, max_iterations=50, gain_threshold=1e-3):
+    """optimize::graph_optimizer::optimize over flat arrays (svgpu_pose_graph_optimize): sim3 N x 8 (qx qy qz qw tx ty tz s), fixed N,
+    edges as two index arrays and E x 8 measurements Sim3_21.  Returns a dict: sim3 (N x 8), pose_cw (N x 3 x 4, [R | t / s]) and the
+    stats lm_iterations, lm_trials, pcg_iterations, pcg_capped, stopped_by_gain, num_free, initial_chi2, final_chi2, lambda_final."""
+    s = np.ascontiguousarray(sim3, np.float64).reshape(-1, 8)
+    f = np.ascontiguousarray(fixed, np.uint8).reshape(-1)
+    e1, e2 = np.ascontiguousarray(edge_v1, np.int32).reshape(-1), np.ascontiguousarray(edge_v2, np.int32).reshape(-1)
+    m = np.ascontiguousarray(edge_sim3_21, np.float64).reshape(-1, 8)
+    if len(f) != len(s) or len(e2) != len(e1) or len(m) != len(e1):
+        raise ValueError("pose_graph_optimize: array lengths disagree")
+    out, pose, st = np.zeros_like(s), np.zeros((len(s), 3, 4), np.float64), _PoseGraphStats()
+    ctx.check(lib().svgpu_pose_graph_optimize(ctx.handle, len(s), _vp(s), _vp(f), len(e1), _vp(e1), _vp(e2), _vp(m), int(bool(fix_scale)), int(max_iterations),
+                                              float(gain_threshold), _vp(out), _vp(pose), C.cast(C.pointer(st), C.c_void_p)), "svgpu_pose_graph_optimize")
+    res = {k: getattr(st, k) for k, _ in _PoseGraphStats._fields_}
+    res.update(sim3=out, pose_cw=pose)
+    return res
+
+
+def correct_landmarks(ctx: Context, sim3_before, sim3_after, ref_vertex, pos_w):
+    """Step 5 of graph_optimizer::optimize (svgpu_pose_graph_correct_landmarks): sim3_after[ref]^-1 .map(sim3_before[ref] .map(pos_w))."""
+    a, b = np.ascontiguousarray(sim3_before, np.float64).reshape(-1, 8), np.ascontiguousarray(sim3_after, np.float64).reshape(-1, 8)
+    r, p = np.ascontiguousarray(ref_vertex, np.int32).reshape(-1), np.ascontiguousarray(pos_w, np.float64).reshape(-1, 3)
+    if len(a) != len(b) or len(r) != len(p):
+        raise ValueError("correct_landmarks: array lengths disagree")
+    out = np.zeros_like(p)
+    ctx.check(lib().svgpu_pose_graph_correct_landmarks(ctx.handle, len(a), _vp(a), _vp(b), len(p), _vp(r), _vp(p), _vp(out)), "svgpu_pose_graph_correct_landmarks")
+    return out
