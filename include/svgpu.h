@@ -972,6 +972,13 @@ int svgpu_selftest_segmented_solve_rank(int nP, int NB, const int* blk_ab, const
  * permutation.  Either half is skipped when its output pointer is NULL.  Host in / out, synchronous. */
 int svgpu_selftest_scan_sort(svgpu_ctx* ctx, int n, const int32_t* values, int32_t* scan_out, const uint32_t* keys, int bits, int32_t* sorted_idx);
 
+/* Which form the replay of the candidate matcher takes for nq queries and nt targets (csrc/match_kernels.hip; NOT a product entry point:
+ * the launch code calls the same function, tests assert with it that a problem reaches the form it was built for).  Host only, needs
+ * no context and no device.  with_cnt != 0: the lists carry explicit counts (the tracked-frame chain).
+ *   modes BEST_ONLY .. TRIANGULATION: K >= 0 = tables in LDS with K staged entries per list, -1 = tables in global memory
+ *   mode AREA: 1 = state in LDS, 0 = state in global memory.                                  -2 = bad arguments */
+int svgpu_selftest_cand_replay_form(int nq, int nt, int with_cnt, int mode);
+
 /* Host in/out, synchronous.  The Levenberg-Marquardt loop (damping trials, rho test, terminate_action) runs on the device; the
  * host enqueues the trials of a stage and reads the control block back once per stage (plus once per rejected trial).
  *   stop        nullable; the caller's force_stop_flag (mapping_module.h:232).  Polled at every damping-trial boundary

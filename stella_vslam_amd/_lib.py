@@ -48,6 +48,8 @@ def lib() -> C.CDLL:
         _LIB.svgpu_pose_graph_optimize.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, i32, i32, C.c_double, vp, vp, vp]
         _LIB.svgpu_pose_graph_correct_landmarks.restype = C.c_int
         _LIB.svgpu_pose_graph_correct_landmarks.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp]
+        _LIB.svgpu_selftest_cand_replay_form.restype = C.c_int
+        _LIB.svgpu_selftest_cand_replay_form.argtypes = [i32, i32, i32, i32]
         if _LIB.svgpu_abi_version() != 1:
             raise ImportError("libsvgpu.so ABI version mismatch")
     return _LIB

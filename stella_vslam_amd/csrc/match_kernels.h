@@ -91,6 +91,7 @@ struct CandProblem {
     int dbg_phase;            // timing experiments only (SVGPU_REPLAY_DBG): 1 = return after the set-up, 2 = one evaluation per chunk, no sweeps
 };
 void sv_launch_cand_replay(svgpu_ctx* ctx, hipStream_t s, const CandProblem& P, int* owner, int* match);  // the replay alone (lists + distances in place)
+int sv_cand_replay_form(int nq, int nt, bool with_cnt, int mode);  // host only: the form the launch code picks (see its definition)
 
 // Device-side candidate lists: data::assign_keypoints_to_grid + data::get_keypoints_in_cell (data/common.cc:83-190)
 struct GridProblem {

@@ -1831,12 +1831,22 @@ void sv_launch_grid_build(hipStream_t s, const GridProblem& G) {
 void sv_launch_grid_fill(hipStream_t s, const GridProblem& G) {
     if (G.nq > 0) hipLaunchKernelGGL(k_grid_walk<true>, dim3((G.nq + 3) / 4), dim3(256), 0, s, G);
 }
+// Which form the replay of (nq queries, nt targets) takes -- the one place that decides it (svgpu_selftest_cand_replay_form reports it).
+//   mode AREA: 1 = k_area_replay keeps holder / distance / match tables in LDS (up to 60 KiB), 0 = in global memory
+//   the other modes: K >= 0 = k_cand_replay_lds with K staged entries per list (as many as fit, at most 64: longer lists are not sorted),
+//                    -1 = the tables alone exceed the budget: k_cand_replay on global memory
+int sv_cand_replay_form(int nq, int nt, bool with_cnt, int mode) {
+    if (mode == SVGPU_MATCH_AREA) return (size_t)(2 * (size_t)nt + (size_t)nq) * sizeof(int) <= 60 * 1024 ? 1 : 0;
+    const size_t tables = cand_lds_bytes(nq, nt, 0, with_cnt);
+    if (tables > CAND_LDS_BUDGET) return -1;
+    return nq > 0 ? (int)std::min<size_t>(64, (CAND_LDS_BUDGET - tables) / ((size_t)nq * 4)) : 0;
+}
 void sv_launch_cand(svgpu_ctx* ctx, hipStream_t s, const CandProblem& P, int* owner, int* match, unsigned* mdist) {
     SvProfScope ps(ctx, s, "k_cand");
     if (P.nq > 0) hipLaunchKernelGGL(k_cand_dist, dim3(P.nq), dim3(64), 0, s, P);
     if (P.mode == SVGPU_MATCH_AREA) {
         const size_t lds = (size_t)(2 * P.nt + P.nq) * sizeof(int);
-        const int use_lds = lds <= 60 * 1024;
+        const int use_lds = sv_cand_replay_form(P.nq, P.nt, false, P.mode);
         hipLaunchKernelGGL(k_area_replay, dim3(1), dim3(64), use_lds ? lds : 0, s, P, owner, match, mdist, use_lds);
         return;
     }
@@ -1848,8 +1858,8 @@ void sv_launch_cand_replay(svgpu_ctx* ctx, hipStream_t s, const CandProblem& P0,
     P.dbg_phase = dbg;
     // the LDS-resident form with as many staged entries per list as fit (at most 64: longer lists are not sorted)
     const bool wc = P.cand_cnt != nullptr;
-    if (cand_lds_bytes(P.nq, P.nt, 0, wc) <= CAND_LDS_BUDGET) {
-        const int K = P.nq > 0 ? (int)std::min<size_t>(64, (CAND_LDS_BUDGET - cand_lds_bytes(P.nq, P.nt, 0, wc)) / ((size_t)P.nq * 4)) : 0;
+    const int K = sv_cand_replay_form(P.nq, P.nt, wc, P.mode);
+    if (K >= 0) {
         (void)sv_allow_dynamic_lds((const void*)k_cand_replay_lds, CAND_LDS_BUDGET);
         hipLaunchKernelGGL(k_cand_replay_lds, dim3(1), dim3(1024), cand_lds_bytes(P.nq, P.nt, K, wc), s, P, K);
     }

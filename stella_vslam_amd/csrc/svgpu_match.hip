@@ -284,6 +284,11 @@ int svgpu_match_candidates(svgpu_ctx* ctx, const uint8_t* qdesc, int nq, const u
     return SVGPU_OK;
 }
 
+int svgpu_selftest_cand_replay_form(int nq, int nt, int with_cnt, int mode) {
+    if (nq < 0 || nt < 0 || mode < SVGPU_MATCH_BEST_ONLY || mode > SVGPU_MATCH_AREA) return -2;
+    return sv_cand_replay_form(nq, nt, with_cnt != 0, mode);
+}
+
 int svgpu_match_in_cells(svgpu_ctx* ctx, const uint8_t* qdesc, int nq, const float* q_xy, const float* q_margin,
                          const int32_t* q_min_level, const int32_t* q_max_level, const uint8_t* q_valid, const float* q_angle,
                          const float* q_xright, const float* q_xr_tol, const uint8_t* tdesc, const float* t_xy,
