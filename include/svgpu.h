@@ -753,6 +753,68 @@ int svgpu_pose_graph_optimize(svgpu_ctx* ctx, int num_vertices, const double* si
 int svgpu_pose_graph_correct_landmarks(svgpu_ctx* ctx, int num_vertices, const double* sim3_before, const double* sim3_after, int num_landmarks,
                                        const int32_t* ref_vertex, const double* pos_w, double* pos_w_out);
 
+/* ------------------------------------------------------------------------------ pairwise Sim3 optimisation (loop validation), batched
+ * optimize::transform_optimizer::optimize (optimize/transform_optimizer.cc:20-158), the step module::loop_detector runs between
+ * match_keyframes_mutually and its inlier threshold (module/loop_detector.cc:581), for every loop candidate of a keyframe in one call.
+ * Problem p is one 7-dof vertex Sim3_12 (8 doubles as in svgpu_pose_graph_optimize) and, per match, two unary reprojection edges:
+ *   forward    e12 = obs1 - project1(S12.map(R_2w pos_w_2 + t_2w))      (optimize/internal/sim3/forward_reproj_edge.h:61-76)
+ *   backward   e21 = obs2 - project2(S12^-1.map(R_1w pos_w_1 + t_1w))   (backward_reproj_edge.h:61-77)
+ * project is fx x / z + cx, fy y / z + cy for perspective, fisheye and radial-division keyframes (their keypoints are undistorted;
+ * mutual_reproj_edge_wrapper.h:64-158) and the atan2 / asin form of forward_reproj_edge.h:110-114 for equirectangular ones; the two views may
+ * differ in model.  Information = inv_sigma_sq (a float, widened) times identity, chi2 = info |e|^2, Huber of width (double)sqrtf(chi_sq) on
+ * every edge in both stages (first-order weighting), g2o's numeric Jacobian (central differences, delta 1e-9, through exp(update) *
+ * estimate; with fix_scale coordinate 6 of every update is zero, transform_vertex.h:61-70), Levenberg-Marquardt as
+ * svgpu_pose_graph_optimize states it but without terminate_action: lambda0 = 1e-5 max diag H at iteration 0 of each stage, at most 10
+ * damping trials per iteration; a stage ends at its iteration count, after 10 rejected trials, on rho == 0 or on a non-finite lambda.
+ *   stage 1     5 iterations over all edges (:98-99); a match survives if chi2_12 < chi_sq && chi2_21 < chi_sq, both strict (:109).  Fewer than
+ *               10 survivors (:121-123): num_inliers = 0, sim3_12_out = the input bit for bit, the rejected matches stay rejected
+ *   stage 2     num_iter iterations over the survivors' edges (:127-128); a survivor is rejected if chi_sq < chi2_12 || chi_sq < chi2_21 (:143)
+ *   The chi2 a gate reads is g2o's cached error of the edge: that of the stage's last evaluation, i.e. its last damping trial, accepted or
+ *   not; with num_iter == 0 the second gate reads stage 1's values.
+ * One persistent workgroup per problem, fp64, sums in a fixed order, no atomics: a problem's result does not depend on the rest of the
+ * batch or on its position in it, and two calls are bit-equal.  Host in/out, synchronous: one upload, one launch, one read-back.
+ *   view1 / view2     camera and pose of keyframe 1 (the current keyframe) and keyframe 2 (the candidate); view2 holds num_problems entries,
+ *                     view1 one entry shared by all problems when view1_shared != 0, else num_problems entries
+ *   match_off         num_problems + 1 offsets into the per-match arrays (match_off[0] = 0; a problem may be empty: 0 inliers, Sim3 unchanged)
+ *   obs1 / obs2       2 doubles per match: the undistorted keypoints; inv_sigma_sq1 / inv_sigma_sq2: inv_level_sigma_sq of their octaves
+ *   pos_w_1 / pos_w_2 3 doubles per match: the landmark of keyframe 1 / of keyframe 2, each in its keyframe's world.  Matches in
+ *                     ascending idx1 order, as the reference adds its edges (:64-94)
+ *   sim3_12 / sim3_12_out   num_problems x 8
+ *   chi_sq / fix_scale / num_iter   of the call (transform_optimizer.h:25,41-43)
+ *   num_inliers       per problem: what optimize returns
+ *   status            one byte per match: SVGPU_SIM3OPT_INLIER, _REJECTED_STAGE1, _REJECTED_STAGE2
+ *   stats             nullable, per problem
+ * SVGPU_ERR_INVALID before anything is launched: non-monotone offsets, a quaternion whose squared norm is further than 1e-9 from 1, a
+ * scale, an inv_sigma_sq or chi_sq that is not positive and finite, num_iter < 0, a camera model outside svgpu_camera_model, a null
+ * required pointer.  num_problems == 0 is a success whatever the other arguments hold. */
+#define SVGPU_SIM3OPT_INLIER 0
+#define SVGPU_SIM3OPT_REJECTED_STAGE1 1
+#define SVGPU_SIM3OPT_REJECTED_STAGE2 2
+typedef struct svgpu_sim3opt_view {
+    svgpu_camera cam;
+    double pose_cw[12]; /* rows 0..2 of [rot_cw | trans_cw], row-major */
+} svgpu_sim3opt_view;
+typedef struct svgpu_sim3opt_stats {
+    int32_t lm_iterations[2]; /* per stage */
+    int32_t lm_trials[2];     /* damping trials per stage */
+    int32_t early_return;     /* fewer than 10 matches survived stage 1 */
+    int32_t num_survivors;    /* matches that survived stage 1 */
+    double first_chi2[2];     /* robust chi2 at the first linearisation of the stage (0 if the stage did not run) */
+    double last_chi2[2];      /* robust chi2 of the estimate when the stage ended */
+    double lambda;            /* damping after the last trial */
+} svgpu_sim3opt_stats;
+int svgpu_sim3_transform_optimize_batch(svgpu_ctx* ctx, int num_problems, const svgpu_sim3opt_view* view1, int view1_shared,
+                                        const svgpu_sim3opt_view* view2, const int32_t* match_off, const double* obs1, const double* obs2,
+                                        const float* inv_sigma_sq1, const float* inv_sigma_sq2, const double* pos_w_1, const double* pos_w_2,
+                                        const double* sim3_12, float chi_sq, int fix_scale, int num_iter, double* sim3_12_out,
+                                        int32_t* num_inliers, uint8_t* status, svgpu_sim3opt_stats* stats);
+
+/* One problem: the batch of one, bit for bit. */
+int svgpu_sim3_transform_optimize(svgpu_ctx* ctx, const svgpu_sim3opt_view* view1, const svgpu_sim3opt_view* view2, int num_matches,
+                                  const double* obs1, const double* obs2, const float* inv_sigma_sq1, const float* inv_sigma_sq2,
+                                  const double* pos_w_1, const double* pos_w_2, const double* sim3_12, float chi_sq, int fix_scale, int num_iter,
+                                  double* sim3_12_out, int32_t* num_inliers, uint8_t* status, svgpu_sim3opt_stats* stats);
+
 /* bow_tree::match_frame_and_keyframe (match/bow_tree.cc:169-256) and bow_tree::match_keyframes (:258-366).
  * Side 1 = the keyframe whose landmarks are handed over (queries: valid1 = keypoint holds a live landmark), side 2 = the frame /
  * the other keyframe (valid2 nullable = every keypoint, or "holds a live landmark" for match_keyframes; occupied2 nullable = keypoints

@@ -48,6 +48,10 @@ def lib() -> C.CDLL:
         _LIB.svgpu_pose_graph_optimize.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, i32, i32, C.c_double, vp, vp, vp]
         _LIB.svgpu_pose_graph_correct_landmarks.restype = C.c_int
         _LIB.svgpu_pose_graph_correct_landmarks.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp]
+        _LIB.svgpu_sim3_transform_optimize_batch.restype = C.c_int
+        _LIB.svgpu_sim3_transform_optimize_batch.argtypes = [vp, i32, vp, i32] + [vp] * 9 + [C.c_float, i32, i32, vp, vp, vp, vp]
+        _LIB.svgpu_sim3_transform_optimize.restype = C.c_int
+        _LIB.svgpu_sim3_transform_optimize.argtypes = [vp, vp, vp, i32] + [vp] * 7 + [C.c_float, i32, i32, vp, vp, vp, vp]
         _LIB.svgpu_selftest_cand_replay_form.restype = C.c_int
         _LIB.svgpu_selftest_cand_replay_form.argtypes = [i32, i32, i32, i32]
         if _LIB.svgpu_abi_version() != 1:

@@ -21,14 +21,6 @@ namespace {
 
 constexpr double PG_DELTA = 1e-9;
 
-__device__ SvVec7 pg_unit_update(int coord, double v) {
-    SvVec7 u;
-    u.w0 = coord == 0 ? v : 0.0, u.w1 = coord == 1 ? v : 0.0, u.w2 = coord == 2 ? v : 0.0;
-    u.u0 = coord == 3 ? v : 0.0, u.u1 = coord == 4 ? v : 0.0, u.u2 = coord == 5 ? v : 0.0;
-    u.sg = coord == 6 ? v : 0.0;
-    return u;
-}
-
 // graph_opt_edge::computeError
 __device__ SvVec7 pg_error(const SvSim3& C, const SvSim3& v1, const SvSim3& v2) { return sv_sim3_log(sv_sim3_mul(sv_sim3_mul(C, v1), sv_sim3_inv(v2))); }
 
@@ -70,7 +62,7 @@ __global__ __launch_bounds__(64) void k_pg_linearize(PgDev D) {
             double d = ((q - 1) & 1) ? -PG_DELTA : PG_DELTA;
             if (D.fix_scale && coord == 6) d = 0.0;  // shot_vertex::oplusImpl
             if (run) {
-                const SvSim3 X = sv_sim3_exp(pg_unit_update(coord, d));
+                const SvSim3 X = sv_sim3_exp(sv_sim3_unit_update(coord, d));
                 if (side) Sj = sv_sim3_mul(X, Sj);
                 else Si = sv_sim3_mul(X, Si);
             }

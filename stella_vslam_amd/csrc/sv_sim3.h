@@ -222,6 +222,15 @@ SV_HD void sv_sim3_to_pose(const SvSim3& a, double* pose12) {
     pose12[8] = R.a20, pose12[9] = R.a21, pose12[10] = R.a22, pose12[11] = a.t.z / s;
 }
 
+// the update that moves one coordinate by v (g2o's numeric Jacobian perturbs one coordinate at a time)
+SV_HD SvVec7 sv_sim3_unit_update(int coord, double v) {
+    SvVec7 u;
+    u.w0 = coord == 0 ? v : 0.0, u.w1 = coord == 1 ? v : 0.0, u.w2 = coord == 2 ? v : 0.0;
+    u.u0 = coord == 3 ? v : 0.0, u.u1 = coord == 4 ? v : 0.0, u.u2 = coord == 5 ? v : 0.0;
+    u.sg = coord == 6 ? v : 0.0;
+    return u;
+}
+
 SV_HD SvSim3 sv_sim3_load(const double* p) { return SvSim3{p[0], p[1], p[2], p[3], SvVec3{p[4], p[5], p[6]}, p[7]}; }
 SV_HD void sv_sim3_store(double* p, const SvSim3& a) {
     p[0] = a.qx, p[1] = a.qy, p[2] = a.qz, p[3] = a.qw, p[4] = a.t.x, p[5] = a.t.y, p[6] = a.t.z, p[7] = a.s;

@@ -226,3 +226,83 @@ def correct_landmarks(ctx: Context, sim3_before, sim3_after, ref_vertex, pos_w):
     out = np.zeros_like(p)
     ctx.check(lib().svgpu_pose_graph_correct_landmarks(ctx.handle, len(a), _vp(a), _vp(b), len(p), _vp(r), _vp(p), _vp(out)), "svgpu_pose_graph_correct_landmarks")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ pairwise Sim3 (loop validation)
+class _Camera(C.Structure):
+    _fields_ = [("model", C.c_int32), ("pad_", C.c_int32), ("cols", C.c_double), ("rows", C.c_double), ("fx", C.c_double), ("fy", C.c_double),
+                ("cx", C.c_double), ("cy", C.c_double), ("dist", C.c_double * 5), ("focal_x_baseline", C.c_double), ("min_x", C.c_float),
+                ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float)]
+
+
+class _Sim3OptView(C.Structure):
+    _fields_ = [("cam", _Camera), ("pose_cw", C.c_double * 12)]
+
+
+class _Sim3OptStats(C.Structure):
+    _fields_ = [("lm_iterations", C.c_int32 * 2), ("lm_trials", C.c_int32 * 2), ("early_return", C.c_int32), ("num_survivors", C.c_int32),
+                ("first_chi2", C.c_double * 2), ("last_chi2", C.c_double * 2), ("lambda_final", C.c_double)]
+
+
+def _sim3opt_view(cam: dict, pose_cw):
+    v = _Sim3OptView()
+    for k in ("model", "cols", "rows", "fx", "fy", "cx", "cy"):
+        setattr(v.cam, k, cam.get(k, 0))
+    v.pose_cw[:] = [float(x) for x in np.asarray(pose_cw, np.float64).reshape(12)]
+    return v
+
+
+def sim3_transform_optimize_batch(ctx: Context, view1, views2, match_off, obs1, obs2, inv_sigma_sq1, inv_sigma_sq2, pos_w_1, pos_w_2, sim3_12,
+                                  chi_sq=10.0, fix_scale=False, num_iter=10):
+    """optimize::transform_optimizer::optimize for several candidates at once (svgpu_sim3_transform_optimize_batch).  view1: one
+    (camera dict, pose_cw) shared by all problems, or a list of them, one per problem; views2: a list of (camera dict, pose_cw); camera
+    dict: model (svgpu_camera_model), fx fy cx cy, cols rows.  match_off: P + 1 offsets into the per-match arrays obs1 / obs2 (n x 2),
+    inv_sigma_sq1 / 2 (n), pos_w_1 / 2 (n x 3).  sim3_12: P x 8.  Returns a dict: sim3 (P x 8), num_inliers (P), status (n) and the
+    per-problem stats lm_iterations, lm_trials, first_chi2, last_chi2 (P x 2 each), early_return, num_survivors, lambda_final (P)."""
+    off = np.ascontiguousarray(match_off, np.int32).reshape(-1)
+    P = len(off) - 1
+    shared = isinstance(view1, tuple)
+    v1 = [view1] if shared else list(view1)
+    if P < 0 or len(views2) != P or (not shared and len(v1) != P):
+        raise ValueError("sim3_transform_optimize_batch: array lengths disagree")
+    V1 = (_Sim3OptView * max(len(v1), 1))(*[_sim3opt_view(c, p) for c, p in v1])
+    V2 = (_Sim3OptView * max(P, 1))(*[_sim3opt_view(c, p) for c, p in views2])
+    o1, o2 = np.ascontiguousarray(obs1, np.float64).reshape(-1, 2), np.ascontiguousarray(obs2, np.float64).reshape(-1, 2)
+    w1, w2 = np.ascontiguousarray(inv_sigma_sq1, np.float32).reshape(-1), np.ascontiguousarray(inv_sigma_sq2, np.float32).reshape(-1)
+    p1, p2 = np.ascontiguousarray(pos_w_1, np.float64).reshape(-1, 3), np.ascontiguousarray(pos_w_2, np.float64).reshape(-1, 3)
+    s = np.ascontiguousarray(sim3_12, np.float64).reshape(-1, 8)
+    n = len(o1)
+    if len(s) != P or any(len(a) != n for a in (o2, w1, w2, p1, p2)) or (P > 0 and off[-1] != n):
+        raise ValueError("sim3_transform_optimize_batch: array lengths disagree")
+    out, inl, status = np.zeros_like(s), np.zeros(max(P, 1), np.int32), np.zeros(max(n, 1), np.uint8)
+    st = (_Sim3OptStats * max(P, 1))()
+    ctx.check(lib().svgpu_sim3_transform_optimize_batch(ctx.handle, P, C.cast(V1, C.c_void_p), int(shared), C.cast(V2, C.c_void_p), _vp(off), _vp(o1), _vp(o2),
+                                                        _vp(w1), _vp(w2), _vp(p1), _vp(p2), _vp(s), C.c_float(chi_sq), int(bool(fix_scale)), int(num_iter),
+                                                        _vp(out), _vp(inl), _vp(status), C.cast(st, C.c_void_p)), "svgpu_sim3_transform_optimize_batch")
+    res = dict(sim3=out, num_inliers=inl[:P].copy(), status=status[:n].copy())
+    for k, _ in _Sim3OptStats._fields_:
+        res[k] = np.array([np.array(getattr(st[p], k)) for p in range(P)])
+    return res
+
+
+def sim3_transform_optimize(ctx: Context, view1, view2, obs1, obs2, inv_sigma_sq1, inv_sigma_sq2, pos_w_1, pos_w_2, sim3_12, chi_sq=10.0,
+                            fix_scale=False, num_iter=10):
+    """One candidate (svgpu_sim3_transform_optimize): view1 / view2 are (camera dict, pose_cw).  Returns the dict of the batch call with
+    the problem axis dropped."""
+    o1, o2 = np.ascontiguousarray(obs1, np.float64).reshape(-1, 2), np.ascontiguousarray(obs2, np.float64).reshape(-1, 2)
+    w1, w2 = np.ascontiguousarray(inv_sigma_sq1, np.float32).reshape(-1), np.ascontiguousarray(inv_sigma_sq2, np.float32).reshape(-1)
+    p1, p2 = np.ascontiguousarray(pos_w_1, np.float64).reshape(-1, 3), np.ascontiguousarray(pos_w_2, np.float64).reshape(-1, 3)
+    s = np.ascontiguousarray(sim3_12, np.float64).reshape(8)
+    n = len(o1)
+    if any(len(a) != n for a in (o2, w1, w2, p1, p2)):
+        raise ValueError("sim3_transform_optimize: array lengths disagree")
+    V1, V2 = _sim3opt_view(*view1), _sim3opt_view(*view2)
+    out, inl, status, st = np.zeros(8), C.c_int32(0), np.zeros(max(n, 1), np.uint8), _Sim3OptStats()
+    ctx.check(lib().svgpu_sim3_transform_optimize(ctx.handle, C.byref(V1), C.byref(V2), n, _vp(o1), _vp(o2), _vp(w1), _vp(w2), _vp(p1), _vp(p2), _vp(s),
+                                                  C.c_float(chi_sq), int(bool(fix_scale)), int(num_iter), _vp(out), C.byref(inl), _vp(status), C.byref(st)),
+              "svgpu_sim3_transform_optimize")
+    res = dict(sim3=out, num_inliers=int(inl.value), status=status[:n].copy())
+    for k, _ in _Sim3OptStats._fields_:
+        v = getattr(st, k)
+        res[k] = np.array(v) if hasattr(v, "__len__") else v
+    return res
