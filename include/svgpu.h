@@ -747,6 +747,39 @@ int svgpu_pose_graph_optimize(svgpu_ctx* ctx, int num_vertices, const double* si
                               const int32_t* edge_v2, const double* edge_sim3_21, int fix_scale, int max_iterations, double gain_threshold,
                               double* sim3_out, double* pose_cw_out, svgpu_pose_graph_stats* stats);
 
+/* The same call with a choice of the linear solver of the damped system (options == NULL: PCG; svgpu_pose_graph_optimize IS this call
+ * with PCG, bit for bit).  SVGPU_PG_SOLVER_ENVELOPE factors the system directly: a block envelope (skyline) LL^T with 7x7 blocks in one
+ * workgroup, in the elimination order -- natural, interleaved from both ends, or reverse Cuthill-McKee -- whose lower envelope is the
+ * smallest (planned on the host).  fp64, fixed summation order, bit-reproducible.  A pivot that is not positive and finite fails the
+ * damping trial, which is then rejected as if chi2 had risen; when all 10 trials of an iteration fail the run ends and the call returns
+ * SVGPU_ERR_NUMERIC (the outputs hold the last estimate).  With the envelope solver pcg_iterations and pcg_capped are 0.
+ * SVGPU_ERR_INVALID before anything is launched, beyond the cases above: an unknown solver, a reserved field that is not 0, an envelope
+ * whose value count (49 per block) does not fit 32-bit indexing.  solver_stats may be NULL. */
+typedef enum svgpu_pose_graph_solver { SVGPU_PG_SOLVER_PCG = 0, SVGPU_PG_SOLVER_ENVELOPE = 1 } svgpu_pose_graph_solver;
+typedef struct svgpu_pose_graph_options {
+    int32_t solver;       /* svgpu_pose_graph_solver */
+    int32_t reserved[3];  /* must be 0 */
+} svgpu_pose_graph_options;
+typedef struct svgpu_pose_graph_solver_stats {
+    int32_t solver;           /* the solver that ran */
+    int32_t ordering;         /* envelope: 0 natural, 1 interleaved, 2 reverse Cuthill-McKee */
+    int32_t envelope_blocks;  /* envelope: 7x7 blocks of the lower envelope, diagonal included */
+    int32_t max_column_rows;  /* envelope: most rows below the diagonal in one block column */
+    int32_t failed_solves;    /* envelope: damping trials whose factorisation met a bad pivot */
+} svgpu_pose_graph_solver_stats;
+int svgpu_pose_graph_optimize_ex(svgpu_ctx* ctx, int num_vertices, const double* sim3, const uint8_t* fixed, int num_edges, const int32_t* edge_v1,
+                                 const int32_t* edge_v2, const double* edge_sim3_21, int fix_scale, int max_iterations, double gain_threshold,
+                                 double* sim3_out, double* pose_cw_out, svgpu_pose_graph_stats* stats, const svgpu_pose_graph_options* options,
+                                 svgpu_pose_graph_solver_stats* solver_stats);
+
+/* Device self-test of the envelope solver (NOT a product entry point; the LM loop is not run): plans, assembles, factors and solves the
+ * block-sparse symmetric system with 7x7 blocks {diag_blocks nfree x 49 row-major, block (pair_a[k], pair_b[k]) = pair_blocks k x 49
+ * row-major and its transpose at (pair_b[k], pair_a[k]); a pair given more than once is summed} x = rhs (7 nfree).  x_out 7 nfree.
+ * SVGPU_ERR_NUMERIC with failed_solves = 1 and x_out untouched when the system is not positive definite. */
+int svgpu_selftest_pose_graph_envelope_solve(svgpu_ctx* ctx, int nfree, int num_pairs, const int32_t* pair_a, const int32_t* pair_b,
+                                             const double* diag_blocks, const double* pair_blocks, const double* rhs, double* x_out,
+                                             svgpu_pose_graph_solver_stats* solver_stats);
+
 /* Step 5 of the same function (:284-301): pos_out = sim3_after[ref]^-1 .map( sim3_before[ref] .map(pos_w) ) for num_landmarks landmarks,
  * ref_vertex being the landmark's reference vertex.  The output feeds svgpu_landmarks_update_geometry.  SVGPU_ERR_INVALID for a
  * reference out of range; num_landmarks == 0 is a success. */

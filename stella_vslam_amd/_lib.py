@@ -46,6 +46,10 @@ def lib() -> C.CDLL:
         vp, i32 = C.c_void_p, C.c_int
         _LIB.svgpu_pose_graph_optimize.restype = C.c_int
         _LIB.svgpu_pose_graph_optimize.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, i32, i32, C.c_double, vp, vp, vp]
+        _LIB.svgpu_pose_graph_optimize_ex.restype = C.c_int
+        _LIB.svgpu_pose_graph_optimize_ex.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, i32, i32, C.c_double, vp, vp, vp, vp, vp]
+        _LIB.svgpu_selftest_pose_graph_envelope_solve.restype = C.c_int
+        _LIB.svgpu_selftest_pose_graph_envelope_solve.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
         _LIB.svgpu_pose_graph_correct_landmarks.restype = C.c_int
         _LIB.svgpu_pose_graph_correct_landmarks.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp]
         _LIB.svgpu_sim3_transform_optimize_batch.restype = C.c_int

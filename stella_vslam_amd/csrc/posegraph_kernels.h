@@ -51,7 +51,32 @@ struct PgDev {
     double* scale_part;     // nfree: the vertex's share of dx^T (lambda dx + b)
     double* out_sim3;       // N x 8
     double* out_pose;       // N x 12: [R | t / s]
+    struct PgEnvCtl* env;   // the envelope solver's control block; null when the PCG solves
 };
+
+// The direct solver (posegraph_envelope.hip): block envelope LL^T of the damped system in the order posegraph_envelope_plan.h chose.
+// Its control block: k_pg_env_factor_solve reports a pivot that is not positive and finite, k_pg_decide counts it as a failed trial.
+struct PgEnvCtl {
+    int solve_failed;         // the trial in flight
+    int failed_solves;        // over the run
+    int failed_in_iteration;  // since the last linearisation
+    int numeric;              // all 10 trials of an iteration failed: the run ended on it
+};
+struct PgEnvDev {
+    const PgCtl* ctl;          // phase and lambda
+    PgEnvCtl* env;
+    int nP, nblocks, max_m;    // block rows, envelope blocks, tallest column (rows below the diagonal)
+    int damped;                // 1: lambda of the control block goes on the diagonal (0: the self-test's system as it is)
+    const double* Hd;          // nP x 49 diagonal blocks, slot order
+    const double* b;           // 7 nP right-hand side, slot order
+    double* x;                 // 7 nP solution, slot order
+    const double* blk;         // per edge: the 7x7 block Ji^T Jj at blk + edge * blk_stride
+    int blk_stride;
+    const int32_t *order, *rowoff, *coloff, *colrows, *colbase, *blk_src, *pair_off, *pair_ent, *pair_flag;
+    double *val, *dinv, *y;    // envelope blocks, inverse diagonal factors, right-hand side in plan order
+};
+void sv_pg_env_assemble(hipStream_t s, const PgEnvDev& K);
+void sv_pg_env_factor_solve(hipStream_t s, const PgEnvDev& K);
 
 void sv_pg_linearize(hipStream_t s, const PgDev& D);
 void sv_pg_assemble(hipStream_t s, const PgDev& D);

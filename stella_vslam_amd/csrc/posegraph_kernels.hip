@@ -9,6 +9,7 @@
 //   k_pg_prepare     chi2 of the estimate, lambda0 = 1e-5 max diag H on the first iteration
 //   k_pg_precond     inverse of every damped diagonal block (block-Jacobi preconditioner)
 //   k_pg_solve       PCG of (H + lambda I) dx = b in ONE workgroup: off-diagonal blocks stay per edge
+//                    (or, per call, the direct solver of posegraph_envelope.hip in place of k_pg_precond and k_pg_solve)
 //   k_pg_update      trial estimate exp(dx) * estimate, the vertex's share of dx^T (lambda dx + b)
 //   k_pg_chi2        error of every edge at the trial estimate
 //   k_pg_decide      rho test, damping update, terminate_action: the rules of k_ba_decide (ba_kernels.hip)
@@ -164,6 +165,7 @@ __global__ __launch_bounds__(256) void k_pg_prepare(PgDev D) {
     }
     k.qmax = 0;
     k.rho = 0.0;
+    if (D.env) D.env->failed_in_iteration = 0;
     k.phase = (it < k.it_max && D.nfree > 0) ? 1 : 2;
 }
 
@@ -343,19 +345,25 @@ __global__ __launch_bounds__(64) void k_pg_chi2(PgDev D) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------- decision
-// OptimizationAlgorithmLevenberg::solve's acceptance test and terminate_action, as lm_decide of ba_kernels.hip states them (no solver
-// failure and no caller's stop flag here)
+// OptimizationAlgorithmLevenberg::solve's acceptance test and terminate_action, as lm_decide of ba_kernels.hip states them (no caller's
+// stop flag here).  A failed solve -- only the envelope solver reports one (PgEnvCtl) -- rejects the trial whatever its chi2, as there.
 __global__ __launch_bounds__(256) void k_pg_decide(PgDev D) {
     __shared__ double sw[4];
     if (D.ctl->phase != 1) return;
     double t_chi = 0.0, t_sc = 0.0;
     for (int e = threadIdx.x; e < D.E; e += 256) t_chi += D.chi_trial[e];
     for (int v = threadIdx.x; v < D.nfree; v += 256) t_sc += D.scale_part[v];
-    const double temp_chi = pg_block_sum<4>(t_chi, sw);
+    const double temp_chi_sum = pg_block_sum<4>(t_chi, sw);
     double scale = pg_block_sum<4>(t_sc, sw);
     if (threadIdx.x != 0) return;
     PgCtl& c = *D.ctl;
     ++c.lm_trials;
+    double temp_chi = temp_chi_sum;
+    if (D.env && D.env->solve_failed) {
+        temp_chi = 1.7976931348623157e308;
+        ++D.env->failed_solves;
+        ++D.env->failed_in_iteration;
+    }
     double rho = c.current_chi - temp_chi;
     scale += 1e-3;
     rho /= scale;
@@ -379,6 +387,7 @@ __global__ __launch_bounds__(256) void k_pg_decide(PgDev D) {
     c.rho = rho;
     if (!lambda_bad && rho < 0 && c.qmax < 10) return;  // another trial on the same linearisation (phase stays 1)
     if (c.qmax == 10 || rho == 0 || !isfinite(c.lambda)) c.ok = 0;
+    if (D.env && c.qmax == 10 && D.env->failed_in_iteration == 10) D.env->numeric = 1;
     // postIteration: terminate_action on the chi2 of the estimate
     if (c.it == 0) c.last_chi = c.current_chi;
     else {

@@ -7,11 +7,14 @@
 #include "svgpu_match_common.h"
 #include "posegraph_kernels.h"
 #include "posegraph_layout.h"
+#include "posegraph_envelope_layout.h"
+#include "posegraph_envelope_plan.h"
 
 using namespace svm;
 
 static_assert(PG_LAYOUT_REC == PG_REC, "posegraph_layout.h and posegraph_kernels.h disagree on the edge record");
 static_assert(sizeof(PgCtl) <= PG_LAYOUT_CTL, "posegraph_layout.h reserves too little for PgCtl");
+static_assert(sizeof(PgEnvCtl) <= PG_ENV_LAYOUT_CTL, "posegraph_envelope_layout.h reserves too little for PgEnvCtl");
 
 namespace {
 
@@ -23,8 +26,9 @@ bool sim3_ok(const double* p) {
     return std::fabs(n2 - 1.0) <= 1e-9 && p[7] > 0.0;
 }
 
-// one damping trial; the kernels of a step that has nothing to do (PgCtl::phase) return at once
-void enqueue_step(svgpu_ctx* ctx, hipStream_t s, const PgDev& D) {
+// one damping trial; the kernels of a step that has nothing to do (PgCtl::phase) return at once.  K: the envelope solver's descriptor
+// when it solves (its two kernels then stand where the preconditioner and the PCG stand), else null
+void enqueue_step(svgpu_ctx* ctx, hipStream_t s, const PgDev& D, const PgEnvDev* K) {
     {
         SvProfScope prof(ctx, s, "k_pg_linearize");
         sv_pg_linearize(s, D);
@@ -34,7 +38,15 @@ void enqueue_step(svgpu_ctx* ctx, hipStream_t s, const PgDev& D) {
         sv_pg_assemble(s, D);
     }
     sv_pg_prepare(s, D);
-    {
+    if (K) {
+        {
+            SvProfScope prof(ctx, s, "k_pg_env_assemble");
+            sv_pg_env_assemble(s, *K);
+        }
+        SvProfScope prof(ctx, s, "k_pg_env_factor_solve");
+        sv_pg_env_factor_solve(s, *K);
+    }
+    else {
         SvProfScope prof(ctx, s, "k_pg_solve");
         sv_pg_precond(s, D);
         sv_pg_solve(s, D);
@@ -47,6 +59,37 @@ void enqueue_step(svgpu_ctx* ctx, hipStream_t s, const PgDev& D) {
     }
 }
 
+int upload_plan(svgpu_ctx* ctx, hipStream_t s, UploadArena& A, const PgEnvPieces& Y, const PgEnvPlan& P) {
+    const PgEnvCtl e0{};
+    const auto up = [&](int32_t* dst, const std::vector<int32_t>& v) { return A.upload(ctx, s, dst, v.data(), v.size() * 4); };
+    int rc;
+    if ((rc = A.upload(ctx, s, Y.ctl, &e0, sizeof e0))) return rc;
+    if ((rc = up(Y.order, P.order)) || (rc = up(Y.rowoff, P.rowoff)) || (rc = up(Y.coloff, P.coloff)) || (rc = up(Y.colrows, P.colrows)) ||
+        (rc = up(Y.colbase, P.colbase)) || (rc = up(Y.blk_src, P.blk_src)) || (rc = up(Y.pair_off, P.pair_off)) || (rc = up(Y.pair_ent, P.pair_ent)) ||
+        (rc = up(Y.pair_flag, P.pair_flag)))
+        return rc;
+    return SVGPU_OK;
+}
+
+PgEnvDev plan_descriptor(const PgEnvPieces& Y, const PgEnvPlan& P) {
+    PgEnvDev K{};
+    K.env = (PgEnvCtl*)Y.ctl;
+    K.nP = P.nfree, K.nblocks = (int)P.nblocks, K.max_m = P.max_column_rows;
+    K.order = Y.order, K.rowoff = Y.rowoff, K.coloff = Y.coloff, K.colrows = Y.colrows, K.colbase = Y.colbase, K.blk_src = Y.blk_src;
+    K.pair_off = Y.pair_off, K.pair_ent = Y.pair_ent, K.pair_flag = Y.pair_flag;
+    K.val = Y.val, K.dinv = Y.dinv, K.y = Y.y;
+    return K;
+}
+
+void fill_solver_stats(svgpu_pose_graph_solver_stats* st, int solver, const PgEnvPlan* P, int failed) {
+    if (!st) return;
+    st->solver = solver;
+    st->ordering = P ? P->ordering : 0;
+    st->envelope_blocks = P ? (int32_t)P->nblocks : 0;
+    st->max_column_rows = P ? P->max_column_rows : 0;
+    st->failed_solves = failed;
+}
+
 }  // namespace
 
 extern "C" {
@@ -54,7 +97,19 @@ extern "C" {
 int svgpu_pose_graph_optimize(svgpu_ctx* ctx, int num_vertices, const double* sim3, const uint8_t* fixed, int num_edges, const int32_t* edge_v1,
                               const int32_t* edge_v2, const double* edge_sim3_21, int fix_scale, int max_iterations, double gain_threshold,
                               double* sim3_out, double* pose_cw_out, svgpu_pose_graph_stats* stats) {
+    return svgpu_pose_graph_optimize_ex(ctx, num_vertices, sim3, fixed, num_edges, edge_v1, edge_v2, edge_sim3_21, fix_scale, max_iterations, gain_threshold,
+                                        sim3_out, pose_cw_out, stats, nullptr, nullptr);
+}
+
+int svgpu_pose_graph_optimize_ex(svgpu_ctx* ctx, int num_vertices, const double* sim3, const uint8_t* fixed, int num_edges, const int32_t* edge_v1,
+                              const int32_t* edge_v2, const double* edge_sim3_21, int fix_scale, int max_iterations, double gain_threshold,
+                                 double* sim3_out, double* pose_cw_out, svgpu_pose_graph_stats* stats, const svgpu_pose_graph_options* options,
+                                 svgpu_pose_graph_solver_stats* solver_stats) {
     const char* who = "svgpu_pose_graph_optimize: bad arguments";
+    const int solver = options ? options->solver : SVGPU_PG_SOLVER_PCG;
+    if (options && (options->reserved[0] || options->reserved[1] || options->reserved[2] || (solver != SVGPU_PG_SOLVER_PCG && solver != SVGPU_PG_SOLVER_ENVELOPE)))
+        return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_pose_graph_optimize_ex: unknown solver or a reserved option that is not zero");
+    const bool direct = solver == SVGPU_PG_SOLVER_ENVELOPE;
     if (!ctx || num_vertices < 1 || num_edges < 1 || max_iterations < 0 || !sim3 || !fixed || !edge_v1 || !edge_v2 || !edge_sim3_21 || !sim3_out)
         return sv_set_error(ctx, SVGPU_ERR_INVALID, who);
     const int N = num_vertices, E = num_edges;
@@ -87,11 +142,23 @@ int svgpu_pose_graph_optimize(svgpu_ctx* ctx, int num_vertices, const double* si
         if (sa >= 0) v_ent[fill[sa]++] = e << 1;
         if (sb >= 0) v_ent[fill[sb]++] = e << 1 | 1;
     }
+    // the envelope solver's plan: elimination order, envelope and pair lists (host only)
+    PgEnvPlan plan;
+    if (direct) {
+        std::vector<int32_t> sa(E), sb(E);
+        for (int e = 0; e < E; ++e) sa[e] = slot[edge_v1[e]], sb[e] = slot[edge_v2[e]];
+        pg_env_plan(nfree, E, sa.data(), sb.data(), plan);
+        if (!plan.fits) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_pose_graph_optimize_ex: the envelope's value count is beyond 32-bit indexing");
+    }
 
     SV_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     PgPieces Y{};
-    const auto layout = [&](UploadArena& A) { pg_optimize_layout(A, (size_t)N, (size_t)E, (size_t)nfree, incident, Y); };
+    PgEnvPieces Ye{};
+    const auto layout = [&](UploadArena& A) {
+        pg_optimize_layout(A, (size_t)N, (size_t)E, (size_t)nfree, incident, Y);
+        if (direct) pg_envelope_layout(A, (size_t)nfree, (size_t)plan.nblocks, (size_t)plan.num_pairs, plan.pair_ent.size(), Ye);
+    };
     const size_t need = arena_measure<UploadArena>(layout);
     int rc;
     if ((rc = sv_ensure_scratch(ctx, need))) return rc;
@@ -113,6 +180,7 @@ int svgpu_pose_graph_optimize(svgpu_ctx* ctx, int num_vertices, const double* si
     if ((rc = A.upload(ctx, s, Y.meas, edge_sim3_21, (size_t)E * 64))) return rc;
     if ((rc = A.upload(ctx, s, Y.v_off, v_off.data(), ((size_t)nfree + 1) * 4))) return rc;
     if ((rc = A.upload(ctx, s, Y.v_ent, v_ent.data(), incident * 4))) return rc;
+    if (direct && (rc = upload_plan(ctx, s, A, Ye, plan))) return rc;
     if ((rc = A.flush(ctx, s))) return rc;
 
     PgDev D{};
@@ -123,6 +191,13 @@ int svgpu_pose_graph_optimize(svgpu_ctx* ctx, int num_vertices, const double* si
     D.rec = Y.rec, D.chi_trial = Y.chi_trial, D.Hd = Y.Hd, D.b = Y.b, D.maxd = Y.maxd, D.Minv = Y.Minv;
     D.x = Y.x, D.r = Y.r, D.z = Y.z, D.p = Y.p, D.Ap = Y.Ap, D.scale_part = Y.scale_part;
     D.out_sim3 = Y.out_sim3, D.out_pose = Y.out_pose;
+    PgEnvDev K{};
+    if (direct) {
+        K = plan_descriptor(Ye, plan);
+        K.ctl = D.ctl, K.damped = 1;
+        K.Hd = Y.Hd, K.b = Y.b, K.x = Y.x, K.blk = Y.rec + PG_REC_HIJ, K.blk_stride = PG_REC;
+        D.env = K.env;
+    }
 
     // at most 10 trials per iteration; the first step also serves max_iterations == 0 (chi2 of the input, then phase 2)
     const long max_steps = std::max(1L, 10L * max_iterations);
@@ -131,7 +206,7 @@ int svgpu_pose_graph_optimize(svgpu_ctx* ctx, int num_vertices, const double* si
     int batch = 8;
     for (;;) {
         const long count = std::min<long>(batch, max_steps - done);
-        for (long k = 0; k < count; ++k) enqueue_step(ctx, s, D);
+        for (long k = 0; k < count; ++k) enqueue_step(ctx, s, D, direct ? &K : nullptr);
         done += count;
         SV_HIP(ctx, hipGetLastError());
         SV_HIP(ctx, hipMemcpyAsync(c_host, Y.ctl, sizeof(PgCtl), hipMemcpyDeviceToHost, s));
@@ -143,6 +218,8 @@ int svgpu_pose_graph_optimize(svgpu_ctx* ctx, int num_vertices, const double* si
     sv_pg_output(s, D);
     SV_HIP(ctx, hipGetLastError());
     Downloads Dl;
+    PgEnvCtl ec{};
+    if (direct) Dl.add(A, &ec, Ye.ctl, sizeof ec);
     Dl.add(A, sim3_out, Y.out_sim3, (size_t)N * 64);
     Dl.add(A, pose_cw_out, Y.out_pose, (size_t)N * 96);
     if ((rc = Dl.fetch(ctx, s, A))) return rc;
@@ -159,6 +236,65 @@ int svgpu_pose_graph_optimize(svgpu_ctx* ctx, int num_vertices, const double* si
         stats->final_chi2 = c.current_chi;
         stats->lambda = c.lambda;
     }
+    fill_solver_stats(solver_stats, solver, direct ? &plan : nullptr, ec.failed_solves);
+    if (ec.numeric) return sv_set_error(ctx, SVGPU_ERR_NUMERIC, "svgpu_pose_graph_optimize_ex: the damped system was not positive definite at any of the 10 dampings of an iteration");
+    return SVGPU_OK;
+}
+
+int svgpu_selftest_pose_graph_envelope_solve(svgpu_ctx* ctx, int nfree, int num_pairs, const int32_t* pair_a, const int32_t* pair_b, const double* diag_blocks,
+                                             const double* pair_blocks, const double* rhs, double* x_out, svgpu_pose_graph_solver_stats* solver_stats) {
+    const char* who = "svgpu_selftest_pose_graph_envelope_solve: bad arguments";
+    if (!ctx || nfree < 1 || num_pairs < 0 || !diag_blocks || !rhs || !x_out || (num_pairs > 0 && (!pair_a || !pair_b || !pair_blocks)))
+        return sv_set_error(ctx, SVGPU_ERR_INVALID, who);
+    for (int k = 0; k < num_pairs; ++k)
+        if (pair_a[k] < 0 || pair_a[k] >= nfree || pair_b[k] < 0 || pair_b[k] >= nfree || pair_a[k] == pair_b[k]) return sv_set_error(ctx, SVGPU_ERR_INVALID, who);
+    PgEnvPlan plan;
+    pg_env_plan(nfree, num_pairs, pair_a, pair_b, plan);
+    if (!plan.fits) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_selftest_pose_graph_envelope_solve: the envelope's value count is beyond 32-bit indexing");
+    SV_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    PgEnvSelftestPieces Y{};
+    const auto layout = [&](UploadArena& A) {
+        pg_envelope_selftest_layout(A, (size_t)nfree, (size_t)plan.nblocks, (size_t)plan.num_pairs, plan.pair_ent.size(), (size_t)num_pairs, Y);
+    };
+    const size_t need = arena_measure<UploadArena>(layout);
+    int rc;
+    if ((rc = sv_ensure_scratch(ctx, need))) return rc;
+    if ((rc = sv_ensure_stage(ctx, need))) return rc;
+    UploadArena A(ctx, ctx->h_stage);
+    layout(A);
+    if (A.overflow) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_selftest_pose_graph_envelope_solve: internal arena overflow");
+    PgCtl c0{};
+    c0.phase = 1;
+    if ((rc = A.upload(ctx, s, Y.ctl, &c0, sizeof c0))) return rc;
+    if ((rc = A.upload(ctx, s, Y.diag, diag_blocks, (size_t)nfree * 392))) return rc;
+    if ((rc = A.upload(ctx, s, Y.blocks, pair_blocks, (size_t)num_pairs * 392))) return rc;
+    if ((rc = A.upload(ctx, s, Y.rhs, rhs, (size_t)nfree * 56))) return rc;
+    if ((rc = upload_plan(ctx, s, A, Y.env, plan))) return rc;
+    if ((rc = A.flush(ctx, s))) return rc;
+    PgEnvDev K = plan_descriptor(Y.env, plan);
+    K.ctl = (const PgCtl*)Y.ctl, K.damped = 0;
+    K.Hd = Y.diag, K.b = Y.rhs, K.x = Y.x, K.blk = Y.blocks, K.blk_stride = 49;
+    {
+        SvProfScope prof(ctx, s, "k_pg_env_assemble");
+        sv_pg_env_assemble(s, K);
+    }
+    {
+        SvProfScope prof(ctx, s, "k_pg_env_factor_solve");
+        sv_pg_env_factor_solve(s, K);
+    }
+    SV_HIP(ctx, hipGetLastError());
+    PgEnvCtl ec{};
+    std::vector<double> x((size_t)nfree * 7);
+    Downloads Dl;
+    Dl.add(A, &ec, Y.env.ctl, sizeof ec);
+    Dl.add(A, x.data(), Y.x, x.size() * 8);
+    if ((rc = Dl.fetch(ctx, s, A))) return rc;
+    SV_HIP(ctx, hipStreamSynchronize(s));
+    Dl.scatter(A);
+    fill_solver_stats(solver_stats, SVGPU_PG_SOLVER_ENVELOPE, &plan, ec.solve_failed ? 1 : 0);
+    if (ec.solve_failed) return sv_set_error(ctx, SVGPU_ERR_NUMERIC, "svgpu_selftest_pose_graph_envelope_solve: the system is not positive definite");
+    std::copy(x.begin(), x.end(), x_out);
     return SVGPU_OK;
 }
 

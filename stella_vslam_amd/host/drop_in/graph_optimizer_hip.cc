@@ -207,9 +207,11 @@ void graph_optimizer::optimize(const std::shared_ptr<data::keyframe>& loop_keyfr
     // 4. the optimisation (:252-257)
     std::vector<double> sim3_out(8 * (size_t)n), pose_out(12 * (size_t)n);
     svgpu_ctx* ctx = stella_vslam::hip::context();
-    stella_vslam::hip::check(svgpu_pose_graph_optimize(ctx, n, sim3_cw.data(), fixed.data(), (int)edges.size(), e1.data(), e2.data(), meas.data(), fix_scale_ ? 1 : 0, 50,
-                                                       1e-3, sim3_out.data(), pose_out.data(), &last_stats_),
-                             "svgpu_pose_graph_optimize");
+    svgpu_pose_graph_options options{};
+    options.solver = solver_;
+    stella_vslam::hip::check(svgpu_pose_graph_optimize_ex(ctx, n, sim3_cw.data(), fixed.data(), (int)edges.size(), e1.data(), e2.data(), meas.data(), fix_scale_ ? 1 : 0,
+                                                          50, 1e-3, sim3_out.data(), pose_out.data(), &last_stats_, &options, &last_solver_stats_),
+                             "svgpu_pose_graph_optimize_ex");
     // 5. poses and point cloud (:259-302)
     std::vector<std::shared_ptr<data::landmark>> lms;
     std::vector<int32_t> ref;

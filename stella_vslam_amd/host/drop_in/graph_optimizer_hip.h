@@ -70,12 +70,17 @@ public:
                   const std::map<std::shared_ptr<data::keyframe>, std::set<std::shared_ptr<data::keyframe>>>& loop_connections,
                   std::unordered_map<unsigned int, unsigned int>& found_lm_to_ref_keyfrm_id) const;
 
+    //! Linear solver of the damped systems (svgpu_pose_graph_optimize_ex); the default is the PCG of svgpu_pose_graph_optimize
+    void set_linear_solver(svgpu_pose_graph_solver solver) { solver_ = solver; }
+
     //! what the last call's device run reported
     mutable svgpu_pose_graph_stats last_stats_{};
+    mutable svgpu_pose_graph_solver_stats last_solver_stats_{};
 
 private:
     const bool fix_scale_;
     const unsigned int min_num_shared_lms_;
+    svgpu_pose_graph_solver solver_ = SVGPU_PG_SOLVER_PCG;
 };
 
 }  // namespace hip

@@ -2,6 +2,7 @@
 // the class is run on two fresh copies of it: poses and landmarks have to come out bit-equal, the root stays, every landmark is
 // refreshed once and chi2 falls.  With a file name: the map is read
 // from that file (the format tests/test_gpu_posegraph.py writes), the class is run, and poses and landmarks are printed with %.17g.
+// A trailing argument "envelope" (or "pcg") selects the linear solver in either mode.
 //   n curr_id loop_id min_num_shared_lms fix_scale
 //   per keyframe: id parent_id(-1 none) is_root erased, 12 doubles pose_cw (3 x 4, row-major), has_non_corrected + 8 doubles,
 //                 has_pre_corrected + 8 doubles, L + L loop-edge ids, C + C (id weight) covisibilities in descending weight
@@ -14,6 +15,7 @@
 #include <fstream>
 #include <memory>
 #include <sstream>
+#include <string>
 #include <vector>
 
 #include "drop_in/graph_optimizer_hip.h"
@@ -188,6 +190,12 @@ std::string builtin_map() {
 }  // namespace
 
 int main(int argc, char** argv) {
+    // an optional trailing "envelope" / "pcg" selects the linear solver (graph_optimizer::set_linear_solver); without it: the default
+    svgpu_pose_graph_solver solver = SVGPU_PG_SOLVER_PCG;
+    if (argc > 1 && (std::string(argv[argc - 1]) == "envelope" || std::string(argv[argc - 1]) == "pcg")) {
+        if (std::string(argv[argc - 1]) == "envelope") solver = SVGPU_PG_SOLVER_ENVELOPE;
+        --argc;
+    }
     toy_map M;
     if (argc > 1) {
         std::ifstream in(argv[1]);
@@ -200,6 +208,7 @@ int main(int argc, char** argv) {
     YAML::Node yaml;
     yaml.kv["min_num_shared_lms"] = std::to_string(M.min_shared);
     optimize::hip::graph_optimizer opt(yaml, M.fix_scale != 0);
+    opt.set_linear_solver(solver);
     const auto curr = M.by_id.at(M.curr_id), loop = M.by_id.at(M.loop_id);
     std::vector<Mat44_t> before;
     for (auto& kf : M.kfs) before.push_back(kf->get_pose_cw());
@@ -216,7 +225,11 @@ int main(int argc, char** argv) {
             const Vec3_t p = lm->get_pos_in_world();
             std::printf("LM %u %.17g %.17g %.17g\n", lm->id_, p(0), p(1), p(2));
         }
-        std::printf("STATS %d %d %d\n", opt.last_stats_.lm_iterations, opt.last_stats_.lm_trials, opt.last_stats_.stopped_by_gain);
+        if (solver == SVGPU_PG_SOLVER_PCG)
+            std::printf("STATS %d %d %d\n", opt.last_stats_.lm_iterations, opt.last_stats_.lm_trials, opt.last_stats_.stopped_by_gain);
+        else  // (the solver that ran and its envelope behind the three figures of the default)
+            std::printf("STATS %d %d %d %d %d\n", opt.last_stats_.lm_iterations, opt.last_stats_.lm_trials, opt.last_stats_.stopped_by_gain,
+                        opt.last_solver_stats_.solver, opt.last_solver_stats_.envelope_blocks);
         return 0;
     }
     // the same run twice on a fresh copy of the map gives the same bits, the fixed keyframes keep their rotation, something moved
@@ -224,6 +237,7 @@ int main(int argc, char** argv) {
     std::istringstream in2(builtin_map());
     CHECK(read_map(in2, M2));
     optimize::hip::graph_optimizer opt2(yaml, false);
+    opt2.set_linear_solver(solver);
     opt2.optimize(M2.by_id.at(M2.loop_id), M2.by_id.at(M2.curr_id), M2.non_corrected, M2.pre_corrected, M2.loop_connections, M2.found);
     double moved = 0.0;
     for (size_t k = 0; k < M.kfs.size(); ++k) {

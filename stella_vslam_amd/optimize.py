@@ -199,22 +199,60 @@ def _vp(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
-def pose_graph_optimize(ctx: Context, sim3, fixed, edge_v1, edge_v2, edge_sim3_21, fix_scale=False, max_iterations=50, gain_threshold=1e-3):
+class _PoseGraphOptions(C.Structure):
+    _fields_ = [("solver", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class _PoseGraphSolverStats(C.Structure):
+    _fields_ = [("solver", C.c_int32), ("ordering", C.c_int32), ("envelope_blocks", C.c_int32), ("max_column_rows", C.c_int32),
+                ("failed_solves", C.c_int32)]
+
+
+PG_SOLVERS = {"pcg": 0, "envelope": 1}  # svgpu_pose_graph_solver
+
+
+def pose_graph_optimize(ctx: Context, sim3, fixed, edge_v1, edge_v2, edge_sim3_21, fix_scale=False, max_iterations=50, gain_threshold=1e-3, solver="pcg"):
     """optimize::graph_optimizer::optimize over flat arrays (svgpu_pose_graph_optimize): sim3 N x 8 (qx qy qz qw tx ty tz s), fixed N,
     edges as two index arrays and E x 8 measurements Sim3_21.  Returns a dict: sim3 (N x 8), pose_cw (N x 3 x 4, [R | t / s]) and the
-    stats lm_iterations, lm_trials, pcg_iterations, pcg_capped, stopped_by_gain, num_free, initial_chi2, final_chi2, lambda_final."""
+    stats lm_iterations, lm_trials, pcg_iterations, pcg_capped, stopped_by_gain, num_free, initial_chi2, final_chi2, lambda_final.
+    solver="envelope" solves the damped systems by the block envelope Cholesky (svgpu_pose_graph_optimize_ex); the dict then also holds
+    solver, ordering, envelope_blocks, max_column_rows and failed_solves ("pcg": solver 0 and zeros)."""
+    if solver not in PG_SOLVERS:
+        raise ValueError(f"pose_graph_optimize: unknown solver {solver!r}")
     s = np.ascontiguousarray(sim3, np.float64).reshape(-1, 8)
     f = np.ascontiguousarray(fixed, np.uint8).reshape(-1)
     e1, e2 = np.ascontiguousarray(edge_v1, np.int32).reshape(-1), np.ascontiguousarray(edge_v2, np.int32).reshape(-1)
     m = np.ascontiguousarray(edge_sim3_21, np.float64).reshape(-1, 8)
     if len(f) != len(s) or len(e2) != len(e1) or len(m) != len(e1):
         raise ValueError("pose_graph_optimize: array lengths disagree")
-    out, pose, st = np.zeros_like(s), np.zeros((len(s), 3, 4), np.float64), _PoseGraphStats()
-    ctx.check(lib().svgpu_pose_graph_optimize(ctx.handle, len(s), _vp(s), _vp(f), len(e1), _vp(e1), _vp(e2), _vp(m), int(bool(fix_scale)), int(max_iterations),
-                                              float(gain_threshold), _vp(out), _vp(pose), C.cast(C.pointer(st), C.c_void_p)), "svgpu_pose_graph_optimize")
+    out, pose, st, sst = np.zeros_like(s), np.zeros((len(s), 3, 4), np.float64), _PoseGraphStats(), _PoseGraphSolverStats()
+    args = (ctx.handle, len(s), _vp(s), _vp(f), len(e1), _vp(e1), _vp(e2), _vp(m), int(bool(fix_scale)), int(max_iterations), float(gain_threshold),
+            _vp(out), _vp(pose), C.cast(C.pointer(st), C.c_void_p))
+    if solver == "pcg":
+        ctx.check(lib().svgpu_pose_graph_optimize(*args), "svgpu_pose_graph_optimize")
+    else:
+        opt = _PoseGraphOptions(PG_SOLVERS[solver], (C.c_int32 * 3)(0, 0, 0))
+        ctx.check(lib().svgpu_pose_graph_optimize_ex(*args, C.cast(C.pointer(opt), C.c_void_p), C.cast(C.pointer(sst), C.c_void_p)), "svgpu_pose_graph_optimize_ex")
     res = {k: getattr(st, k) for k, _ in _PoseGraphStats._fields_}
+    res.update({k: getattr(sst, k) for k, _ in _PoseGraphSolverStats._fields_})
     res.update(sim3=out, pose_cw=pose)
     return res
+
+
+def envelope_selftest_solve(ctx: Context, pair_a, pair_b, diag_blocks, pair_blocks, rhs):
+    """svgpu_selftest_pose_graph_envelope_solve: the envelope solver alone on the block-sparse symmetric system with 7x7 blocks
+    {diag_blocks (n, 7, 7), block (pair_a[k], pair_b[k]) = pair_blocks[k] and its transpose} x = rhs (n, 7).  Returns (status, x (n, 7),
+    dict of the solver stats); status 6 (SVGPU_ERR_NUMERIC) with failed_solves 1 when the system is not positive definite."""
+    d = np.ascontiguousarray(diag_blocks, np.float64).reshape(-1, 49)
+    a, b = np.ascontiguousarray(pair_a, np.int32).reshape(-1), np.ascontiguousarray(pair_b, np.int32).reshape(-1)
+    blk = np.ascontiguousarray(pair_blocks, np.float64).reshape(-1, 49)
+    r = np.ascontiguousarray(rhs, np.float64).reshape(-1)
+    if len(b) != len(a) or len(blk) != len(a) or len(r) != 7 * len(d):
+        raise ValueError("envelope_selftest_solve: array lengths disagree")
+    x, sst = np.zeros((len(d), 7)), _PoseGraphSolverStats()
+    status = lib().svgpu_selftest_pose_graph_envelope_solve(ctx.handle, len(d), len(a), _vp(a) if len(a) else None, _vp(b) if len(a) else None, _vp(d),
+                                                            _vp(blk) if len(a) else None, _vp(r), _vp(x), C.cast(C.pointer(sst), C.c_void_p))
+    return status, x, {k: getattr(sst, k) for k, _ in _PoseGraphSolverStats._fields_}
 
 
 def correct_landmarks(ctx: Context, sim3_before, sim3_after, ref_vertex, pos_w):
