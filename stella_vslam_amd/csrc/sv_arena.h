@@ -2,7 +2,10 @@
 // on a measuring arena (no base) whose `off` is then the byte count to ask sv_ensure_scratch / sv_ensure_stage for, and on the placing
 // arena over the buffer that call returned.  Plain C++ (no HIP): the same header is compiled by the host-only tests.
 #pragma once
+#include <algorithm>
 #include <cstddef>
+#include <utility>
+#include <vector>
 
 inline size_t pad(size_t bytes) { return (bytes + 255) & ~size_t(255); }
 
@@ -32,4 +35,17 @@ size_t arena_measure(Layout&& layout) {
     A m;
     layout(m);
     return m.off;
+}
+
+// The copies that cover a set of spans of the arena (Span: anything with `off` and `bytes`).  The spans are sorted by offset, in place; one
+// that starts no further than `gap` bytes behind the end of the range before it joins that range.  Returns the (lo, hi) byte ranges, ascending.
+template <class Span>
+std::vector<std::pair<size_t, size_t>> sv_merge_ranges(std::vector<Span>& spans, size_t gap) {
+    std::sort(spans.begin(), spans.end(), [](const Span& a, const Span& b) { return a.off < b.off; });
+    std::vector<std::pair<size_t, size_t>> ranges;
+    for (const Span& sp : spans) {
+        if (!ranges.empty() && sp.off <= ranges.back().second + gap) ranges.back().second = std::max(ranges.back().second, sp.off + sp.bytes);
+        else ranges.push_back({sp.off, sp.off + sp.bytes});
+    }
+    return ranges;
 }

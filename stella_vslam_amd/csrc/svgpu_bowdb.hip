@@ -4,10 +4,8 @@
 #include <algorithm>
 #include <mutex>
 
-#include "svgpu_match_common.h"
+#include "sv_staged_call.h"
 #include "bowdb_kernels.h"
-
-using namespace svm;
 
 struct svgpu_bowdb {
     int device = 0;
@@ -147,14 +145,14 @@ int query_core(svgpu_ctx* ctx, svgpu_bowdb* db, const char* who, int Q, const in
         for (int i = 0; list && i < n_list; ++i) out_score[i] = -1.0f;
         return SVGPU_OK;
     }
-    SV_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     const size_t total = (size_t)q_off[Q], per = (size_t)Q * items;
     BowdbProblem P{};
     const int32_t* d_rej_list = nullptr;
     uint8_t* zero_lo = nullptr;
     size_t zero_bytes = 0;
-    auto layout = [&](UploadArena& A) -> int {
+    StagedCall C;
+    int rc = C.open(ctx, "svgpu_bowdb: internal arena overflow", [&](UploadArena& A) -> int {
         int rc = SVGPU_OK;
         P.q_off = A.put(ctx, s, q_off, (size_t)Q + 1, true, rc);
         P.q_ids = A.put(ctx, s, words, total, true, rc);
@@ -178,17 +176,10 @@ int query_core(svgpu_ctx* ctx, svgpu_bowdb* db, const char* who, int Q, const in
         P.out_common = A.take<uint32_t>((size_t)Q * cap);
         P.out_score = A.take<float>((size_t)Q * cap);
         return rc;
-    };
-    const size_t need = arena_measure<UploadArena>(layout);
-    int rc;
-    if ((rc = sv_ensure_scratch(ctx, need))) return rc;
-    if ((rc = sv_ensure_stage(ctx, need))) return rc;
-    UploadArena A(ctx, ctx->h_stage);
-    if ((rc = layout(A))) return rc;
-    if (A.overflow) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_bowdb: internal arena overflow");
+    });
+    if (rc) return rc;
     P.pool_ids = db->d_ids, P.pool_w = db->d_w, P.slots = db->d_slots;
     P.num_slots = ns, P.score_form = db->score_form, P.num_queries = Q, P.ratio = ratio, P.num_list = n_list, P.cap = cap;
-    Downloads D;
     if (!list) {
         SV_HIP(ctx, hipMemsetAsync(zero_lo, 0, zero_bytes, s));
         sv_launch_bowdb_reject(s, d_rej_list, n_reject, const_cast<uint8_t*>(P.reject), ns);
@@ -201,22 +192,18 @@ int query_core(svgpu_ctx* ctx, svgpu_bowdb* db, const char* who, int Q, const in
             sv_launch_bowdb_score(s, P);
             sv_launch_bowdb_emit(s, P);
         }
-        D.add(A, n_out, P.n_out, (size_t)Q * 4);
-        D.add(A, max_common, P.max_common, (size_t)Q * 4);
-        D.add(A, out_slots, P.out_slots, (size_t)Q * cap * 4);
-        D.add(A, out_common, P.out_common, (size_t)Q * cap * 4);
-        D.add(A, out_score, P.out_score, (size_t)Q * cap * 4);
+        C.down((uint32_t*)n_out, P.n_out, Q);
+        C.down(max_common, P.max_common, Q);
+        C.down(out_slots, P.out_slots, (size_t)Q * cap);
+        C.down(out_common, P.out_common, (size_t)Q * cap);
+        C.down(out_score, P.out_score, (size_t)Q * cap);
     }
     else {
         SvProfScope prof(ctx, s, "k_bowdb_score");
         sv_launch_bowdb_score(s, P);
-        D.add(A, out_score, P.score, (size_t)n_list * 4);
+        C.down(out_score, P.score, n_list);
     }
-    SV_HIP(ctx, hipGetLastError());
-    if ((rc = D.fetch(ctx, s, A))) return rc;
-    SV_HIP(ctx, hipStreamSynchronize(s));
-    D.scatter(A);
-    return SVGPU_OK;
+    return C.finish();
 }
 
 }  // namespace

@@ -144,13 +144,14 @@ int svgpu_match_bruteforce(svgpu_ctx* ctx, const uint8_t* desc1, const float* an
     if (n1 == 0 || n2 == 0) return SVGPU_OK;
     if (!desc1 || !desc2 || (check_orientation && (!angle1 || !angle2)))
         return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_match_bruteforce: null input");
-    SV_HIP(ctx, hipSetDevice(ctx->device));
     uint32_t *d1, *d2;
     float *a1, *a2;
     uint8_t* v2;
     int *g_owner, *g_match;
     BfProblem P{};
-    auto layout = [&](Arena& A) {
+    // inputs through the page-locked mirror of the arena: one copy down (the five arrays are the first takes: one contiguous range), one up
+    StagedCall C;
+    int rc = C.open(ctx, "svgpu_match_bruteforce: internal arena overflow", [&](UploadArena& A) {
         d1 = A.take<uint32_t>((size_t)n1 * 8);
         d2 = A.take<uint32_t>((size_t)n2 * 8);
         a1 = A.take<float>(n1);
@@ -163,27 +164,17 @@ int svgpu_match_bruteforce(svgpu_ctx* ctx, const uint8_t* desc1, const float* an
         g_match = A.take<int>(n2);
         P.num = A.take<int32_t>(1);
         take_sort(A, P, 1, n1, n2);
-    };
-    const size_t need = arena_measure(layout);
-    int rc = sv_ensure_scratch(ctx, need);
+    });
     if (rc) return rc;
-    hipStream_t s = ctx->stream;
-    // inputs through the page-locked mirror of the arena: one copy down (the five arrays are the first takes: one contiguous range), one up
-    if ((rc = sv_ensure_stage(ctx, need))) return rc;
-    UploadArena A(ctx, ctx->h_stage);
-    layout(A);
-    if (A.overflow) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_match_bruteforce: internal arena overflow");
-    if ((rc = A.upload(ctx, s, d1, desc1, (size_t)n1 * 32))) return rc;
-    if ((rc = A.upload(ctx, s, d2, desc2, (size_t)n2 * 32))) return rc;
-    if (angle1) rc = A.upload(ctx, s, a1, angle1, (size_t)n1 * 4);
-    else memset(A.mirror + ((char*)a1 - A.base), 0, (size_t)n1 * 4);
-    if (rc) return rc;
-    if (angle2) rc = A.upload(ctx, s, a2, angle2, (size_t)n2 * 4);
-    else memset(A.mirror + ((char*)a2 - A.base), 0, (size_t)n2 * 4);
-    if (rc) return rc;
-    if (valid2 && (rc = A.upload(ctx, s, v2, valid2, n2))) return rc;
-    if (!angle1 || !angle2) A.up_lo = 0, A.up_hi = std::max(A.up_hi, (size_t)((char*)(a2 + n2) - A.base));  // the zeroed angle rows travel with the range
-    if ((rc = A.flush(ctx, s))) return rc;
+    hipStream_t s = C.s;
+    C.up(d1, (const uint32_t*)desc1, (size_t)n1 * 8);
+    C.up(d2, (const uint32_t*)desc2, (size_t)n2 * 8);
+    if (angle1) C.up(a1, angle1, n1);
+    else memset(C.stage(a1, n1), 0, (size_t)n1 * 4);  // no angles: zeroed rows, written in the mirror, travel with the range
+    if (angle2) C.up(a2, angle2, n2);
+    else memset(C.stage(a2, n2), 0, (size_t)n2 * 4);
+    C.up(v2, valid2, n2);
+    if ((rc = C.flush())) return rc;
     P.desc1 = d1;
     P.desc2 = d2;
     P.angle1 = a1;
@@ -197,14 +188,10 @@ int svgpu_match_bruteforce(svgpu_ctx* ctx, const uint8_t* desc1, const float* an
     P.lowe_ratio = lowe_ratio;
     P.check_orientation = check_orientation;
     sv_launch_bf(ctx, s, P, 1, g_owner, g_match);
-    SV_HIP(ctx, hipGetLastError());
     int32_t num = 0;
-    Downloads D;
-    D.add(A, matched_2_in_1, P.matched, (size_t)n1 * 4);
-    D.add(A, &num, P.num, 4);
-    if ((rc = D.fetch(ctx, s, A))) return rc;
-    SV_HIP(ctx, hipStreamSynchronize(s));
-    D.scatter(A);
+    C.down(matched_2_in_1, P.matched, n1);
+    C.down(&num, P.num, 1);
+    if ((rc = C.finish())) return rc;
     *num_matches = num;
     return SVGPU_OK;
 }
@@ -229,12 +216,12 @@ int svgpu_match_candidates(svgpu_ctx* ctx, const uint8_t* qdesc, int nq, const u
         if (cand_off[q + 1] < cand_off[q]) return sv_set_error(ctx, SVGPU_ERR_INVALID, "cand_off not monotone");
     for (int c = 0; c < nc; ++c)
         if (cand_idx[c] < 0 || cand_idx[c] >= nt) return sv_set_error(ctx, SVGPU_ERR_INVALID, "cand_idx out of range");
-    SV_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     CandProblem P{};
     int *owner, *match;
     unsigned* mdist;
-    auto layout = [&](UploadArena& A) -> int {
+    StagedCall C;
+    int rc = C.open(ctx, "svgpu_match_candidates: internal arena overflow", [&](UploadArena& A) -> int {
         int rc = SVGPU_OK;
         P.qdesc = (const uint32_t*)A.put(ctx, s, qdesc, (size_t)nq * 32, true, rc);
         P.tdesc = (const uint32_t*)A.put(ctx, s, tdesc, (size_t)nt * 32, true, rc);
@@ -256,15 +243,9 @@ int svgpu_match_candidates(svgpu_ctx* ctx, const uint8_t* qdesc, int nq, const u
         match = A.take<int>(nq);
         mdist = A.take<unsigned>(nt);
         return rc;
-    };
-    const size_t need = arena_measure<UploadArena>(layout);
-    int rc = sv_ensure_scratch(ctx, need);
+    });
     if (rc) return rc;
-    if ((rc = sv_ensure_stage(ctx, need))) return rc;
-    UploadArena A(ctx, ctx->h_stage);  // batched upload / read-back (UploadArena::upload, Downloads)
-    if ((rc = layout(A))) return rc;
-    if (A.overflow) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_match_candidates: internal arena overflow");
-    if ((rc = A.flush(ctx, s))) return rc;
+    if ((rc = C.flush())) return rc;
     P.nq = nq;
     P.nt = nt;
     P.check_orientation = check_orientation;
@@ -272,14 +253,10 @@ int svgpu_match_candidates(svgpu_ctx* ctx, const uint8_t* qdesc, int nq, const u
     P.lowe_ratio = lowe_ratio;
     P.mode = mode;
     sv_launch_cand(ctx, s, P, owner, match, mdist);
-    SV_HIP(ctx, hipGetLastError());
     int32_t num = 0;
-    Downloads D;
-    D.add(A, match_q, P.match_q, (size_t)nq * 4);
-    D.add(A, &num, P.num, 4);
-    if ((rc = D.fetch(ctx, s, A))) return rc;
-    SV_HIP(ctx, hipStreamSynchronize(s));
-    D.scatter(A);
+    C.down(match_q, P.match_q, nq);
+    C.down(&num, P.num, 1);
+    if ((rc = C.finish())) return rc;
     *num_matches = num;
     return SVGPU_OK;
 }
@@ -516,32 +493,22 @@ int svgpu_reproject_landmarks(svgpu_ctx* ctx, const svgpu_camera* cam, const dou
     if (rc) return rc;
     if (n == 0) return SVGPU_OK;
     if (!visible || !reproj || !x_right || !pred_scale_level) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_reproject_landmarks: null output");
-    SV_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    // one upload and one read-back through the page-locked mirror of the arena (UploadArena::upload / Downloads): nine separate copies
-    // from / to pageable memory were nine staging kernels on the stream
-    auto layout = [&](UploadArena& A) -> int {
+    // one upload and one read-back through the page-locked mirror of the arena (StagedCall): nine separate copies from / to pageable
+    // memory were nine staging kernels on the stream
+    StagedCall C;
+    rc = C.open(ctx, "svgpu_reproject_landmarks: internal arena overflow", [&](UploadArena& A) -> int {
         int ru = SVGPU_OK;
         take_reproj(ctx, s, A, true, R, n, pos_w, mean_normal, min_valid_dist, max_valid_dist, skip, ru);
         return ru ? ru : A.flush(ctx, s);
-    };
-    const size_t need = arena_measure<UploadArena>(layout);
-    if ((rc = sv_ensure_scratch(ctx, need))) return rc;
-    if ((rc = sv_ensure_stage(ctx, need))) return rc;
-    UploadArena A(ctx, ctx->h_stage);
-    if ((rc = layout(A))) return rc;
-    if (A.overflow) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_reproject_landmarks: internal arena overflow");
+    });
+    if (rc) return rc;
     sv_launch_reproject(s, R);
-    SV_HIP(ctx, hipGetLastError());
-    Downloads D;
-    D.add(A, visible, R.visible, n);
-    D.add(A, reproj, R.reproj, (size_t)n * 16);
-    D.add(A, x_right, R.x_right, (size_t)n * 4);
-    D.add(A, pred_scale_level, R.pred_level, (size_t)n * 4);
-    if ((rc = D.fetch(ctx, s, A))) return rc;
-    SV_HIP(ctx, hipStreamSynchronize(s));
-    D.scatter(A);
-    return SVGPU_OK;
+    C.down(visible, R.visible, n);
+    C.down(reproj, R.reproj, 2 * (size_t)n);
+    C.down(x_right, R.x_right, n);
+    C.down(pred_scale_level, R.pred_level, n);
+    return C.finish();
 }
 
 int svgpu_match_frame_and_landmarks(svgpu_ctx* ctx, const svgpu_camera* cam, const double* rot_cw, const double* trans_cw,

@@ -1,4 +1,4 @@
-// Shared host-side pieces of the matcher entry points (svgpu_match.hip, svgpu_match2.hip): scratch arena, the frame side of the
+// Shared host-side pieces of the matcher entry points (svgpu_match.hip, svgpu_match2.hip): the sort scratch, the frame side of the
 // cell matchers, and the two-pass "grid build -> candidate lists -> candidate matcher" driver.
 #pragma once
 #include <algorithm>
@@ -10,79 +10,11 @@
 #include <utility>
 #include <vector>
 
-#include "svgpu_internal.h"
+#include "sv_staged_call.h"
 #include "match_kernels.h"
 #include "frame_kernels.h"
 
 namespace svm {
-
-// The scratch arena (sv_arena.h) with batched uploads: with a page-locked mirror of the arena (ctx->h_stage) every host array is copied to the
-// mirror at its arena offset and ONE host-to-device copy of the touched range follows (flush) -- the runtime turns every small copy from
-// pageable memory into a staging kernel of its own (~5 us each on the stream: ten of them per cell-matcher call were half of what the call
-// waited for).  Device-only pieces inside the range receive stale bytes, harmlessly: the kernels that produce them run behind the copy.
-// On a measuring arena upload / put / flush do nothing.
-struct UploadArena : Arena {
-    char* mirror = nullptr;
-    size_t up_lo = ~size_t(0), up_hi = 0;
-    UploadArena() = default;
-    explicit UploadArena(svgpu_ctx* ctx, char* mirror_ = nullptr) : Arena(ctx->d_scratch, ctx->scratch_bytes), mirror(mirror_) {}
-    int upload(svgpu_ctx* ctx, hipStream_t s, void* dst, const void* src, size_t bytes) {
-        if (!dst || !bytes) return SVGPU_OK;
-        if (!mirror) {
-            SV_HIP(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));
-            return SVGPU_OK;
-        }
-        const size_t o = (size_t)((char*)dst - base);
-        memcpy(mirror + o, src, bytes);
-        up_lo = std::min(up_lo, o);
-        up_hi = std::max(up_hi, o + bytes);
-        return SVGPU_OK;
-    }
-    // take n elements for an optional host array and, when `fresh`, upload it; no source: no piece, null.  The first failure stays in `rc`.
-    template <class T>
-    T* put(svgpu_ctx* ctx, hipStream_t s, const T* src, size_t n, bool fresh, int& rc) {
-        if (!src) return nullptr;
-        T* dst = take<T>(n);
-        if (fresh && !rc) rc = upload(ctx, s, dst, src, n * sizeof(T));
-        return dst;
-    }
-    int flush(svgpu_ctx* ctx, hipStream_t s) {
-        if (mirror && up_hi > up_lo) SV_HIP(ctx, hipMemcpyAsync(base + up_lo, mirror + up_lo, up_hi - up_lo, hipMemcpyHostToDevice, s));
-        up_lo = ~size_t(0), up_hi = 0;
-        return SVGPU_OK;
-    }
-};
-
-// Batched read-backs, the counterpart of Arena::upload: results that live in the arena are requested with add(), fetch() copies the
-// range(s) that cover them into the page-locked mirror (requests closer than 32 KB share one copy), and after the stream has been
-// synchronised scatter() hands them to the caller's arrays.
-struct Downloads {
-    struct Item {
-        void* dst;
-        size_t off, bytes;
-    };
-    std::vector<Item> items;
-    void add(const UploadArena& A, void* dst, const void* src, size_t bytes) {
-        if (dst && bytes) items.push_back({dst, (size_t)((const char*)src - A.base), bytes});
-    }
-    int fetch(svgpu_ctx* ctx, hipStream_t s, const UploadArena& A) {
-        std::sort(items.begin(), items.end(), [](const Item& a, const Item& b) { return a.off < b.off; });
-        size_t k = 0;
-        while (k < items.size()) {
-            size_t lo = items[k].off, hi = lo + items[k].bytes;
-            ++k;
-            while (k < items.size() && items[k].off <= hi + 32768) {
-                hi = std::max(hi, items[k].off + items[k].bytes);
-                ++k;
-            }
-            SV_HIP(ctx, hipMemcpyAsync(A.mirror + lo, A.base + lo, hi - lo, hipMemcpyDeviceToHost, s));
-        }
-        return SVGPU_OK;
-    }
-    void scatter(const UploadArena& A) const {
-        for (const Item& it : items) memcpy(it.dst, A.mirror + it.off, it.bytes);
-    }
-};
 
 // scratch for the angle-bin sorted copies of both sides (see k_bf_binsort)
 inline void take_sort(Arena& A, BfProblem& P, int pairs, int cap1, int cap2) {

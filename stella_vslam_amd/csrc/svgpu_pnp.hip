@@ -2,21 +2,13 @@
 // and out, synchronous: one upload, the launches on the context's stream, one read-back and one synchronisation per call.
 #include <cmath>
 
-#include "svgpu_match_common.h"
+#include "sv_staged_call.h"
+#include "sv_validate.h"
 #include "pnp_kernels.h"
 #include "pnp_layout.h"
 #include "sv_trig.h"
 
-using namespace svm;
-
 namespace {
-
-bool offsets_ok(const int32_t* off, int n) {
-    if (off[0] != 0) return false;
-    for (int k = 0; k < n; ++k)
-        if (off[k + 1] < off[k]) return false;
-    return true;
-}
 
 int ransac_core(svgpu_ctx* ctx, const char* who, int num_problems, const int32_t* match_off, const double* bearings, const double* pos_w,
                 const int32_t* octaves, const float* scale_factors, int num_levels, int min_num_inliers, int num_iter, const uint32_t* samples,
@@ -24,7 +16,7 @@ int ransac_core(svgpu_ctx* ctx, const char* who, int num_problems, const int32_t
                 int32_t* hyp_num_inliers, double* hyp_cost) {
     if (!ctx || num_problems < 0 || min_num_inliers < 0 || num_iter < 0 || gn_iter < 0) return sv_set_error(ctx, SVGPU_ERR_INVALID, who);
     if (num_problems == 0) return SVGPU_OK;
-    if (!match_off || !valid || !pose_cw || !best_iter || !scale_factors || num_levels < 1 || !offsets_ok(match_off, num_problems))
+    if (!match_off || !valid || !pose_cw || !best_iter || !scale_factors || num_levels < 1 || !sv_offsets_ok(match_off, num_problems))
         return sv_set_error(ctx, SVGPU_ERR_INVALID, who);
     const int P = num_problems, I = num_iter, n = match_off[P];
     if (n > 0 && (!bearings || !pos_w || !octaves || !is_inlier)) return sv_set_error(ctx, SVGPU_ERR_INVALID, who);
@@ -53,24 +45,20 @@ int ransac_core(svgpu_ctx* ctx, const char* who, int num_problems, const int32_t
     }
     const int num_active = (int)active.size();
     if (num_active > 0) {
-        SV_HIP(ctx, hipSetDevice(ctx->device));
-        hipStream_t s = ctx->stream;
         PnpRansacPieces Y{};
-        const auto layout = [&](UploadArena& A) { pnp_ransac_layout(A, (size_t)P, (size_t)n, (size_t)I, (size_t)num_active, recompute != 0, Y); };
-        const size_t need = arena_measure<UploadArena>(layout);
-        int rc;
-        if ((rc = sv_ensure_scratch(ctx, need))) return rc;
-        if ((rc = sv_ensure_stage(ctx, need))) return rc;
-        UploadArena A(ctx, ctx->h_stage);
-        layout(A);
-        if (A.overflow) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_pnp_ransac: internal arena overflow");
-        if ((rc = A.upload(ctx, s, Y.bearings, bearings, (size_t)n * 24))) return rc;
-        if ((rc = A.upload(ctx, s, Y.pos_w, pos_w, (size_t)n * 24))) return rc;
-        if ((rc = A.upload(ctx, s, Y.max_cos, max_cos.data(), (size_t)n * 4))) return rc;
-        if ((rc = A.upload(ctx, s, Y.match_off, match_off, ((size_t)P + 1) * 4))) return rc;
-        if ((rc = A.upload(ctx, s, Y.samples, samples, (size_t)P * I * 16))) return rc;
-        if ((rc = A.upload(ctx, s, Y.active, active.data(), (size_t)num_active * 4))) return rc;
-        if ((rc = A.flush(ctx, s))) return rc;
+        StagedCall C;
+        int rc = C.open(ctx, "svgpu_pnp_ransac: internal arena overflow", [&](UploadArena& A) {
+            pnp_ransac_layout(A, (size_t)P, (size_t)n, (size_t)I, (size_t)num_active, recompute != 0, Y);
+        });
+        if (rc) return rc;
+        hipStream_t s = C.s;
+        C.up(Y.bearings, bearings, 3 * (size_t)n);
+        C.up(Y.pos_w, pos_w, 3 * (size_t)n);
+        C.up(Y.max_cos, max_cos.data(), n);
+        C.up(Y.match_off, match_off, (size_t)P + 1);
+        C.up(Y.samples, samples, 4 * (size_t)P * I);
+        C.up(Y.active, active.data(), num_active);
+        if ((rc = C.flush())) return rc;
         PnpRansacProblem R{};
         R.bearings = Y.bearings, R.pos_w = Y.pos_w, R.max_cos = Y.max_cos, R.match_off = Y.match_off, R.samples = Y.samples, R.active = Y.active;
         R.num_problems = P, R.num_active = num_active, R.num_iter = I, R.gn_iter = gn_iter;
@@ -93,18 +81,14 @@ int ransac_core(svgpu_ctx* ctx, const char* who, int num_problems, const int32_t
             SvProfScope prof(ctx, s, "k_pnp_pose");
             sv_launch_pnp_pose(s, Q);
         }
-        SV_HIP(ctx, hipGetLastError());
-        Downloads D;
-        D.add(A, valid, Y.valid, P);
-        D.add(A, pose_cw, Y.pose, (size_t)P * 96);
-        D.add(A, is_inlier, Y.is_inlier, n);
-        D.add(A, best_iter, Y.best_iter, (size_t)P * 4);
-        D.add(A, hyp_pose, Y.hyp_pose, (size_t)P * I * 96);
-        D.add(A, hyp_num_inliers, Y.hyp_num_inliers, (size_t)P * I * 4);
-        D.add(A, hyp_cost, Y.hyp_cost, (size_t)P * I * 8);
-        if ((rc = D.fetch(ctx, s, A))) return rc;
-        SV_HIP(ctx, hipStreamSynchronize(s));
-        D.scatter(A);
+        C.down(valid, Y.valid, P);
+        C.down(pose_cw, Y.pose, 12 * (size_t)P);
+        C.down(is_inlier, Y.is_inlier, n);
+        C.down(best_iter, Y.best_iter, P);
+        C.down(hyp_pose, Y.hyp_pose, 12 * (size_t)P * I);
+        C.down(hyp_num_inliers, Y.hyp_num_inliers, (size_t)P * I);
+        C.down(hyp_cost, Y.hyp_cost, (size_t)P * I);
+        if ((rc = C.finish())) return rc;
     }
     // a problem that did not run: solution_is_valid_ = false, nothing else is defined by the reference -- zeros here
     size_t next = 0;
@@ -133,39 +117,28 @@ int svgpu_pnp_compute_pose(svgpu_ctx* ctx, int num_sets, const int32_t* set_off,
     const char* who = "svgpu_pnp_compute_pose: bad arguments";
     if (!ctx || num_sets < 0 || gauss_newton_num_iter < 0) return sv_set_error(ctx, SVGPU_ERR_INVALID, who);
     if (num_sets == 0) return SVGPU_OK;
-    if (!set_off || !bearings || !pos_w || !pose_cw || !offsets_ok(set_off, num_sets)) return sv_set_error(ctx, SVGPU_ERR_INVALID, who);
+    if (!set_off || !bearings || !pos_w || !pose_cw || !sv_offsets_ok(set_off, num_sets)) return sv_set_error(ctx, SVGPU_ERR_INVALID, who);
     for (int k = 0; k < num_sets; ++k)
         if (set_off[k + 1] - set_off[k] < 4) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_pnp_compute_pose: a set of fewer than 4 correspondences");
     const size_t n = (size_t)set_off[num_sets];
-    SV_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
     PnpPosePieces Y{};
-    const auto layout = [&](UploadArena& A) { pnp_pose_layout(A, (size_t)num_sets, n, Y); };
-    const size_t need = arena_measure<UploadArena>(layout);
-    int rc;
-    if ((rc = sv_ensure_scratch(ctx, need))) return rc;
-    if ((rc = sv_ensure_stage(ctx, need))) return rc;
-    UploadArena A(ctx, ctx->h_stage);
-    layout(A);
-    if (A.overflow) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_pnp_compute_pose: internal arena overflow");
-    if ((rc = A.upload(ctx, s, Y.bearings, bearings, n * 24))) return rc;
-    if ((rc = A.upload(ctx, s, Y.pos_w, pos_w, n * 24))) return rc;
-    if ((rc = A.upload(ctx, s, Y.off, set_off, ((size_t)num_sets + 1) * 4))) return rc;
-    if ((rc = A.flush(ctx, s))) return rc;
+    StagedCall C;
+    int rc = C.open(ctx, "svgpu_pnp_compute_pose: internal arena overflow", [&](UploadArena& A) { pnp_pose_layout(A, (size_t)num_sets, n, Y); });
+    if (rc) return rc;
+    hipStream_t s = C.s;
+    C.up(Y.bearings, bearings, 3 * n);
+    C.up(Y.pos_w, pos_w, 3 * n);
+    C.up(Y.off, set_off, (size_t)num_sets + 1);
+    if ((rc = C.flush())) return rc;
     PnpPoseProblem Q{};
     Q.bearings = Y.bearings, Q.pos_w = Y.pos_w, Q.off = Y.off, Q.pose = Y.pose, Q.err = Y.err, Q.num_sets = num_sets, Q.gn_iter = gauss_newton_num_iter;
     {
         SvProfScope prof(ctx, s, "k_pnp_pose");
         sv_launch_pnp_pose(s, Q);
     }
-    SV_HIP(ctx, hipGetLastError());
-    Downloads D;
-    D.add(A, pose_cw, Y.pose, (size_t)num_sets * 96);
-    D.add(A, reproj_error, Y.err, (size_t)num_sets * 8);
-    if ((rc = D.fetch(ctx, s, A))) return rc;
-    SV_HIP(ctx, hipStreamSynchronize(s));
-    D.scatter(A);
-    return SVGPU_OK;
+    C.down(pose_cw, Y.pose, 12 * (size_t)num_sets);
+    C.down(reproj_error, Y.err, num_sets);
+    return C.finish();
 }
 
 int svgpu_pnp_ransac_batch(svgpu_ctx* ctx, int num_problems, const int32_t* match_off, const double* bearings, const double* pos_w,

@@ -2,29 +2,21 @@
 // in and out, synchronous: one upload, the launches on the context's stream, one read-back.  The Levenberg-Marquardt decisions are taken
 // on the device (PgCtl); the host enqueues batches of damping trials and reads the control block between batches only to learn whether the
 // run has ended.
+#include <algorithm>
 #include <cmath>
 
-#include "svgpu_match_common.h"
+#include "sv_staged_call.h"
+#include "sv_validate.h"
 #include "posegraph_kernels.h"
 #include "posegraph_layout.h"
 #include "posegraph_envelope_layout.h"
 #include "posegraph_envelope_plan.h"
-
-using namespace svm;
 
 static_assert(PG_LAYOUT_REC == PG_REC, "posegraph_layout.h and posegraph_kernels.h disagree on the edge record");
 static_assert(sizeof(PgCtl) <= PG_LAYOUT_CTL, "posegraph_layout.h reserves too little for PgCtl");
 static_assert(sizeof(PgEnvCtl) <= PG_ENV_LAYOUT_CTL, "posegraph_envelope_layout.h reserves too little for PgEnvCtl");
 
 namespace {
-
-bool sim3_ok(const double* p) {
-    double n2 = 0.0;
-    for (int k = 0; k < 8; ++k)
-        if (!std::isfinite(p[k])) return false;
-    for (int k = 0; k < 4; ++k) n2 += p[k] * p[k];
-    return std::fabs(n2 - 1.0) <= 1e-9 && p[7] > 0.0;
-}
 
 // one damping trial; the kernels of a step that has nothing to do (PgCtl::phase) return at once.  K: the envelope solver's descriptor
 // when it solves (its two kernels then stand where the preconditioner and the PCG stand), else null
@@ -59,16 +51,12 @@ void enqueue_step(svgpu_ctx* ctx, hipStream_t s, const PgDev& D, const PgEnvDev*
     }
 }
 
-int upload_plan(svgpu_ctx* ctx, hipStream_t s, UploadArena& A, const PgEnvPieces& Y, const PgEnvPlan& P) {
+void upload_plan(StagedCall& C, const PgEnvPieces& Y, const PgEnvPlan& P) {
     const PgEnvCtl e0{};
-    const auto up = [&](int32_t* dst, const std::vector<int32_t>& v) { return A.upload(ctx, s, dst, v.data(), v.size() * 4); };
-    int rc;
-    if ((rc = A.upload(ctx, s, Y.ctl, &e0, sizeof e0))) return rc;
-    if ((rc = up(Y.order, P.order)) || (rc = up(Y.rowoff, P.rowoff)) || (rc = up(Y.coloff, P.coloff)) || (rc = up(Y.colrows, P.colrows)) ||
-        (rc = up(Y.colbase, P.colbase)) || (rc = up(Y.blk_src, P.blk_src)) || (rc = up(Y.pair_off, P.pair_off)) || (rc = up(Y.pair_ent, P.pair_ent)) ||
-        (rc = up(Y.pair_flag, P.pair_flag)))
-        return rc;
-    return SVGPU_OK;
+    const auto up = [&](int32_t* dst, const std::vector<int32_t>& v) { C.up(dst, v.data(), v.size()); };
+    C.up(Y.ctl, (const char*)&e0, sizeof e0);
+    up(Y.order, P.order), up(Y.rowoff, P.rowoff), up(Y.coloff, P.coloff), up(Y.colrows, P.colrows), up(Y.colbase, P.colbase);
+    up(Y.blk_src, P.blk_src), up(Y.pair_off, P.pair_off), up(Y.pair_ent, P.pair_ent), up(Y.pair_flag, P.pair_flag);
 }
 
 PgEnvDev plan_descriptor(const PgEnvPieces& Y, const PgEnvPlan& P) {
@@ -117,7 +105,7 @@ int svgpu_pose_graph_optimize_ex(svgpu_ctx* ctx, int num_vertices, const double*
     std::vector<int32_t> slot(N);
     int nfree = 0;
     for (int v = 0; v < N; ++v) {
-        if (!sim3_ok(sim3 + 8 * (size_t)v)) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_pose_graph_optimize: a vertex is not a Sim3 (unit quaternion, positive scale)");
+        if (!sv_sim3_ok(sim3 + 8 * (size_t)v)) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_pose_graph_optimize: a vertex is not a Sim3 (unit quaternion, positive scale)");
         slot[v] = fixed[v] ? -1 : nfree++;
     }
     if (nfree == N) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_pose_graph_optimize: no fixed vertex");
@@ -126,7 +114,7 @@ int svgpu_pose_graph_optimize_ex(svgpu_ctx* ctx, int num_vertices, const double*
         const int a = edge_v1[e], b = edge_v2[e];
         if (a < 0 || a >= N || b < 0 || b >= N) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_pose_graph_optimize: vertex index out of range");
         if (a == b) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_pose_graph_optimize: an edge from a vertex to itself");
-        if (!sim3_ok(edge_sim3_21 + 8 * (size_t)e)) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_pose_graph_optimize: a measurement is not a Sim3");
+        if (!sv_sim3_ok(edge_sim3_21 + 8 * (size_t)e)) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_pose_graph_optimize: a measurement is not a Sim3");
         if (slot[a] >= 0) ++v_off[slot[a] + 1];
         if (slot[b] >= 0) ++v_off[slot[b] + 1];
     }
@@ -151,37 +139,31 @@ int svgpu_pose_graph_optimize_ex(svgpu_ctx* ctx, int num_vertices, const double*
         if (!plan.fits) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_pose_graph_optimize_ex: the envelope's value count is beyond 32-bit indexing");
     }
 
-    SV_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
     PgPieces Y{};
     PgEnvPieces Ye{};
-    const auto layout = [&](UploadArena& A) {
+    StagedCall C;
+    int rc = C.open(ctx, "svgpu_pose_graph_optimize: internal arena overflow", [&](UploadArena& A) {
         pg_optimize_layout(A, (size_t)N, (size_t)E, (size_t)nfree, incident, Y);
         if (direct) pg_envelope_layout(A, (size_t)nfree, (size_t)plan.nblocks, (size_t)plan.num_pairs, plan.pair_ent.size(), Ye);
-    };
-    const size_t need = arena_measure<UploadArena>(layout);
-    int rc;
-    if ((rc = sv_ensure_scratch(ctx, need))) return rc;
-    if ((rc = sv_ensure_stage(ctx, need))) return rc;
-    UploadArena A(ctx, ctx->h_stage);
-    layout(A);
-    if (A.overflow) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_pose_graph_optimize: internal arena overflow");
+    });
+    if (rc) return rc;
+    hipStream_t s = C.s;
     PgCtl c0{};
     c0.ni = 2.0;
     c0.gain_thr = gain_threshold;
     c0.it_max = max_iterations;
     c0.ok = 1;
-    if ((rc = A.upload(ctx, s, Y.ctl, &c0, sizeof c0))) return rc;
-    if ((rc = A.upload(ctx, s, Y.est0, sim3, (size_t)N * 64))) return rc;
-    if ((rc = A.upload(ctx, s, Y.fixed, fixed, (size_t)N))) return rc;
-    if ((rc = A.upload(ctx, s, Y.slot, slot.data(), (size_t)N * 4))) return rc;
-    if ((rc = A.upload(ctx, s, Y.e_i, edge_v1, (size_t)E * 4))) return rc;
-    if ((rc = A.upload(ctx, s, Y.e_j, edge_v2, (size_t)E * 4))) return rc;
-    if ((rc = A.upload(ctx, s, Y.meas, edge_sim3_21, (size_t)E * 64))) return rc;
-    if ((rc = A.upload(ctx, s, Y.v_off, v_off.data(), ((size_t)nfree + 1) * 4))) return rc;
-    if ((rc = A.upload(ctx, s, Y.v_ent, v_ent.data(), incident * 4))) return rc;
-    if (direct && (rc = upload_plan(ctx, s, A, Ye, plan))) return rc;
-    if ((rc = A.flush(ctx, s))) return rc;
+    C.up(Y.ctl, (const char*)&c0, sizeof c0);
+    C.up(Y.est0, sim3, 8 * (size_t)N);
+    C.up(Y.fixed, fixed, N);
+    C.up(Y.slot, slot.data(), N);
+    C.up(Y.e_i, edge_v1, E);
+    C.up(Y.e_j, edge_v2, E);
+    C.up(Y.meas, edge_sim3_21, 8 * (size_t)E);
+    C.up(Y.v_off, v_off.data(), (size_t)nfree + 1);
+    C.up(Y.v_ent, v_ent.data(), incident);
+    if (direct) upload_plan(C, Ye, plan);
+    if ((rc = C.flush())) return rc;
 
     PgDev D{};
     D.N = N, D.E = E, D.nfree = nfree, D.n = 7 * nfree, D.fix_scale = fix_scale != 0;
@@ -201,7 +183,7 @@ int svgpu_pose_graph_optimize_ex(svgpu_ctx* ctx, int num_vertices, const double*
 
     // at most 10 trials per iteration; the first step also serves max_iterations == 0 (chi2 of the input, then phase 2)
     const long max_steps = std::max(1L, 10L * max_iterations);
-    PgCtl* c_host = (PgCtl*)(A.mirror + (Y.ctl - A.base));
+    PgCtl* c_host = (PgCtl*)C.host(Y.ctl);
     long done = 0;
     int batch = 8;
     for (;;) {
@@ -216,15 +198,11 @@ int svgpu_pose_graph_optimize_ex(svgpu_ctx* ctx, int num_vertices, const double*
     }
     const PgCtl c = *c_host;
     sv_pg_output(s, D);
-    SV_HIP(ctx, hipGetLastError());
-    Downloads Dl;
     PgEnvCtl ec{};
-    if (direct) Dl.add(A, &ec, Ye.ctl, sizeof ec);
-    Dl.add(A, sim3_out, Y.out_sim3, (size_t)N * 64);
-    Dl.add(A, pose_cw_out, Y.out_pose, (size_t)N * 96);
-    if ((rc = Dl.fetch(ctx, s, A))) return rc;
-    SV_HIP(ctx, hipStreamSynchronize(s));
-    Dl.scatter(A);
+    if (direct) C.down((char*)&ec, Ye.ctl, sizeof ec);
+    C.down(sim3_out, Y.out_sim3, 8 * (size_t)N);
+    C.down(pose_cw_out, Y.out_pose, 12 * (size_t)N);
+    if ((rc = C.finish())) return rc;
     if (stats) {
         stats->lm_iterations = c.it;
         stats->lm_trials = c.lm_trials;
@@ -251,27 +229,21 @@ int svgpu_selftest_pose_graph_envelope_solve(svgpu_ctx* ctx, int nfree, int num_
     PgEnvPlan plan;
     pg_env_plan(nfree, num_pairs, pair_a, pair_b, plan);
     if (!plan.fits) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_selftest_pose_graph_envelope_solve: the envelope's value count is beyond 32-bit indexing");
-    SV_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
     PgEnvSelftestPieces Y{};
-    const auto layout = [&](UploadArena& A) {
+    StagedCall C;
+    int rc = C.open(ctx, "svgpu_selftest_pose_graph_envelope_solve: internal arena overflow", [&](UploadArena& A) {
         pg_envelope_selftest_layout(A, (size_t)nfree, (size_t)plan.nblocks, (size_t)plan.num_pairs, plan.pair_ent.size(), (size_t)num_pairs, Y);
-    };
-    const size_t need = arena_measure<UploadArena>(layout);
-    int rc;
-    if ((rc = sv_ensure_scratch(ctx, need))) return rc;
-    if ((rc = sv_ensure_stage(ctx, need))) return rc;
-    UploadArena A(ctx, ctx->h_stage);
-    layout(A);
-    if (A.overflow) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_selftest_pose_graph_envelope_solve: internal arena overflow");
+    });
+    if (rc) return rc;
+    hipStream_t s = C.s;
     PgCtl c0{};
     c0.phase = 1;
-    if ((rc = A.upload(ctx, s, Y.ctl, &c0, sizeof c0))) return rc;
-    if ((rc = A.upload(ctx, s, Y.diag, diag_blocks, (size_t)nfree * 392))) return rc;
-    if ((rc = A.upload(ctx, s, Y.blocks, pair_blocks, (size_t)num_pairs * 392))) return rc;
-    if ((rc = A.upload(ctx, s, Y.rhs, rhs, (size_t)nfree * 56))) return rc;
-    if ((rc = upload_plan(ctx, s, A, Y.env, plan))) return rc;
-    if ((rc = A.flush(ctx, s))) return rc;
+    C.up(Y.ctl, (const char*)&c0, sizeof c0);
+    C.up(Y.diag, diag_blocks, 49 * (size_t)nfree);
+    C.up(Y.blocks, pair_blocks, 49 * (size_t)num_pairs);
+    C.up(Y.rhs, rhs, 7 * (size_t)nfree);
+    upload_plan(C, Y.env, plan);
+    if ((rc = C.flush())) return rc;
     PgEnvDev K = plan_descriptor(Y.env, plan);
     K.ctl = (const PgCtl*)Y.ctl, K.damped = 0;
     K.Hd = Y.diag, K.b = Y.rhs, K.x = Y.x, K.blk = Y.blocks, K.blk_stride = 49;
@@ -283,15 +255,11 @@ int svgpu_selftest_pose_graph_envelope_solve(svgpu_ctx* ctx, int nfree, int num_
         SvProfScope prof(ctx, s, "k_pg_env_factor_solve");
         sv_pg_env_factor_solve(s, K);
     }
-    SV_HIP(ctx, hipGetLastError());
     PgEnvCtl ec{};
     std::vector<double> x((size_t)nfree * 7);
-    Downloads Dl;
-    Dl.add(A, &ec, Y.env.ctl, sizeof ec);
-    Dl.add(A, x.data(), Y.x, x.size() * 8);
-    if ((rc = Dl.fetch(ctx, s, A))) return rc;
-    SV_HIP(ctx, hipStreamSynchronize(s));
-    Dl.scatter(A);
+    C.down((char*)&ec, Y.env.ctl, sizeof ec);
+    C.down(x.data(), Y.x, x.size());
+    if ((rc = C.finish())) return rc;
     fill_solver_stats(solver_stats, SVGPU_PG_SOLVER_ENVELOPE, &plan, ec.solve_failed ? 1 : 0);
     if (ec.solve_failed) return sv_set_error(ctx, SVGPU_ERR_NUMERIC, "svgpu_selftest_pose_graph_envelope_solve: the system is not positive definite");
     std::copy(x.begin(), x.end(), x_out);
@@ -309,37 +277,26 @@ int svgpu_pose_graph_correct_landmarks(svgpu_ctx* ctx, int num_vertices, const d
         if (ref_vertex[l] < 0 || ref_vertex[l] >= num_vertices)
             return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_pose_graph_correct_landmarks: reference vertex out of range");
     for (size_t v = 0; v < N; ++v)
-        if (!sim3_ok(sim3_before + 8 * v) || !sim3_ok(sim3_after + 8 * v))
+        if (!sv_sim3_ok(sim3_before + 8 * v) || !sv_sim3_ok(sim3_after + 8 * v))
             return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_pose_graph_correct_landmarks: a vertex is not a Sim3");
-    SV_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
     PgLandmarkPieces Y{};
-    const auto layout = [&](UploadArena& A) { pg_landmarks_layout(A, N, L, Y); };
-    const size_t need = arena_measure<UploadArena>(layout);
-    int rc;
-    if ((rc = sv_ensure_scratch(ctx, need))) return rc;
-    if ((rc = sv_ensure_stage(ctx, need))) return rc;
-    UploadArena A(ctx, ctx->h_stage);
-    layout(A);
-    if (A.overflow) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_pose_graph_correct_landmarks: internal arena overflow");
-    if ((rc = A.upload(ctx, s, Y.before, sim3_before, N * 64))) return rc;
-    if ((rc = A.upload(ctx, s, Y.after, sim3_after, N * 64))) return rc;
-    if ((rc = A.upload(ctx, s, Y.ref, ref_vertex, L * 4))) return rc;
-    if ((rc = A.upload(ctx, s, Y.pos_in, pos_w, L * 24))) return rc;
-    if ((rc = A.flush(ctx, s))) return rc;
+    StagedCall C;
+    int rc = C.open(ctx, "svgpu_pose_graph_correct_landmarks: internal arena overflow", [&](UploadArena& A) { pg_landmarks_layout(A, N, L, Y); });
+    if (rc) return rc;
+    hipStream_t s = C.s;
+    C.up(Y.before, sim3_before, 8 * N);
+    C.up(Y.after, sim3_after, 8 * N);
+    C.up(Y.ref, ref_vertex, L);
+    C.up(Y.pos_in, pos_w, 3 * L);
+    if ((rc = C.flush())) return rc;
     PgLandmarks P{};
     P.L = num_landmarks, P.N = num_vertices, P.sim3_before = Y.before, P.sim3_after = Y.after, P.ref = Y.ref, P.pos_in = Y.pos_in, P.pos_out = Y.pos_out;
     {
         SvProfScope prof(ctx, s, "k_pg_correct_landmarks");
         sv_pg_correct_landmarks(s, P);
     }
-    SV_HIP(ctx, hipGetLastError());
-    Downloads Dl;
-    Dl.add(A, pos_w_out, Y.pos_out, L * 24);
-    if ((rc = Dl.fetch(ctx, s, A))) return rc;
-    SV_HIP(ctx, hipStreamSynchronize(s));
-    Dl.scatter(A);
-    return SVGPU_OK;
+    C.down(pos_w_out, Y.pos_out, 3 * L);
+    return C.finish();
 }
 
 }  // extern "C"

@@ -3,26 +3,15 @@
 // the batch size.
 #include <cmath>
 
-#include "svgpu_match_common.h"
+#include "sv_staged_call.h"
+#include "sv_validate.h"
 #include "sim3opt_kernels.h"
 #include "sim3opt_layout.h"
-
-using namespace svm;
 
 static_assert(sizeof(Sim3OptProblem) == S3O_LAYOUT_PROBLEM, "sim3opt_layout.h and sim3opt_kernels.h disagree on the problem descriptor");
 static_assert(sizeof(svgpu_sim3opt_stats) == S3O_LAYOUT_STATS, "sim3opt_layout.h and svgpu.h disagree on svgpu_sim3opt_stats");
 
 namespace {
-
-bool positive_finite(double v) { return std::isfinite(v) && v > 0.0; }
-
-bool sim3_ok(const double* p) {
-    double n2 = 0.0;
-    for (int k = 0; k < 8; ++k)
-        if (!std::isfinite(p[k])) return false;
-    for (int k = 0; k < 4; ++k) n2 += p[k] * p[k];
-    return std::fabs(n2 - 1.0) <= 1e-9 && p[7] > 0.0;
-}
 
 // the edge's camera (mutual_reproj_edge_wrapper.h:64-158): false for a model the edges do not cover
 bool fill_view(const svgpu_sim3opt_view& v, Sim3OptView& o) {
@@ -52,21 +41,20 @@ int optimize_core(svgpu_ctx* ctx, const char* who, int num_problems, const svgpu
                   uint8_t* status, svgpu_sim3opt_stats* stats) {
     if (!ctx || num_problems < 0) return sv_set_error(ctx, SVGPU_ERR_INVALID, who);
     if (num_problems == 0) return SVGPU_OK;
-    if (num_iter < 0 || !positive_finite(chi_sq)) return sv_set_error(ctx, SVGPU_ERR_INVALID, who);
+    if (num_iter < 0 || !sv_positive_finite(chi_sq)) return sv_set_error(ctx, SVGPU_ERR_INVALID, who);
     if (!view1 || !view2 || !match_off || !sim3_12 || !sim3_out || !num_inliers) return sv_set_error(ctx, SVGPU_ERR_INVALID, who);
     // ---- validation: nothing is launched before all of it has passed
     const int P = num_problems;
     if (match_off[0] != 0) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_sim3_transform_optimize: match_off[0] is not 0");
-    for (int p = 0; p < P; ++p)
-        if (match_off[p + 1] < match_off[p]) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_sim3_transform_optimize: offsets are not monotone");
+    if (!sv_offsets_ok(match_off, P)) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_sim3_transform_optimize: offsets are not monotone");
     const size_t n = (size_t)match_off[P];
     if (n > 0 && (!obs1 || !obs2 || !w1 || !w2 || !pos1 || !pos2 || !status)) return sv_set_error(ctx, SVGPU_ERR_INVALID, who);
     for (size_t i = 0; i < n; ++i)
-        if (!positive_finite(w1[i]) || !positive_finite(w2[i]))
+        if (!sv_positive_finite(w1[i]) || !sv_positive_finite(w2[i]))
             return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_sim3_transform_optimize: an inv_sigma_sq is not positive and finite");
     std::vector<Sim3OptProblem> prob(P);
     for (int p = 0; p < P; ++p) {
-        if (!sim3_ok(sim3_12 + 8 * (size_t)p))
+        if (!sv_sim3_ok(sim3_12 + 8 * (size_t)p))
             return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_sim3_transform_optimize: a Sim3_12 is not a Sim3 (unit quaternion, positive scale)");
         if (!fill_view(view1[view1_shared ? 0 : p], prob[p].view[0]) || !fill_view(view2[p], prob[p].view[1]))
             return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_sim3_transform_optimize: a camera model the edges do not cover");
@@ -74,25 +62,19 @@ int optimize_core(svgpu_ctx* ctx, const char* who, int num_problems, const svgpu
         prob[p].m_lo = match_off[p], prob[p].m_hi = match_off[p + 1];
     }
 
-    SV_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
     Sim3OptPieces Y{};
-    const auto layout = [&](UploadArena& A) { sim3opt_layout(A, (size_t)P, n, Y); };
-    const size_t need = arena_measure<UploadArena>(layout);
-    int rc;
-    if ((rc = sv_ensure_scratch(ctx, need))) return rc;
-    if ((rc = sv_ensure_stage(ctx, need))) return rc;
-    UploadArena A(ctx, ctx->h_stage);
-    layout(A);
-    if (A.overflow) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_sim3_transform_optimize: internal arena overflow");
-    if ((rc = A.upload(ctx, s, Y.prob, prob.data(), (size_t)P * sizeof(Sim3OptProblem)))) return rc;
-    if ((rc = A.upload(ctx, s, Y.obs1, obs1, n * 16))) return rc;
-    if ((rc = A.upload(ctx, s, Y.obs2, obs2, n * 16))) return rc;
-    if ((rc = A.upload(ctx, s, Y.w1, w1, n * 4))) return rc;
-    if ((rc = A.upload(ctx, s, Y.w2, w2, n * 4))) return rc;
-    if ((rc = A.upload(ctx, s, Y.pos1, pos1, n * 24))) return rc;
-    if ((rc = A.upload(ctx, s, Y.pos2, pos2, n * 24))) return rc;
-    if ((rc = A.flush(ctx, s))) return rc;
+    StagedCall C;
+    int rc = C.open(ctx, "svgpu_sim3_transform_optimize: internal arena overflow", [&](UploadArena& A) { sim3opt_layout(A, (size_t)P, n, Y); });
+    if (rc) return rc;
+    hipStream_t s = C.s;
+    C.up(Y.prob, (const char*)prob.data(), (size_t)P * S3O_LAYOUT_PROBLEM);
+    C.up(Y.obs1, obs1, 2 * n);
+    C.up(Y.obs2, obs2, 2 * n);
+    C.up(Y.w1, w1, n);
+    C.up(Y.w2, w2, n);
+    C.up(Y.pos1, pos1, 3 * n);
+    C.up(Y.pos2, pos2, 3 * n);
+    if ((rc = C.flush())) return rc;
 
     Sim3OptDev D{};
     D.num_problems = P, D.fix_scale = fix_scale != 0, D.num_iter = num_iter, D.chi_sq = chi_sq;
@@ -104,16 +86,11 @@ int optimize_core(svgpu_ctx* ctx, const char* who, int num_problems, const svgpu
         SvProfScope prof(ctx, s, "k_sim3_opt");
         sv_launch_sim3opt(s, D);
     }
-    SV_HIP(ctx, hipGetLastError());
-    Downloads Dl;
-    Dl.add(A, sim3_out, Y.sim3_out, (size_t)P * 64);
-    Dl.add(A, num_inliers, Y.num_inliers, (size_t)P * 4);
-    Dl.add(A, status, Y.status, n);
-    Dl.add(A, stats, Y.stats, (size_t)P * sizeof(svgpu_sim3opt_stats));
-    if ((rc = Dl.fetch(ctx, s, A))) return rc;
-    SV_HIP(ctx, hipStreamSynchronize(s));
-    Dl.scatter(A);
-    return SVGPU_OK;
+    C.down(sim3_out, Y.sim3_out, 8 * (size_t)P);
+    C.down(num_inliers, Y.num_inliers, P);
+    C.down(status, Y.status, n);
+    C.down((char*)stats, Y.stats, (size_t)P * S3O_LAYOUT_STATS);
+    return C.finish();
 }
 
 }  // namespace

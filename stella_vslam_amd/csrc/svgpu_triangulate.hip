@@ -1,11 +1,11 @@
 // svgpu_triangulate_two_views / _batch: host glue of k_triangulate_two_views (triangulate_kernels.hip).  Host arrays in and out,
 // synchronous; one upload, one launch and one read-back per call whatever the number of neighbours.
+#include <algorithm>
 #include <cmath>
 
-#include "svgpu_match_common.h"
+#include "sv_staged_call.h"
+#include "sv_validate.h"
 #include "triangulate_kernels.h"
-
-using namespace svm;
 
 namespace {
 
@@ -41,8 +41,9 @@ int tri_core(svgpu_ctx* ctx, const char* who, const svgpu_triangulate_view* v1, 
              double* pos_w, uint8_t* status, int* num_accepted) {
     if (!ctx || !v1 || K < 0 || (K > 0 && (!nb || !off)) || !scale_factors || !level_sigma_sq || num_levels < 1 || num_levels > SV_MAX_LEVELS || !view_ok(*v1))
         return sv_set_error(ctx, SVGPU_ERR_INVALID, who);
+    if (K > 0 && !sv_offsets_ok(off, K)) return sv_set_error(ctx, SVGPU_ERR_INVALID, who);
     for (int k = 0; k < K; ++k)
-        if (!view_ok(nb[k]) || off[k + 1] < off[k] || (k == 0 && off[0] != 0)) return sv_set_error(ctx, SVGPU_ERR_INVALID, who);
+        if (!view_ok(nb[k])) return sv_set_error(ctx, SVGPU_ERR_INVALID, who);
     const int M = K > 0 ? off[K] : 0;
     if (M > 0 && (!idx1 || !pos_w || !status)) return sv_set_error(ctx, SVGPU_ERR_INVALID, who);
     if (num_accepted)
@@ -67,11 +68,11 @@ int tri_core(svgpu_ctx* ctx, const char* who, const svgpu_triangulate_view* v1, 
                 return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_triangulate_two_views: stereo keypoint of an equirectangular camera");
         }
     }
-    SV_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     TriProblem P{};
     std::vector<TriView> views(K);
-    auto layout = [&](UploadArena& A) -> int {
+    StagedCall C;
+    int rc = C.open(ctx, "svgpu_triangulate_two_views: internal arena overflow", [&](UploadArena& A) -> int {
         int rc = stage_view(ctx, s, A, *v1, v1->scale_factor, P.v1);
         for (int k = 0; k < K && !rc; ++k) rc = stage_view(ctx, s, A, nb[k], v1->scale_factor, views[k]);
         P.nb = A.put(ctx, s, views.data(), K, true, rc);  // (the views carry device pointers: staged above, copied here)
@@ -83,14 +84,8 @@ int tri_core(svgpu_ctx* ctx, const char* who, const svgpu_triangulate_view* v1, 
         P.pos_w = A.take<double>((size_t)M * 3);
         P.status = A.take<uint8_t>(M);
         return rc;
-    };
-    const size_t need = arena_measure<UploadArena>(layout);
-    int rc;
-    if ((rc = sv_ensure_scratch(ctx, need))) return rc;
-    if ((rc = sv_ensure_stage(ctx, need))) return rc;
-    UploadArena A(ctx, ctx->h_stage);
-    if ((rc = layout(A))) return rc;
-    if (A.overflow) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_triangulate_two_views: internal arena overflow");
+    });
+    if (rc) return rc;
     P.num_matches = M;
     for (int l = 0; l < num_levels; ++l) P.scale_factors[l] = scale_factors[l], P.level_sigma_sq[l] = level_sigma_sq[l];
     P.cos_rays_parallax_thr = (float)std::cos(rays_parallax_deg_thr * M_PI / 180.0);  // two_view_triangulator.cc:17 (a float member)
@@ -98,13 +93,9 @@ int tri_core(svgpu_ctx* ctx, const char* who, const svgpu_triangulate_view* v1, 
         SvProfScope prof(ctx, s, "k_triangulate_two_views");
         sv_launch_triangulate_two_views(s, P);
     }
-    SV_HIP(ctx, hipGetLastError());
-    Downloads D;
-    D.add(A, pos_w, P.pos_w, (size_t)M * 24);
-    D.add(A, status, P.status, M);
-    if ((rc = D.fetch(ctx, s, A))) return rc;
-    SV_HIP(ctx, hipStreamSynchronize(s));
-    D.scatter(A);
+    C.down(pos_w, P.pos_w, 3 * (size_t)M);
+    C.down(status, P.status, M);
+    if ((rc = C.finish())) return rc;
     if (num_accepted)
         for (int m = 0; m < M; ++m) num_accepted[nb_of[m]] += status[m] == SVGPU_TRI_ACCEPTED;
     return SVGPU_OK;

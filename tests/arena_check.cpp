@@ -1,11 +1,16 @@
-// Host-only check of the scratch arena (stella_vslam_amd/csrc/sv_arena.h): built and run by tests/test_arena.py.
+// Host-only check of the scratch arena (stella_vslam_amd/csrc/sv_arena.h) and of the shared argument checks (sv_validate.h): built and run
+// by tests/test_arena.py.
 // Every layout is run on a measuring arena and on placing arenas over a host buffer (the pointers are compared, never dereferenced).
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <functional>
+#include <limits>
+#include <utility>
 #include <vector>
 
 #include "sv_arena.h"
+#include "sv_validate.h"
 
 static int failures = 0;
 #define CHECK(cond)                                                      \
@@ -56,7 +61,84 @@ static void check_layout(const char* name, const Layout& lay) {
     std::printf("ok %s: %zu bytes, %zu takes\n", name, need, got.size());
 }
 
+// the read-back ranges of Downloads::fetch: spans (offset, bytes) closer than `gap` share one copy
+struct Span {
+    size_t off, bytes;
+};
+using Spans = std::vector<Span>;
+using Ranges = std::vector<std::pair<size_t, size_t>>;
+static Ranges merged(Spans spans) { return sv_merge_ranges(spans, 32768); }
+static void check_merge_covers(const Spans& spans, const Ranges& ranges) {
+    for (size_t k = 0; k < ranges.size(); ++k) {
+        CHECK(ranges[k].first < ranges[k].second);                        // no empty range
+        if (k) CHECK(ranges[k].first > ranges[k - 1].second + 32768);     // ascending, and really further apart than the gap
+    }
+    for (const auto& sp : spans) {
+        bool inside = false;
+        for (const auto& r : ranges) inside = inside || (r.first <= sp.off && sp.off + sp.bytes <= r.second);
+        CHECK(inside);
+    }
+}
+static void check_merge() {
+    CHECK(merged({}).empty());
+    CHECK((merged({{512, 100}}) == Ranges{{512, 612}}));
+    {  // end to start exactly the gap: one copy; one byte more: two
+        const Spans near{{0, 256}, {256 + 32768, 64}}, far{{0, 256}, {256 + 32769, 64}};
+        CHECK((merged(near) == Ranges{{0, 256 + 32768 + 64}}));
+        CHECK((merged(far) == Ranges{{0, 256}, {256 + 32769, 256 + 32769 + 64}}));
+        check_merge_covers(near, merged(near));
+        check_merge_covers(far, merged(far));
+    }
+    {  // unsorted input; the spans come back sorted
+        Spans in{{200000, 16}, {0, 4}, {100000, 8}, {256, 1024}};
+        check_merge_covers(in, merged(in));
+        CHECK((sv_merge_ranges(in, 32768) == Ranges{{0, 1280}, {100000, 100008}, {200000, 200016}}));
+        CHECK(in[0].off == 0 && in[1].off == 256 && in[2].off == 100000 && in[3].off == 200000);
+    }
+    {  // a span wholly inside an earlier one: the end does not shrink
+        const Spans in{{1000, 5000}, {2000, 100}};
+        CHECK((merged(in) == Ranges{{1000, 6000}}));
+    }
+    {  // a chain: each near the one before it, the first and the last far apart
+        const Spans in{{0, 100}, {30000, 100}, {60000, 100}};
+        CHECK((merged(in) == Ranges{{0, 60100}}));
+        check_merge_covers(in, merged(in));
+    }
+}
+
+static void check_validate() {
+    {
+        const int32_t a[] = {0}, b[] = {0, 0, 3}, c[] = {1, 2}, d[] = {0, 3, 2};
+        CHECK(sv_offsets_ok(a, 0));
+        CHECK(sv_offsets_ok(b, 2));
+        CHECK(!sv_offsets_ok(c, 1));
+        CHECK(!sv_offsets_ok(d, 2));
+    }
+    const double nan = std::numeric_limits<double>::quiet_NaN(), inf = std::numeric_limits<double>::infinity();
+    CHECK(sv_positive_finite(1e-300) && !sv_positive_finite(0.0) && !sv_positive_finite(-1.0) && !sv_positive_finite(nan) && !sv_positive_finite(inf));
+    const double id[8] = {0, 0, 0, 1, 1, 2, 3, 0.5};
+    CHECK(sv_sim3_ok(id));
+    for (const double off : {0.9e-9, -0.9e-9, 1.1e-9, -1.1e-9}) {  // squared norm 1 + off (w alone carries the quaternion)
+        double p[8] = {0, 0, 0, std::sqrt(1.0 + off), 1, 2, 3, 0.5};
+        const bool inside = std::fabs(p[3] * p[3] - 1.0) <= 1e-9;
+        CHECK(inside == (std::fabs(off) < 1e-9));  // the rounding of the square root does not move the case across the bound
+        CHECK(sv_sim3_ok(p) == (std::fabs(off) < 1e-9));
+    }
+    for (const double scale : {0.0, -1.0, -0.5}) {
+        double p[8] = {0, 0, 0, 1, 1, 2, 3, scale};
+        CHECK(!sv_sim3_ok(p));
+    }
+    for (int k = 0; k < 8; ++k)
+        for (const double bad : {nan, inf}) {
+            double p[8] = {0, 0, 0, 1, 1, 2, 3, 0.5};
+            p[k] = bad;
+            CHECK(!sv_sim3_ok(p));
+        }
+}
+
 int main() {
+    check_merge();
+    check_validate();
     CHECK(pad(0) == 0 && pad(1) == 256 && pad(255) == 256 && pad(256) == 256 && pad(257) == 512);
 
     check_layout("plain", [](Arena& A, std::vector<void*>& p) {
