@@ -1108,6 +1108,25 @@ int svgpu_pose_optimize_device(svgpu_ctx* ctx, const double* pose_cw, int n, con
                                int num_trials, int num_each_iter, int reset_stop_flag_each_round, double* pose_out,
                                uint8_t* outlier_flags, int* num_valid, int* lm_iterations);
 
+/* The same for several problems over ONE frame observation -- the candidates of relocalizer::reloc_by_candidates or
+ * loop_detector::select_loop_candidate_via_Sim3 right behind svgpu_pnp_ransac_batch -- in one call: one upload, one launch (one workgroup
+ * per problem), one read-back, one synchronisation.  Problem p is the entries obs_off[p] .. obs_off[p + 1] (obs_off[0] = 0; a problem may
+ * be empty) of pos_w / uvr / inv_sigma_sq / huber_delta whose `select` byte is non-zero (select null: all of them), in entry order; the
+ * device compacts them.  is_inlier, valid and pose_cw of svgpu_pnp_ransac_batch are a valid select, active and pose_cw (match_off = obs_off
+ * when the match arrays are the same).  A problem with active[p] == 0 or fewer than 5 selected entries is skipped: num_valid 0,
+ * lm_iterations 0, pose_out = its pose_cw, flags 0.  outlier_flags holds one byte per ENTRY, 0 for an unselected one (a keypoint without a
+ * landmark).  Every problem's pose, flags, count and iteration count are bit for bit what svgpu_pose_optimize returns for its selected
+ * entries, whatever else the batch holds.  The intrinsics are the current frame's and shared.  num_problems == 0 succeeds whatever else is
+ * passed; lm_iterations may be null.  Host in/out, synchronous. */
+int svgpu_pose_optimize_batch(svgpu_ctx* ctx, int num_problems, const int32_t* obs_off,
+                              const double* pose_cw,      /* num_problems x 12 */
+                              const uint8_t* active,      /* nullable, num_problems */
+                              const double* pos_w, const float* uvr, const float* inv_sigma_sq, const float* huber_delta,
+                              const uint8_t* select,      /* nullable, one byte per entry */
+                              const double* intrinsics,   /* shared: the current (key)frame's camera, as svgpu_pose_optimize */
+                              int num_trials_robust, int num_trials, int num_each_iter, int reset_stop_flag_each_round,
+                              double* pose_out, uint8_t* outlier_flags, int32_t* num_valid, int32_t* lm_iterations);
+
 /* Global BA core (optimize/global_bundle_adjuster.cc:26-192, 279-412): the same graph over ALL keyframes (spanning root
  * fixed), ONE Levenberg-Marquardt run of problem->num_first_iter iterations with the terminate rule, optional Huber
  * (obs_huber_delta), no outlier gate (num_second_iter is ignored).  The caller applies the reference's post-conditions

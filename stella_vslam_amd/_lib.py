@@ -56,6 +56,8 @@ def lib() -> C.CDLL:
         _LIB.svgpu_sim3_transform_optimize_batch.argtypes = [vp, i32, vp, i32] + [vp] * 9 + [C.c_float, i32, i32, vp, vp, vp, vp]
         _LIB.svgpu_sim3_transform_optimize.restype = C.c_int
         _LIB.svgpu_sim3_transform_optimize.argtypes = [vp, vp, vp, i32] + [vp] * 7 + [C.c_float, i32, i32, vp, vp, vp, vp]
+        _LIB.svgpu_pose_optimize_batch.restype = C.c_int
+        _LIB.svgpu_pose_optimize_batch.argtypes = [vp, i32] + [vp] * 9 + [i32] * 4 + [vp] * 4
         _LIB.svgpu_selftest_cand_replay_form.restype = C.c_int
         _LIB.svgpu_selftest_cand_replay_form.argtypes = [i32, i32, i32, i32]
         if _LIB.svgpu_abi_version() != 1:

@@ -162,9 +162,17 @@ struct PoseOptDev {
     int* host_result;              // [0] num_valid [1] LM iterations [2] num_bad [3] observations (page-locked)
     int32_t* trk_counter_reset;    // nullable: a device word zeroed at the end (the next matcher's list allocation counter)
     unsigned long long* stamps;    // nullable (SVGPU_TRACK_STAMPS): wall_clock64 at the kernel's phase boundaries, [0] = how many
+    // ---- batch form (k_pose_opt_batch<EQ>): workgroup p optimises the selected entries bat_off[p] .. bat_off[p + 1] of pos_w / uvr /
+    //      inv_sigma_sq / huber, which it first compacts into trk_pos / trk_uvr / trk_w / trk_h (trk_kp_of: observation -> entry of the
+    //      problem).  pose_in_dev and pose_out are num_problems x 12, result num_problems x 4 ([3] = selected entries); outlier / level / robust are per entry.
+    const int32_t* bat_off;        // num_problems + 1
+    const uint8_t* bat_select;     // nullable, per entry: 0 = the entry is not part of its problem
+    const uint8_t* bat_active;     // nullable, per problem: 0 = skipped
+    uint8_t* bat_flags;            // per entry: outlier flag (0 for an unselected entry)
 };
 struct svgpu_ctx;
 void sv_pose_opt(svgpu_ctx* ctx, hipStream_t s, const PoseOptDev& P);
+void sv_pose_opt_batch(svgpu_ctx* ctx, hipStream_t s, const PoseOptDev& P, int num_problems);  // grid = problems; the launch takes an SvProfScope "k_pose_opt_batch"
 void sv_ba_linearize(svgpu_ctx* ctx, hipStream_t s, const BaDev& D, int do_prepare);
 void sv_ba_reduce(svgpu_ctx* ctx, hipStream_t s, const BaDev& D);  // Schur complement blocks + right-hand side
 void sv_ba_solve(svgpu_ctx* ctx, hipStream_t s, const BaDev& D);   // on-chip dense LL^T

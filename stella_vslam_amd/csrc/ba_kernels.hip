@@ -857,8 +857,11 @@ __device__ __forceinline__ bool po_chol6(HP H, double lambda, HP b, double* x) {
 
 // TRK: the tracked-frame chain's form (PoseOptDev::trk_*): the workgroup first applies the matcher's result to the frame's landmark ids and
 // compacts the observations (keypoint order = the order pose_optimizer_g2o.cc:88-107 adds its edges in) out of the resident landmark table.
-template <bool EQ, bool TRK = false>  // EQ false: the camera is not equirectangular (decided on the host from the intrinsics): no atan2 / asin path, fewer registers
-__global__ __launch_bounds__(PO_THREADS) void k_pose_opt(PoseOptDev P) {
+// BATCH: the form of svgpu_pose_optimize_batch (PoseOptDev::bat_*): the workgroup is problem blockIdx.x of a batch; it first compacts the selected
+// entries of its slice, in entry order, into compacted copies and then runs on those exactly as the plain form runs on its arrays.
+// The body of k_pose_opt and k_pose_opt_batch: ONE Levenberg-Marquardt implementation, inlined into either kernel.
+template <bool EQ, bool TRK, bool BATCH>  // EQ false: the camera is not equirectangular (decided on the host from the intrinsics): no atan2 / asin path, fewer registers
+__device__ __forceinline__ void po_run(PoseOptDev P) {
     extern __shared__ __attribute__((aligned(16))) double s_wred[];  // PO_THREADS / 64 transposition buffers of WRED_DOUBLES (dynamic: 81 KB)
     __shared__ double s_part[PO_THREADS / 64][32];
     __shared__ double s_red[32];
@@ -989,23 +992,95 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_opt(PoseOptDev P) {
             return;
         }
     }
-    if (tid < 12) s_T[tid] = (TRK && P.pose_in_dev) ? P.pose_in_dev[tid] : P.pose_in[tid];
+    // A field of the problem: the call's own (the kernel argument, read where it is used, as before there was a batch form), or (BATCH) that
+    // of the workgroup's slice of the batch's arrays.  PO must stay a COMPILE-TIME select on BATCH: the plain and tracked instantiations then
+    // read P.field straight from the kernel argument at every use and keep their register allocation (locals loaded once
+    // at the top, or a per-problem copy of P, cost VGPRs or scratch).
+    struct {
+        const double* pos_w;
+        const float *uvr, *inv_sigma_sq, *huber;
+        uint8_t *level, *robust, *outlier;
+        const double* pose_in_dev;
+        double* pose_out;
+        int* result;
+    } bat{};
+#define PO(field) (BATCH ? bat.field : P.field)
+    if constexpr (BATCH) {
+        const int p = blockIdx.x;
+        const int lo = P.bat_off[p], cnt = P.bat_off[p + 1] - lo;
+        uint8_t* const flags = P.bat_flags + lo;
+        bat.pose_in_dev = P.pose_in_dev + 12 * (size_t)p;
+        bat.pose_out = P.pose_out + 12 * (size_t)p;
+        bat.result = P.result + 4 * (size_t)p;
+        for (int k = tid; k < cnt; k += PO_THREADS) flags[k] = 0;  // an unselected entry is a keypoint without a landmark: never an outlier
+        n = 0;
+        if (!P.bat_active || P.bat_active[p]) {
+            // entry order = edge order: per round of PO_THREADS entries a wave ballot + popcount, the waves' counts through LDS (as the
+            // tracked form above; the counts are double-buffered, so a round costs one barrier)
+            __shared__ int s_wcnt[2][PO_THREADS / 64];
+            const int lane = tid & 63, wave = tid >> 6;
+            const uint8_t* const sel = P.bat_select ? P.bat_select + lo : nullptr;
+            for (int base = 0, par = 0; base < cnt; base += PO_THREADS, par ^= 1) {
+                const int k = base + tid;
+                const bool in = k < cnt && (!sel || sel[k]);
+                const unsigned long long b = __ballot(in);
+                if (lane == 0) s_wcnt[par][wave] = __popcll(b);
+                __syncthreads();
+                int before = 0, round_total = 0;
+#pragma unroll
+                for (int w = 0; w < PO_THREADS / 64; ++w) {
+                    const int c = s_wcnt[par][w];
+                    before += w < wave ? c : 0;
+                    round_total += c;
+                }
+                if (in) {
+                    const size_t e = (size_t)lo + k;
+                    const size_t j = (size_t)lo + n + before + __popcll(b & ((1ull << lane) - 1ull));  // j <= e: the copies never outgrow the slice
+                    P.trk_pos[3 * j] = P.pos_w[3 * e];
+                    P.trk_pos[3 * j + 1] = P.pos_w[3 * e + 1];
+                    P.trk_pos[3 * j + 2] = P.pos_w[3 * e + 2];
+                    P.trk_uvr[3 * j] = P.uvr[3 * e];
+                    P.trk_uvr[3 * j + 1] = P.uvr[3 * e + 1];
+                    P.trk_uvr[3 * j + 2] = P.uvr[3 * e + 2];
+                    P.trk_w[j] = P.inv_sigma_sq[e];
+                    P.trk_h[j] = P.huber[e];
+                    P.trk_kp_of[j] = k;
+                }
+                n += round_total;
+            }
+            n = __builtin_amdgcn_readfirstlane(n);  // (the same in every thread)
+        }
+        if (n < 5) {  // inactive, or pose_optimizer_g2o.cc:109-111: the pose is returned as it came.  The whole workgroup leaves here.
+            if (tid < 12) bat.pose_out[tid] = bat.pose_in_dev[tid];
+            if (tid == 0) bat.result[0] = 0, bat.result[1] = 0, bat.result[2] = 0, bat.result[3] = n;
+            return;
+        }
+        bat.pos_w = P.trk_pos + 3 * (size_t)lo;
+        bat.uvr = P.trk_uvr + 3 * (size_t)lo;
+        bat.inv_sigma_sq = P.trk_w + lo;
+        bat.huber = P.trk_h + lo;
+        bat.level = P.level + lo;
+        bat.robust = P.robust + lo;
+        bat.outlier = P.outlier + lo;
+        __syncthreads();  // the compacted copies are read by other threads than the ones that wrote them
+    }
+    if (tid < 12) s_T[tid] = ((TRK || BATCH) && PO(pose_in_dev)) ? PO(pose_in_dev)[tid] : P.pose_in[tid];
     for (int i = tid; i < n; i += PO_THREADS) {
-        P.level[i] = 0;
-        P.robust[i] = (P.num_trials_robust != 0) && P.huber[i] > 0.f;
-        P.outlier[i] = 0;
+        PO(level)[i] = 0;
+        PO(robust)[i] = (P.num_trials_robust != 0) && PO(huber)[i] > 0.f;
+        PO(outlier)[i] = 0;
     }
     __syncthreads();
     auto chi_at = [&](int i, const double* T, double* r, double* pc) {
-        cam_point(T, P.pos_w + (size_t)i * 3, pc);
+        cam_point(T, PO(pos_w) + (size_t)i * 3, pc);
         double u = P.intr[0] * pc[0] / pc[2] + P.intr[2], v = P.intr[1] * pc[1] / pc[2] + P.intr[3];
         const bool eq = EQ && cam_is_equirect(P.intr);
         if (eq) equirect_project(P.intr, pc, &u, &v);
-        const float* o = P.uvr + (size_t)i * 3;
+        const float* o = PO(uvr) + (size_t)i * 3;
         r[0] = (double)o[0] - u;
         r[1] = (double)o[1] - v;
         r[2] = (o[2] < 0.f || eq) ? 0.0 : (double)o[2] - (u - P.intr[4] / pc[2]);
-        return (r[0] * r[0] + r[1] * r[1] + r[2] * r[2]) * (double)P.inv_sigma_sq[i];
+        return (r[0] * r[0] + r[1] * r[1] + r[2] * r[2]) * (double)PO(inv_sigma_sq)[i];
     };
     bool flag = false;      // the terminate action's own stop flag (no caller flag exists in this path)
     double last_chi = 0.0;  // terminate_action::_lastChi persists across optimize() calls
@@ -1020,12 +1095,12 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_opt(PoseOptDev P) {
             double acc[29];
             for (int k = 0; k < 29; ++k) acc[k] = 0.0;
             for (int i = tid; i < n; i += PO_THREADS) {
-                if (P.level[i]) continue;
+                if (PO(level)[i]) continue;
                 double r[3], pc[3];
                 const double chi = chi_at(i, s_T, r, pc);
                 const double x = pc[0], y = pc[1], z = pc[2], z_sq = z * z, fx = P.intr[0], fy = P.intr[1], fxb = P.intr[4];
                 const bool eq = EQ && cam_is_equirect(P.intr);
-                const bool stereo = !(P.uvr[(size_t)i * 3 + 2] < 0.f) && !eq;
+                const bool stereo = !(PO(uvr)[(size_t)i * 3 + 2] < 0.f) && !eq;
                 double J[18];
                 J[0] = x * y / z_sq * fx;
                 J[1] = -(1.0 + (x * x / z_sq)) * fx;
@@ -1047,8 +1122,8 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_opt(PoseOptDev P) {
                 J[17] = stereo ? J[5] - fxb / z_sq : 0.0;
                 if (eq) equirect_jacobians(P.intr, pc, nullptr, nullptr, J);  // equirectangular_pose_opt_edge.h:70-118 (rows 0, 1)
                 double rho0 = chi, rho1 = 1.0;
-                if (P.robust[i]) huber(chi, (double)P.huber[i], &rho0, &rho1);
-                const double w = (double)P.inv_sigma_sq[i] * rho1;
+                if (PO(robust)[i]) huber(chi, (double)PO(huber)[i], &rho0, &rho1);
+                const double w = (double)PO(inv_sigma_sq)[i] * rho1;
                 int k = 0;
                 for (int a = 0; a < 6; ++a)
                     for (int c = a; c < 6; ++c) {
@@ -1093,11 +1168,11 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_opt(PoseOptDev P) {
                 stamp();
                 double tmp[1] = {0.0};
                 for (int i = tid; i < n; i += PO_THREADS) {
-                    if (P.level[i]) continue;
+                    if (PO(level)[i]) continue;
                     double r[3], pc[3];
                     const double chi = chi_at(i, s_Tt, r, pc);
                     double rho0 = chi, rho1 = 1.0;
-                    if (P.robust[i]) huber(chi, (double)P.huber[i], &rho0, &rho1);
+                    if (PO(robust)[i]) huber(chi, (double)PO(huber)[i], &rho0, &rho1);
                     tmp[0] += rho0;
                 }
                 po_reduce<1>(tmp, s_wred, s_part, s_red);
@@ -1141,12 +1216,12 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_opt(PoseOptDev P) {
             for (int i = tid; i < n; i += PO_THREADS) {
                 double r[3], pc[3];
                 const double chi = chi_at(i, s_T, r, pc);
-                const double thr = P.uvr[(size_t)i * 3 + 2] < 0.f ? (double)5.99146f : (double)7.81473f;
+                const double thr = PO(uvr)[(size_t)i * 3 + 2] < 0.f ? (double)5.99146f : (double)7.81473f;
                 const bool out = thr < chi;
-                P.outlier[i] = out;
-                P.level[i] = out;
+                PO(outlier)[i] = out;
+                PO(level)[i] = out;
                 bad[0] += out;
-                if (P.num_trials != 0 && trial + 1 == P.num_trials_robust) P.robust[i] = 0;
+                if (P.num_trials != 0 && trial + 1 == P.num_trials_robust) PO(robust)[i] = 0;
             }
             po_reduce<1>(bad, s_wred, s_part, s_red);
             stamp();
@@ -1155,22 +1230,22 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_opt(PoseOptDev P) {
             iters_at_classification = total_iters;
         }
         else if (P.num_trials != 0 && trial + 1 == P.num_trials_robust) {
-            for (int i = tid; i < n; i += PO_THREADS) P.robust[i] = 0;
+            for (int i = tid; i < n; i += PO_THREADS) PO(robust)[i] = 0;
             __syncthreads();
         }
         if (n - num_bad < 5) break;
     }
-    if (tid < 12) P.pose_out[tid] = s_T[tid];
+    if (tid < 12) PO(pose_out)[tid] = s_T[tid];
     if (tid == 0) {
-        P.result[0] = n - num_bad;
-        P.result[1] = total_iters;
-        P.result[2] = num_bad;
+        PO(result)[0] = n - num_bad;
+        PO(result)[1] = total_iters;
+        PO(result)[2] = num_bad;
     }
     if constexpr (TRK) {  // results where the host reads them after the chain's one synchronisation: outlier flags per KEYPOINT, pose, counts
         (void)trk_nt;
         for (int i = tid; i < n; i += PO_THREADS) {
             const int k = P.trk_kp_of[i];
-            const uint8_t o = P.outlier[i];
+            const uint8_t o = PO(outlier)[i];
             P.trk_outlier_kp[k] = o;
             if (o) P.host_outlier_kp[k] = 1;
         }
@@ -1181,6 +1256,23 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_opt(PoseOptDev P) {
             if (P.trk_counter_reset) *P.trk_counter_reset = 0;
         }
     }
+    if constexpr (BATCH) {  // flags per ENTRY (every thread scatters the observations it classified itself)
+        const int lo = P.bat_off[blockIdx.x];
+        for (int i = tid; i < n; i += PO_THREADS) P.bat_flags[lo + P.trk_kp_of[lo + i]] = PO(outlier)[i];
+        if (tid == 0) bat.result[3] = n;  // selected entries
+    }
+}
+#undef PO
+template <bool EQ, bool TRK = false>
+__global__ __launch_bounds__(PO_THREADS) void k_pose_opt(PoseOptDev P) {
+    po_run<EQ, TRK, false>(P);
+}
+// One persistent workgroup per problem of a batch (grid = problems).  The 81 KB of reduction buffers leave room for one workgroup per CU:
+// a batch of more problems than the device has CUs simply queues.  Workgroups share nothing: no atomics on global memory, no
+// dependence between them, and a skipped problem's workgroup writes its defaults and leaves as a whole.
+template <bool EQ>
+__global__ __launch_bounds__(PO_THREADS) void k_pose_opt_batch(PoseOptDev P) {
+    po_run<EQ, false, true>(P);
 }
 
 // ================================================================================================ fused trial pipeline
@@ -2517,6 +2609,15 @@ void sv_pose_opt(svgpu_ctx* ctx, hipStream_t s, const PoseOptDev& P) {
     }
     else if (eq) hipLaunchKernelGGL((k_pose_opt<true, false>), dim3(1), dim3(PO_THREADS), lds, s, P);
     else hipLaunchKernelGGL((k_pose_opt<false, false>), dim3(1), dim3(PO_THREADS), lds, s, P);
+}
+
+void sv_pose_opt_batch(svgpu_ctx* ctx, hipStream_t s, const PoseOptDev& P, int num_problems) {
+    SvProfScope ps(ctx, s, "k_pose_opt_batch");
+    const size_t lds = sizeof(double) * (PO_THREADS / 64) * WRED_DOUBLES;
+    const bool eq = P.intr[0] == 0.0 && P.intr[1] == 0.0;  // cam_is_equirect
+    (void)sv_allow_dynamic_lds(eq ? (const void*)k_pose_opt_batch<true> : (const void*)k_pose_opt_batch<false>, lds);
+    if (eq) hipLaunchKernelGGL((k_pose_opt_batch<true>), dim3(num_problems), dim3(PO_THREADS), lds, s, P);
+    else hipLaunchKernelGGL((k_pose_opt_batch<false>), dim3(num_problems), dim3(PO_THREADS), lds, s, P);
 }
 
 void sv_ba_zero_inactive(hipStream_t s, const BaDev& D) {

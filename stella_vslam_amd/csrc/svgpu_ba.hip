@@ -16,6 +16,9 @@
 
 #include "svgpu_internal.h"
 #include "ba_kernels.h"
+#include "poseopt_batch_layout.h"
+#include "sv_staged_call.h"
+#include "sv_validate.h"
 
 void sv_ba_maxdiag(hipStream_t s, const BaDev& D);
 void sv_ba_maxslot(hipStream_t s, const BaDev& D);
@@ -1537,6 +1540,63 @@ int svgpu_pose_optimize_device(svgpu_ctx* ctx, const double* pose_cw, int n, con
     P.pos_w = pos_w_dev, P.uvr = uvr_dev, P.inv_sigma_sq = inv_sigma_sq_dev, P.huber = huber_delta_dev;
     return pose_optimize_run(ctx, P, Y, pose_cw, n, intrinsics, num_trials_robust, num_trials, num_each_iter, reset_stop_flag_each_round, ctx->h_stage, pose_out,
                              outlier_flags, num_valid, lm_iterations);
+}
+
+// Several problems over one frame observation (the candidates of a relocalisation or a loop validation), one workgroup each: one upload,
+// one launch, one read-back and one synchronisation per call, whatever the batch size.
+int svgpu_pose_optimize_batch(svgpu_ctx* ctx, int num_problems, const int32_t* obs_off, const double* pose_cw, const uint8_t* active,
+                              const double* pos_w, const float* uvr, const float* inv_sigma_sq, const float* huber_delta, const uint8_t* select,
+                              const double* intrinsics, int num_trials_robust, int num_trials, int num_each_iter, int reset_stop_flag_each_round,
+                              double* pose_out, uint8_t* outlier_flags, int32_t* num_valid, int32_t* lm_iterations) {
+    const char* const bad = "svgpu_pose_optimize_batch: bad arguments";
+    if (!ctx || num_problems < 0) return sv_set_error(ctx, SVGPU_ERR_INVALID, bad);
+    if (num_problems == 0) return SVGPU_OK;
+    // ---- validation: nothing is launched before all of it has passed
+    if (!obs_off || !pose_cw || !pose_out || !num_valid || num_trials_robust < 0 || num_trials < 0 || num_each_iter < 0)
+        return sv_set_error(ctx, SVGPU_ERR_INVALID, bad);
+    const size_t P = (size_t)num_problems;
+    if (!sv_offsets_ok(obs_off, num_problems)) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_pose_optimize_batch: obs_off does not start at 0 or is not monotone");
+    const size_t n = (size_t)obs_off[P];
+    if (n > 0 && (!pos_w || !uvr || !inv_sigma_sq || !huber_delta || !intrinsics || !outlier_flags)) return sv_set_error(ctx, SVGPU_ERR_INVALID, bad);
+
+    PoseOptBatchPieces Y{};
+    StagedCall C;
+    int rc = C.open(ctx, "svgpu_pose_optimize_batch: internal arena overflow", [&](UploadArena& A) { poseopt_batch_layout(A, P, n, Y); });
+    if (rc) return rc;
+    C.up(Y.obs_off, obs_off, P + 1);
+    C.up(Y.pose_in, pose_cw, 12 * P);
+    C.up(Y.active, active, P);
+    C.up(Y.pos_w, pos_w, 3 * n);
+    C.up(Y.uvr, uvr, 3 * n);
+    C.up(Y.w, inv_sigma_sq, n);
+    C.up(Y.huber, huber_delta, n);
+    C.up(Y.select, select, n);
+    if ((rc = C.flush())) return rc;
+
+    PoseOptDev D;
+    memset(&D, 0, sizeof(D));
+    if (intrinsics) memcpy(D.intr, intrinsics, sizeof(double) * 5);
+    else D.intr[0] = D.intr[1] = 1.0;  // (no entry at all: every problem is skipped)
+    D.num_trials_robust = num_trials_robust, D.num_trials = num_trials, D.num_each_iter = num_each_iter;
+    D.reset_flag_each_round = reset_stop_flag_each_round;
+    D.gain_thr = 1e-3;  // terminateAction->setGainThreshold(1e-3), pose_optimizer_g2o.cc:55
+    D.pos_w = Y.pos_w, D.uvr = Y.uvr, D.inv_sigma_sq = Y.w, D.huber = Y.huber;
+    D.trk_pos = Y.c_pos, D.trk_uvr = Y.c_uvr, D.trk_w = Y.c_w, D.trk_h = Y.c_huber, D.trk_kp_of = Y.entry_of;
+    D.level = Y.level, D.robust = Y.robust, D.outlier = Y.outlier;
+    D.pose_in_dev = Y.pose_in, D.pose_out = Y.pose_out, D.result = Y.result;
+    D.bat_off = Y.obs_off, D.bat_select = select ? Y.select : nullptr, D.bat_active = active ? Y.active : nullptr, D.bat_flags = Y.flags;
+    sv_pose_opt_batch(ctx, C.s, D, num_problems);
+
+    std::vector<int32_t> result(4 * P);
+    C.down(pose_out, Y.pose_out, 12 * P);
+    C.down(result.data(), Y.result, 4 * P);
+    C.down(outlier_flags, Y.flags, n);
+    if ((rc = C.finish())) return rc;
+    for (size_t p = 0; p < P; ++p) {
+        num_valid[p] = result[4 * p];
+        if (lm_iterations) lm_iterations[p] = result[4 * p + 1];
+    }
+    return SVGPU_OK;
 }
 
 int svgpu_global_ba(svgpu_ctx* ctx, const svgpu_ba_problem* problem, volatile uint8_t* stop, double* pose_out, double* points_out,

@@ -49,6 +49,15 @@ public:
     unsigned int optimize(const data::keyframe* keyfrm, Mat44_t& optimized_pose, std::vector<bool>& outlier_flags) const override;
     unsigned int optimize(const Mat44_t& cam_pose_cw, const data::frame_observation& frm_obs, const feature::orb_params* orb_params, const camera::base* camera,
                           const std::vector<std::shared_ptr<data::landmark>>& landmarks, Mat44_t& optimized_pose, std::vector<bool>& outlier_flags) const override;
+    //! The third overload for several landmark assignments of ONE frame observation -- the candidates of relocalizer::reloc_by_candidates or
+    //! loop_detector::select_loop_candidate_via_Sim3, each with the pose its PnP gave: the gather runs per candidate, then ONE
+    //! svgpu_pose_optimize_batch call (one launch, one workgroup per candidate).  Returns the valid-observation count per candidate; every
+    //! output equals what the single overload gives for that candidate (an optimized_poses entry of a candidate with fewer than 5
+    //! observations is left as it was passed).  last_lm_iterations_ becomes the sum over the candidates.
+    std::vector<unsigned int> optimize_batch(const std::vector<Mat44_t>& cam_poses_cw, const data::frame_observation& frm_obs,
+                                             const feature::orb_params* orb_params, const camera::base* camera,
+                                             const std::vector<std::vector<std::shared_ptr<data::landmark>>>& landmarks_per_candidate,
+                                             std::vector<Mat44_t>& optimized_poses, std::vector<std::vector<bool>>& outlier_flags) const;
     //! Levenberg-Marquardt iterations of the last call, all rounds (diagnostics; the reference logs nothing here)
     mutable int last_lm_iterations_ = 0;
     //! 0 = g2o's literal behaviour: the stop flag the gain rule raised keeps suppressing the later rounds (svgpu.h, svgpu_pose_optimize)

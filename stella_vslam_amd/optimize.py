@@ -173,6 +173,30 @@ class pose_optimizer:
                                                  p(outl), C.byref(nv), C.byref(it)), "svgpu_pose_optimize")
         return nv.value, out, outl[:n].copy(), it.value
 
+    def optimize_batch_flat(self, poses_cw, obs_off, pos_w, uvr, inv_sigma_sq, huber, intr, select=None, active=None):
+        """Several problems over one frame observation in one device call (svgpu_pose_optimize_batch): problem p is the entries
+        obs_off[p] .. obs_off[p + 1] of the per-entry arrays whose `select` byte is non-zero (None: all), skipped when active[p] == 0 or
+        fewer than 5 are selected.  Returns (num_valid[P], pose[P, 12], outlier[total], lm_iterations[P])."""
+        off = np.ascontiguousarray(obs_off, np.int32).reshape(-1)
+        P = len(off) - 1
+        pose = np.ascontiguousarray(poses_cw, np.float64).reshape(-1, 12)
+        pw, uv = np.ascontiguousarray(pos_w, np.float64).reshape(-1, 3), np.ascontiguousarray(uvr, np.float32).reshape(-1, 3)
+        w, hb = np.ascontiguousarray(inv_sigma_sq, np.float32).reshape(-1), np.ascontiguousarray(huber, np.float32).reshape(-1)
+        K = np.ascontiguousarray(intr, np.float64).reshape(5)
+        sel = None if select is None else np.ascontiguousarray(select, np.uint8).reshape(-1)
+        act = None if active is None else np.ascontiguousarray(active, np.uint8).reshape(-1)
+        n = len(pw)
+        if (P < 0 or len(pose) != P or any(len(a) != n for a in (uv, w, hb)) or (sel is not None and len(sel) != n)
+                or (act is not None and len(act) != P) or (P > 0 and off[-1] != n)):
+            raise ValueError("optimize_batch_flat: array lengths disagree")
+        out, outl = np.zeros((max(P, 1), 12)), np.zeros(max(n, 1), np.uint8)
+        nv, it = np.zeros(max(P, 1), np.int32), np.zeros(max(P, 1), np.int32)
+        self.ctx.check(lib().svgpu_pose_optimize_batch(self.ctx.handle, P, _vp(off), _vp(pose), _vp(act), _vp(pw), _vp(uv), _vp(w), _vp(hb), _vp(sel), _vp(K),
+                                                       self.num_trials_robust_, self.num_trials_, self.num_each_iter_,
+                                                       int(self.reset_stop_flag_each_round_), _vp(out), _vp(outl), _vp(nv), _vp(it)),
+                       "svgpu_pose_optimize_batch")
+        return nv[:P].copy(), out[:P].copy(), outl[:n].copy(), it[:P].copy()
+
     def optimize_device(self, pose_cw, n: int, pos_w_dev, uvr_dev, inv_sigma_sq_dev, huber_dev, intr):
         """Same with the observation arrays already on the device (torch tensors or raw device addresses)."""
         pose = np.ascontiguousarray(pose_cw, np.float64).reshape(12)
