@@ -5,7 +5,7 @@
 // bow_feat_vec maps is the host adaptor's (they are std::map in the reference).
 // 8 lanes per descriptor: lane j holds dword j of the descriptor and reads dword j of every child (one coalesced 32-byte
 // row per child), distances are summed with three xor-shuffles; the upper tree levels are shared by all descriptors and live in L2.
-#include "svgpu_internal.h"
+#include "sv_staged_call.h"
 
 struct svgpu_vocabulary {
     int device;
@@ -179,20 +179,20 @@ static int bow_transform_impl(svgpu_ctx* ctx, const svgpu_vocabulary* vocab, con
     if (!ctx || !vocab || n < 0 || vocab->device != ctx->device || (n > 0 && (!desc || !word_id || !weight || !node_id)))
         return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_bow_transform: bad arguments");
     if (n == 0) return SVGPU_OK;
-    SV_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
     uint32_t* d_desc;
     int32_t *d_word, *d_node;
     float* d_w;
-    auto layout = [&](Arena& A) {
+    StagedCall C;
+    int rc = C.open(ctx, "svgpu_bow_transform: internal arena overflow", [&](UploadArena& A) {
         d_desc = A.take<uint32_t>((size_t)n * 8);
         d_word = A.take<int32_t>(n);
         d_w = A.take<float>(n);
         d_node = A.take<int32_t>(n);
-    };
-    int rc = sv_scratch_layout(ctx, "svgpu_bow_transform: internal arena overflow", layout);
+    });
     if (rc) return rc;
-    SV_HIP(ctx, hipMemcpyAsync(d_desc, desc, (size_t)n * 32, hipMemcpyHostToDevice, s));
+    hipStream_t s = C.s;
+    C.up(d_desc, (const uint32_t*)desc, (size_t)n * 8);
+    if ((rc = C.flush())) return rc;
     if (fbow_k > 0) {
         int nbits = 0;
         while ((1 << nbits) < fbow_k) ++nbits;
@@ -202,12 +202,10 @@ static int bow_transform_impl(svgpu_ctx* ctx, const svgpu_vocabulary* vocab, con
     else
         hipLaunchKernelGGL(k_bow_descend, dim3(((size_t)n * 8 + 255) / 256), dim3(256), 0, s, n, d_desc, vocab->child_off, vocab->children, vocab->node_desc,
                            vocab->node_weight, vocab->word_id, node_level, d_word, d_w, d_node);
-    SV_HIP(ctx, hipGetLastError());
-    SV_HIP(ctx, hipMemcpyAsync(word_id, d_word, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-    SV_HIP(ctx, hipMemcpyAsync(weight, d_w, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-    SV_HIP(ctx, hipMemcpyAsync(node_id, d_node, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-    SV_HIP(ctx, hipStreamSynchronize(s));
-    return SVGPU_OK;
+    C.down(word_id, d_word, n);
+    C.down(weight, d_w, n);
+    C.down(node_id, d_node, n);
+    return C.finish();
 }
 
 }  // extern "C"

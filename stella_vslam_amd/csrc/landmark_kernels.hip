@@ -8,7 +8,7 @@
 // counted by recomputing the row (8 xor + 8 popcount per entry, descriptors stay in L2) gives the element at sorted index
 // floor(0.5 (k-1)) exactly.  A second thread-per-landmark pass takes the first row with the smallest median (the reference's
 // strict "<" scan) and does the fp64 geometry in the reference's operation order.
-#include "svgpu_internal.h"
+#include "sv_staged_call.h"
 
 namespace {
 
@@ -111,30 +111,29 @@ int svgpu_landmarks_compute_descriptor(svgpu_ctx* ctx, int n, const int32_t* obs
     if (rc || n == 0) return rc;
     if (!obs_desc || !best_obs || !descriptor) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_landmarks_compute_descriptor: null pointer");
     const int total = obs_off[n];
-    SV_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
     int32_t *d_off, *d_owner, *d_best;
     uint4 *d_desc, *d_out;
     uint16_t* d_med;
-    auto layout = [&](Arena& A) {
+    StagedCall C;
+    rc = C.open(ctx, "svgpu_landmarks_compute_descriptor: internal arena overflow", [&](UploadArena& A) {
         d_off = A.take<int32_t>(n + 1);
         d_desc = A.take<uint4>((size_t)total * 2);
         d_owner = A.take<int32_t>(total);
         d_med = A.take<uint16_t>(total);
         d_best = A.take<int32_t>(n);
         d_out = A.take<uint4>((size_t)n * 2);
-    };
-    if ((rc = sv_scratch_layout(ctx, "svgpu_landmarks_compute_descriptor: internal arena overflow", layout))) return rc;
-    SV_HIP(ctx, hipMemcpyAsync(d_off, obs_off, (size_t)(n + 1) * 4, hipMemcpyHostToDevice, s));
-    SV_HIP(ctx, hipMemcpyAsync(d_desc, obs_desc, (size_t)total * 32, hipMemcpyHostToDevice, s));
+    });
+    if (rc) return rc;
+    hipStream_t s = C.s;
+    C.up(d_off, obs_off, (size_t)n + 1);
+    C.up(d_desc, (const uint4*)obs_desc, (size_t)total * 2);
+    if ((rc = C.flush())) return rc;
     hipLaunchKernelGGL(k_lm_owner, dim3((n + 255) / 256), dim3(256), 0, s, n, d_off, d_owner);
     hipLaunchKernelGGL(k_lm_median, dim3((total + 255) / 256), dim3(256), 0, s, total, d_off, d_owner, d_desc, d_med);
     hipLaunchKernelGGL(k_lm_pick, dim3((n + 255) / 256), dim3(256), 0, s, n, d_off, d_med, d_desc, d_best, d_out);
-    SV_HIP(ctx, hipGetLastError());
-    SV_HIP(ctx, hipMemcpyAsync(best_obs, d_best, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-    SV_HIP(ctx, hipMemcpyAsync(descriptor, d_out, (size_t)n * 32, hipMemcpyDeviceToHost, s));
-    SV_HIP(ctx, hipStreamSynchronize(s));
-    return SVGPU_OK;
+    C.down(best_obs, d_best, n);
+    C.down((uint4*)descriptor, d_out, (size_t)n * 2);
+    return C.finish();
 }
 
 int svgpu_landmarks_update_geometry(svgpu_ctx* ctx, int n, const int32_t* obs_off, const double* obs_trans_wc, const double* pos_w,
@@ -145,34 +144,32 @@ int svgpu_landmarks_update_geometry(svgpu_ctx* ctx, int n, const int32_t* obs_of
     const int total = obs_off[n];
     if ((total > 0 && !obs_trans_wc) || !pos_w || !ref_trans_wc || !ref_scale_factor || !mean_normal || !max_valid_dist || !min_valid_dist)
         return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_landmarks_update_geometry: null pointer");
-    SV_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
     int32_t* d_off;
     double *d_c, *d_p, *d_r, *d_m;
     float *d_sf, *d_mx, *d_mn;
-    auto layout = [&](Arena& A) {
-        d_off = A.take<int32_t>(n + 1);
+    StagedCall C;
+    rc = C.open(ctx, "svgpu_landmarks_update_geometry: internal arena overflow", [&](UploadArena& A) {
+        d_off = A.take<int32_t>(n + 1);  // the five inputs first: one contiguous upload
         d_c = A.take<double>((size_t)total * 3 + 1);
         d_p = A.take<double>((size_t)n * 3);
         d_r = A.take<double>((size_t)n * 3);
-        d_m = A.take<double>((size_t)n * 3);
         d_sf = A.take<float>(n);
+        d_m = A.take<double>((size_t)n * 3);
         d_mx = A.take<float>(n);
         d_mn = A.take<float>(n);
-    };
-    if ((rc = sv_scratch_layout(ctx, "svgpu_landmarks_update_geometry: internal arena overflow", layout))) return rc;
-    SV_HIP(ctx, hipMemcpyAsync(d_off, obs_off, (size_t)(n + 1) * 4, hipMemcpyHostToDevice, s));
-    if (total > 0) SV_HIP(ctx, hipMemcpyAsync(d_c, obs_trans_wc, (size_t)total * 24, hipMemcpyHostToDevice, s));
-    SV_HIP(ctx, hipMemcpyAsync(d_p, pos_w, (size_t)n * 24, hipMemcpyHostToDevice, s));
-    SV_HIP(ctx, hipMemcpyAsync(d_r, ref_trans_wc, (size_t)n * 24, hipMemcpyHostToDevice, s));
-    SV_HIP(ctx, hipMemcpyAsync(d_sf, ref_scale_factor, (size_t)n * 4, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_lm_geometry, dim3((n + 255) / 256), dim3(256), 0, s, n, d_off, d_c, d_p, d_r, d_sf, inv_scale_factor_last, d_m, d_mx, d_mn);
-    SV_HIP(ctx, hipGetLastError());
-    SV_HIP(ctx, hipMemcpyAsync(mean_normal, d_m, (size_t)n * 24, hipMemcpyDeviceToHost, s));
-    SV_HIP(ctx, hipMemcpyAsync(max_valid_dist, d_mx, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-    SV_HIP(ctx, hipMemcpyAsync(min_valid_dist, d_mn, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-    SV_HIP(ctx, hipStreamSynchronize(s));
-    return SVGPU_OK;
+    });
+    if (rc) return rc;
+    C.up(d_off, obs_off, (size_t)n + 1);
+    C.up(d_c, obs_trans_wc, (size_t)total * 3);
+    C.up(d_p, pos_w, (size_t)n * 3);
+    C.up(d_r, ref_trans_wc, (size_t)n * 3);
+    C.up(d_sf, ref_scale_factor, n);
+    if ((rc = C.flush())) return rc;
+    hipLaunchKernelGGL(k_lm_geometry, dim3((n + 255) / 256), dim3(256), 0, C.s, n, d_off, d_c, d_p, d_r, d_sf, inv_scale_factor_last, d_m, d_mx, d_mn);
+    C.down(mean_normal, d_m, (size_t)n * 3);
+    C.down(max_valid_dist, d_mx, n);
+    C.down(min_valid_dist, d_mn, n);
+    return C.finish();
 }
 
 }  // extern "C"

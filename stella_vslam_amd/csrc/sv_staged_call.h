@@ -49,15 +49,20 @@ struct UploadArena : Arena {
 
 // Batched read-backs, the counterpart of UploadArena::upload: results that live in the arena are requested with add(), fetch() copies the
 // range(s) that cover them into the page-locked mirror (requests closer than 32 KB share one copy: sv_merge_ranges), and after the stream
-// has been synchronised scatter() hands them to the caller's arrays.
+// has been synchronised scatter() hands them to the caller's arrays (an item without a destination stays in the mirror).
 struct Downloads {
     struct Item {
         void* dst;
         size_t off, bytes;
     };
     std::vector<Item> items;
+    // an optional output the caller did not ask for (no destination) is no request ...
     void add(const UploadArena& A, void* dst, const void* src, size_t bytes) {
-        if (dst && bytes) items.push_back({dst, (size_t)((const char*)src - A.base), bytes});
+        if (dst) keep(A, src, bytes, dst);
+    }
+    // ... while keep() fetches into the mirror whether or not scatter() has somewhere to hand the bytes
+    void keep(const UploadArena& A, const void* src, size_t bytes, void* dst = nullptr) {
+        if (bytes) items.push_back({dst, (size_t)((const char*)src - A.base), bytes});
     }
     int fetch(svgpu_ctx* ctx, hipStream_t s, const UploadArena& A) {
         for (const auto& [lo, hi] : sv_merge_ranges(items, 32768))
@@ -65,7 +70,8 @@ struct Downloads {
         return SVGPU_OK;
     }
     void scatter(const UploadArena& A) const {
-        for (const Item& it : items) memcpy(it.dst, A.mirror + it.off, it.bytes);
+        for (const Item& it : items)
+            if (it.dst) memcpy(it.dst, A.mirror + it.off, it.bytes);
     }
 };
 
@@ -116,6 +122,11 @@ struct StagedCall {
     template <class T>
     void down(T* dst, const T* src, size_t count) {
         D.add(A, dst, src, count * sizeof(T));
+    }
+    // a result wanted in the mirror only: after finish() the caller reads it at host(src)
+    template <class T>
+    void keep(const T* src, size_t count) {
+        D.keep(A, src, count * sizeof(T));
     }
     int finish() {
         SV_HIP(ctx, hipGetLastError());

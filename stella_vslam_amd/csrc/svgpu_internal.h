@@ -157,7 +157,7 @@ struct svgpu_ctx {
     void* d_scratch = nullptr;
     double* h_pinned = nullptr;     // page-locked read-back buffer of the BA loops (small per-trial partial sums)
     size_t pinned_doubles = 0;
-    char* h_stage = nullptr;        // page-locked staging of the BA entry points: inputs are written here in device layout, one copy each way
+    char* h_stage = nullptr;        // page-locked mirror of d_scratch (StagedCall, sv_staged_call.h; BA's own images): inputs are written here in device layout, one copy each way
     size_t stage_bytes = 0;
     size_t scratch_bytes = 0;
     // bundle adjustment

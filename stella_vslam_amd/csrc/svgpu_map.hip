@@ -5,7 +5,7 @@
 // the mutators of data::landmark keep it current through svgpu_map_upsert / svgpu_map_erase.
 #include <algorithm>
 
-#include "svgpu_internal.h"
+#include "sv_staged_call.h"
 
 static_assert(sizeof(svgpu_landmark_record) == 96, "svgpu_landmark_record is a 96-byte record");
 
@@ -67,6 +67,30 @@ int map_grow(svgpu_ctx* ctx, svgpu_map* m, int need) {
     m->rec = fresh;
     m->cap = (int)cap;
     return SVGPU_OK;
+}
+// the page-locked image of an upsert: ids | records, with repeated ids collapsed to their LAST entry (the scatter is unordered); returns the
+// number of entries written
+int map_collapse(int n, const uint32_t* ids, const svgpu_landmark_record* records, uint32_t* h_ids, svgpu_landmark_record* h_rec) {
+    bool repeat = false;
+    if (n > 1) {
+        std::vector<uint32_t> sorted(ids, ids + n);
+        std::sort(sorted.begin(), sorted.end());
+        for (int i = 1; i < n && !repeat; ++i) repeat = sorted[i] == sorted[i - 1];
+    }
+    if (!repeat) {
+        memcpy(h_ids, ids, (size_t)n * 4);
+        memcpy(h_rec, records, (size_t)n * sizeof(svgpu_landmark_record));
+        return n;
+    }
+    std::map<uint32_t, int> where;
+    for (int i = 0; i < n; ++i) where[ids[i]] = i;
+    int kept = 0;
+    for (const auto& kv : where) {
+        h_ids[kept] = kv.first;
+        h_rec[kept] = records[kv.second];
+        ++kept;
+    }
+    return kept;
 }
 }  // namespace
 
@@ -143,46 +167,25 @@ int svgpu_map_upsert(svgpu_ctx* ctx, svgpu_map* m, int n, const uint32_t* ids, c
     std::lock_guard<std::mutex> lock(m->mtx);
     int rc = map_grow(ctx, m, (int)max_id + 1);
     if (rc) return rc;
-    // page-locked image: ids | records, with repeated ids collapsed to their LAST entry (the scatter is unordered)
-    const size_t o_rec = pad((size_t)n * 4), total = o_rec + (size_t)n * sizeof(svgpu_landmark_record);
-    if ((rc = sv_ensure_stage(ctx, total))) return rc;
-    if ((rc = sv_ensure_scratch(ctx, total))) return rc;
-    uint32_t* h_ids = (uint32_t*)ctx->h_stage;
-    svgpu_landmark_record* h_rec = (svgpu_landmark_record*)(ctx->h_stage + o_rec);
-    int kept = 0;
-    {
-        bool repeat = false;
-        if (n > 1) {
-            std::vector<uint32_t> sorted(ids, ids + n);
-            std::sort(sorted.begin(), sorted.end());
-            for (int i = 1; i < n && !repeat; ++i) repeat = sorted[i] == sorted[i - 1];
-        }
-        if (!repeat) {
-            memcpy(h_ids, ids, (size_t)n * 4);
-            memcpy(h_rec, records, (size_t)n * sizeof(svgpu_landmark_record));
-            kept = n;
-        }
-        else {
-            std::map<uint32_t, int> where;
-            for (int i = 0; i < n; ++i) where[ids[i]] = i;
-            for (const auto& kv : where) {
-                h_ids[kept] = kv.first;
-                h_rec[kept] = records[kv.second];
-                ++kept;
-            }
-        }
-    }
-    hipStream_t s = ctx->stream;
+    uint32_t* d_ids;
+    svgpu_landmark_record* d_rec;
+    StagedCall C;  // opened behind map_grow: growth synchronises and may use the stream
+    rc = C.open(ctx, "svgpu_map_upsert: internal arena overflow", [&](UploadArena& A) {
+        d_ids = A.take<uint32_t>(n);
+        d_rec = A.take<svgpu_landmark_record>(n);
+    });
+    if (rc) return rc;
+    const int kept = map_collapse(n, ids, records, C.host(d_ids), C.host(d_rec));
+    C.stage(d_ids, kept), C.stage(d_rec, kept);  // written in the mirror above: the upload covers `kept` records, not n
+    hipStream_t s = C.s;
     if ((rc = map_wait_readers(ctx, m, s))) return rc;
     if (m->wrote) SV_HIP(ctx, hipStreamWaitEvent(s, m->ev_write, 0));
-    char* d = (char*)ctx->d_scratch;
-    SV_HIP(ctx, hipMemcpyAsync(d, ctx->h_stage, o_rec + (size_t)kept * sizeof(svgpu_landmark_record), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_map_scatter, dim3((kept * 6 + 255) / 256), dim3(256), 0, s, (const uint32_t*)d, (const uint4*)(d + o_rec), kept, (uint4*)m->rec, m->cap);
+    if ((rc = C.flush())) return rc;
+    hipLaunchKernelGGL(k_map_scatter, dim3((kept * 6 + 255) / 256), dim3(256), 0, s, d_ids, (const uint4*)d_rec, kept, (uint4*)m->rec, m->cap);
     SV_HIP(ctx, hipGetLastError());
     SV_HIP(ctx, hipEventRecord(m->ev_write, s));
     m->wrote = true;
-    SV_HIP(ctx, hipStreamSynchronize(s));  // the staging buffers belong to the context's next call
-    return SVGPU_OK;
+    return C.finish();  // synchronises: the staging buffers belong to the context's next call
 }
 
 int svgpu_map_erase(svgpu_ctx* ctx, svgpu_map* m, int n, const uint32_t* ids) {
@@ -192,20 +195,20 @@ int svgpu_map_erase(svgpu_ctx* ctx, svgpu_map* m, int n, const uint32_t* ids) {
     SV_HIP(ctx, hipSetDevice(ctx->device));
     std::lock_guard<std::mutex> lock(m->mtx);
     if (m->cap == 0) return SVGPU_OK;
-    int rc = sv_ensure_stage(ctx, (size_t)n * 4);
+    uint32_t* d_ids;
+    StagedCall C;
+    int rc = C.open(ctx, "svgpu_map_erase: internal arena overflow", [&](UploadArena& A) { d_ids = A.take<uint32_t>(n); });
     if (rc) return rc;
-    if ((rc = sv_ensure_scratch(ctx, (size_t)n * 4))) return rc;
-    memcpy(ctx->h_stage, ids, (size_t)n * 4);
-    hipStream_t s = ctx->stream;
+    C.up(d_ids, ids, n);
+    hipStream_t s = C.s;
     if ((rc = map_wait_readers(ctx, m, s))) return rc;
     if (m->wrote) SV_HIP(ctx, hipStreamWaitEvent(s, m->ev_write, 0));
-    SV_HIP(ctx, hipMemcpyAsync(ctx->d_scratch, ctx->h_stage, (size_t)n * 4, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_map_erase, dim3((n + 255) / 256), dim3(256), 0, s, (const uint32_t*)ctx->d_scratch, n, m->rec, m->cap);
+    if ((rc = C.flush())) return rc;
+    hipLaunchKernelGGL(k_map_erase, dim3((n + 255) / 256), dim3(256), 0, s, d_ids, n, m->rec, m->cap);
     SV_HIP(ctx, hipGetLastError());
     SV_HIP(ctx, hipEventRecord(m->ev_write, s));
     m->wrote = true;
-    SV_HIP(ctx, hipStreamSynchronize(s));
-    return SVGPU_OK;
+    return C.finish();
 }
 
 int svgpu_map_download(svgpu_ctx* ctx, const svgpu_map* cm, int n, const uint32_t* ids, svgpu_landmark_record* records) {
@@ -215,23 +218,24 @@ int svgpu_map_download(svgpu_ctx* ctx, const svgpu_map* cm, int n, const uint32_
     if (n == 0) return SVGPU_OK;
     SV_HIP(ctx, hipSetDevice(ctx->device));
     std::lock_guard<std::mutex> lock(m->mtx);
-    const size_t o_rec = pad((size_t)n * 4), total = o_rec + (size_t)n * sizeof(svgpu_landmark_record);
-    int rc = sv_ensure_stage(ctx, total);
+    uint32_t* d_ids;
+    svgpu_landmark_record* d_rec;
+    StagedCall C;
+    int rc = C.open(ctx, "svgpu_map_download: internal arena overflow", [&](UploadArena& A) {
+        d_ids = A.take<uint32_t>(n);
+        d_rec = A.take<svgpu_landmark_record>(n);
+    });
     if (rc) return rc;
-    if ((rc = sv_ensure_scratch(ctx, total))) return rc;
-    memcpy(ctx->h_stage, ids, (size_t)n * 4);
-    hipStream_t s = ctx->stream;
+    C.up(d_ids, ids, n);
+    hipStream_t s = C.s;
     SvMapReadScope scope(ctx, m, s);
     if ((rc = scope.begin())) return rc;
-    char* d = (char*)ctx->d_scratch;
-    SV_HIP(ctx, hipMemcpyAsync(d, ctx->h_stage, (size_t)n * 4, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_map_gather, dim3((n * 6 + 255) / 256), dim3(256), 0, s, (const uint32_t*)d, n, (const uint4*)m->rec, m->cap, (uint4*)(d + o_rec));
+    if ((rc = C.flush())) return rc;
+    hipLaunchKernelGGL(k_map_gather, dim3((n * 6 + 255) / 256), dim3(256), 0, s, d_ids, n, (const uint4*)m->rec, m->cap, (uint4*)d_rec);
     SV_HIP(ctx, hipGetLastError());
-    SV_HIP(ctx, hipMemcpyAsync(ctx->h_stage + o_rec, d + o_rec, (size_t)n * sizeof(svgpu_landmark_record), hipMemcpyDeviceToHost, s));
-    if ((rc = scope.end())) return rc;
-    SV_HIP(ctx, hipStreamSynchronize(s));
-    memcpy(records, ctx->h_stage + o_rec, (size_t)n * sizeof(svgpu_landmark_record));
-    return SVGPU_OK;
+    C.down(records, d_rec, n);
+    if ((rc = C.finish())) return rc;
+    return scope.end();  // (behind the read-back, as it always was: a read event in front of it delays a small download by a fifth)
 }
 
 }  // extern "C"

@@ -12,46 +12,41 @@ extern "C" {
 int svgpu_hamming_distance(svgpu_ctx* ctx, const uint8_t* a, const uint8_t* b, int n, uint32_t* dist) {
     if (!ctx || n < 0 || (n > 0 && (!a || !b || !dist))) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_hamming_distance");
     if (n == 0) return SVGPU_OK;
-    SV_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t nb = (size_t)n * 32;
     uint32_t *da, *db, *dd;
-    auto layout = [&](Arena& A) {
+    StagedCall C;
+    int rc = C.open(ctx, "svgpu_hamming_distance: internal arena overflow", [&](UploadArena& A) {
         da = A.take<uint32_t>((size_t)n * 8);
         db = A.take<uint32_t>((size_t)n * 8);
         dd = A.take<uint32_t>(n);
-    };
-    int rc = sv_scratch_layout(ctx, "svgpu_hamming_distance: internal arena overflow", layout);
+    });
     if (rc) return rc;
-    hipStream_t s = ctx->stream;
-    SV_HIP(ctx, hipMemcpyAsync(da, a, nb, hipMemcpyHostToDevice, s));
-    SV_HIP(ctx, hipMemcpyAsync(db, b, nb, hipMemcpyHostToDevice, s));
-    sv_launch_hamming_pairs(s, da, db, n, dd);
-    SV_HIP(ctx, hipMemcpyAsync(dist, dd, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-    SV_HIP(ctx, hipStreamSynchronize(s));
-    return SVGPU_OK;
+    C.up(da, (const uint32_t*)a, (size_t)n * 8);
+    C.up(db, (const uint32_t*)b, (size_t)n * 8);
+    if ((rc = C.flush())) return rc;
+    sv_launch_hamming_pairs(C.s, da, db, n, dd);
+    C.down(dist, dd, n);
+    return C.finish();
 }
 
 int svgpu_hamming_matrix(svgpu_ctx* ctx, const uint8_t* desc1, int n1, const uint8_t* desc2, int n2, uint16_t* out) {
     if (!ctx || n1 < 0 || n2 < 0) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_hamming_matrix");
     if (n1 == 0 || n2 == 0) return SVGPU_OK;
     if (!desc1 || !desc2 || !out) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_hamming_matrix: null pointer");
-    SV_HIP(ctx, hipSetDevice(ctx->device));
     uint32_t *d1, *d2;
     uint16_t* dm;
-    auto layout = [&](Arena& A) {
+    StagedCall C;
+    int rc = C.open(ctx, "svgpu_hamming_matrix: internal arena overflow", [&](UploadArena& A) {
         d1 = A.take<uint32_t>((size_t)n1 * 8);
         d2 = A.take<uint32_t>((size_t)n2 * 8);
-        dm = A.take<uint16_t>((size_t)n1 * n2);
-    };
-    int rc = sv_scratch_layout(ctx, "svgpu_hamming_matrix: internal arena overflow", layout);
+        dm = A.take<uint16_t>((size_t)n1 * n2);  // behind both inputs: the upload stops short of it
+    });
     if (rc) return rc;
-    hipStream_t s = ctx->stream;
-    SV_HIP(ctx, hipMemcpyAsync(d1, desc1, (size_t)n1 * 32, hipMemcpyHostToDevice, s));
-    SV_HIP(ctx, hipMemcpyAsync(d2, desc2, (size_t)n2 * 32, hipMemcpyHostToDevice, s));
-    sv_launch_hamming_matrix(s, d1, n1, d2, n2, dm);
-    SV_HIP(ctx, hipMemcpyAsync(out, dm, (size_t)n1 * n2 * 2, hipMemcpyDeviceToHost, s));
-    SV_HIP(ctx, hipStreamSynchronize(s));
-    return SVGPU_OK;
+    C.up(d1, (const uint32_t*)desc1, (size_t)n1 * 8);
+    C.up(d2, (const uint32_t*)desc2, (size_t)n2 * 8);
+    if ((rc = C.flush())) return rc;
+    sv_launch_hamming_matrix(C.s, d1, n1, d2, n2, dm);
+    C.down(out, dm, (size_t)n1 * n2);
+    return C.finish();
 }
 
 }  // extern "C"
@@ -373,12 +368,11 @@ int svgpu_frame_observation(svgpu_ctx* ctx, const svgpu_camera* cam, const svgpu
         if (want_grid) std::memset(cell_off, 0, (size_t)(ncell + 1) * sizeof(int32_t));
         return SVGPU_OK;
     }
-    SV_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
     FrameObsProblem P{};
     GridProblem G{};
     svgpu_keypoint* d_in;
-    auto layout = [&](Arena& A) {
+    StagedCall C;
+    int rc = C.open(ctx, "svgpu_frame_observation: internal arena overflow", [&](UploadArena& A) {
         P.kps = d_in = A.take<svgpu_keypoint>(n);
         P.undist = undist_kps ? A.take<svgpu_keypoint>(n) : nullptr;
         P.undist_xy = A.take<float>((size_t)n * 2);
@@ -389,15 +383,16 @@ int svgpu_frame_observation(svgpu_ctx* ctx, const svgpu_camera* cam, const svgpu
             G.cell_items = A.take<int32_t>(n);
             G.cand_off = A.take<int32_t>(1);
         }
-    };
-    int rc = sv_scratch_layout(ctx, "svgpu_frame_observation: internal arena overflow", layout);
+    });
     if (rc) return rc;
+    hipStream_t s = C.s;
     P.cam = *cam;
     P.n = n;
-    SV_HIP(ctx, hipMemcpyAsync(d_in, kps, (size_t)n * sizeof(svgpu_keypoint), hipMemcpyHostToDevice, s));
+    C.up(d_in, kps, n);
+    if ((rc = C.flush())) return rc;
     sv_launch_frame_observation(s, P);
-    if (undist_kps) SV_HIP(ctx, hipMemcpyAsync(undist_kps, P.undist, (size_t)n * sizeof(svgpu_keypoint), hipMemcpyDeviceToHost, s));
-    if (bearings) SV_HIP(ctx, hipMemcpyAsync(bearings, P.bearings, (size_t)n * 24, hipMemcpyDeviceToHost, s));
+    C.down(undist_kps, P.undist, n);
+    C.down(bearings, P.bearings, 3 * (size_t)n);
     if (want_grid) {
         G.t_xy = P.undist_xy;
         G.nt = n;
@@ -409,13 +404,11 @@ int svgpu_frame_observation(svgpu_ctx* ctx, const svgpu_camera* cam, const svgpu
         G.rows = grid_rows;
         G.nq = 0;
         sv_launch_grid_build(s, G);
-        SV_HIP(ctx, hipMemcpyAsync(cell_off, G.cell_off, (size_t)(ncell + 1) * 4, hipMemcpyDeviceToHost, s));
-        SV_HIP(ctx, hipStreamSynchronize(s));
-        if (cell_items && cell_off[ncell] > 0)
-            SV_HIP(ctx, hipMemcpyAsync(cell_items, G.cell_items, (size_t)cell_off[ncell] * 4, hipMemcpyDeviceToHost, s));
+        C.down(cell_off, G.cell_off, (size_t)ncell + 1);
+        if (cell_items) C.keep(G.cell_items, n);  // how many of them count is known only with cell_off: the whole piece comes back
     }
-    SV_HIP(ctx, hipGetLastError());
-    SV_HIP(ctx, hipStreamSynchronize(s));
+    if ((rc = C.finish())) return rc;
+    if (want_grid && cell_items && cell_off[ncell] > 0) std::memcpy(cell_items, C.host(G.cell_items), (size_t)cell_off[ncell] * sizeof(int32_t));
     return SVGPU_OK;
 }
 
@@ -423,25 +416,22 @@ int svgpu_keypoints_to_bearings(svgpu_ctx* ctx, const svgpu_camera* cam, const s
     if (!ctx || !cam || n < 0 || cam->model < SVGPU_CAM_PERSPECTIVE || cam->model > SVGPU_CAM_RADIAL_DIVISION || (n > 0 && (!undist_kps || !bearings)))
         return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_keypoints_to_bearings: bad arguments");
     if (n == 0) return SVGPU_OK;
-    SV_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
     FrameObsProblem P{};
     svgpu_keypoint* d_in;
-    auto layout = [&](Arena& A) {
+    StagedCall C;
+    int rc = C.open(ctx, "svgpu_keypoints_to_bearings: internal arena overflow", [&](UploadArena& A) {
         P.kps = d_in = A.take<svgpu_keypoint>(n);
         P.bearings = A.take<double>((size_t)n * 3);
-    };
-    int rc = sv_scratch_layout(ctx, "svgpu_keypoints_to_bearings: internal arena overflow", layout);
+    });
     if (rc) return rc;
     P.cam = *cam;
     P.n = n;
     P.already_undistorted = 1;
-    SV_HIP(ctx, hipMemcpyAsync(d_in, undist_kps, (size_t)n * sizeof(svgpu_keypoint), hipMemcpyHostToDevice, s));
-    sv_launch_frame_observation(s, P);
-    SV_HIP(ctx, hipGetLastError());
-    SV_HIP(ctx, hipMemcpyAsync(bearings, P.bearings, (size_t)n * 24, hipMemcpyDeviceToHost, s));
-    SV_HIP(ctx, hipStreamSynchronize(s));
-    return SVGPU_OK;
+    C.up(d_in, undist_kps, n);
+    if ((rc = C.flush())) return rc;
+    sv_launch_frame_observation(C.s, P);
+    C.down(bearings, P.bearings, 3 * (size_t)n);
+    return C.finish();
 }
 
 }  // extern "C"
@@ -613,7 +603,8 @@ int svgpu_stereo_match(svgpu_ctx* ctx_left, svgpu_ctx* ctx_right, const svgpu_ke
     StereoProblem P{};
     svgpu_keypoint *dkl, *dkr;
     uint32_t *ddl, *ddr;
-    auto layout = [&](Arena& A) {
+    StagedCall C;  // staged on the left context
+    int rc = C.open(ctx, "svgpu_stereo_match: internal arena overflow", [&](UploadArena& A) {
         dkl = A.take<svgpu_keypoint>(n_left);
         dkr = A.take<svgpu_keypoint>(n_right);
         ddl = A.take<uint32_t>((size_t)n_left * 8);
@@ -624,15 +615,15 @@ int svgpu_stereo_match(svgpu_ctx* ctx_left, svgpu_ctx* ctx_right, const svgpu_ke
         P.row_off = A.take<int32_t>((size_t)rows + 1);
         P.row_fill = A.take<int32_t>(rows);
         P.row_items = A.take<int32_t>((size_t)n_right * rows_per_kp);
-    };
-    int rc = sv_scratch_layout(ctx, "svgpu_stereo_match: internal arena overflow", layout);
+    });
     if (rc) return rc;
     P.rows = rows, P.rows_per_kp = rows_per_kp;
-    hipStream_t s = ctx->stream;
-    SV_HIP(ctx, hipMemcpyAsync(dkl, kps_left, (size_t)n_left * 28, hipMemcpyHostToDevice, s));
-    SV_HIP(ctx, hipMemcpyAsync(dkr, kps_right, (size_t)n_right * 28, hipMemcpyHostToDevice, s));
-    SV_HIP(ctx, hipMemcpyAsync(ddl, desc_left, (size_t)n_left * 32, hipMemcpyHostToDevice, s));
-    SV_HIP(ctx, hipMemcpyAsync(ddr, desc_right, (size_t)n_right * 32, hipMemcpyHostToDevice, s));
+    hipStream_t s = C.s;
+    C.up(dkl, kps_left, n_left);
+    C.up(dkr, kps_right, n_right);
+    C.up(ddl, (const uint32_t*)desc_left, (size_t)n_left * 8);
+    C.up(ddr, (const uint32_t*)desc_right, (size_t)n_right * 8);
+    if ((rc = C.flush())) return rc;
     P.kl = dkl;
     P.kr = dkr;
     P.dl = ddl;
@@ -665,11 +656,9 @@ int svgpu_stereo_match(svgpu_ctx* ctx_left, svgpu_ctx* ctx_right, const svgpu_ke
     P.thr = 75;                                       // (HAMMING_DIST_THR_HIGH + HAMMING_DIST_THR_LOW) / 2, stereo.h:99
     sv_launch_stereo(ctx, s, P);
     sv_launch_stereo_median(s, P, 1);  // median filter of the correlations (stereo.cc:94-113) on the device
-    SV_HIP(ctx, hipGetLastError());
-    SV_HIP(ctx, hipMemcpyAsync(stereo_x_right, P.xr, (size_t)n_left * 4, hipMemcpyDeviceToHost, s));
-    SV_HIP(ctx, hipMemcpyAsync(depths, P.depth, (size_t)n_left * 4, hipMemcpyDeviceToHost, s));
-    SV_HIP(ctx, hipStreamSynchronize(s));
-    return SVGPU_OK;
+    C.down(stereo_x_right, P.xr, n_left);
+    C.down(depths, P.depth, n_left);
+    return C.finish();
 }
 
 int svgpu_stereo_match_batch_device(svgpu_ctx* ctx_left, svgpu_ctx* ctx_right, int pairs, const svgpu_keypoint* kps_left_dev, const uint8_t* desc_left_dev,
