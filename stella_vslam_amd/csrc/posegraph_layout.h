@@ -12,60 +12,60 @@
 
 struct PgPieces {
     // uploaded
-    char* ctl;
-    double* est0;  // the estimate buffer the input goes to
-    uint8_t* fixed;
-    int32_t *slot, *e_i, *e_j;
-    double* meas;
-    int32_t *v_off, *v_ent;
+    Piece<char> ctl;
+    Piece<double> est0;  // the estimate buffer the input goes to
+    Piece<uint8_t> fixed;
+    Piece<int32_t> slot, e_i, e_j;
+    Piece<double> meas;
+    Piece<int32_t> v_off, v_ent;
     // device only
-    double* est1;
-    double *rec, *chi_trial, *Hd, *b, *maxd, *Minv, *x, *r, *z, *p, *Ap, *scale_part;
+    Piece<double> est1;
+    Piece<double> rec, chi_trial, Hd, b, maxd, Minv, x, r, z, p, Ap, scale_part;
     // results
-    double *out_sim3, *out_pose;
+    Piece<double> out_sim3, out_pose;
 };
 // svgpu_pose_graph_optimize: N vertices of which nfree are free, E edges, `incident` entries in the free vertices' edge lists (<= 2 E)
 template <class A>
 void pg_optimize_layout(A& arena, size_t N, size_t E, size_t nfree, size_t incident, PgPieces& Y) {
     const size_t n = 7 * nfree;
-    Y.ctl = arena.template take<char>(PG_LAYOUT_CTL);
-    Y.est0 = arena.template take<double>(8 * N);
-    Y.fixed = arena.template take<uint8_t>(N);
-    Y.slot = arena.template take<int32_t>(N);
-    Y.e_i = arena.template take<int32_t>(E);
-    Y.e_j = arena.template take<int32_t>(E);
-    Y.meas = arena.template take<double>(8 * E);
-    Y.v_off = arena.template take<int32_t>(nfree + 1);
-    Y.v_ent = arena.template take<int32_t>(incident);
-    Y.est1 = arena.template take<double>(8 * N);
-    Y.rec = arena.template take<double>(PG_LAYOUT_REC * E);
-    Y.chi_trial = arena.template take<double>(E);
-    Y.Hd = arena.template take<double>(49 * nfree);
-    Y.b = arena.template take<double>(n);
-    Y.maxd = arena.template take<double>(nfree);
-    Y.Minv = arena.template take<double>(49 * nfree);
-    Y.x = arena.template take<double>(n);
-    Y.r = arena.template take<double>(n);
-    Y.z = arena.template take<double>(n);
-    Y.p = arena.template take<double>(n);
-    Y.Ap = arena.template take<double>(n);
-    Y.scale_part = arena.template take<double>(nfree);
-    Y.out_sim3 = arena.template take<double>(8 * N);
-    Y.out_pose = arena.template take<double>(12 * N);
+    Y.ctl = arena.template piece<char>(PG_LAYOUT_CTL);
+    Y.est0 = arena.template piece<double>(8 * N);
+    Y.fixed = arena.template piece<uint8_t>(N);
+    Y.slot = arena.template piece<int32_t>(N);
+    Y.e_i = arena.template piece<int32_t>(E);
+    Y.e_j = arena.template piece<int32_t>(E);
+    Y.meas = arena.template piece<double>(8 * E);
+    Y.v_off = arena.template piece<int32_t>(nfree + 1);
+    Y.v_ent = arena.template piece<int32_t>(incident);
+    Y.est1 = arena.template piece<double>(8 * N);
+    Y.rec = arena.template piece<double>(PG_LAYOUT_REC * E);
+    Y.chi_trial = arena.template piece<double>(E);
+    Y.Hd = arena.template piece<double>(49 * nfree);
+    Y.b = arena.template piece<double>(n);
+    Y.maxd = arena.template piece<double>(nfree);
+    Y.Minv = arena.template piece<double>(49 * nfree);
+    Y.x = arena.template piece<double>(n);
+    Y.r = arena.template piece<double>(n);
+    Y.z = arena.template piece<double>(n);
+    Y.p = arena.template piece<double>(n);
+    Y.Ap = arena.template piece<double>(n);
+    Y.scale_part = arena.template piece<double>(nfree);
+    Y.out_sim3 = arena.template piece<double>(8 * N);
+    Y.out_pose = arena.template piece<double>(12 * N);
 }
 
 struct PgLandmarkPieces {
-    double *before, *after;  // uploaded
-    int32_t* ref;
-    double* pos_in;
-    double* pos_out;         // result
+    Piece<double> before, after;  // uploaded
+    Piece<int32_t> ref;
+    Piece<double> pos_in;
+    Piece<double> pos_out;        // result
 };
 // svgpu_pose_graph_correct_landmarks: N vertices, L landmarks
 template <class A>
 void pg_landmarks_layout(A& arena, size_t N, size_t L, PgLandmarkPieces& Y) {
-    Y.before = arena.template take<double>(8 * N);
-    Y.after = arena.template take<double>(8 * N);
-    Y.ref = arena.template take<int32_t>(L);
-    Y.pos_in = arena.template take<double>(3 * L);
-    Y.pos_out = arena.template take<double>(3 * L);
+    Y.before = arena.template piece<double>(8 * N);
+    Y.after = arena.template piece<double>(8 * N);
+    Y.ref = arena.template piece<int32_t>(L);
+    Y.pos_in = arena.template piece<double>(3 * L);
+    Y.pos_out = arena.template piece<double>(3 * L);
 }

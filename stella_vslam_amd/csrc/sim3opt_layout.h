@@ -12,31 +12,31 @@
 
 struct Sim3OptPieces {
     // uploaded
-    char* prob;
-    double *obs1, *obs2;
-    float *w1, *w2;
-    double *pos1, *pos2;
+    Piece<char> prob;
+    Piece<double> obs1, obs2;
+    Piece<float> w1, w2;
+    Piece<double> pos1, pos2;
     // device only
-    double* chi_cache;  // the cached chi2 of every edge: two per match
+    Piece<double> chi_cache;  // the cached chi2 of every edge: two per match
     // results
-    double* sim3_out;
-    int32_t* num_inliers;
-    uint8_t* status;
-    char* stats;
+    Piece<double> sim3_out;
+    Piece<int32_t> num_inliers;
+    Piece<uint8_t> status;
+    Piece<char> stats;
 };
 // P problems with n matches in all
 template <class A>
 void sim3opt_layout(A& arena, size_t P, size_t n, Sim3OptPieces& Y) {
-    Y.prob = arena.template take<char>(S3O_LAYOUT_PROBLEM * P);
-    Y.obs1 = arena.template take<double>(2 * n);
-    Y.obs2 = arena.template take<double>(2 * n);
-    Y.w1 = arena.template take<float>(n);
-    Y.w2 = arena.template take<float>(n);
-    Y.pos1 = arena.template take<double>(3 * n);
-    Y.pos2 = arena.template take<double>(3 * n);
-    Y.chi_cache = arena.template take<double>(2 * n);
-    Y.sim3_out = arena.template take<double>(8 * P);
-    Y.num_inliers = arena.template take<int32_t>(P);
-    Y.status = arena.template take<uint8_t>(n);
-    Y.stats = arena.template take<char>(S3O_LAYOUT_STATS * P);
+    Y.prob = arena.template piece<char>(S3O_LAYOUT_PROBLEM * P);
+    Y.obs1 = arena.template piece<double>(2 * n);
+    Y.obs2 = arena.template piece<double>(2 * n);
+    Y.w1 = arena.template piece<float>(n);
+    Y.w2 = arena.template piece<float>(n);
+    Y.pos1 = arena.template piece<double>(3 * n);
+    Y.pos2 = arena.template piece<double>(3 * n);
+    Y.chi_cache = arena.template piece<double>(2 * n);
+    Y.sim3_out = arena.template piece<double>(8 * P);
+    Y.num_inliers = arena.template piece<int32_t>(P);
+    Y.status = arena.template piece<uint8_t>(n);
+    Y.stats = arena.template piece<char>(S3O_LAYOUT_STATS * P);
 }

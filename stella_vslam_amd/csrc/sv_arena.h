@@ -9,6 +9,16 @@
 
 inline size_t pad(size_t bytes) { return (bytes + 255) & ~size_t(255); }
 
+// A piece of the arena with the element count its layout asked for: what a copy into or out of the piece may move.  Converts to its
+// pointer, so it stands wherever the pointer did; an empty piece (a conditional one that was not taken) is null with n == 0.
+template <class T>
+struct Piece {
+    T* p = nullptr;
+    size_t n = 0;
+    operator T*() const { return p; }
+    size_t bytes() const { return n * sizeof(T); }
+};
+
 struct Arena {
     char* base = nullptr;
     size_t cap = 0, off = 0;
@@ -27,6 +37,8 @@ struct Arena {
         }
         return (T*)(base + o);
     }
+    template <class T>
+    Piece<T> piece(size_t n) { return {take<T>(n), n}; }  // take() that remembers its count, also where the pointer is null (measuring, overflow)
 };
 
 // bytes a layout takes: the layout run on a measuring arena (A: Arena or a type layered on it)

@@ -77,13 +77,15 @@ struct Downloads {
 
 // One synchronous call on host arrays.  open() sizes both buffers from the layout and places it; up() copies host arrays to their pieces'
 // places in the mirror and flush() sends the touched range; the caller launches on `s`; down() names the results and finish() brings them
-// back.  Counts are in elements, the ones the layout gave to take<T>.
+// back.  A Piece (sv_arena.h) carries the count its layout gave it, so up / down / keep / stage on a piece move the whole of it; a transfer
+// that is deliberately shorter names its count, in elements, and one longer than its piece fails the call instead of being copied.  The
+// forms on plain pointers, with a count, serve the layouts that place their pieces straight into a kernel's problem struct.
 struct StagedCall {
     svgpu_ctx* ctx = nullptr;
     hipStream_t s = nullptr;
     UploadArena A;
     Downloads D;
-    int rc = SVGPU_OK;  // the first failure of an up()
+    int rc = SVGPU_OK;  // the first failure of an up(), or a count beyond its piece
 
     // `layout(UploadArena&)` returns void, or an int status (the layouts that upload as they take, through UploadArena::put): that of the
     // placing run is returned as it is
@@ -105,6 +107,10 @@ struct StagedCall {
     void up(T* dst, const T* src, size_t count) {
         if (!rc && src) rc = A.upload(ctx, s, dst, src, count * sizeof(T));
     }
+    template <class T>
+    void up(Piece<T> dst, const T* src) { up(dst.p, src, dst.n); }
+    template <class T>
+    void up(Piece<T> dst, const T* src, size_t count) { if (fits(count, dst.n)) up(dst.p, src, count); }
     int flush() { return rc ? rc : A.flush(ctx, s); }
     // the place of an arena piece in the mirror
     template <class T>
@@ -120,6 +126,8 @@ struct StagedCall {
         return host(dev);
     }
     template <class T>
+    T* stage(Piece<T> dev) { return stage(dev.p, dev.n); }
+    template <class T>
     void down(T* dst, const T* src, size_t count) {
         D.add(A, dst, src, count * sizeof(T));
     }
@@ -128,12 +136,22 @@ struct StagedCall {
     void keep(const T* src, size_t count) {
         D.keep(A, src, count * sizeof(T));
     }
+    template <class T>
+    void down(T* dst, Piece<T> src) { down(dst, src.p, src.n); }
+    template <class T>
+    void down(T* dst, Piece<T> src, size_t count) { if (fits(count, src.n)) down(dst, src.p, count); }
+    template <class T>
+    void keep(Piece<T> src) { keep(src.p, src.n); }
+    bool fits(size_t count, size_t n) {  // a count beside a piece may fall short of it, never exceed it: nothing is copied then and the call fails
+        if (count > n && !rc) rc = sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu: internal count mismatch (a transfer longer than its arena piece)");
+        return count <= n;
+    }
     int finish() {
         SV_HIP(ctx, hipGetLastError());
         const int r = D.fetch(ctx, s, A);
         if (r) return r;
         SV_HIP(ctx, hipStreamSynchronize(s));
         D.scatter(A);
-        return SVGPU_OK;
+        return rc;
     }
 };

@@ -1563,14 +1563,8 @@ int svgpu_pose_optimize_batch(svgpu_ctx* ctx, int num_problems, const int32_t* o
     StagedCall C;
     int rc = C.open(ctx, "svgpu_pose_optimize_batch: internal arena overflow", [&](UploadArena& A) { poseopt_batch_layout(A, P, n, Y); });
     if (rc) return rc;
-    C.up(Y.obs_off, obs_off, P + 1);
-    C.up(Y.pose_in, pose_cw, 12 * P);
-    C.up(Y.active, active, P);
-    C.up(Y.pos_w, pos_w, 3 * n);
-    C.up(Y.uvr, uvr, 3 * n);
-    C.up(Y.w, inv_sigma_sq, n);
-    C.up(Y.huber, huber_delta, n);
-    C.up(Y.select, select, n);
+    C.up(Y.obs_off, obs_off), C.up(Y.pose_in, pose_cw), C.up(Y.active, active), C.up(Y.pos_w, pos_w);
+    C.up(Y.uvr, uvr), C.up(Y.w, inv_sigma_sq), C.up(Y.huber, huber_delta), C.up(Y.select, select);  // active, select: optional, null is no upload
     if ((rc = C.flush())) return rc;
 
     PoseOptDev D;
@@ -1587,10 +1581,8 @@ int svgpu_pose_optimize_batch(svgpu_ctx* ctx, int num_problems, const int32_t* o
     D.bat_off = Y.obs_off, D.bat_select = select ? Y.select : nullptr, D.bat_active = active ? Y.active : nullptr, D.bat_flags = Y.flags;
     sv_pose_opt_batch(ctx, C.s, D, num_problems);
 
-    std::vector<int32_t> result(4 * P);
-    C.down(pose_out, Y.pose_out, 12 * P);
-    C.down(result.data(), Y.result, 4 * P);
-    C.down(outlier_flags, Y.flags, n);
+    std::vector<int32_t> result(Y.result.n);
+    C.down(pose_out, Y.pose_out), C.down(result.data(), Y.result), C.down(outlier_flags, Y.flags);
     if ((rc = C.finish())) return rc;
     for (size_t p = 0; p < P; ++p) {
         num_valid[p] = result[4 * p];

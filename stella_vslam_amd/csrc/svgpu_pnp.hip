@@ -52,12 +52,8 @@ int ransac_core(svgpu_ctx* ctx, const char* who, int num_problems, const int32_t
         });
         if (rc) return rc;
         hipStream_t s = C.s;
-        C.up(Y.bearings, bearings, 3 * (size_t)n);
-        C.up(Y.pos_w, pos_w, 3 * (size_t)n);
-        C.up(Y.max_cos, max_cos.data(), n);
-        C.up(Y.match_off, match_off, (size_t)P + 1);
-        C.up(Y.samples, samples, 4 * (size_t)P * I);
-        C.up(Y.active, active.data(), num_active);
+        C.up(Y.bearings, bearings), C.up(Y.pos_w, pos_w), C.up(Y.max_cos, max_cos.data());
+        C.up(Y.match_off, match_off), C.up(Y.samples, samples), C.up(Y.active, active.data());
         if ((rc = C.flush())) return rc;
         PnpRansacProblem R{};
         R.bearings = Y.bearings, R.pos_w = Y.pos_w, R.max_cos = Y.max_cos, R.match_off = Y.match_off, R.samples = Y.samples, R.active = Y.active;
@@ -81,13 +77,8 @@ int ransac_core(svgpu_ctx* ctx, const char* who, int num_problems, const int32_t
             SvProfScope prof(ctx, s, "k_pnp_pose");
             sv_launch_pnp_pose(s, Q);
         }
-        C.down(valid, Y.valid, P);
-        C.down(pose_cw, Y.pose, 12 * (size_t)P);
-        C.down(is_inlier, Y.is_inlier, n);
-        C.down(best_iter, Y.best_iter, P);
-        C.down(hyp_pose, Y.hyp_pose, 12 * (size_t)P * I);
-        C.down(hyp_num_inliers, Y.hyp_num_inliers, (size_t)P * I);
-        C.down(hyp_cost, Y.hyp_cost, (size_t)P * I);
+        C.down(valid, Y.valid), C.down(pose_cw, Y.pose), C.down(is_inlier, Y.is_inlier), C.down(best_iter, Y.best_iter);
+        C.down(hyp_pose, Y.hyp_pose), C.down(hyp_num_inliers, Y.hyp_num_inliers), C.down(hyp_cost, Y.hyp_cost);  // optional: null is no request
         if ((rc = C.finish())) return rc;
     }
     // a problem that did not run: solution_is_valid_ = false, nothing else is defined by the reference -- zeros here
@@ -126,9 +117,7 @@ int svgpu_pnp_compute_pose(svgpu_ctx* ctx, int num_sets, const int32_t* set_off,
     int rc = C.open(ctx, "svgpu_pnp_compute_pose: internal arena overflow", [&](UploadArena& A) { pnp_pose_layout(A, (size_t)num_sets, n, Y); });
     if (rc) return rc;
     hipStream_t s = C.s;
-    C.up(Y.bearings, bearings, 3 * n);
-    C.up(Y.pos_w, pos_w, 3 * n);
-    C.up(Y.off, set_off, (size_t)num_sets + 1);
+    C.up(Y.bearings, bearings), C.up(Y.pos_w, pos_w), C.up(Y.off, set_off);
     if ((rc = C.flush())) return rc;
     PnpPoseProblem Q{};
     Q.bearings = Y.bearings, Q.pos_w = Y.pos_w, Q.off = Y.off, Q.pose = Y.pose, Q.err = Y.err, Q.num_sets = num_sets, Q.gn_iter = gauss_newton_num_iter;
@@ -136,8 +125,7 @@ int svgpu_pnp_compute_pose(svgpu_ctx* ctx, int num_sets, const int32_t* set_off,
         SvProfScope prof(ctx, s, "k_pnp_pose");
         sv_launch_pnp_pose(s, Q);
     }
-    C.down(pose_cw, Y.pose, 12 * (size_t)num_sets);
-    C.down(reproj_error, Y.err, num_sets);
+    C.down(pose_cw, Y.pose), C.down(reproj_error, Y.err);
     return C.finish();
 }
 

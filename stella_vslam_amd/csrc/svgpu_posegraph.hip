@@ -53,15 +53,16 @@ void enqueue_step(svgpu_ctx* ctx, hipStream_t s, const PgDev& D, const PgEnvDev*
 
 void upload_plan(StagedCall& C, const PgEnvPieces& Y, const PgEnvPlan& P) {
     const PgEnvCtl e0{};
-    const auto up = [&](int32_t* dst, const std::vector<int32_t>& v) { C.up(dst, v.data(), v.size()); };
-    C.up(Y.ctl, (const char*)&e0, sizeof e0);
+    // (the vector's own length, which the plan promises to be the piece's: one that disagreed is refused, not read or written past its end)
+    const auto up = [&](Piece<int32_t> dst, const std::vector<int32_t>& v) { C.up(dst, v.data(), v.size()); };
+    C.up(Y.ctl, (const char*)&e0, sizeof e0);  // the reservation is rounder than PgEnvCtl
     up(Y.order, P.order), up(Y.rowoff, P.rowoff), up(Y.coloff, P.coloff), up(Y.colrows, P.colrows), up(Y.colbase, P.colbase);
     up(Y.blk_src, P.blk_src), up(Y.pair_off, P.pair_off), up(Y.pair_ent, P.pair_ent), up(Y.pair_flag, P.pair_flag);
 }
 
 PgEnvDev plan_descriptor(const PgEnvPieces& Y, const PgEnvPlan& P) {
     PgEnvDev K{};
-    K.env = (PgEnvCtl*)Y.ctl;
+    K.env = (PgEnvCtl*)Y.ctl.p;
     K.nP = P.nfree, K.nblocks = (int)P.nblocks, K.max_m = P.max_column_rows;
     K.order = Y.order, K.rowoff = Y.rowoff, K.coloff = Y.coloff, K.colrows = Y.colrows, K.colbase = Y.colbase, K.blk_src = Y.blk_src;
     K.pair_off = Y.pair_off, K.pair_ent = Y.pair_ent, K.pair_flag = Y.pair_flag;
@@ -153,21 +154,15 @@ int svgpu_pose_graph_optimize_ex(svgpu_ctx* ctx, int num_vertices, const double*
     c0.gain_thr = gain_threshold;
     c0.it_max = max_iterations;
     c0.ok = 1;
-    C.up(Y.ctl, (const char*)&c0, sizeof c0);
-    C.up(Y.est0, sim3, 8 * (size_t)N);
-    C.up(Y.fixed, fixed, N);
-    C.up(Y.slot, slot.data(), N);
-    C.up(Y.e_i, edge_v1, E);
-    C.up(Y.e_j, edge_v2, E);
-    C.up(Y.meas, edge_sim3_21, 8 * (size_t)E);
-    C.up(Y.v_off, v_off.data(), (size_t)nfree + 1);
-    C.up(Y.v_ent, v_ent.data(), incident);
+    C.up(Y.ctl, (const char*)&c0, sizeof c0);  // the reservation is rounder than PgCtl
+    C.up(Y.est0, sim3), C.up(Y.fixed, fixed), C.up(Y.slot, slot.data());
+    C.up(Y.e_i, edge_v1), C.up(Y.e_j, edge_v2), C.up(Y.meas, edge_sim3_21), C.up(Y.v_off, v_off.data()), C.up(Y.v_ent, v_ent.data());
     if (direct) upload_plan(C, Ye, plan);
     if ((rc = C.flush())) return rc;
 
     PgDev D{};
     D.N = N, D.E = E, D.nfree = nfree, D.n = 7 * nfree, D.fix_scale = fix_scale != 0;
-    D.ctl = (PgCtl*)Y.ctl;
+    D.ctl = (PgCtl*)Y.ctl.p;
     D.est[0] = Y.est0, D.est[1] = Y.est1;
     D.fixed = Y.fixed, D.slot = Y.slot, D.e_i = Y.e_i, D.e_j = Y.e_j, D.meas = Y.meas, D.v_off = Y.v_off, D.v_ent = Y.v_ent;
     D.rec = Y.rec, D.chi_trial = Y.chi_trial, D.Hd = Y.Hd, D.b = Y.b, D.maxd = Y.maxd, D.Minv = Y.Minv;
@@ -183,7 +178,7 @@ int svgpu_pose_graph_optimize_ex(svgpu_ctx* ctx, int num_vertices, const double*
 
     // at most 10 trials per iteration; the first step also serves max_iterations == 0 (chi2 of the input, then phase 2)
     const long max_steps = std::max(1L, 10L * max_iterations);
-    PgCtl* c_host = (PgCtl*)C.host(Y.ctl);
+    PgCtl* c_host = (PgCtl*)C.host(Y.ctl.p);
     long done = 0;
     int batch = 8;
     for (;;) {
@@ -199,9 +194,8 @@ int svgpu_pose_graph_optimize_ex(svgpu_ctx* ctx, int num_vertices, const double*
     const PgCtl c = *c_host;
     sv_pg_output(s, D);
     PgEnvCtl ec{};
-    if (direct) C.down((char*)&ec, Ye.ctl, sizeof ec);
-    C.down(sim3_out, Y.out_sim3, 8 * (size_t)N);
-    C.down(pose_cw_out, Y.out_pose, 12 * (size_t)N);
+    if (direct) C.down((char*)&ec, Ye.ctl, sizeof ec);  // PgEnvCtl, in front of its reservation
+    C.down(sim3_out, Y.out_sim3), C.down(pose_cw_out, Y.out_pose);
     if ((rc = C.finish())) return rc;
     if (stats) {
         stats->lm_iterations = c.it;
@@ -238,14 +232,12 @@ int svgpu_selftest_pose_graph_envelope_solve(svgpu_ctx* ctx, int nfree, int num_
     hipStream_t s = C.s;
     PgCtl c0{};
     c0.phase = 1;
-    C.up(Y.ctl, (const char*)&c0, sizeof c0);
-    C.up(Y.diag, diag_blocks, 49 * (size_t)nfree);
-    C.up(Y.blocks, pair_blocks, 49 * (size_t)num_pairs);
-    C.up(Y.rhs, rhs, 7 * (size_t)nfree);
+    C.up(Y.ctl, (const char*)&c0, sizeof c0);  // the reservation is rounder than PgCtl
+    C.up(Y.diag, diag_blocks), C.up(Y.blocks, pair_blocks), C.up(Y.rhs, rhs);
     upload_plan(C, Y.env, plan);
     if ((rc = C.flush())) return rc;
     PgEnvDev K = plan_descriptor(Y.env, plan);
-    K.ctl = (const PgCtl*)Y.ctl, K.damped = 0;
+    K.ctl = (const PgCtl*)Y.ctl.p, K.damped = 0;
     K.Hd = Y.diag, K.b = Y.rhs, K.x = Y.x, K.blk = Y.blocks, K.blk_stride = 49;
     {
         SvProfScope prof(ctx, s, "k_pg_env_assemble");
@@ -256,9 +248,9 @@ int svgpu_selftest_pose_graph_envelope_solve(svgpu_ctx* ctx, int nfree, int num_
         sv_pg_env_factor_solve(s, K);
     }
     PgEnvCtl ec{};
-    std::vector<double> x((size_t)nfree * 7);
-    C.down((char*)&ec, Y.env.ctl, sizeof ec);
-    C.down(x.data(), Y.x, x.size());
+    std::vector<double> x(Y.x.n);
+    C.down((char*)&ec, Y.env.ctl, sizeof ec);  // PgEnvCtl, in front of its reservation
+    C.down(x.data(), Y.x);
     if ((rc = C.finish())) return rc;
     fill_solver_stats(solver_stats, SVGPU_PG_SOLVER_ENVELOPE, &plan, ec.solve_failed ? 1 : 0);
     if (ec.solve_failed) return sv_set_error(ctx, SVGPU_ERR_NUMERIC, "svgpu_selftest_pose_graph_envelope_solve: the system is not positive definite");
@@ -284,10 +276,7 @@ int svgpu_pose_graph_correct_landmarks(svgpu_ctx* ctx, int num_vertices, const d
     int rc = C.open(ctx, "svgpu_pose_graph_correct_landmarks: internal arena overflow", [&](UploadArena& A) { pg_landmarks_layout(A, N, L, Y); });
     if (rc) return rc;
     hipStream_t s = C.s;
-    C.up(Y.before, sim3_before, 8 * N);
-    C.up(Y.after, sim3_after, 8 * N);
-    C.up(Y.ref, ref_vertex, L);
-    C.up(Y.pos_in, pos_w, 3 * L);
+    C.up(Y.before, sim3_before), C.up(Y.after, sim3_after), C.up(Y.ref, ref_vertex), C.up(Y.pos_in, pos_w);
     if ((rc = C.flush())) return rc;
     PgLandmarks P{};
     P.L = num_landmarks, P.N = num_vertices, P.sim3_before = Y.before, P.sim3_after = Y.after, P.ref = Y.ref, P.pos_in = Y.pos_in, P.pos_out = Y.pos_out;
@@ -295,7 +284,7 @@ int svgpu_pose_graph_correct_landmarks(svgpu_ctx* ctx, int num_vertices, const d
         SvProfScope prof(ctx, s, "k_pg_correct_landmarks");
         sv_pg_correct_landmarks(s, P);
     }
-    C.down(pos_w_out, Y.pos_out, 3 * L);
+    C.down(pos_w_out, Y.pos_out);
     return C.finish();
 }
 

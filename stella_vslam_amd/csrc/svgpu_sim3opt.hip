@@ -67,29 +67,21 @@ int optimize_core(svgpu_ctx* ctx, const char* who, int num_problems, const svgpu
     int rc = C.open(ctx, "svgpu_sim3_transform_optimize: internal arena overflow", [&](UploadArena& A) { sim3opt_layout(A, (size_t)P, n, Y); });
     if (rc) return rc;
     hipStream_t s = C.s;
-    C.up(Y.prob, (const char*)prob.data(), (size_t)P * S3O_LAYOUT_PROBLEM);
-    C.up(Y.obs1, obs1, 2 * n);
-    C.up(Y.obs2, obs2, 2 * n);
-    C.up(Y.w1, w1, n);
-    C.up(Y.w2, w2, n);
-    C.up(Y.pos1, pos1, 3 * n);
-    C.up(Y.pos2, pos2, 3 * n);
+    C.up(Y.prob, (const char*)prob.data());
+    C.up(Y.obs1, obs1), C.up(Y.obs2, obs2), C.up(Y.w1, w1), C.up(Y.w2, w2), C.up(Y.pos1, pos1), C.up(Y.pos2, pos2);
     if ((rc = C.flush())) return rc;
 
     Sim3OptDev D{};
     D.num_problems = P, D.fix_scale = fix_scale != 0, D.num_iter = num_iter, D.chi_sq = chi_sq;
-    D.prob = (const Sim3OptProblem*)Y.prob;
+    D.prob = (const Sim3OptProblem*)Y.prob.p;
     D.obs1 = Y.obs1, D.obs2 = Y.obs2, D.w1 = Y.w1, D.w2 = Y.w2, D.pos1 = Y.pos1, D.pos2 = Y.pos2;
     D.chi_cache = Y.chi_cache, D.sim3_out = Y.sim3_out, D.num_inliers = Y.num_inliers, D.status = Y.status;
-    D.stats = (svgpu_sim3opt_stats*)Y.stats;
+    D.stats = (svgpu_sim3opt_stats*)Y.stats.p;
     {
         SvProfScope prof(ctx, s, "k_sim3_opt");
         sv_launch_sim3opt(s, D);
     }
-    C.down(sim3_out, Y.sim3_out, 8 * (size_t)P);
-    C.down(num_inliers, Y.num_inliers, P);
-    C.down(status, Y.status, n);
-    C.down((char*)stats, Y.stats, (size_t)P * S3O_LAYOUT_STATS);
+    C.down(sim3_out, Y.sim3_out), C.down(num_inliers, Y.num_inliers), C.down(status, Y.status), C.down((char*)stats, Y.stats);
     return C.finish();
 }
 

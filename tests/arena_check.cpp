@@ -1,5 +1,5 @@
 // Host-only check of the scratch arena (stella_vslam_amd/csrc/sv_arena.h) and of the shared argument checks (sv_validate.h): built and run
-// by tests/test_arena.py.
+// by tests/test_arena_layouts.py.
 // Every layout is run on a measuring arena and on placing arenas over a host buffer (the pointers are compared, never dereferenced).
 #include <cmath>
 #include <cstdint>
@@ -9,17 +9,9 @@
 #include <utility>
 #include <vector>
 
+#include "layout_check.h"
 #include "sv_arena.h"
 #include "sv_validate.h"
-
-static int failures = 0;
-#define CHECK(cond)                                                      \
-    do {                                                                 \
-        if (!(cond)) {                                                   \
-            std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);  \
-            ++failures;                                                  \
-        }                                                                \
-    } while (0)
 
 // a layout records what every take returned
 using Layout = std::function<void(Arena&, std::vector<void*>&)>;
@@ -193,10 +185,25 @@ int main() {
         CHECK(A.take<char>(1) == nullptr);
         CHECK(A.off == 256 + 512 + 256);
     }
-    if (failures) {
-        std::printf("%d check(s) failed\n", failures);
-        return 1;
+    {  // a piece is its take with the count beside it, and stands where the pointer did
+        std::vector<char> buf(1024);
+        Arena A(buf.data(), 1024), T(buf.data(), 1024);
+        const Piece<double> a = A.piece<double>(7);
+        const Piece<uint8_t> b = A.piece<uint8_t>(3);
+        CHECK(a.p == T.take<double>(7) && b.p == T.take<uint8_t>(3) && A.off == T.off);
+        CHECK(a.n == 7 && a.bytes() == 56 && b.n == 3 && b.bytes() == 3);
+        double* q = a;
+        const void* v = b;
+        CHECK(q == a.p && v == b.p && a + 2 == a.p + 2);
+        Arena M;  // measuring: null, the count kept
+        const Piece<double> m = M.piece<double>(7);
+        CHECK(m.p == nullptr && m.n == 7 && m.bytes() == 56 && M.off == 256 && !M.overflow);
+        const Piece<char> o = A.piece<char>(513);  // overflow: null, the count kept, and so in every later piece
+        const Piece<int32_t> l = A.piece<int32_t>(1);
+        CHECK(A.overflow && o.p == nullptr && o.n == 513 && l.p == nullptr && l.n == 1 && l.bytes() == 4);
+        const Piece<float> none{};  // a conditional piece that was not taken
+        float* f = none;
+        CHECK(f == nullptr && none.n == 0 && none.bytes() == 0);
     }
-    std::printf("arena ok\n");
-    return 0;
+    return layout_check_result("arena ok");
 }

@@ -1,0 +1,31 @@
+"""The scratch arena (stella_vslam_amd/csrc/sv_arena.h) and the layouts of the entry points whose pieces carry their counts (pnp_layout.h,
+posegraph_layout.h, posegraph_envelope_layout.h, sim3opt_layout.h, poseopt_batch_layout.h) are plain C++.  Each check program is built with
+g++ against those headers alone.  arena_check.cpp checks the arena itself, the read-back range merge and the shared argument checks; the
+other five run tests/layout_check.h for the smallest and the largest shape of their GPU test: measuring hands out no pointer and keeps
+every count, the measured size covers every piece the same layout places, the bytes per piece written out by hand in the program are the
+pieces' own, no two pieces overlap, and a capacity one byte short latches the overflow flag."""
+import pytest
+
+from tests.host_check import ROOT, build_and_run
+
+PROGRAMS = {
+    "arena_check.cpp": "arena ok",
+    "pnp_arena_check.cpp": "pnp arena ok",
+    "posegraph_arena_check.cpp": "posegraph arena ok",
+    "posegraph_envelope_arena_check.cpp": "posegraph envelope arena ok",
+    "sim3opt_arena_check.cpp": "sim3opt arena ok",
+    "poseopt_batch_arena_check.cpp": "poseopt batch arena ok",
+}
+
+
+@pytest.mark.parametrize("source", list(PROGRAMS))
+def test_measure_covers_what_the_layout_takes(source, tmp_path):
+    build_and_run(source, PROGRAMS[source], tmp_path)
+
+
+def test_the_checked_shapes_are_those_of_the_gpu_test():
+    from tests import poseopt_batch_problems as PB
+    src = (ROOT / "tests" / "poseopt_batch_arena_check.cpp").read_text()
+    for call, ps in PB.classes().items():
+        assert f"check({len(ps)}, {sum(len(p['pos_w']) for p in ps)});" in src, call
+    assert "check(300, 19500);" in src and "check(1, 0);" in src

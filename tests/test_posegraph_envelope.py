@@ -1,18 +1,12 @@
 """CPU tests of the pose graph's direct solver: the envelope planner and the plain fp64 elimination
-(stella_vslam_amd/csrc/posegraph_envelope_plan.h) through tests/posegraph_envelope_check.cpp, built with g++ against that header alone,
-and the scratch layout (posegraph_envelope_layout.h) through tests/posegraph_envelope_arena_check.cpp, built against it and sv_arena.h.
+(stella_vslam_amd/csrc/posegraph_envelope_plan.h) through tests/posegraph_envelope_check.cpp, built with g++ against that header alone
+(the solver's scratch layout is checked with the other layouts, in tests/test_arena_layouts.py).
 The envelopes of the natural and of the interleaved order are computed here, independently, and handed to the check program: the
 planner's choice may not be larger than either."""
-import pathlib
-import shutil
-import subprocess
-
 import pytest
 
 from tests import posegraph_envelope_graphs as G
 from tests import posegraph_problems as T
-
-ROOT = pathlib.Path(__file__).resolve().parent.parent
 
 GRAPHS = {
     "one free vertex": lambda: (1, [(0, -1), (-1, 0)]),
@@ -52,15 +46,3 @@ def test_one_long_row_beats_a_wider_band_on_the_chain_of_2049():
     _, _, info = G.run_check(*G.chain(2049, 3))
     assert info["natural"] == 4 * 2049 - 6 + 2049 - 4 and info["blocks"] <= info["natural"] < info["interleaved"]
 
-
-def test_envelope_arena_measure_covers_what_the_layout_takes(tmp_path):
-    cxx = shutil.which("g++")
-    if cxx is None:
-        pytest.fail("g++ is needed to build tests/posegraph_envelope_arena_check.cpp")
-    exe = tmp_path / "posegraph_envelope_arena_check"
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I", str(ROOT / "stella_vslam_amd" / "csrc"),
-                           str(ROOT / "tests" / "posegraph_envelope_arena_check.cpp"), "-o", str(exe)])
-    r = subprocess.run([str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "posegraph envelope arena ok" in r.stdout
-    assert "FAIL" not in r.stdout
