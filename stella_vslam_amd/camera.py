@@ -10,7 +10,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import lib
+from ._lib import lib, ptr as _p
 from .feature import Context, KEYPOINT_DTYPE
 
 MODEL_PERSPECTIVE, MODEL_FISHEYE, MODEL_EQUIRECTANGULAR, MODEL_RADIAL_DIVISION = 0, 1, 2, 3  # camera/base.h:24-29
@@ -22,10 +22,6 @@ class svgpu_camera(C.Structure):
                 ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("dist", C.c_double * 5),
                 ("focal_x_baseline", C.c_double), ("min_x", C.c_float), ("max_x", C.c_float), ("min_y", C.c_float),
                 ("max_y", C.c_float)]
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 class image_bounds:
@@ -96,7 +92,7 @@ class base:
         lsf = float(np.log(np.float32(1.2))) if log_scale_factor is None else float(log_scale_factor)
         vis, rp, xr, lv = np.zeros(n, np.uint8), np.zeros((n, 2), np.float64), np.zeros(n, np.float32), np.zeros(n, np.int32)
         self.ctx.check(lib().svgpu_reproject_landmarks(self.ctx.handle, C.byref(self.c_), _p(R), _p(t), _p(twc), n, _p(pw), _p(nv), _p(mn), _p(mx),
-                                                       _p(sk), C.c_float(ray_cos_thr), int(num_levels), C.c_float(lsf), _p(vis), _p(rp), _p(xr),
+                                                       _p(sk), ray_cos_thr, int(num_levels), lsf, _p(vis), _p(rp), _p(xr),
                                                        _p(lv)), "svgpu_reproject_landmarks")
         return vis, rp, xr, lv
 

@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import camera as _camera
-from ._lib import lib
+from ._lib import lib, ptr as _p
 from .feature import Context
 
 
@@ -31,10 +31,6 @@ class frame_observation:
     def indices_in_cell(self, col: int, row: int) -> np.ndarray:
         c = col * self.num_grid_rows_ + row
         return self.cell_items_[self.cell_off_[c]:self.cell_off_[c + 1]]
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 class resident_frame:
@@ -117,7 +113,7 @@ def landmarks_update_mean_normal_and_obs_scale_variance(ctx: Context, obs_off, o
     sfr = np.ascontiguousarray(ref_scale_factor, np.float32)
     n = len(off) - 1
     mnrm, mx, mn = np.zeros((n, 3), np.float64), np.zeros(n, np.float32), np.zeros(n, np.float32)
-    ctx.check(lib().svgpu_landmarks_update_geometry(ctx.handle, n, _p(off), _p(c), _p(p), _p(r), _p(sfr), C.c_float(inv_scale_factor_last),
+    ctx.check(lib().svgpu_landmarks_update_geometry(ctx.handle, n, _p(off), _p(c), _p(p), _p(r), _p(sfr), inv_scale_factor_last,
                                                     _p(mnrm), _p(mx), _p(mn)), "svgpu_landmarks_update_geometry")
     return mnrm, mx, mn
 
@@ -267,7 +263,7 @@ class bow_database:
         cap = self.diagnostics()["num_slots"] if cap is None else int(cap)
         slots, common, score = np.zeros(cap, np.int32), np.zeros(cap, np.uint32), np.zeros(cap, np.float32)
         n, mc = C.c_int32(0), C.c_uint32(0)
-        self.ctx.check(lib().svgpu_bowdb_acquire(self.ctx.handle, self._h, len(w), _p(w), _p(v), C.c_float(min_score), C.c_float(num_common_words_thr_ratio),
+        self.ctx.check(lib().svgpu_bowdb_acquire(self.ctx.handle, self._h, len(w), _p(w), _p(v), min_score, num_common_words_thr_ratio,
                                                  len(rej), _p(rej), cap, _p(slots), _p(common), _p(score), C.byref(n), C.byref(mc)), "svgpu_bowdb_acquire")
         k = min(n.value, cap)
         r = (slots[:k], common[:k], score[:k])
@@ -288,7 +284,7 @@ class bow_database:
         cap = self.diagnostics()["num_slots"] if cap is None else int(cap)
         slots, common, score = np.zeros((q, cap), np.int32), np.zeros((q, cap), np.uint32), np.zeros((q, cap), np.float32)
         n, mc = np.zeros(q, np.int32), np.zeros(q, np.uint32)
-        self.ctx.check(lib().svgpu_bowdb_acquire_batch(self.ctx.handle, self._h, q, _p(off), _p(w), _p(v), _p(ms), C.c_float(num_common_words_thr_ratio),
+        self.ctx.check(lib().svgpu_bowdb_acquire_batch(self.ctx.handle, self._h, q, _p(off), _p(w), _p(v), _p(ms), num_common_words_thr_ratio,
                                                        len(rej), _p(rej), cap, _p(slots), _p(common), _p(score), _p(n), _p(mc)), "svgpu_bowdb_acquire_batch")
         return [(slots[i, :min(n[i], cap)], common[i, :min(n[i], cap)], score[i, :min(n[i], cap)], int(n[i]), int(mc[i])) for i in range(q)]
 

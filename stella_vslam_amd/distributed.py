@@ -114,14 +114,14 @@ def init_comm(ctx, group=None) -> None:
     run with allreduce = NULL: RCCL calls on the library's stream, no Python in the damping loop."""
     import torch
     import torch.distributed as dist
-    from ._lib import lib
+    from ._lib import lib, ptr
     rank, world = dist.get_rank(group), dist.get_world_size(group)
     ident = np.zeros(128, np.uint8)
     if rank == 0:
-        ctx.check(lib().svgpu_comm_unique_id(C.c_void_p(ident.ctypes.data)), "svgpu_comm_unique_id")
+        ctx.check(lib().svgpu_comm_unique_id(ptr(ident)), "svgpu_comm_unique_id")
     t = torch.from_numpy(ident)
     if dist.get_backend(group) == "nccl":
         t = t.cuda()
     dist.broadcast(t, src=0, group=group)
     ident = t.cpu().numpy().copy()
-    ctx.check(lib().svgpu_comm_init(ctx.handle, rank, world, C.c_void_p(ident.ctypes.data)), "svgpu_comm_init")
+    ctx.check(lib().svgpu_comm_init(ctx.handle, rank, world, ptr(ident)), "svgpu_comm_init")

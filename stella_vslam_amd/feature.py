@@ -10,7 +10,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import SvgpuError, lib
+from ._lib import SvgpuError, lib, ptr as _p
 
 KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"),
                            ("octave", "<i4"), ("class_id", "<i4")])
@@ -66,7 +66,7 @@ class orb_params:
         self.ini_fast_thr_ = int(ini_fast_thr)
         self.min_fast_thr_ = int(min_fast_thr)
         tabs = [np.zeros(num_levels, np.float32) for _ in range(4)]
-        rc = lib().svgpu_orb_scale_tables(C.c_float(scale_factor), num_levels, *[t.ctypes.data_as(C.c_void_p) for t in tabs])
+        rc = lib().svgpu_orb_scale_tables(scale_factor, num_levels, *[_p(t) for t in tabs])
         if rc:
             raise SvgpuError(rc, "svgpu_orb_scale_tables")
         self.scale_factors_, self.inv_scale_factors_, self.level_sigma_sq_, self.inv_level_sigma_sq_ = tabs
@@ -109,9 +109,8 @@ class orb_extractor:
         if self._geom == (w, h):
             return
         p = self.orb_params_
-        self.ctx.check(lib().svgpu_orb_configure(self.ctx.handle, w, h, self.max_batch, C.c_float(p.scale_factor_),
-                                                 p.num_levels_, p.ini_fast_thr_, p.min_fast_thr_, C.c_uint(self.min_area_)),
-                       "svgpu_orb_configure")
+        self.ctx.check(lib().svgpu_orb_configure(self.ctx.handle, w, h, self.max_batch, p.scale_factor_, p.num_levels_, p.ini_fast_thr_,
+                                                 p.min_fast_thr_, self.min_area_), "svgpu_orb_configure")
         self._geom = (w, h)
         self._rect_mask = None
 
@@ -153,11 +152,9 @@ class orb_extractor:
         desc = np.zeros((cap, 32), np.uint8)
         n = C.c_int(0)
         counts = np.zeros(self.orb_params_.num_levels_, np.int32)
-        self.ctx.check(lib().svgpu_orb_extract(self.ctx.handle, C.c_void_p(in_image.ctypes.data), in_image.strides[0],
-                                               None if mask is None else C.c_void_p(mask.ctypes.data),
-                                               0 if mask is None else mask.strides[0],
-                                               kps.ctypes.data_as(C.c_void_p), desc.ctypes.data_as(C.c_void_p), cap,
-                                               C.byref(n), counts.ctypes.data_as(C.c_void_p)), "svgpu_orb_extract")
+        self.ctx.check(lib().svgpu_orb_extract(self.ctx.handle, _p(in_image), in_image.strides[0], _p(mask),
+                                               0 if mask is None else mask.strides[0], _p(kps), _p(desc), cap,
+                                               C.byref(n), _p(counts)), "svgpu_orb_extract")
         self.level_counts_ = counts
         return kps[:n.value].copy(), desc[:n.value].copy()
 
@@ -168,7 +165,7 @@ class orb_extractor:
         for l in range(self.orb_params_.num_levels_):
             w, h = self.level_size(l)
             a = np.zeros((h, w), np.uint8)
-            self.ctx.check(lib().svgpu_orb_pyramid_download(self.ctx.handle, 0, l, a.ctypes.data_as(C.c_void_p), w),
+            self.ctx.check(lib().svgpu_orb_pyramid_download(self.ctx.handle, 0, l, _p(a), w),
                            "svgpu_orb_pyramid_download")
             out.append(a)
         return out
@@ -178,7 +175,7 @@ class orb_extractor:
         for l in range(self.orb_params_.num_levels_):
             w, h = self.level_size(l)
             a = np.zeros((h, w), np.uint8)
-            self.ctx.check(lib().svgpu_orb_blurred_download(self.ctx.handle, 0, l, a.ctypes.data_as(C.c_void_p), w),
+            self.ctx.check(lib().svgpu_orb_blurred_download(self.ctx.handle, 0, l, _p(a), w),
                            "svgpu_orb_blurred_download")
             out.append(a)
         return out

@@ -8,32 +8,12 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import lib
+from ._lib import lib, ptr as _p
 from .feature import Context
 
 COLOR_GRAY, COLOR_RGB, COLOR_BGR = 0, 1, 2      # camera::color_order_t
 DEPTH_NONE, DEPTH_U16, DEPTH_F32 = 0, 1, 2
 _ORDERS = {"gray": COLOR_GRAY, "rgb": COLOR_RGB, "bgr": COLOR_BGR}
-
-
-def _p(a):
-    return None if a is None else C.c_void_p(a.ctypes.data)
-
-
-def _bind():
-    L = lib()
-    if getattr(L, "_ingest_bound", False):
-        return L
-    L.svgpu_ingest_gray_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
-    L.svgpu_ingest_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-    L.svgpu_ingest_destroy.argtypes = [C.c_void_p]
-    L.svgpu_ingest_destroy.restype = None
-    L.svgpu_ingest_gray.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
-    L.svgpu_ingest_depth.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_int]
-    L.svgpu_ingest_depth_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_int, C.c_void_p]
-    L.svgpu_tracker_set_ingest.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double]
-    L._ingest_bound = True
-    return L
 
 
 class Ingest:
@@ -55,7 +35,7 @@ class Ingest:
             if mx.shape != (self.height, self.width) or my.shape != mx.shape:
                 raise ValueError("the maps must have the image's size")
             stride = mx.strides[0]
-        ctx.check(_bind().svgpu_ingest_create(ctx.handle, self.width, self.height, self.channels, self.color_order, _p(mx), _p(my), stride, C.byref(self._h)),
+        ctx.check(lib().svgpu_ingest_create(ctx.handle, self.width, self.height, self.channels, self.color_order, _p(mx), _p(my), stride, C.byref(self._h)),
                   "svgpu_ingest_create")
 
     def _raw(self, img):
@@ -74,7 +54,7 @@ class Ingest:
         if out is None:
             out = np.empty((self.height, self.width), np.uint8)
         assert out.dtype == np.uint8 and out.shape == (self.height, self.width) and out.strides[1] == 1
-        c.check(_bind().svgpu_ingest_gray(c.handle, self._h, _p(im), im.strides[0], _p(out), out.strides[0]), "svgpu_ingest_gray")
+        c.check(lib().svgpu_ingest_gray(c.handle, self._h, _p(im), im.strides[0], _p(out), out.strides[0]), "svgpu_ingest_gray")
         return out
 
     def gray_batch_device(self, src_dev: int, batch: int, src_frame_stride: int, src_row_stride: int, dst_dev: int, dst_frame_stride: int, dst_row_stride: int,
@@ -82,12 +62,12 @@ class Ingest:
         """`batch` raw frames in HBM -> grey frames in HBM, asynchronous (svgpu_ingest_gray_batch_device); pointers as integers
         (torch: tensor.data_ptr()).  The output layout is svgpu_orb_extract_batch_device's imgs_dev."""
         c = ctx or self.ctx
-        c.check(_bind().svgpu_ingest_gray_batch_device(c.handle, self._h, C.c_void_p(src_dev), batch, src_frame_stride, src_row_stride, C.c_void_p(dst_dev),
-                                                       dst_frame_stride, dst_row_stride, C.c_void_p(stream) if stream else None), "svgpu_ingest_gray_batch_device")
+        c.check(lib().svgpu_ingest_gray_batch_device(c.handle, self._h, src_dev, batch, src_frame_stride, src_row_stride, dst_dev,
+                                                     dst_frame_stride, dst_row_stride, stream or None), "svgpu_ingest_gray_batch_device")
 
     def close(self):
         if self._h:
-            _bind().svgpu_ingest_destroy(self._h)
+            lib().svgpu_ingest_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
@@ -129,12 +109,12 @@ def depth(ctx: Context, img: np.ndarray, depthmap_factor: float) -> np.ndarray:
     if d.strides[1] != d.itemsize:
         d = np.ascontiguousarray(d)
     out = np.empty(d.shape, np.float32)
-    ctx.check(_bind().svgpu_ingest_depth(ctx.handle, _p(d), t, d.strides[0], d.shape[1], d.shape[0], float(depthmap_factor), _p(out), out.strides[0]),
+    ctx.check(lib().svgpu_ingest_depth(ctx.handle, _p(d), t, d.strides[0], d.shape[1], d.shape[0], float(depthmap_factor), _p(out), out.strides[0]),
               "svgpu_ingest_depth")
     return out
 
 
 def depth_device(ctx: Context, src_dev: int, src_type: int, src_stride: int, width: int, height: int, depthmap_factor: float, dst_dev: int, dst_stride: int,
                  stream: int | None = None):
-    ctx.check(_bind().svgpu_ingest_depth_device(ctx.handle, C.c_void_p(src_dev), src_type, src_stride, width, height, float(depthmap_factor), C.c_void_p(dst_dev),
-                                                dst_stride, C.c_void_p(stream) if stream else None), "svgpu_ingest_depth_device")
+    ctx.check(lib().svgpu_ingest_depth_device(ctx.handle, src_dev, src_type, src_stride, width, height, float(depthmap_factor), dst_dev,
+                                              dst_stride, stream or None), "svgpu_ingest_depth_device")

@@ -11,7 +11,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import lib
+from ._lib import lib, ptr as _p
 from .feature import Context
 
 HAMMING_DIST_THR_LOW = 50
@@ -23,10 +23,6 @@ MATCH_RATIO_SAME_OCTAVE = 1
 MATCH_RATIO = 2          # bow_tree::match_frame_and_keyframe / match_keyframes
 MATCH_TRIANGULATION = 3  # bow_tree / robust ::match_for_triangulation
 MATCH_AREA = 4           # area::match_in_consistent_area
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 def _c(a, t):
@@ -66,7 +62,7 @@ class robust(base):
         out = np.full(len(d1), -1, np.int32)
         num = C.c_int(0)
         self.ctx.check(lib().svgpu_match_bruteforce(self.ctx.handle, _p(d1), _p(a1), len(d1), _p(d2), _p(a2), _p(v2), len(d2),
-                                                    C.c_float(self.lowe_ratio_), int(self.check_orientation_), _p(out),
+                                                    self.lowe_ratio_, int(self.check_orientation_), _p(out),
                                                     C.byref(num)), "svgpu_match_bruteforce")
         idx1 = np.flatnonzero(out >= 0)
         assert len(idx1) == num.value
@@ -89,7 +85,7 @@ class projection(base):
         num = C.c_int(0)
         self.ctx.check(lib().svgpu_match_candidates(self.ctx.handle, _p(qd), len(qd), _p(td), _p(toct), len(td), _p(off), _p(idx),
                                                     _p(skip), _p(qv), _p(occ), _p(qa), _p(ta), int(self.check_orientation_), _p(qx),
-                                                    _p(tx), _p(qt), C.c_uint(thr), C.c_float(self.lowe_ratio_), mode, _p(out),
+                                                    _p(tx), _p(qt), thr, self.lowe_ratio_, mode, _p(out),
                                                     C.byref(num)), "svgpu_match_candidates")
         return out, num.value
 
@@ -112,9 +108,9 @@ class projection(base):
             self.ctx.check(lib().svgpu_match_set_query_blocks(self.ctx.handle, _p(qb)), "svgpu_match_set_query_blocks")
         self.ctx.check(lib().svgpu_match_in_cells(self.ctx.handle, _p(qd), len(qd), _p(qxy), _p(qm), _p(qlo), _p(qhi), _p(qv), _p(qa), _p(qx),
                                                   _p(qt), _p(td), _p(txy), _p(toct), len(td), _p(occ), _p(ta), _p(tx),
-                                                  C.c_float(bounds[0]), C.c_float(bounds[1]), C.c_float(bounds[2]), C.c_float(bounds[3]),
-                                                  grid_cols, grid_rows, int(self.check_orientation_ and qa is not None and ta is not None), C.c_uint(thr),
-                                                  C.c_float(self.lowe_ratio_), mode, _p(out), C.byref(num)), "svgpu_match_in_cells")
+                                                  bounds[0], bounds[1], bounds[2], bounds[3],
+                                                  grid_cols, grid_rows, int(self.check_orientation_ and qa is not None and ta is not None), thr,
+                                                  self.lowe_ratio_, mode, _p(out), C.byref(num)), "svgpu_match_in_cells")
         return out, num.value
 
 
@@ -146,8 +142,8 @@ class projection(base):
         vis, rp, xr, lv = np.zeros(n, np.uint8), np.zeros((n, 2), np.float64), np.zeros(n, np.float32), np.zeros(n, np.int32)
         self.ctx.check(lib().svgpu_match_frame_and_landmarks(
             self.ctx.handle, C.byref(camera.c_), _p(R), _p(t), _p(twc), n, _p(pw), _p(nv), _p(mn), _p(mx), _p(sk), _p(qd),
-            C.c_float(ray_cos_thr), len(sf), _p(sf), C.c_float(log_scale_factor), C.c_float(margin), _p(td), _p(txy), _p(toct), len(td),
-            _p(occ), _p(tx), frm_obs.num_grid_cols_, frm_obs.num_grid_rows_, C.c_uint(HAMMING_DIST_THR_HIGH), C.c_float(self.lowe_ratio_),
+            ray_cos_thr, len(sf), _p(sf), log_scale_factor, margin, _p(td), _p(txy), _p(toct), len(td),
+            _p(occ), _p(tx), frm_obs.num_grid_cols_, frm_obs.num_grid_rows_, HAMMING_DIST_THR_HIGH, self.lowe_ratio_,
             _p(out), C.byref(num), _p(vis), _p(rp), _p(xr), _p(lv)), "svgpu_match_frame_and_landmarks")
         return out, num.value, vis, rp, xr, lv
 
@@ -180,7 +176,7 @@ class stereo:
         xr, dp = np.full(max(n, 1), -1, np.float32), np.full(max(n, 1), -1, np.float32)
         ctx = self.el.ctx
         ctx.check(lib().svgpu_stereo_match(ctx.handle, self.er.ctx.handle, _p(self.kl), _p(self.dl), n, _p(self.kr), _p(self.dr),
-                                           len(self.kr), C.c_float(self.focal_x_baseline_), C.c_float(self.true_baseline_),
+                                           len(self.kr), self.focal_x_baseline_, self.true_baseline_,
                                            _p(xr), _p(dp)), "svgpu_stereo_match")
         return xr[:n].copy(), dp[:n].copy()
 
@@ -210,9 +206,9 @@ class projection_flat(base):
         n, sf = len(pw), _c(scale_factors, np.float32)
         td = _c(tdesc, np.uint8)
         out, num = np.full(n, -1, np.int32), C.c_int(0)
-        a = [C.byref(cam.c_), _p(_f64(rot_cw)), _p(_f64(trans_cw)), _p(_f64(rot_lw)), _p(_f64(trans_lw)), int(is_monocular), C.c_float(true_baseline),
+        a = [C.byref(cam.c_), _p(_f64(rot_cw)), _p(_f64(trans_cw)), _p(_f64(rot_lw)), _p(_f64(trans_lw)), int(is_monocular), true_baseline,
              n, _p(pw), _p(_c(valid, np.uint8)), _p(_c(lm_desc, np.uint8)), _p(_c(octave_last, np.int32)), _p(_c(angle_last, np.float32)),
-             _p(_c(lm_has_observation, np.uint8)), len(sf), _p(sf), C.c_float(margin), _p(td), _p(_c(t_xy, np.float32)), _p(_c(t_octave, np.int32)),
+             _p(_c(lm_has_observation, np.uint8)), len(sf), _p(sf), margin, _p(td), _p(_c(t_xy, np.float32)), _p(_c(t_octave, np.int32)),
              _p(_c(t_angle, np.float32)), len(td), _p(_c(occupied, np.uint8)), _p(_c(t_xright, np.float32)), grid_cols, grid_rows,
              int(self.check_orientation_), _p(out), C.byref(num)]
         keep = a  # noqa: F841  (the temporaries stay alive until the call returns)
@@ -226,8 +222,8 @@ class projection_flat(base):
         out, num = np.full(n, -1, np.int32), C.c_int(0)
         _call(self.ctx, "svgpu_match_frame_and_keyframe_projection",
               [C.byref(cam.c_), _p(_f64(rot_cw)), _p(_f64(trans_cw)), n, _p(pw), _p(_c(valid, np.uint8)), _p(_c(min_valid_dist, np.float32)),
-               _p(_c(max_valid_dist, np.float32)), _p(_c(lm_desc, np.uint8)), _p(_c(angle_kf, np.float32)), len(sf), _p(sf), C.c_float(log_scale_factor),
-               C.c_float(margin), C.c_uint(hamm_dist_thr), _p(td), _p(_c(t_xy, np.float32)), _p(_c(t_octave, np.int32)), _p(_c(t_angle, np.float32)),
+               _p(_c(max_valid_dist, np.float32)), _p(_c(lm_desc, np.uint8)), _p(_c(angle_kf, np.float32)), len(sf), _p(sf), log_scale_factor,
+               margin, hamm_dist_thr, _p(td), _p(_c(t_xy, np.float32)), _p(_c(t_octave, np.int32)), _p(_c(t_angle, np.float32)),
                len(td), _p(_c(occupied, np.uint8)), grid_cols, grid_rows, int(self.check_orientation_), _p(out), C.byref(num)])
         return out, num.value
 
@@ -238,7 +234,7 @@ class projection_flat(base):
         out, num = np.full(n, -1, np.int32), C.c_int(0)
         _call(self.ctx, "svgpu_match_by_sim3_transform",
               [C.byref(cam.c_), _p(_f64(sim3_cw)), n, _p(pw), _p(_c(valid, np.uint8)), _p(_c(min_valid_dist, np.float32)), _p(_c(max_valid_dist, np.float32)),
-               _p(_f64(mean_normal)), _p(_c(lm_desc, np.uint8)), len(sf), _p(sf), C.c_float(log_scale_factor), C.c_float(margin), _p(td),
+               _p(_f64(mean_normal)), _p(_c(lm_desc, np.uint8)), len(sf), _p(sf), log_scale_factor, margin, _p(td),
                _p(_c(t_xy, np.float32)), _p(_c(t_octave, np.int32)), len(td), _p(_c(occupied, np.uint8)), grid_cols, grid_rows, _p(out), C.byref(num)])
         return out, num.value
 
@@ -255,8 +251,8 @@ class projection_flat(base):
         n1, n2 = len(kf1["pos_w"]), len(kf2["pos_w"])
         m21, m12, mut, num = np.full(n1, -1, np.int32), np.full(n2, -1, np.int32), np.full(n1, -1, np.int32), C.c_int(0)
         _call(self.ctx, "svgpu_match_keyframes_mutually",
-              [C.byref(cam1.c_), C.byref(cam2.c_), _p(_f64(rot_1w)), _p(_f64(trans_1w)), _p(_f64(rot_2w)), _p(_f64(trans_2w)), C.c_float(s_12), _p(_f64(rot_12)),
-               _p(_f64(trans_12))] + side(kf1) + side(kf2) + [len(sf), _p(sf), C.c_float(log_scale_factor), C.c_float(margin), grid_cols, grid_rows, _p(m21),
+              [C.byref(cam1.c_), C.byref(cam2.c_), _p(_f64(rot_1w)), _p(_f64(trans_1w)), _p(_f64(rot_2w)), _p(_f64(trans_2w)), s_12, _p(_f64(rot_12)),
+               _p(_f64(trans_12))] + side(kf1) + side(kf2) + [len(sf), _p(sf), log_scale_factor, margin, grid_cols, grid_rows, _p(m21),
                                                              _p(m12), _p(mut), C.byref(num)])
         return m21, m12, mut, num.value
 
@@ -277,7 +273,7 @@ class fuse:
         _call(self.ctx, "svgpu_fuse_detect_duplication",
               [C.byref(cam.c_), _p(_f64(rot_cw)), _p(_f64(trans_cw)), n, _p(pw), _p(_c(valid, np.uint8)), _p(_c(min_valid_dist, np.float32)),
                _p(_c(max_valid_dist, np.float32)), _p(_f64(mean_normal)), _p(_c(lm_desc, np.uint8)), len(sf), _p(sf), _p(_c(inv_level_sigma_sq, np.float32)),
-               C.c_float(log_scale_factor), C.c_float(margin), int(do_reprojection_matching), _p(td), _p(_c(t_xy, np.float32)), _p(_c(t_octave, np.int32)),
+               log_scale_factor, margin, int(do_reprojection_matching), _p(td), _p(_c(t_xy, np.float32)), _p(_c(t_octave, np.int32)),
                _p(_c(t_xright, np.float32)), len(td), grid_cols, grid_rows, _p(out), C.byref(num)])
         return out, num.value
 
@@ -298,7 +294,7 @@ def match_for_triangulation(ctx, lowe_ratio, check_orientation, desc1, angle1, o
         ctx.handle, _p(d1), _p(_c(angle1, np.float32)), _p(_c(octave1, np.int32)), _p(_f64(bearings1)), _p(_c(has_lm1, np.uint8)), _p(_c(xright1, np.float32)),
         len(d1), _p(d2), _p(_c(angle2, np.float32)), _p(_f64(bearings2)), _p(_c(has_lm2, np.uint8)), _p(_c(xright2, np.float32)), len(d2),
         _p(_c(node1, np.int32)), _p(_c(node2, np.int32)), _p(_f64(E_12)), _p(_f64(epipole_in_2)), int(valid_epipole), _p(sf), len(sf),
-        C.c_float(residual_rad_thr), C.c_float(lowe_ratio), int(check_orientation), _p(out), C.byref(num)), "svgpu_match_for_triangulation")
+        residual_rad_thr, lowe_ratio, int(check_orientation), _p(out), C.byref(num)), "svgpu_match_for_triangulation")
     return out, num.value
 
 
@@ -336,10 +332,9 @@ def triangulate_two_views(ctx, view1, view2, scale_factors, level_sigma_sq, idx1
     m = len(i1)
     pos, st, num = np.zeros((m, 3), np.float64), np.zeros(m, np.uint8), C.c_int(0)
     ctx.check(lib().svgpu_triangulate_two_views(
-        ctx.handle, C.c_void_p(v1.cam), C.c_void_p(v1.pose_cw), C.c_double(v1.true_baseline), C.c_void_p(v1.xy), C.c_void_p(v1.octave), C.c_void_p(v1.bearings),
-        C.c_void_p(v1.xright), C.c_void_p(v1.depth), v1.n, C.c_void_p(v2.cam), C.c_void_p(v2.pose_cw), C.c_double(v2.true_baseline), C.c_void_p(v2.xy),
-        C.c_void_p(v2.octave), C.c_void_p(v2.bearings), C.c_void_p(v2.xright), C.c_void_p(v2.depth), v2.n, _p(sf), _p(sg), len(sf),
-        C.c_float(v1.scale_factor), C.c_float(v2.scale_factor), C.c_float(rays_parallax_deg_thr), _p(i1), _p(i2), m, _p(pos), _p(st), C.byref(num)),
+        ctx.handle, v1.cam, v1.pose_cw, v1.true_baseline, v1.xy, v1.octave, v1.bearings, v1.xright, v1.depth, v1.n,
+        v2.cam, v2.pose_cw, v2.true_baseline, v2.xy, v2.octave, v2.bearings, v2.xright, v2.depth, v2.n, _p(sf), _p(sg), len(sf),
+        v1.scale_factor, v2.scale_factor, rays_parallax_deg_thr, _p(i1), _p(i2), m, _p(pos), _p(st), C.byref(num)),
         "svgpu_triangulate_two_views")
     return pos, st, num.value
 
@@ -355,7 +350,7 @@ def triangulate_two_views_batch(ctx, view1, neighbours, match_off, scale_factors
     sf, sg, i1, i2 = _c(scale_factors, np.float32), _c(level_sigma_sq, np.float32), _c(idx1, np.int32), _c(idx2, np.int32)
     m = len(i1)
     pos, st, num = np.zeros((m, 3), np.float64), np.zeros(m, np.uint8), np.zeros(max(k, 1), np.int32)
-    ctx.check(lib().svgpu_triangulate_two_views_batch(ctx.handle, C.byref(v1), nb, k, _p(off), _p(sf), _p(sg), len(sf), C.c_float(rays_parallax_deg_thr),
+    ctx.check(lib().svgpu_triangulate_two_views_batch(ctx.handle, C.byref(v1), nb, k, _p(off), _p(sf), _p(sg), len(sf), rays_parallax_deg_thr,
                                                       _p(i1), _p(i2), _p(pos), _p(st), _p(num)), "svgpu_triangulate_two_views_batch")
     return pos, st, num[:k]
 
@@ -369,7 +364,7 @@ class bow_tree(base):
         out, num = np.full(len(d1), -1, np.int32), C.c_int(0)
         self.ctx.check(lib().svgpu_bow_match(self.ctx.handle, _p(d1), _p(_c(angle1, np.float32)), _p(_c(valid1, np.uint8)), _p(_c(node1, np.int32)),
                                              len(d1), _p(d2), _p(_c(angle2, np.float32)), _p(_c(valid2, np.uint8)), _p(_c(node2, np.int32)), len(d2),
-                                             _p(_c(occupied2, np.uint8)), C.c_float(self.lowe_ratio_), int(self.check_orientation_), _p(out),
+                                             _p(_c(occupied2, np.uint8)), self.lowe_ratio_, int(self.check_orientation_), _p(out),
                                              C.byref(num)), "svgpu_bow_match")
         return out, num.value
 

@@ -12,7 +12,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import lib
+from ._lib import lib, ptr as _p
 from .feature import Context
 
 
@@ -42,7 +42,7 @@ def partition_keyframe_segments(scene: dict, world: int):
     ptr = lambda x: None if x is None else x.ctypes.data
     prob = _BaProblem(len(pose), len(pts), len(keep[1]), ptr(pose), ptr(keep[0]), ptr(pts), ptr(pf), ptr(keep[1]), ptr(keep[2]), None, None, None, None, 0, 0, 0.0)
     ranks, info = np.zeros(max(len(pts), 1), np.int32), np.zeros(12, np.int32)
-    rc = lib().svgpu_ba_partition_keyframe_segments(C.byref(prob), int(world), C.c_void_p(ranks.ctypes.data), C.c_void_p(info.ctypes.data))
+    rc = lib().svgpu_ba_partition_keyframe_segments(C.byref(prob), int(world), _p(ranks), _p(info))
     if rc:
         raise RuntimeError(f"svgpu_ba_partition_keyframe_segments failed: {rc}")
     keys = ("segmented", "jobs", "cuts", "separator_keyframes", "landmarks_on_separators", "landmarks_on_separators_only", "free_keyframes", "kept_blocks", "separator_blocks", "job_exchange_doubles")
@@ -67,21 +67,21 @@ class local_bundle_adjuster:
 
     def set_solver(self, solver: int = SOLVER_AUTO, pcg_tolerance: float = 1e-10, pcg_max_iterations: int = 0):
         """Linear solver of the reduced camera system (svgpu_ba_set_solver): on-chip LL^T / block-Jacobi PCG / dense LL^T in global memory / block envelope Cholesky."""
-        self.ctx.check(lib().svgpu_ba_set_solver(self.ctx.handle, int(solver), C.c_double(pcg_tolerance), int(pcg_max_iterations)),
+        self.ctx.check(lib().svgpu_ba_set_solver(self.ctx.handle, int(solver), pcg_tolerance, int(pcg_max_iterations)),
                        "svgpu_ba_set_solver")
         return self
 
     def last_envelope_plan(self) -> dict:
         """How the context's last envelope factorisation was planned (svgpu_ba_last_envelope_plan)."""
         info = np.zeros(8, np.int32)
-        self.ctx.check(lib().svgpu_ba_last_envelope_plan(self.ctx.handle, C.c_void_p(info.ctypes.data)), "svgpu_ba_last_envelope_plan")
+        self.ctx.check(lib().svgpu_ba_last_envelope_plan(self.ctx.handle, _p(info)), "svgpu_ba_last_envelope_plan")
         return dict(kind=("one-sided", "two-sided", "segmented")[int(info[0])], rows=int(info[1]), widest_column=int(info[2]), cuts=int(info[3]),
                     jobs=int(info[4]), jobs_local=int(info[5]), separator_rows=int(info[6]), longest_job=int(info[7]))
 
     def last_exchange(self) -> dict:
         """What the context's last sharded solve all-reduced (svgpu_ba_last_exchange); bytes are payload per rank."""
         info = np.zeros(10, np.int64)
-        self.ctx.check(lib().svgpu_ba_last_exchange(self.ctx.handle, C.c_void_p(info.ctypes.data)), "svgpu_ba_last_exchange")
+        self.ctx.check(lib().svgpu_ba_last_exchange(self.ctx.handle, _p(info)), "svgpu_ba_last_exchange")
         trials, lins = max(int(info[8]), 1), max(int(info[9]), 1)
         per_trial = (int(info[3]) + int(info[4]) + int(info[5]) + int(info[6])) / trials + int(info[2]) / lins
         return dict(mode=("none", "whole reduced system", "keyframe segments")[int(info[0])], setup_bytes=int(info[1]), pose_block_bytes=int(info[2]),
@@ -132,8 +132,8 @@ class local_bundle_adjuster:
         pose_out, pts_out = np.zeros_like(pose), np.zeros_like(pts)
         outl = np.zeros(1 if _global else max(E, 1), np.uint8)  # (the global adjuster has no outlier list: no 10 MB of flags to fault in and copy at 9.6 M observations)
         st = _BaStats()
-        stop = None if force_stop_flag is None else C.c_void_p(force_stop_flag.ctypes.data)
-        outs = (C.c_void_p(pose_out.ctypes.data), C.c_void_p(pts_out.ctypes.data), C.c_void_p(outl.ctypes.data), C.byref(st))
+        stop = _p(force_stop_flag)
+        outs = (_p(pose_out), _p(pts_out), _p(outl), C.byref(st))
         if _global and _sharded is not None:
             rank, world, cb = _sharded
             rc = lib().svgpu_global_ba_sharded(self.ctx.handle, C.byref(prob), rank, world, cb, None, stop, outs[0], outs[1], outs[3])
@@ -167,10 +167,9 @@ class pose_optimizer:
         n = len(pw)
         out, outl = np.zeros(12), np.zeros(max(n, 1), np.uint8)
         nv, it = C.c_int(0), C.c_int(0)
-        p = lambda a: C.c_void_p(a.ctypes.data)
-        self.ctx.check(lib().svgpu_pose_optimize(self.ctx.handle, p(pose), n, p(pw), p(uv), p(w), p(hb), p(K), self.num_trials_robust_,
-                                                 self.num_trials_, self.num_each_iter_, int(self.reset_stop_flag_each_round_), p(out),
-                                                 p(outl), C.byref(nv), C.byref(it)), "svgpu_pose_optimize")
+        self.ctx.check(lib().svgpu_pose_optimize(self.ctx.handle, _p(pose), n, _p(pw), _p(uv), _p(w), _p(hb), _p(K), self.num_trials_robust_,
+                                                 self.num_trials_, self.num_each_iter_, int(self.reset_stop_flag_each_round_), _p(out),
+                                                 _p(outl), C.byref(nv), C.byref(it)), "svgpu_pose_optimize")
         return nv.value, out, outl[:n].copy(), it.value
 
     def optimize_batch_flat(self, poses_cw, obs_off, pos_w, uvr, inv_sigma_sq, huber, intr, select=None, active=None):
@@ -191,9 +190,9 @@ class pose_optimizer:
             raise ValueError("optimize_batch_flat: array lengths disagree")
         out, outl = np.zeros((max(P, 1), 12)), np.zeros(max(n, 1), np.uint8)
         nv, it = np.zeros(max(P, 1), np.int32), np.zeros(max(P, 1), np.int32)
-        self.ctx.check(lib().svgpu_pose_optimize_batch(self.ctx.handle, P, _vp(off), _vp(pose), _vp(act), _vp(pw), _vp(uv), _vp(w), _vp(hb), _vp(sel), _vp(K),
+        self.ctx.check(lib().svgpu_pose_optimize_batch(self.ctx.handle, P, _p(off), _p(pose), _p(act), _p(pw), _p(uv), _p(w), _p(hb), _p(sel), _p(K),
                                                        self.num_trials_robust_, self.num_trials_, self.num_each_iter_,
-                                                       int(self.reset_stop_flag_each_round_), _vp(out), _vp(outl), _vp(nv), _vp(it)),
+                                                       int(self.reset_stop_flag_each_round_), _p(out), _p(outl), _p(nv), _p(it)),
                        "svgpu_pose_optimize_batch")
         return nv[:P].copy(), out[:P].copy(), outl[:n].copy(), it[:P].copy()
 
@@ -203,11 +202,9 @@ class pose_optimizer:
         K = np.ascontiguousarray(intr, np.float64).reshape(5)
         out, outl = np.zeros(12), np.zeros(max(n, 1), np.uint8)
         nv, it = C.c_int(0), C.c_int(0)
-        p = lambda a: C.c_void_p(a.ctypes.data)
-        d = lambda t: C.c_void_p(t.data_ptr() if hasattr(t, "data_ptr") else int(t))
-        self.ctx.check(lib().svgpu_pose_optimize_device(self.ctx.handle, p(pose), n, d(pos_w_dev), d(uvr_dev), d(inv_sigma_sq_dev), d(huber_dev), p(K),
+        self.ctx.check(lib().svgpu_pose_optimize_device(self.ctx.handle, _p(pose), n, _p(pos_w_dev), _p(uvr_dev), _p(inv_sigma_sq_dev), _p(huber_dev), _p(K),
                                                         self.num_trials_robust_, self.num_trials_, self.num_each_iter_,
-                                                        int(self.reset_stop_flag_each_round_), p(out), p(outl), C.byref(nv), C.byref(it)),
+                                                        int(self.reset_stop_flag_each_round_), _p(out), _p(outl), C.byref(nv), C.byref(it)),
                        "svgpu_pose_optimize_device")
         return nv.value, out, outl[:n].copy(), it.value
 
@@ -217,10 +214,6 @@ class _PoseGraphStats(C.Structure):
     _fields_ = [("lm_iterations", C.c_int32), ("lm_trials", C.c_int32), ("pcg_iterations", C.c_int32), ("pcg_capped", C.c_int32),
                 ("stopped_by_gain", C.c_int32), ("num_free", C.c_int32), ("initial_chi2", C.c_double), ("final_chi2", C.c_double),
                 ("lambda_final", C.c_double)]
-
-
-def _vp(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 class _PoseGraphOptions(C.Structure):
@@ -250,8 +243,8 @@ def pose_graph_optimize(ctx: Context, sim3, fixed, edge_v1, edge_v2, edge_sim3_2
     if len(f) != len(s) or len(e2) != len(e1) or len(m) != len(e1):
         raise ValueError("pose_graph_optimize: array lengths disagree")
     out, pose, st, sst = np.zeros_like(s), np.zeros((len(s), 3, 4), np.float64), _PoseGraphStats(), _PoseGraphSolverStats()
-    args = (ctx.handle, len(s), _vp(s), _vp(f), len(e1), _vp(e1), _vp(e2), _vp(m), int(bool(fix_scale)), int(max_iterations), float(gain_threshold),
-            _vp(out), _vp(pose), C.cast(C.pointer(st), C.c_void_p))
+    args = (ctx.handle, len(s), _p(s), _p(f), len(e1), _p(e1), _p(e2), _p(m), int(bool(fix_scale)), int(max_iterations), float(gain_threshold),
+            _p(out), _p(pose), C.cast(C.pointer(st), C.c_void_p))
     if solver == "pcg":
         ctx.check(lib().svgpu_pose_graph_optimize(*args), "svgpu_pose_graph_optimize")
     else:
@@ -274,8 +267,8 @@ def envelope_selftest_solve(ctx: Context, pair_a, pair_b, diag_blocks, pair_bloc
     if len(b) != len(a) or len(blk) != len(a) or len(r) != 7 * len(d):
         raise ValueError("envelope_selftest_solve: array lengths disagree")
     x, sst = np.zeros((len(d), 7)), _PoseGraphSolverStats()
-    status = lib().svgpu_selftest_pose_graph_envelope_solve(ctx.handle, len(d), len(a), _vp(a) if len(a) else None, _vp(b) if len(a) else None, _vp(d),
-                                                            _vp(blk) if len(a) else None, _vp(r), _vp(x), C.cast(C.pointer(sst), C.c_void_p))
+    status = lib().svgpu_selftest_pose_graph_envelope_solve(ctx.handle, len(d), len(a), _p(a) if len(a) else None, _p(b) if len(a) else None, _p(d),
+                                                            _p(blk) if len(a) else None, _p(r), _p(x), C.cast(C.pointer(sst), C.c_void_p))
     return status, x, {k: getattr(sst, k) for k, _ in _PoseGraphSolverStats._fields_}
 
 
@@ -286,7 +279,7 @@ def correct_landmarks(ctx: Context, sim3_before, sim3_after, ref_vertex, pos_w):
     if len(a) != len(b) or len(r) != len(p):
         raise ValueError("correct_landmarks: array lengths disagree")
     out = np.zeros_like(p)
-    ctx.check(lib().svgpu_pose_graph_correct_landmarks(ctx.handle, len(a), _vp(a), _vp(b), len(p), _vp(r), _vp(p), _vp(out)), "svgpu_pose_graph_correct_landmarks")
+    ctx.check(lib().svgpu_pose_graph_correct_landmarks(ctx.handle, len(a), _p(a), _p(b), len(p), _p(r), _p(p), _p(out)), "svgpu_pose_graph_correct_landmarks")
     return out
 
 
@@ -338,9 +331,9 @@ def sim3_transform_optimize_batch(ctx: Context, view1, views2, match_off, obs1, 
         raise ValueError("sim3_transform_optimize_batch: array lengths disagree")
     out, inl, status = np.zeros_like(s), np.zeros(max(P, 1), np.int32), np.zeros(max(n, 1), np.uint8)
     st = (_Sim3OptStats * max(P, 1))()
-    ctx.check(lib().svgpu_sim3_transform_optimize_batch(ctx.handle, P, C.cast(V1, C.c_void_p), int(shared), C.cast(V2, C.c_void_p), _vp(off), _vp(o1), _vp(o2),
-                                                        _vp(w1), _vp(w2), _vp(p1), _vp(p2), _vp(s), C.c_float(chi_sq), int(bool(fix_scale)), int(num_iter),
-                                                        _vp(out), _vp(inl), _vp(status), C.cast(st, C.c_void_p)), "svgpu_sim3_transform_optimize_batch")
+    ctx.check(lib().svgpu_sim3_transform_optimize_batch(ctx.handle, P, C.cast(V1, C.c_void_p), int(shared), C.cast(V2, C.c_void_p), _p(off), _p(o1), _p(o2),
+                                                        _p(w1), _p(w2), _p(p1), _p(p2), _p(s), chi_sq, int(bool(fix_scale)), int(num_iter),
+                                                        _p(out), _p(inl), _p(status), C.cast(st, C.c_void_p)), "svgpu_sim3_transform_optimize_batch")
     res = dict(sim3=out, num_inliers=inl[:P].copy(), status=status[:n].copy())
     for k, _ in _Sim3OptStats._fields_:
         res[k] = np.array([np.array(getattr(st[p], k)) for p in range(P)])
@@ -360,8 +353,8 @@ def sim3_transform_optimize(ctx: Context, view1, view2, obs1, obs2, inv_sigma_sq
         raise ValueError("sim3_transform_optimize: array lengths disagree")
     V1, V2 = _sim3opt_view(*view1), _sim3opt_view(*view2)
     out, inl, status, st = np.zeros(8), C.c_int32(0), np.zeros(max(n, 1), np.uint8), _Sim3OptStats()
-    ctx.check(lib().svgpu_sim3_transform_optimize(ctx.handle, C.byref(V1), C.byref(V2), n, _vp(o1), _vp(o2), _vp(w1), _vp(w2), _vp(p1), _vp(p2), _vp(s),
-                                                  C.c_float(chi_sq), int(bool(fix_scale)), int(num_iter), _vp(out), C.byref(inl), _vp(status), C.byref(st)),
+    ctx.check(lib().svgpu_sim3_transform_optimize(ctx.handle, C.byref(V1), C.byref(V2), n, _p(o1), _p(o2), _p(w1), _p(w2), _p(p1), _p(p2), _p(s),
+                                                  chi_sq, int(bool(fix_scale)), int(num_iter), _p(out), C.byref(inl), _p(status), C.byref(st)),
               "svgpu_sim3_transform_optimize")
     res = dict(sim3=out, num_inliers=int(inl.value), status=status[:n].copy())
     for k, _ in _Sim3OptStats._fields_:

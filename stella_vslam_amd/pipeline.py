@@ -6,11 +6,9 @@ PyTorch is only the owner of the HBM buffers and streams here (the data path is 
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
-from ._lib import lib
+from ._lib import lib, ptr as _p
 from .feature import Context, orb_params
 
 KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"), ("octave", "<i4"), ("class_id", "<i4")])
@@ -26,8 +24,8 @@ class BatchExtractor:
         self.W, self.H, self.B = width, height, batch
         L = lib()
         p = self.params
-        self.ctx.check(L.svgpu_orb_configure(self.ctx.handle, width, height, batch, C.c_float(p.scale_factor_), p.num_levels_, p.ini_fast_thr_,
-                                             p.min_fast_thr_, C.c_uint(min_area)), "svgpu_orb_configure")
+        self.ctx.check(L.svgpu_orb_configure(self.ctx.handle, width, height, batch, p.scale_factor_, p.num_levels_, p.ini_fast_thr_,
+                                             p.min_fast_thr_, min_area), "svgpu_orb_configure")
         self.cap = L.svgpu_orb_max_keypoints(self.ctx.handle)
         self.nc = 1 + p.num_levels_
         self.stream = torch.cuda.ExternalStream(self.ctx.stream)
@@ -47,9 +45,8 @@ class BatchExtractor:
 
     def extract(self):
         """Asynchronous on the context's stream."""
-        self.ctx.check(lib().svgpu_orb_extract_batch_device(self.ctx.handle, C.c_void_p(self.frames.data_ptr()), self.B, C.c_size_t(self.W * self.H), self.W,
-                                                           None, C.c_size_t(0), 0, C.c_void_p(self.kps.data_ptr()), C.c_void_p(self.desc.data_ptr()), self.cap,
-                                                           C.c_void_p(self.counts.data_ptr()), None), "svgpu_orb_extract_batch_device")
+        self.ctx.check(lib().svgpu_orb_extract_batch_device(self.ctx.handle, _p(self.frames), self.B, self.W * self.H, self.W, None, 0, 0,
+                                                           _p(self.kps), _p(self.desc), self.cap, _p(self.counts), None), "svgpu_orb_extract_batch_device")
 
     def download(self):
         """[(keypoints structured array, descriptors n x 32)] per frame (synchronises)."""
@@ -69,9 +66,7 @@ def stereo_batch(left: BatchExtractor, right: BatchExtractor, focal_x_baseline: 
     if out is None:
         with torch.cuda.stream(left.stream):
             out = (torch.empty(left.B * left.cap, dtype=torch.float32, device="cuda"), torch.empty(left.B * left.cap, dtype=torch.float32, device="cuda"))
-    left.ctx.check(lib().svgpu_stereo_match_batch_device(left.ctx.handle, right.ctx.handle, left.B, C.c_void_p(left.kps.data_ptr()), C.c_void_p(left.desc.data_ptr()),
-                                                         C.c_void_p(left.counts.data_ptr()), C.c_void_p(right.kps.data_ptr()), C.c_void_p(right.desc.data_ptr()),
-                                                         C.c_void_p(right.counts.data_ptr()), left.cap, left.nc, C.c_float(focal_x_baseline),
-                                                         C.c_float(true_baseline), C.c_void_p(out[0].data_ptr()), C.c_void_p(out[1].data_ptr()),
-                                                         None if stream is None else C.c_void_p(stream)), "svgpu_stereo_match_batch_device")
+    left.ctx.check(lib().svgpu_stereo_match_batch_device(left.ctx.handle, right.ctx.handle, left.B, _p(left.kps), _p(left.desc), _p(left.counts),
+                                                         _p(right.kps), _p(right.desc), _p(right.counts), left.cap, left.nc, focal_x_baseline,
+                                                         true_baseline, _p(out[0]), _p(out[1]), stream), "svgpu_stereo_match_batch_device")
     return out

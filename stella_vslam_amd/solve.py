@@ -3,16 +3,10 @@
 util::create_random_array from a std::mt19937)."""
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
-from ._lib import lib
+from ._lib import lib, ptr as _p
 from .feature import Context
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 def compute_pose(ctx: Context, bearings, pos_w, set_off=None, gauss_newton_num_iter=10):

@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import camera as _camera
-from ._lib import lib
+from ._lib import lib, ptr as _p
 from .data import resident_frame
 from .feature import KEYPOINT_DTYPE, Context
 
@@ -19,10 +19,6 @@ LM_PRESENT, LM_HAS_OBSERVATION, LM_HAS_DESCRIPTOR = 1, 2, 4
 LANDMARK_RECORD_DTYPE = np.dtype([("pos_w", "<f8", 3), ("mean_normal", "<f8", 3), ("min_valid_dist", "<f4"), ("max_valid_dist", "<f4"),
                                   ("descriptor", "u1", 32), ("flags", "<u4"), ("reserved", "<u4")])
 assert LANDMARK_RECORD_DTYPE.itemsize == 96
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 def landmark_records(pos_w, mean_normal, min_valid_dist, max_valid_dist, descriptor, flags=None) -> np.ndarray:
@@ -121,10 +117,8 @@ class tracker:
     def set_ingest(self, ingest_left=None, ingest_right=None, depth_type: int = 0, depthmap_factor: float = 1.0):
         """svgpu_tracker_set_ingest: afterwards `img` / `img_left` / `img_right` / `depth` of the track_motion* calls are RAW frames in the ingests'
         input formats (ingest.Ingest; a uint16 / float32 depth map with depth_type = ingest.DEPTH_U16 / DEPTH_F32).  None / 0 = that input stays as it was."""
-        from . import ingest as _ingest
-        L = _ingest._bind()
-        self.ctx.check(L.svgpu_tracker_set_ingest(self._h, ingest_left._h if ingest_left is not None else None, ingest_right._h if ingest_right is not None else None,
-                                                  int(depth_type), float(depthmap_factor)), "svgpu_tracker_set_ingest")
+        self.ctx.check(lib().svgpu_tracker_set_ingest(self._h, ingest_left._h if ingest_left is not None else None, ingest_right._h if ingest_right is not None else None,
+                                                      int(depth_type), float(depthmap_factor)), "svgpu_tracker_set_ingest")
         self._ingest = (ingest_left, ingest_right)   # (kept alive: the tracker reads them at every call)
         self._depth_type = int(depth_type)
         return self
@@ -145,14 +139,14 @@ class tracker:
             kps, desc = np.zeros(cap, KEYPOINT_DTYPE), np.zeros((cap, 32), np.uint8)
             und, brg = np.zeros(cap, KEYPOINT_DTYPE), np.zeros((cap, 3), np.float64)
             outl = np.zeros(cap, np.uint8)
-            self.ctx.check(lib().svgpu_track_motion(self._h, cur._h, _p(im), im.strides[0], last._h, _p(ids), _p(guess), _p(plast), C.c_float(margin),
+            self.ctx.check(lib().svgpu_track_motion(self._h, cur._h, _p(im), im.strides[0], last._h, _p(ids), _p(guess), _p(plast), margin,
                                                     int(check_orientation), _p(kps), _p(desc), _p(und), _p(brg), cap, _p(match), _p(outl), C.byref(res)),
                            "svgpu_track_motion")
             n = res.n_keypoints
             out.update(keypts=kps[:n].copy(), descriptors=desc[:n].copy(), undist_keypts=und[:n].copy(), bearings=brg[:n].copy())
         else:
             outl = np.zeros(max(cur.size, 1), np.uint8)
-            self.ctx.check(lib().svgpu_track_motion(self._h, cur._h, None, 0, last._h, _p(ids), _p(guess), _p(plast), C.c_float(margin), int(check_orientation),
+            self.ctx.check(lib().svgpu_track_motion(self._h, cur._h, None, 0, last._h, _p(ids), _p(guess), _p(plast), margin, int(check_orientation),
                                                     None, None, None, None, 0, _p(match), _p(outl), C.byref(res)), "svgpu_track_motion")
             n = cur.size
         out.update(match_last=match[:len(ids)].copy(), outlier=outl[:n].copy(), result=res.as_dict())
@@ -182,11 +176,11 @@ class tracker:
             dm = np.ascontiguousarray(depth, (np.uint16 if raw_depth == 1 else np.float32))
             assert dm.shape == il.shape[:2]
             self.ctx.check(lib().svgpu_track_motion_rgbd(self._h, cur._h, _p(il), il.strides[0], _p(dm), dm.strides[0] if raw_depth else dm.strides[0] // 4, last._h, _p(ids), _p(guess), _p(plast),
-                                                         C.c_float(margin), int(check_orientation), cap, _p(match), _p(outl), C.byref(res)), "svgpu_track_motion_rgbd")
+                                                         margin, int(check_orientation), cap, _p(match), _p(outl), C.byref(res)), "svgpu_track_motion_rgbd")
         else:
             ir = np.ascontiguousarray(img_right, np.uint8)
             self.ctx.check(lib().svgpu_track_motion_stereo(self._h, ctx_right.handle, cur._h, _p(il), il.strides[0], _p(ir), ir.strides[0], last._h, _p(ids), _p(guess),
-                                                           _p(plast), C.c_float(margin), int(check_orientation), cap, _p(match), _p(outl), C.byref(res)),
+                                                           _p(plast), margin, int(check_orientation), cap, _p(match), _p(outl), C.byref(res)),
                            "svgpu_track_motion_stereo")
         n = res.n_keypoints
         pk, pd, pu, pb, px, pz = (C.c_void_p() for _ in range(6))
@@ -212,8 +206,8 @@ class tracker:
         match, vis = np.full(max(len(li), 1), -1, np.int32), np.zeros(max(len(li), 1), np.uint8)
         outl = np.zeros(max(cur.size, 1), np.uint8)
         res = _TrackResult()
-        self.ctx.check(lib().svgpu_track_local_map(self._h, cur._h, _p(cl), len(li), _p(li), _p(pose), C.c_float(margin), C.c_float(lowe_ratio),
-                                                   C.c_float(ray_cos_thr), _p(match), _p(vis), _p(outl), C.byref(res)), "svgpu_track_local_map")
+        self.ctx.check(lib().svgpu_track_local_map(self._h, cur._h, _p(cl), len(li), _p(li), _p(pose), margin, lowe_ratio,
+                                                   ray_cos_thr, _p(match), _p(vis), _p(outl), C.byref(res)), "svgpu_track_local_map")
         self._n_local = len(li)
         return dict(match_local=match[:len(li)].copy(), visible=vis[:len(li)].copy(), outlier=outl[:cur.size].copy(), result=res.as_dict())
 

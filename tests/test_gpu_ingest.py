@@ -369,7 +369,7 @@ def test_refusals_launch_nothing(ctx):
     stride below a row, a stereo pair of different geometry: status 1, and neither the profiler nor the tracker counts a launch"""
     from stella_vslam_amd import camera, data, feature, ingest, synthetic, tracking
     from stella_vslam_amd._lib import lib
-    L = ingest._bind()
+    L = lib()
     w, h = 640, 480
     assert L.svgpu_profile_select(ctx.handle, b"k_ingest_gray") == 0
     hnd = C.c_void_p()

@@ -274,7 +274,6 @@ def test_invalid_arguments_are_refused_before_any_launch(ctx):
 def test_profile_knows_the_kernel_classes():
     from stella_vslam_amd._lib import lib
     L = lib()
-    L.svgpu_profile_kernels.restype = C.c_char_p
     names = L.svgpu_profile_kernels().decode().split(",")
     assert {"k_pnp_pose", "k_pnp_ransac", "k_pnp_select"} <= set(names)
 

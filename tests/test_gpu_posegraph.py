@@ -202,7 +202,6 @@ def test_empty_graphs_and_bad_landmark_references_are_refused(ctx):
 def test_profiling_classes_are_registered():
     from stella_vslam_amd._lib import lib
     L = lib()
-    L.svgpu_profile_kernels.restype = C.c_char_p
     names = L.svgpu_profile_kernels().decode().split(",")
     assert {"k_pg_linearize", "k_pg_assemble", "k_pg_solve", "k_pg_trial", "k_pg_correct_landmarks"} <= set(names)
 

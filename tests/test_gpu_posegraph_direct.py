@@ -216,7 +216,6 @@ def test_bad_options_are_refused_before_any_launch(ctx, options):
 def test_profiling_classes_are_registered():
     from stella_vslam_amd._lib import lib
     L = lib()
-    L.svgpu_profile_kernels.restype = C.c_char_p
     assert set(PG_CLASSES) <= set(L.svgpu_profile_kernels().decode().split(","))
 
 

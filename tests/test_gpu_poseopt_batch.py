@@ -239,7 +239,6 @@ def test_mirror_rejects_disagreeing_lengths(ctx):
 def test_kernel_is_listed_for_profiling():
     from stella_vslam_amd._lib import lib
     L = lib()
-    L.svgpu_profile_kernels.restype = C.c_char_p
     assert "k_pose_opt_batch" in L.svgpu_profile_kernels().decode().split(",")
 
 

@@ -205,7 +205,6 @@ def test_profiling_class_is_registered():
     import ctypes as C
     from stella_vslam_amd._lib import lib
     L = lib()
-    L.svgpu_profile_kernels.restype = C.c_char_p
     assert "k_sim3_opt" in L.svgpu_profile_kernels().decode().split(",")
 
 

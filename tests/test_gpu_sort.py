@@ -12,7 +12,6 @@ def _run(ctx, L, values=None, keys=None, bits=32):
     scan = np.zeros(n + 1, np.int32) if values is not None else None
     idx = np.zeros(max(n, 1), np.int32) if keys is not None else None
     p = lambda a: None if a is None else C.c_void_p(a.ctypes.data)
-    L.svgpu_selftest_scan_sort.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     rc = L.svgpu_selftest_scan_sort(ctx.handle, n, p(values), p(scan), p(keys), bits, p(idx))
     ctx.check(rc, "svgpu_selftest_scan_sort")
     return scan, idx

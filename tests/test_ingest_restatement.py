@@ -19,8 +19,8 @@ def _ingest_names():
 
 
 def test_header_names_are_exported_and_refuse_without_a_device():
-    from stella_vslam_amd import ingest
-    L = ingest._bind()
+    from stella_vslam_amd._lib import lib
+    L = lib()
     names = _ingest_names()
     assert {"svgpu_ingest_create", "svgpu_ingest_destroy", "svgpu_ingest_gray", "svgpu_ingest_gray_batch_device", "svgpu_ingest_depth",
             "svgpu_ingest_depth_device", "svgpu_tracker_set_ingest"} <= set(names)

@@ -116,8 +116,8 @@ def test_header_declares_the_symbol_and_the_mirror_sets_its_argtypes():
     assert m is not None
     args = [a for a in re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S).split(",") if a.strip()]
     assert len(args) == 19
-    lib_py = (ROOT / "stella_vslam_amd" / "_lib.py").read_text()
-    assert "svgpu_pose_optimize_batch.argtypes" in lib_py and "svgpu_pose_optimize_batch.restype" in lib_py
+    import ctypes as C
     from stella_vslam_amd import _lib
     fn = _lib.lib().svgpu_pose_optimize_batch
-    assert len(fn.argtypes) == 19
+    vp, i32 = C.c_void_p, C.c_int
+    assert fn.restype is C.c_int and fn.argtypes == [vp, i32] + [vp] * 9 + [i32] * 4 + [vp] * 4
