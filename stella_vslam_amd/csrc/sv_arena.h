@@ -19,6 +19,10 @@ struct Piece {
     size_t bytes() const { return n * sizeof(T); }
 };
 
+// an optional array the caller did not pass is no piece: its pointer stays null (A: Arena or a type layered on it)
+template <class T, class A>
+Piece<T> optional_piece(A& arena, bool present, size_t n) { return present ? arena.template piece<T>(n) : Piece<T>{}; }
+
 struct Arena {
     char* base = nullptr;
     size_t cap = 0, off = 0;

@@ -3,8 +3,8 @@
 // halves; StagedCall owns the sequence.
 #pragma once
 #include <algorithm>
+#include <cassert>
 #include <cstring>
-#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -14,7 +14,7 @@
 // mirror at its arena offset and ONE host-to-device copy of the touched range follows (flush) -- the runtime turns every small copy from
 // pageable memory into a staging kernel of its own (~5 us each on the stream: ten of them per cell-matcher call were half of what the call
 // waited for).  Device-only pieces inside the range receive stale bytes, harmlessly: the kernels that produce them run behind the copy.
-// On a measuring arena upload / put / flush do nothing.
+// Without a mirror (the bucket matcher's calls) every upload is a copy of its own.  On a measuring arena upload / flush do nothing.
 struct UploadArena : Arena {
     char* mirror = nullptr;
     size_t up_lo = ~size_t(0), up_hi = 0;
@@ -32,14 +32,6 @@ struct UploadArena : Arena {
         up_hi = std::max(up_hi, o + bytes);
         return SVGPU_OK;
     }
-    // take n elements for an optional host array and, when `fresh`, upload it; no source: no piece, null.  The first failure stays in `rc`.
-    template <class T>
-    T* put(svgpu_ctx* ctx, hipStream_t s, const T* src, size_t n, bool fresh, int& rc) {
-        if (!src) return nullptr;
-        T* dst = take<T>(n);
-        if (fresh && !rc) rc = upload(ctx, s, dst, src, n * sizeof(T));
-        return dst;
-    }
     int flush(svgpu_ctx* ctx, hipStream_t s) {
         if (mirror && up_hi > up_lo) SV_HIP(ctx, hipMemcpyAsync(base + up_lo, mirror + up_lo, up_hi - up_lo, hipMemcpyHostToDevice, s));
         up_lo = ~size_t(0), up_hi = 0;
@@ -49,7 +41,8 @@ struct UploadArena : Arena {
 
 // Batched read-backs, the counterpart of UploadArena::upload: results that live in the arena are requested with add(), fetch() copies the
 // range(s) that cover them into the page-locked mirror (requests closer than 32 KB share one copy: sv_merge_ranges), and after the stream
-// has been synchronised scatter() hands them to the caller's arrays (an item without a destination stays in the mirror).
+// has been synchronised scatter() hands them to the caller's arrays (an item without a destination stays in the mirror).  Without a
+// mirror fetch() copies every item straight to its destination, in request order, and scatter() has nothing left to do.
 struct Downloads {
     struct Item {
         void* dst;
@@ -65,11 +58,16 @@ struct Downloads {
         if (bytes) items.push_back({dst, (size_t)((const char*)src - A.base), bytes});
     }
     int fetch(svgpu_ctx* ctx, hipStream_t s, const UploadArena& A) {
+        if (!A.mirror) {
+            for (const Item& it : items) SV_HIP(ctx, hipMemcpyAsync(it.dst, A.base + it.off, it.bytes, hipMemcpyDeviceToHost, s));
+            return SVGPU_OK;
+        }
         for (const auto& [lo, hi] : sv_merge_ranges(items, 32768))
             SV_HIP(ctx, hipMemcpyAsync(A.mirror + lo, A.base + lo, hi - lo, hipMemcpyDeviceToHost, s));
         return SVGPU_OK;
     }
     void scatter(const UploadArena& A) const {
+        if (!A.mirror) return;
         for (const Item& it : items)
             if (it.dst) memcpy(it.dst, A.mirror + it.off, it.bytes);
     }
@@ -87,21 +85,42 @@ struct StagedCall {
     Downloads D;
     int rc = SVGPU_OK;  // the first failure of an up(), or a count beyond its piece
 
-    // `layout(UploadArena&)` returns void, or an int status (the layouts that upload as they take, through UploadArena::put): that of the
-    // placing run is returned as it is
+    const char* overflow_msg = "";
+    bool mirrored = true;
+
+    // `mirrored == false`: no page-locked mirror is asked for; up() is a copy of its own per array and down() one per result, straight
+    // to the caller's array (keep / stage assert a mirror: there is none to read them in)
     template <class Layout>
-    int open(svgpu_ctx* ctx_, const char* overflow_msg, Layout&& layout) {
+    int open(svgpu_ctx* ctx_, const char* overflow_msg_, Layout&& layout, bool mirrored_ = true) {
         ctx = ctx_;
+        overflow_msg = overflow_msg_;
+        mirrored = mirrored_;
         SV_HIP(ctx, hipSetDevice(ctx->device));
         s = ctx->stream;
+        bool survived;
+        return reopen(layout, survived);
+    }
+    // A further pass of the same call under another layout: measures, grows scratch and mirror, places.  `survived`: the scratch arena
+    // did not regrow, so what the passes before left in it is still there (for the pieces the new layout places where the old one did).
+    // Upload range and read-back requests start empty.
+    template <class Layout>
+    int reopen(Layout&& layout, bool& survived) {
         const size_t need = arena_measure<UploadArena>(layout);
+        survived = need <= ctx->scratch_bytes;
         int r;
         if ((r = sv_ensure_scratch(ctx, need))) return r;
-        if ((r = sv_ensure_stage(ctx, need))) return r;
-        A = UploadArena(ctx, ctx->h_stage);
-        if constexpr (std::is_void_v<decltype(layout(A))>) layout(A);
-        else if ((r = layout(A))) return r;
+        if (mirrored && (r = sv_ensure_stage(ctx, need))) return r;
+        A = UploadArena(ctx, mirrored ? ctx->h_stage : nullptr);
+        D.items.clear();
+        layout(A);
         return A.overflow ? sv_set_error(ctx, SVGPU_ERR_INVALID, overflow_msg) : SVGPU_OK;
+    }
+    // one small value in the middle of the call, with a synchronisation of its own (the candidate total of a two-pass matcher)
+    template <class T>
+    int read_now(T* dst, const T* src) {
+        SV_HIP(ctx, hipMemcpyAsync(dst, src, sizeof(T), hipMemcpyDeviceToHost, s));
+        SV_HIP(ctx, hipStreamSynchronize(s));
+        return SVGPU_OK;
     }
     template <class T>
     void up(T* dst, const T* src, size_t count) {
@@ -111,6 +130,8 @@ struct StagedCall {
     void up(Piece<T> dst, const T* src) { up(dst.p, src, dst.n); }
     template <class T>
     void up(Piece<T> dst, const T* src, size_t count) { if (fits(count, dst.n)) up(dst.p, src, count); }
+    template <class T, class U, class... More>  // several whole pieces, as (piece, source) pairs, in the order written
+    void up(Piece<T> dst, const T* src, Piece<U> dst2, const U* src2, More... more) { up(dst, src), up(dst2, src2, more...); }
     int flush() { return rc ? rc : A.flush(ctx, s); }
     // the place of an arena piece in the mirror
     template <class T>
@@ -120,6 +141,7 @@ struct StagedCall {
     // the same for a piece the caller fills there itself: its bytes travel with the next flush
     template <class T>
     T* stage(T* dev, size_t count) {
+        assert(mirrored);
         const size_t o = (size_t)((char*)dev - A.base);
         A.up_lo = std::min(A.up_lo, o);
         A.up_hi = std::max(A.up_hi, o + count * sizeof(T));
@@ -134,6 +156,7 @@ struct StagedCall {
     // a result wanted in the mirror only: after finish() the caller reads it at host(src)
     template <class T>
     void keep(const T* src, size_t count) {
+        assert(mirrored);
         D.keep(A, src, count * sizeof(T));
     }
     template <class T>

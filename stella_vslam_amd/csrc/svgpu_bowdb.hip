@@ -145,22 +145,22 @@ int query_core(svgpu_ctx* ctx, svgpu_bowdb* db, const char* who, int Q, const in
         for (int i = 0; list && i < n_list; ++i) out_score[i] = -1.0f;
         return SVGPU_OK;
     }
-    hipStream_t s = ctx->stream;
     const size_t total = (size_t)q_off[Q], per = (size_t)Q * items;
     BowdbProblem P{};
-    const int32_t* d_rej_list = nullptr;
+    Piece<int32_t> d_off, d_rej_list, d_list;
+    Piece<uint32_t> d_ids;
+    Piece<double> d_w;
+    Piece<float> d_min;
     uint8_t* zero_lo = nullptr;
     size_t zero_bytes = 0;
     StagedCall C;
-    int rc = C.open(ctx, "svgpu_bowdb: internal arena overflow", [&](UploadArena& A) -> int {
-        int rc = SVGPU_OK;
-        P.q_off = A.put(ctx, s, q_off, (size_t)Q + 1, true, rc);
-        P.q_ids = A.put(ctx, s, words, total, true, rc);
-        P.q_w = A.put(ctx, s, weights, total, true, rc);
-        P.min_score = A.put(ctx, s, min_score, Q, true, rc);
-        d_rej_list = A.put(ctx, s, reject_slots, n_reject, true, rc);
-        P.list = A.put(ctx, s, list, n_list, true, rc);
-        if (!rc) rc = A.flush(ctx, s);
+    int rc = C.open(ctx, "svgpu_bowdb: internal arena overflow", [&](UploadArena& A) {
+        P.q_off = d_off = A.piece<int32_t>((size_t)Q + 1);
+        P.q_ids = d_ids = optional_piece<uint32_t>(A, words, total);
+        P.q_w = d_w = optional_piece<double>(A, weights, total);
+        P.min_score = d_min = optional_piece<float>(A, min_score, Q);
+        d_rej_list = optional_piece<int32_t>(A, reject_slots, n_reject);
+        P.list = d_list = optional_piece<int32_t>(A, list, n_list);
         // zeroed in one go: the reject bytes and the maxima
         uint8_t* rej = A.take<uint8_t>(ns);
         P.max_common = A.take<uint32_t>(Q);
@@ -175,9 +175,11 @@ int query_core(svgpu_ctx* ctx, svgpu_bowdb* db, const char* who, int Q, const in
         P.out_slots = A.take<int32_t>((size_t)Q * cap);
         P.out_common = A.take<uint32_t>((size_t)Q * cap);
         P.out_score = A.take<float>((size_t)Q * cap);
-        return rc;
     });
     if (rc) return rc;
+    hipStream_t s = C.s;
+    C.up(d_off, q_off, d_ids, words, d_w, weights, d_min, min_score, d_rej_list, reject_slots, d_list, list);
+    if ((rc = C.flush())) return rc;
     P.pool_ids = db->d_ids, P.pool_w = db->d_w, P.slots = db->d_slots;
     P.num_slots = ns, P.score_form = db->score_form, P.num_queries = Q, P.ratio = ratio, P.num_list = n_list, P.cap = cap;
     if (!list) {

@@ -211,42 +211,40 @@ int svgpu_match_candidates(svgpu_ctx* ctx, const uint8_t* qdesc, int nq, const u
         if (cand_off[q + 1] < cand_off[q]) return sv_set_error(ctx, SVGPU_ERR_INVALID, "cand_off not monotone");
     for (int c = 0; c < nc; ++c)
         if (cand_idx[c] < 0 || cand_idx[c] >= nt) return sv_set_error(ctx, SVGPU_ERR_INVALID, "cand_idx out of range");
-    hipStream_t s = ctx->stream;
     CandProblem P{};
+    Piece<uint8_t> d_qdesc, d_tdesc, d_skip, d_qvalid, d_occ;
+    Piece<int32_t> d_toct, d_off, d_idx;
+    Piece<float> d_qang, d_tang, d_qxr, d_txr, d_qtol;
     int *owner, *match;
     unsigned* mdist;
     StagedCall C;
-    int rc = C.open(ctx, "svgpu_match_candidates: internal arena overflow", [&](UploadArena& A) -> int {
-        int rc = SVGPU_OK;
-        P.qdesc = (const uint32_t*)A.put(ctx, s, qdesc, (size_t)nq * 32, true, rc);
-        P.tdesc = (const uint32_t*)A.put(ctx, s, tdesc, (size_t)nt * 32, true, rc);
-        P.t_octave = A.put(ctx, s, t_octave, nt, true, rc);
-        P.cand_off = A.put(ctx, s, cand_off, nq + 1, true, rc);
-        P.cand_idx = A.put(ctx, s, cand_idx, nc, true, rc);
-        P.cand_skip = A.put(ctx, s, cand_skip, nc, true, rc);
-        P.q_valid = A.put(ctx, s, q_valid, nq, true, rc);
-        P.occupied = A.put(ctx, s, occupied, nt, true, rc);
-        P.q_angle = A.put(ctx, s, q_angle, nq, true, rc);
-        P.t_angle = A.put(ctx, s, t_angle, nt, true, rc);
-        P.q_xright = A.put(ctx, s, q_xright, nq, true, rc);
-        P.t_xright = A.put(ctx, s, t_xright, nt, true, rc);
-        P.q_xr_tol = A.put(ctx, s, q_xr_tol, nq, true, rc);
+    int rc = C.open(ctx, "svgpu_match_candidates: internal arena overflow", [&](UploadArena& A) {
+        P.qdesc = (const uint32_t*)(d_qdesc = A.piece<uint8_t>((size_t)nq * 32)).p;  // (descriptors, offsets and indices were checked above)
+        P.tdesc = (const uint32_t*)(d_tdesc = A.piece<uint8_t>((size_t)nt * 32)).p;
+        P.t_octave = d_toct = optional_piece<int32_t>(A, t_octave, nt);
+        P.cand_off = d_off = A.piece<int32_t>((size_t)nq + 1);
+        P.cand_idx = d_idx = A.piece<int32_t>(nc);
+        P.cand_skip = d_skip = optional_piece<uint8_t>(A, cand_skip, nc);
+        P.q_valid = d_qvalid = optional_piece<uint8_t>(A, q_valid, nq);
+        P.occupied = d_occ = optional_piece<uint8_t>(A, occupied, nt);
+        P.q_angle = d_qang = optional_piece<float>(A, q_angle, nq);
+        P.t_angle = d_tang = optional_piece<float>(A, t_angle, nt);
+        P.q_xright = d_qxr = optional_piece<float>(A, q_xright, nq);
+        P.t_xright = d_txr = optional_piece<float>(A, t_xright, nt);
+        P.q_xr_tol = d_qtol = optional_piece<float>(A, q_xr_tol, nq);
         P.dist = A.take<uint32_t>(nc);
         P.match_q = A.take<int32_t>(nq);
         P.num = A.take<int32_t>(1);
         owner = A.take<int>(nt);
         match = A.take<int>(nq);
         mdist = A.take<unsigned>(nt);
-        return rc;
     });
     if (rc) return rc;
+    hipStream_t s = C.s;
+    C.up(d_qdesc, qdesc, d_tdesc, tdesc, d_toct, t_octave, d_off, cand_off, d_idx, cand_idx, d_skip, cand_skip, d_qvalid, q_valid, d_occ, occupied);
+    C.up(d_qang, q_angle, d_tang, t_angle, d_qxr, q_xright, d_txr, t_xright, d_qtol, q_xr_tol);
     if ((rc = C.flush())) return rc;
-    P.nq = nq;
-    P.nt = nt;
-    P.check_orientation = check_orientation;
-    P.thr = thr;
-    P.lowe_ratio = lowe_ratio;
-    P.mode = mode;
+    P.nq = nq, P.nt = nt, P.check_orientation = check_orientation, P.thr = thr, P.lowe_ratio = lowe_ratio, P.mode = mode;
     sv_launch_cand(ctx, s, P, owner, match, mdist);
     int32_t num = 0;
     C.down(match_q, P.match_q, nq);
@@ -291,24 +289,23 @@ int svgpu_match_in_cells(svgpu_ctx* ctx, const uint8_t* qdesc, int nq, const flo
         return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_match_in_cells: inconsistent inputs");
     InCellsFrame F{tdesc, t_xy, t_octave, nt, occupied, t_angle, t_xright, min_x, max_x, min_y, max_y, grid_cols, grid_rows};
     F.res = rf;
-    hipStream_t s = ctx->stream;
+    const CellQuery S{qdesc, q_xy, q_margin, q_min_level, q_max_level, q_valid, q_angle, q_xright, q_xr_tol, q_blocks};
+    CellQueryPieces Q;
     return in_cells_core(
         ctx, nq, F, check_orientation, thr, lowe_ratio, mode,
-        [&](UploadArena& A, bool fresh, CandProblem& P, GridProblem& G) -> int {
-            int rc = SVGPU_OK;
-            P.qdesc = (const uint32_t*)A.put(ctx, s, qdesc, (size_t)nq * 32, fresh, rc);
-            G.q_xy = A.put(ctx, s, q_xy, (size_t)nq * 2, fresh, rc);
-            G.q_margin = A.put(ctx, s, q_margin, nq, fresh, rc);
-            G.q_min_level = A.put(ctx, s, q_min_level, nq, fresh, rc);
-            G.q_max_level = A.put(ctx, s, q_max_level, nq, fresh, rc);
-            G.q_valid = P.q_valid = A.put(ctx, s, q_valid, nq, fresh, rc);
-            P.q_angle = A.put(ctx, s, q_angle, nq, fresh, rc);
-            P.q_xright = A.put(ctx, s, q_xright, nq, fresh, rc);
-            P.q_xr_tol = A.put(ctx, s, q_xr_tol, nq, fresh, rc);
-            P.q_blocks = A.put(ctx, s, q_blocks, nq, fresh, rc);
-            return rc;
+        [&](UploadArena& A, CandProblem& P, GridProblem& G) {
+            cell_query_layout(A, nq, S, Q);
+            P.qdesc = (const uint32_t*)Q.desc.p;
+            G.q_xy = Q.xy, G.q_margin = Q.margin, G.q_min_level = Q.min_level, G.q_max_level = Q.max_level;
+            G.q_valid = P.q_valid = Q.valid;
+            P.q_angle = Q.angle, P.q_xright = Q.xright, P.q_xr_tol = Q.xr_tol, P.q_blocks = Q.blocks;
         },
-        [&](const CandProblem&, const UploadArena&, Downloads&) -> int { return SVGPU_OK; }, match_q, num_matches);
+        [&](StagedCall& C) {
+            C.up(Q.desc, S.desc, Q.xy, S.xy, Q.margin, S.margin, Q.min_level, S.min_level, Q.max_level, S.max_level);
+            C.up(Q.valid, S.valid, Q.angle, S.angle, Q.xright, S.xright, Q.xr_tol, S.xr_tol, Q.blocks, S.blocks);
+            return C.flush();
+        },
+        [](StagedCall&) {}, match_q, num_matches);
 }
 
 int svgpu_camera_image_bounds(svgpu_ctx* ctx, svgpu_camera* cam) {
@@ -455,19 +452,6 @@ int fill_reproj(svgpu_ctx* ctx, const char* who, ReprojProblem& R, const svgpu_c
     R.log_scale_factor = log_scale_factor;
     return SVGPU_OK;
 }
-// The landmark side of a reprojection in the arena: inputs (uploaded when `fresh`) and observability outputs.
-void take_reproj(svgpu_ctx* ctx, hipStream_t s, UploadArena& A, bool fresh, ReprojProblem& R, int n, const double* pos_w, const double* mean_normal,
-                 const float* min_valid_dist, const float* max_valid_dist, const uint8_t* skip, int& rc) {
-    R.pos_w = A.put(ctx, s, pos_w, (size_t)n * 3, fresh, rc);
-    R.mean_normal = A.put(ctx, s, mean_normal, (size_t)n * 3, fresh, rc);
-    R.min_valid_dist = A.put(ctx, s, min_valid_dist, n, fresh, rc);
-    R.max_valid_dist = A.put(ctx, s, max_valid_dist, n, fresh, rc);
-    R.skip = A.put(ctx, s, skip, n, fresh, rc);
-    R.visible = A.take<uint8_t>(n);
-    R.reproj = A.take<double>((size_t)n * 2);
-    R.x_right = A.take<float>(n);
-    R.pred_level = A.take<int32_t>(n);
-}
 }  // namespace
 
 extern "C" {
@@ -483,21 +467,16 @@ int svgpu_reproject_landmarks(svgpu_ctx* ctx, const svgpu_camera* cam, const dou
     if (rc) return rc;
     if (n == 0) return SVGPU_OK;
     if (!visible || !reproj || !x_right || !pred_scale_level) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_reproject_landmarks: null output");
-    hipStream_t s = ctx->stream;
     // one upload and one read-back through the page-locked mirror of the arena (StagedCall): nine separate copies from / to pageable
     // memory were nine staging kernels on the stream
+    const ReprojQuery Q{nullptr, pos_w, mean_normal, min_valid_dist, max_valid_dist, skip, nullptr, nullptr, nullptr};
+    ReprojPieces Y;
     StagedCall C;
-    rc = C.open(ctx, "svgpu_reproject_landmarks: internal arena overflow", [&](UploadArena& A) -> int {
-        int ru = SVGPU_OK;
-        take_reproj(ctx, s, A, true, R, n, pos_w, mean_normal, min_valid_dist, max_valid_dist, skip, ru);
-        return ru ? ru : A.flush(ctx, s);
-    });
+    rc = C.open(ctx, "svgpu_reproject_landmarks: internal arena overflow", [&](UploadArena& A) { reproj_layout(A, (size_t)n, Q, false, Y); });
     if (rc) return rc;
-    sv_launch_reproject(s, R);
-    C.down(visible, R.visible, n);
-    C.down(reproj, R.reproj, 2 * (size_t)n);
-    C.down(x_right, R.x_right, n);
-    C.down(pred_scale_level, R.pred_level, n);
+    reproj_bind(Y, R);
+    if ((rc = reproj_first(C, Q, Y, R))) return rc;
+    reproj_down(C, Y, visible, reproj, x_right, pred_scale_level);
     return C.finish();
 }
 
@@ -534,43 +513,19 @@ int svgpu_match_frame_and_landmarks(svgpu_ctx* ctx, const svgpu_camera* cam, con
     for (int l = 0; l < num_levels; ++l) R.scale_factors[l] = scale_factors[l];
     InCellsFrame F{tdesc, t_xy, t_octave, nt, occupied, nullptr, t_xright, cam->min_x, cam->max_x, cam->min_y, cam->max_y, grid_cols, grid_rows};
     if (rf) F.min_x = rf->min_x, F.max_x = rf->max_x, F.min_y = rf->min_y, F.max_y = rf->max_y, F.res = rf;
-    hipStream_t s = ctx->stream;
+    const ReprojQuery Q{lm_desc, pos_w, mean_normal, min_valid_dist, max_valid_dist, skip, nullptr, nullptr, nullptr};
+    ReprojPieces Y;
     return in_cells_core(
         ctx, n, F, 0, thr, lowe_ratio, SVGPU_MATCH_RATIO_SAME_OCTAVE,
-        [&](UploadArena& A, bool fresh, CandProblem& P, GridProblem& G) -> int {
-            int ru = SVGPU_OK;
-            uint8_t* d_q = A.put(ctx, s, lm_desc, (size_t)n * 32, fresh, ru);
-            take_reproj(ctx, s, A, fresh, R, n, pos_w, mean_normal, min_valid_dist, max_valid_dist, skip, ru);
-            R.q_xy = A.take<float>((size_t)n * 2);
-            R.q_margin = A.take<float>(n);
-            R.q_min_level = A.take<int32_t>(n);
-            R.q_max_level = A.take<int32_t>(n);
-            if (fresh) {  // one batched upload (UploadArena::put / flush), then the reprojection that consumes it
-                if (!ru) ru = A.flush(ctx, s);
-                if (ru) return ru;
-                sv_launch_reproject(s, R);
-            }
-            G.q_xy = R.q_xy;
-            G.q_margin = R.q_margin;
-            G.q_min_level = R.q_min_level;
-            G.q_max_level = R.q_max_level;
-            G.q_valid = R.visible;
-            P.qdesc = (const uint32_t*)d_q;
-            P.q_valid = R.visible;
+        [&](UploadArena& A, CandProblem& P, GridProblem& G) {
+            reproj_place(A, Q, Y, R, P, G);
             if (t_xright) {  // projection.cc:57-62: |lm_to_x_right - stereo_x_right| against margin * scale
                 P.q_xright = R.x_right;
                 P.q_xr_tol = R.q_margin;
             }
-            return SVGPU_OK;
         },
-        [&](const CandProblem&, const UploadArena& A, Downloads& D) -> int {
-            D.add(A, visible, R.visible, n);
-            D.add(A, reproj, R.reproj, (size_t)n * 16);
-            D.add(A, x_right, R.x_right, (size_t)n * 4);
-            D.add(A, pred_scale_level, R.pred_level, (size_t)n * 4);
-            return SVGPU_OK;
-        },
-        match_lm, num_matches);
+        [&](StagedCall& C) { return reproj_first(C, Q, Y, R); },
+        [&](StagedCall& C) { reproj_down(C, Y, visible, reproj, x_right, pred_scale_level); }, match_lm, num_matches);
 }
 
 int svgpu_stereo_match(svgpu_ctx* ctx_left, svgpu_ctx* ctx_right, const svgpu_keypoint* kps_left, const uint8_t* desc_left,

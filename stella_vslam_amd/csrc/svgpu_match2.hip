@@ -84,39 +84,12 @@ int proj_match(svgpu_ctx* ctx, const char* who, const svgpu_camera* cam, const d
     }
     InCellsFrame Fq = F;
     if (!O.stereo_gate && !O.chi_gate) Fq.t_xright = nullptr;
-    hipStream_t s = ctx->stream;
+    const ReprojQuery RQ{Q.desc, Q.pos_w, Q.mean_normal, Q.min_valid_dist, Q.max_valid_dist, Q.valid ? skip.data() : nullptr, Q.q_level, Q.q_angle, Q.q_blocks};
+    ReprojPieces Y;
     return in_cells_core(
         ctx, n, Fq, O.check_orientation, O.thr, O.lowe_ratio, O.mode,
-        [&](UploadArena& A, bool fresh, CandProblem& P, GridProblem& G) -> int {
-            int ru = SVGPU_OK;
-            P.qdesc = (const uint32_t*)A.put(ctx, s, Q.desc, (size_t)n * 32, fresh, ru);
-            R.pos_w = A.put(ctx, s, Q.pos_w, (size_t)n * 3, fresh, ru);
-            R.mean_normal = A.put(ctx, s, Q.mean_normal, (size_t)n * 3, fresh, ru);
-            R.min_valid_dist = A.put(ctx, s, Q.min_valid_dist, n, fresh, ru);
-            R.max_valid_dist = A.put(ctx, s, Q.max_valid_dist, n, fresh, ru);
-            R.skip = A.put(ctx, s, Q.valid ? skip.data() : nullptr, n, fresh, ru);
-            R.q_level = A.put(ctx, s, Q.q_level, n, fresh, ru);
-            P.q_angle = A.put(ctx, s, Q.q_angle, n, fresh, ru);
-            P.q_blocks = A.put(ctx, s, Q.q_blocks, n, fresh, ru);
-            R.visible = A.take<uint8_t>(n);
-            R.reproj = A.take<double>((size_t)n * 2);
-            R.x_right = A.take<float>(n);
-            R.pred_level = A.take<int32_t>(n);
-            R.q_xy = A.take<float>((size_t)n * 2);
-            R.q_margin = A.take<float>(n);
-            R.q_min_level = A.take<int32_t>(n);
-            R.q_max_level = A.take<int32_t>(n);
-            if (fresh) {  // one batched upload (UploadArena::put / flush), then the reprojection that consumes it
-                if (!ru) ru = A.flush(ctx, s);
-                if (ru) return ru;
-                sv_launch_reproject(s, R);
-            }
-            G.q_xy = R.q_xy;
-            G.q_margin = R.q_margin;
-            G.q_min_level = R.q_min_level;
-            G.q_max_level = R.q_max_level;
-            G.q_valid = R.visible;
-            P.q_valid = R.visible;
+        [&](UploadArena& A, CandProblem& P, GridProblem& G) {
+            reproj_place(A, RQ, Y, R, P, G);
             P.no_claims = O.no_claims;
             if (O.stereo_gate && F.t_xright) {
                 P.q_xright = R.x_right;
@@ -128,16 +101,9 @@ int proj_match(svgpu_ctx* ctx, const char* who, const svgpu_camera* cam, const d
                 P.q_reproj_xr = R.x_right;
                 for (int l = 0; l < num_levels; ++l) P.inv_level_sigma_sq[l] = O.inv_level_sigma_sq[l];
             }
-            return SVGPU_OK;
         },
-        [&](const CandProblem&, const UploadArena& A, Downloads& D) -> int {
-            D.add(A, visible, R.visible, n);
-            D.add(A, reproj, R.reproj, (size_t)n * 16);
-            D.add(A, x_right, R.x_right, (size_t)n * 4);
-            D.add(A, pred_level, R.pred_level, (size_t)n * 4);
-            return SVGPU_OK;
-        },
-        match_q, num_matches);
+        [&](StagedCall& C) { return reproj_first(C, RQ, Y, R); },
+        [&](StagedCall& C) { reproj_down(C, Y, visible, reproj, x_right, pred_level); }, match_q, num_matches);
 }
 
 // -R^T t and R v + t as the reference writes them (Eigen 3-vectors: ((a0 b0 + a1 b1) + a2 b2); compiled without contraction)
@@ -153,16 +119,6 @@ inline void mat_mul(const double* A, const double* B, double* C) {
 }
 
 // bucketed candidate lists (bucket_kernels.hip) + candidate matcher; match_1to2[i] = side-2 keypoint or -1
-struct BucketSide {
-    const uint8_t* desc;
-    const float* angle;
-    const uint8_t* valid;
-    const int32_t* node;     // nullable on both sides = one bucket
-    const int32_t* octave;   // side 1, triangulation
-    const double* bearings;  // triangulation
-    const float* xright;     // nullable
-    int n;
-};
 int bucket_match(svgpu_ctx* ctx, const char* who, const BucketSide& S1, const BucketSide& S2, const uint8_t* occupied2, int tri, const double* E12,
                  const double* epipole, int valid_epipole, const float* scale_factors, int num_levels, float residual_rad_thr, unsigned thr,
                  float lowe_ratio, int check_orientation, int mode, int32_t* match_1to2, int* num_matches) {
@@ -177,76 +133,19 @@ int bucket_match(svgpu_ctx* ctx, const char* who, const BucketSide& S1, const Bu
     if (tri)
         for (int i = 0; i < n1; ++i)
             if (S1.octave[i] < 0 || S1.octave[i] >= num_levels) return sv_set_error(ctx, SVGPU_ERR_INVALID, who);
-    SV_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
     const size_t sortb = std::max(sv_bucket_sort_bytes(n1), sv_bucket_sort_bytes(n2));
-    // The arena of one pass, described once; with `lists`, the candidate lists of `total` entries behind it.
-    struct Pieces {
-        uint8_t *d_d2, *d_occ;
-        int32_t *d_n1, *d_n2, *match_rows, *d_match, *d_num;
-        unsigned *key1, *key2, *mdist;
-        int *q_idx, *t_sorted, *owner, *match;
-        uint32_t* qdesc_rows;
-        float* qangle_rows;
-        void* sort_scratch;
-    };
-    auto layout = [&](UploadArena& A, bool fresh, bool lists, size_t total, Pieces& Y, BucketProblem& B, CandProblem& P) -> int {
-        int rc = SVGPU_OK;
-        B.desc1 = (const uint32_t*)A.put(ctx, s, S1.desc, (size_t)n1 * 32, fresh, rc);
-        B.desc2 = (const uint32_t*)(Y.d_d2 = A.put(ctx, s, S2.desc, (size_t)n2 * 32, fresh, rc));
-        B.angle1 = A.put(ctx, s, S1.angle, n1, fresh, rc);
-        B.angle2 = A.put(ctx, s, S2.angle, n2, fresh, rc);
-        B.valid1 = A.put(ctx, s, S1.valid, n1, fresh, rc);
-        B.valid2 = A.put(ctx, s, S2.valid, n2, fresh, rc);
-        Y.d_n1 = A.put(ctx, s, S1.node, n1, fresh, rc);
-        Y.d_n2 = A.put(ctx, s, S2.node, n2, fresh, rc);
-        B.octave1 = A.put(ctx, s, S1.octave, n1, fresh, rc);
-        B.bearings1 = A.put(ctx, s, S1.bearings, (size_t)n1 * 3, fresh, rc);
-        B.bearings2 = A.put(ctx, s, S2.bearings, (size_t)n2 * 3, fresh, rc);
-        B.xright1 = A.put(ctx, s, S1.xright, n1, fresh, rc);
-        B.xright2 = A.put(ctx, s, S2.xright, n2, fresh, rc);
-        Y.d_occ = A.put(ctx, s, occupied2, n2, fresh, rc);
-        B.key1 = Y.key1 = A.take<unsigned>(n1);
-        B.q_idx = Y.q_idx = A.take<int>(n1);
-        B.key2 = Y.key2 = A.take<unsigned>(n2);
-        B.t_sorted = Y.t_sorted = A.take<int>(n2);
-        B.row_lo = A.take<int>(n1);
-        B.row_hi = A.take<int>(n1);
-        B.q_valid = A.take<uint8_t>(n1);
-        B.cand_off = A.take<int32_t>(n1 + 1);
-        Y.qdesc_rows = A.take<uint32_t>((size_t)n1 * 8);
-        Y.qangle_rows = A.take<float>(n1);
-        Y.match_rows = A.take<int32_t>(n1);
-        Y.d_match = A.take<int32_t>(n1);
-        Y.d_num = A.take<int32_t>(1);
-        Y.owner = A.take<int>(n2);
-        Y.match = A.take<int>(n1);
-        Y.mdist = A.take<unsigned>(n2);
-        Y.sort_scratch = A.take<char>(sortb);
-        if (lists) {
-            B.cand_idx = A.take<int32_t>(total);
-            P.dist = A.take<uint32_t>(total);
-        }
-        return rc;
-    };
-    int total = 0;
-    for (int pass = 0; pass < 2; ++pass) {
-        Pieces Y{};
-        BucketProblem B{};
-        CandProblem P{};
-        const size_t need = arena_measure<UploadArena>([&](UploadArena& M) { layout(M, false, pass != 0, (size_t)total, Y, B, P); });
-        const bool regrow = need > ctx->scratch_bytes;
-        int rc = sv_ensure_scratch(ctx, need);
-        if (rc) return rc;
-        const bool fresh = !pass || regrow;
-        UploadArena A(ctx);
-        if ((rc = layout(A, fresh, pass != 0, (size_t)total, Y, B, P))) return rc;
-        if (A.overflow) return sv_set_error(ctx, SVGPU_ERR_INVALID, "bucket matcher: internal arena overflow");
-        B.n1 = n1;
-        B.n2 = n2;
-        B.check_orientation = check_orientation;
-        B.tri = tri;
-        B.thr = thr;
+    BucketPieces Y;
+    BucketProblem B;
+    CandProblem P;
+    bool lists = false;
+    int32_t total = 0, num = 0;
+    auto layout = [&](UploadArena& A) {
+        bucket_layout(A, S1, S2, occupied2, sortb, lists, (size_t)total, Y);
+        B = BucketProblem{};
+        B.n1 = n1, B.n2 = n2, B.check_orientation = check_orientation, B.tri = tri, B.thr = thr;
+        B.desc1 = (const uint32_t*)Y.desc1.p, B.desc2 = (const uint32_t*)Y.desc2.p;
+        B.angle1 = Y.angle1, B.angle2 = Y.angle2, B.valid1 = Y.valid1, B.valid2 = Y.valid2;
+        B.octave1 = Y.octave1, B.bearings1 = Y.bearings1, B.bearings2 = Y.bearings2, B.xright1 = Y.xright1, B.xright2 = Y.xright2;
         if (tri) {
             std::memcpy(B.E12, E12, sizeof B.E12);
             std::memcpy(B.epipole, epipole, sizeof B.epipole);
@@ -254,46 +153,46 @@ int bucket_match(svgpu_ctx* ctx, const char* who, const BucketSide& S1, const Bu
             for (int l = 0; l < num_levels; ++l) B.scale_factors[l] = scale_factors[l];
             B.residual_rad_thr = residual_rad_thr;
         }
-        if (fresh) {
-            rc = sv_bucket_sort(ctx, s, Y.d_n1, n1, Y.sort_scratch, sortb, Y.key1, Y.q_idx);
-            if (rc) return rc;
-            rc = sv_bucket_sort(ctx, s, Y.d_n2, n2, Y.sort_scratch, sortb, Y.key2, Y.t_sorted);
-            if (rc) return rc;
-            sv_bucket_rows(s, B);
-            sv_bucket_count(s, B);
-        }
-        if (!pass) {
-            SV_HIP(ctx, hipMemcpyAsync(&total, B.cand_off + n1, 4, hipMemcpyDeviceToHost, s));
-            SV_HIP(ctx, hipStreamSynchronize(s));
-            if (total == 0) return SVGPU_OK;
-            continue;
-        }
-        sv_bucket_fill(s, B);
-        sv_bucket_gather_rows(s, B, Y.qdesc_rows, Y.qangle_rows);
-        P.qdesc = Y.qdesc_rows;
-        P.tdesc = (const uint32_t*)Y.d_d2;
-        P.nq = n1;
-        P.nt = n2;
-        P.cand_off = B.cand_off;
-        P.cand_idx = B.cand_idx;
-        P.q_valid = B.q_valid;
-        P.occupied = Y.d_occ;
+        B.key1 = Y.key1, B.q_idx = Y.q_idx, B.key2 = Y.key2, B.t_sorted = Y.t_sorted, B.row_lo = Y.row_lo, B.row_hi = Y.row_hi;
+        P = CandProblem{};
+        P.q_valid = B.q_valid = Y.q_valid, P.cand_off = B.cand_off = Y.cand_off, P.cand_idx = B.cand_idx = Y.cand_idx;
+        P.qdesc = Y.qdesc_rows, P.tdesc = B.desc2, P.nq = n1, P.nt = n2, P.occupied = Y.occupied2;
         P.check_orientation = 0;  // gated in the scan
-        P.thr = thr;
-        P.lowe_ratio = lowe_ratio;
-        P.mode = mode;
-        P.match_q = Y.match_rows;
-        P.num = Y.d_num;
-        sv_launch_cand(ctx, s, P, Y.owner, Y.match, Y.mdist);
-        SV_HIP(ctx, hipMemsetAsync(Y.d_match, 0xFF, (size_t)n1 * 4, s));
-        sv_bucket_scatter(s, B, Y.match_rows, Y.d_match);
-        SV_HIP(ctx, hipGetLastError());
-        int32_t num = 0;
-        SV_HIP(ctx, hipMemcpyAsync(match_1to2, Y.d_match, (size_t)n1 * 4, hipMemcpyDeviceToHost, s));
-        SV_HIP(ctx, hipMemcpyAsync(&num, Y.d_num, 4, hipMemcpyDeviceToHost, s));
-        SV_HIP(ctx, hipStreamSynchronize(s));
-        *num_matches = num;
-    }
+        P.thr = thr, P.lowe_ratio = lowe_ratio, P.mode = mode;
+        P.dist = Y.dist, P.match_q = Y.match_rows, P.num = Y.num;
+    };
+    StagedCall C;
+    auto count = [&]() -> int {  // uploads, sorts, rows and the candidate count: pass 0, and again if the arena regrew for the lists
+        C.up(Y.desc1, S1.desc, Y.desc2, S2.desc, Y.angle1, S1.angle, Y.angle2, S2.angle, Y.valid1, S1.valid, Y.valid2, S2.valid);
+        C.up(Y.node1, S1.node, Y.node2, S2.node, Y.octave1, S1.octave, Y.bearings1, S1.bearings, Y.bearings2, S2.bearings);
+        C.up(Y.xright1, S1.xright, Y.xright2, S2.xright, Y.occupied2, occupied2);
+        int r = C.flush();
+        if (!r) r = sv_bucket_sort(ctx, C.s, Y.node1, n1, Y.sort_scratch, sortb, Y.key1, Y.q_idx);
+        if (!r) r = sv_bucket_sort(ctx, C.s, Y.node2, n2, Y.sort_scratch, sortb, Y.key2, Y.t_sorted);
+        if (r) return r;
+        sv_bucket_rows(C.s, B);
+        sv_bucket_count(C.s, B);
+        return SVGPU_OK;
+    };
+    // The two passes, always sized exactly (no guess), and no page-locked mirror, on purpose: every array is a copy of its own and the
+    // results come straight to the caller's arrays.  The second pass reuses the arena of the first unless it regrew (prefix invariant).
+    int rc = C.open(ctx, "bucket matcher: internal arena overflow", layout, false);
+    if (!rc) rc = count();
+    if (!rc) rc = C.read_now(&total, B.cand_off + n1);
+    if (rc || total == 0) return rc;
+    bool survived = false;
+    lists = true;
+    if ((rc = C.reopen(layout, survived))) return rc;
+    if (!survived && (rc = count())) return rc;
+    sv_bucket_fill(C.s, B);
+    sv_bucket_gather_rows(C.s, B, Y.qdesc_rows, Y.qangle_rows);
+    sv_launch_cand(ctx, C.s, P, Y.owner, Y.match_of_row, Y.mdist);
+    SV_HIP(ctx, hipMemsetAsync(Y.match, 0xFF, (size_t)n1 * 4, C.s));
+    sv_bucket_scatter(C.s, B, Y.match_rows, Y.match);
+    C.down(match_1to2, Y.match);
+    C.down(&num, Y.num);
+    if ((rc = C.finish())) return rc;
+    *num_matches = num;
     return SVGPU_OK;
 }
 

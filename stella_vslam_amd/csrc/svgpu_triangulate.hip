@@ -14,8 +14,14 @@ bool view_ok(const svgpu_triangulate_view& v) {
            && (v.n == 0 || (v.xy && v.octave && v.bearings));
 }
 
-// camera, pose and derived constants of one side; the keypoint arrays go into the arena
-int stage_view(svgpu_ctx* ctx, hipStream_t s, UploadArena& A, const svgpu_triangulate_view& v, float scale_factor_1, TriView& T) {
+struct ViewPieces {
+    Piece<float> xy;
+    Piece<int32_t> octave;
+    Piece<double> bearings;
+    Piece<float> xright, depth;
+};
+// camera, pose and derived constants of one side; the keypoint arrays get their places in the arena
+void place_view(UploadArena& A, const svgpu_triangulate_view& v, float scale_factor_1, TriView& T, ViewPieces& Y) {
     T.cam = *v.cam;
     std::memcpy(T.pose_cw, v.pose_cw, sizeof T.pose_cw);
     const double* P = v.pose_cw;
@@ -27,13 +33,14 @@ int stage_view(svgpu_ctx* ctx, hipStream_t s, UploadArena& A, const svgpu_triang
     T.ratio_factor = 2.0f * std::max(scale_factor_1, v.scale_factor);
     T.n = v.n;
     const size_t n = (size_t)v.n;
-    int rc = SVGPU_OK;
-    T.xy = A.put(ctx, s, v.xy, n * 2, true, rc);
-    T.octave = A.put(ctx, s, v.octave, n, true, rc);
-    T.bearings = A.put(ctx, s, v.bearings, n * 3, true, rc);
-    T.xright = A.put(ctx, s, v.xright, n, true, rc);
-    T.depth = A.put(ctx, s, v.depth, n, true, rc);
-    return rc;
+    T.xy = Y.xy = optional_piece<float>(A, v.xy, n * 2);
+    T.octave = Y.octave = optional_piece<int32_t>(A, v.octave, n);
+    T.bearings = Y.bearings = optional_piece<double>(A, v.bearings, n * 3);
+    T.xright = Y.xright = optional_piece<float>(A, v.xright, n);
+    T.depth = Y.depth = optional_piece<float>(A, v.depth, n);
+}
+void up_view(StagedCall& C, const svgpu_triangulate_view& v, const ViewPieces& Y) {
+    C.up(Y.xy, v.xy, Y.octave, v.octave, Y.bearings, v.bearings, Y.xright, v.xright, Y.depth, v.depth);
 }
 
 int tri_core(svgpu_ctx* ctx, const char* who, const svgpu_triangulate_view* v1, const svgpu_triangulate_view* nb, int K, const int32_t* off,
@@ -68,24 +75,30 @@ int tri_core(svgpu_ctx* ctx, const char* who, const svgpu_triangulate_view* v1, 
                 return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_triangulate_two_views: stereo keypoint of an equirectangular camera");
         }
     }
-    hipStream_t s = ctx->stream;
     TriProblem P{};
     std::vector<TriView> views(K);
+    std::vector<ViewPieces> VY(K + 1);
+    Piece<TriView> d_views;
+    Piece<int32_t> d_first, d_of, d_idx1, d_idx2;
     StagedCall C;
-    int rc = C.open(ctx, "svgpu_triangulate_two_views: internal arena overflow", [&](UploadArena& A) -> int {
-        int rc = stage_view(ctx, s, A, *v1, v1->scale_factor, P.v1);
-        for (int k = 0; k < K && !rc; ++k) rc = stage_view(ctx, s, A, nb[k], v1->scale_factor, views[k]);
-        P.nb = A.put(ctx, s, views.data(), K, true, rc);  // (the views carry device pointers: staged above, copied here)
-        P.nb_first = A.put(ctx, s, nb_first.data(), K, true, rc);
-        P.nb_of_match = A.put(ctx, s, nb_of.data(), M, true, rc);
-        P.idx1 = A.put(ctx, s, idx1, M, true, rc);
-        P.idx2 = A.put(ctx, s, idx2, M, true, rc);
-        if (!rc) rc = A.flush(ctx, s);
+    int rc = C.open(ctx, "svgpu_triangulate_two_views: internal arena overflow", [&](UploadArena& A) {
+        place_view(A, *v1, v1->scale_factor, P.v1, VY[K]);
+        for (int k = 0; k < K; ++k) place_view(A, nb[k], v1->scale_factor, views[k], VY[k]);
+        P.nb = d_views = A.piece<TriView>(K);
+        P.nb_first = d_first = A.piece<int32_t>(K);
+        P.nb_of_match = d_of = A.piece<int32_t>(M);
+        P.idx1 = d_idx1 = A.piece<int32_t>(M);
+        P.idx2 = d_idx2 = optional_piece<int32_t>(A, idx2, M);
         P.pos_w = A.take<double>((size_t)M * 3);
         P.status = A.take<uint8_t>(M);
-        return rc;
     });
     if (rc) return rc;
+    hipStream_t s = C.s;
+    up_view(C, *v1, VY[K]);
+    for (int k = 0; k < K; ++k) up_view(C, nb[k], VY[k]);
+    // (the views carry device pointers: placed above, copied here; M > 0, so there is a view, and idx1 was checked: only idx2 is optional)
+    C.up(d_views, views.data(), d_first, nb_first.data(), d_of, nb_of.data(), d_idx1, idx1, d_idx2, idx2);
+    if ((rc = C.flush())) return rc;
     P.num_matches = M;
     for (int l = 0; l < num_levels; ++l) P.scale_factors[l] = scale_factors[l], P.level_sigma_sq[l] = level_sigma_sq[l];
     P.cos_rays_parallax_thr = (float)std::cos(rays_parallax_deg_thr * M_PI / 180.0);  // two_view_triangulator.cc:17 (a float member)
