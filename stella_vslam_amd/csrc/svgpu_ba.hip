@@ -16,6 +16,7 @@
 
 #include "svgpu_internal.h"
 #include "ba_kernels.h"
+#include "ba_layout.h"
 #include "poseopt_batch_layout.h"
 #include "sv_staged_call.h"
 #include "sv_validate.h"
@@ -168,6 +169,87 @@ void sv_comm_release(svgpu_ctx* ctx) {
     if (ctx) ctx->comm = nullptr;
 }
 
+static_assert(sizeof(BaCtl) == BA_LAYOUT_CTL, "ba_layout.h and ba_kernels.h disagree on the control block");
+static_assert(sizeof(BaInt2) == sizeof(int2) && alignof(BaInt2) == alignof(int2), "ba_layout.h: BaInt2 is not laid out like int2");
+static_assert(sizeof(BaInt4) == sizeof(int4) && alignof(BaInt4) == alignof(int4), "ba_layout.h: BaInt4 is not laid out like int4");
+
+namespace {
+
+// The pointer fields of the kernels' argument struct, from the placed pieces (everything else starts as zero).  A renumbered solve reads
+// the rn_* arrays where the others read the uploaded ones (the caller's order), which stay the sources of the permutation kernels.
+void ba_bind(BaDev& D, const BaSizes& Z, const BaIn& in, const BaOut& out, const BaWork& w, bool sharded) {
+    memset(&D, 0, sizeof(D));
+    D.P = Z.P, D.L = Z.L, D.E = Z.E, D.world = Z.world;
+    D.ctl = (BaCtl*)out.ctl.p;
+    D.pose_buf[0] = in.pose, D.pose_buf[1] = w.pose1;
+    D.pt_buf[0] = Z.renumber ? w.rn_pts : in.points, D.pt_buf[1] = w.pt1;
+    D.e_pose = Z.renumber ? w.rn_e_pose : in.e_pose;
+    D.e_point = Z.renumber ? w.rn_e_point : in.e_point;
+    D.e_uvr = Z.renumber ? w.rn_uvr : in.e_uvr;
+    D.e_w = Z.renumber ? w.rn_w : in.e_w;
+    D.e_huber = Z.renumber ? w.rn_hub : in.e_hub;
+    D.lm_off = Z.renumber ? w.rn_lm_off : in.lm_off;
+    D.lm_order = w.rn_order;                               // (null unless renumbered)
+    D.lm_off_caller = Z.renumber ? in.lm_off.p : nullptr;
+    D.e_level = w.e_level, D.e_robust = in.e_robust, D.e_chi = w.e_chi;
+    D.intr = in.intr;
+    D.pose_slot = w.pose_slot, D.pt_free = w.pt_free, D.slot_pose = w.slot_pose;
+    D.pe_off = in.pe_off, D.pe_idx = in.pe_idx;
+    D.pm_point = w.pm_point, D.pm_uvr = w.pm_uvr, D.pm_w = w.pm_w, D.pm_hub = w.pm_hub;
+    D.blk_off = w.blk_off, D.blk_pairs = (const int2*)w.blk_pairs.p, D.blk_ab = (const int2*)w.blk_ab.p, D.blk_pair_l = w.blk_pair_l;
+    D.W = w.W, D.lp_part = w.lp_part, D.lm_max = w.lm_max, D.sc_part = w.sc_part, D.rhs_part = w.rhs_part;  // (lm_max: nb_lm == sv_ba_lm_blocks(L))
+    D.Hll = w.Hll, D.bl = w.bl, D.Hpp = w.Hpp, D.bp = w.bp, D.Sblk = w.Sblk, D.S = w.S, D.dp = w.dp;
+    D.red = w.red;  // chi2 parts | step-scale parts | flags
+    D.red_chi_off = 0, D.red_chi_n = Z.nb_lm;
+    D.red_scale_off = Z.nb_lm, D.red_scale_n = Z.nb_lm + Z.nb_pose;
+    D.red_flag_off = Z.nb_lm + Z.nb_lm + Z.nb_pose;
+    D.dbg = w.dbg;
+    D.any_owner = w.any_owner;
+    D.maxslots = w.sc + 8;
+    D.xsum = sharded ? w.sc.p : nullptr;
+    D.prow_off = w.prow_off, D.prow_ent = (const int2*)w.prow_ent.p, D.diag_blk = w.diag_blk;
+    D.pcg_Minv = w.pcg_Minv, D.pcg_rws = w.pcg_rws, D.pcg_own = w.pcg_own, D.pcg_parts = w.pcg_parts, D.pcg_scal = w.pcg_scal;
+}
+
+// Copies between host memory and the pieces of the device arena, on the solve's stream.  A copy into or out of a piece moves the whole
+// piece; one that is deliberately shorter names its count, in elements, and one longer than its piece fails the call instead of being
+// copied (StagedCall's rule).
+struct BaCopy {
+    svgpu_ctx* ctx;
+    hipStream_t s;
+    bool fits(size_t count, size_t n) const {
+        if (count > n) sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_local_ba: internal count mismatch (a transfer longer than its arena piece)");
+        return count <= n;
+    }
+    template <class T>
+    int h2d(Piece<T> dst, const T* src, size_t count) const {
+        if (!fits(count, dst.n)) return SVGPU_ERR_INVALID;
+        SV_HIP(ctx, hipMemcpyAsync(dst.p, src, count * sizeof(T), hipMemcpyHostToDevice, s));
+        return SVGPU_OK;
+    }
+    template <class T>
+    int h2d(Piece<T> dst, const T* src) const { return h2d(dst, src, dst.n); }
+    template <class T>
+    int h2d(Piece<T> dst, Piece<T> src) const { return h2d(dst, src.p, src.n); }  // (a host piece of another count than its device piece fails the call)
+    template <class T>
+    int h2d(Piece<T> dst, Piece<T> src, size_t count) const { return fits(count, src.n) ? h2d(dst, src.p, count) : SVGPU_ERR_INVALID; }
+    // a run of adjacent pieces of the input block in one copy, padding included: from `first` up to where `behind` begins (both placements
+    // come from one layout: the run is as long in the host image)
+    template <class T, class U>
+    int h2d_run(Piece<T> first, Piece<U> behind, Piece<T> src) const {
+        SV_HIP(ctx, hipMemcpyAsync(first.p, src.p, (size_t)((const char*)behind.p - (const char*)first.p), hipMemcpyHostToDevice, s));
+        return SVGPU_OK;
+    }
+    template <class T>
+    int d2h(T* dst, Piece<T> src, size_t count) const {
+        if (!fits(count, src.n)) return SVGPU_ERR_INVALID;
+        SV_HIP(ctx, hipMemcpyAsync(dst, src.p, count * sizeof(T), hipMemcpyDeviceToHost, s));
+        return SVGPU_OK;
+    }
+};
+
+}  // namespace
+
 static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single_stage, int rank, int world,
                          svgpu_allreduce_fn allreduce, void* ar_user, volatile uint8_t* stop, double* pose_out, double* points_out, uint8_t* outlier_out,
                          svgpu_ba_stats* stats) {
@@ -226,75 +308,34 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
     }
     hipStream_t s = ctx->stream;
 
-    // ---- page-locked staging laid out exactly like the input block at the head of the device arena (one copy carries everything):
-    //      poses | points | intrinsics | e_pose | e_point | e_uvr | e_w | e_huber | e_robust | lm_off | pe_off | pe_idx.  The observations
-    //      are written sorted by landmark (stable; a plain copy when they arrive that way): landmark-major kernels then read
-    //      contiguous runs.  pe_* = pose -> edge lists.  Behind it, the output block's host image.
-    // The offsets come from the description that later places the device arrays (lay_in / lay_out, run here on a measuring arena).
-    struct InBlock {
-        size_t pose, points, intr, e_pose, e_point, e_uvr, e_w, e_hub, robust, lm_off, pe_off, pe_idx, total;
-    } in;
-    struct OutBlock {  // control block | poses | points | outlier flags
-        size_t ctl, state, outlier, total;
-    } out;
-    double *d_pose0 = nullptr, *d_pt0 = nullptr, *d_intr = nullptr, *d_state_out = nullptr;
-    int *d_e_pose = nullptr, *d_e_point = nullptr, *d_lm_off = nullptr, *d_pe_off = nullptr, *d_pe_idx = nullptr;
-    float *d_e_uvr = nullptr, *d_e_w = nullptr, *d_e_hub = nullptr;
-    uint8_t *d_e_robust = nullptr, *d_outlier = nullptr;
-    BaCtl* d_ctl = nullptr;
-    auto lay_in = [&](Arena& A, InBlock& o) {
-        const size_t o0 = A.off;
-        o.pose = A.off - o0, d_pose0 = A.take<double>(12 * (size_t)P);
-        o.points = A.off - o0, d_pt0 = A.take<double>(3 * (size_t)L);
-        o.intr = A.off - o0, d_intr = A.take<double>(5 * (size_t)P);
-        o.e_pose = A.off - o0, d_e_pose = A.take<int>(E);
-        o.e_point = A.off - o0, d_e_point = A.take<int>(E);
-        o.e_uvr = A.off - o0, d_e_uvr = A.take<float>(3 * (size_t)E);
-        o.e_w = A.off - o0, d_e_w = A.take<float>(E);
-        o.e_hub = A.off - o0, d_e_hub = A.take<float>(E);
-        o.robust = A.off - o0, d_e_robust = A.take<uint8_t>(E);
-        o.lm_off = A.off - o0, d_lm_off = A.take<int>(L + 1);
-        o.pe_off = A.off - o0, d_pe_off = A.take<int>(P + 1);
-        o.pe_idx = A.off - o0, d_pe_idx = A.take<int>(E);
-        o.total = A.off - o0;
-    };
-    auto lay_out = [&](Arena& A, OutBlock& o) {
-        const size_t o0 = A.off;
-        o.ctl = A.off - o0, d_ctl = (BaCtl*)A.take<char>(sizeof(BaCtl));
-        o.state = A.off - o0, d_state_out = A.take<double>(12 * (size_t)P + 3 * (size_t)L);
-        o.outlier = A.off - o0, d_outlier = A.take<uint8_t>(E + 1);
-        o.total = A.off - o0;
-    };
-    // structure block (host image only; its pieces go to separate device arrays): pt_free | pose_slot | slot_pose | blk_ab, prow_off, diag | prow_ent
-    const size_t nb_cap_h = (size_t)P * (P + 1) / 2;
-    size_t st_pt_free, st_pose_slot, st_pe, st_blk, st_prow;
-    const size_t stage_total = arena_measure([&](Arena& M) {  // the whole host image: input block | output block | structure block
-        lay_in(M, in);
-        lay_out(M, out);
-        const size_t o0 = M.off;
-        st_pt_free = M.off - o0, M.take<char>(L);
-        st_pose_slot = M.off - o0, M.take<char>(4 * (size_t)P);
-        st_pe = M.off - o0, M.take<char>(4 * (size_t)P);
-        st_blk = M.off - o0, M.take<char>(8 * nb_cap_h + 4 * (2 * (size_t)P + 2));
-        st_prow = M.off - o0, M.take<char>(8 * 2 * (nb_cap_h + 1));
-    });
-    const size_t out_ctl = out.ctl, out_state = out.state, out_outlier = out.outlier, out_total = out.total;
+    // ---- page-locked staging (ba_layout.h): input block | output block | structure block, the input block laid out exactly like the one at
+    //      the head of the device arena (one copy carries everything).  The observations are written sorted by landmark (stable; a plain
+    //      copy when they arrive that way): landmark-major kernels then read contiguous runs.
+    BaIn hin, din;    // h*: placed over the host image, d*: over the device arena (once its sizes are known, below)
+    BaOut hout, dout;
+    BaStructure hst;
+    BaWork dw;
     {
-        const int r = sv_ensure_stage(ctx, stage_total);
+        const BaSizes shape = ba_sizes(P, L, E, world, nullptr, false, false, false, BA_DBG_OFF);  // (the landmark offsets are written into this image)
+        const auto image = [&](Arena& A) { ba_host_layout(A, shape, hin, hout, hst); };
+        const int r = sv_ensure_stage(ctx, arena_measure(image));
         if (r) {
             if (team_sized) memcpy(points_out, pr->points, sizeof(double) * 3 * (size_t)L);
             return r;
         }
+        Arena A(ctx->h_stage, ctx->stage_bytes);
+        image(A);
+        if (A.overflow) {
+            if (team_sized) memcpy(points_out, pr->points, sizeof(double) * 3 * (size_t)L);
+            return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_local_ba: internal staging overflow");
+        }
     }
-    char* const hs = ctx->h_stage;
-    char* const hs_out = hs + in.total;
-    char* const hs_struct = hs_out + out_total;
-    int* const lm_off = (int*)(hs + in.lm_off);
-    int* const e_pose = (int*)(hs + in.e_pose);
-    int* const e_point = (int*)(hs + in.e_point);
-    float* const e_uvr = (float*)(hs + in.e_uvr);
-    float* const e_w = (float*)(hs + in.e_w);
-    float* const e_hub = (float*)(hs + in.e_hub);
+    int* const lm_off = hin.lm_off;
+    int* const e_pose = hin.e_pose;
+    int* const e_point = hin.e_point;
+    float* const e_uvr = hin.e_uvr;
+    float* const e_w = hin.e_w;
+    float* const e_hub = hin.e_hub;
     auto copy_measurements = [&](size_t a, size_t b) {
         memcpy(e_uvr + 3 * a, pr->obs_uvr + 3 * a, 12 * (b - a));
         memcpy(e_w + a, pr->obs_inv_sigma_sq + a, 4 * (b - a));
@@ -328,7 +369,6 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
         std::atomic<int> gate{0};    // 0: the team is being created, 1: run, 2: creation failed, leave
         std::atomic<int> staged{0};  // workers whose share of the measurements is in the staging image
         std::atomic<int> go{0};  // 0: the arena is not known yet, 1: upload, 2: abandon (the caller returns early or stages the observations itself)
-        char* d_in = nullptr;
         hipStream_t s2 = nullptr;
         int err[16] = {0};
         bool running = false;
@@ -420,19 +460,21 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
             // (every hipMemcpyAsync holds the runtime's lock for ~15 us, and this thread's launches queue behind it: below 4 M observations the
             //  worker that finishes LAST uploads the whole image in four copies; beyond, every worker uploads its chunks as they are staged)
             const bool chunked = E >= (4 << 20);
+            // elements [first, first + count) of a staged piece to the same elements of its device piece (placed before `go` said 1)
+            auto up = [&](auto dev, auto host, size_t first, size_t count) {
+                if (first + count > dev.n) he = hipErrorInvalidValue;
+                if (count && he == hipSuccess) he = hipMemcpyAsync(dev.p + first, host.p + first, count * sizeof(*dev.p), hipMemcpyHostToDevice, team.s2);
+            };
             auto flush = [&](size_t e_staged, size_t l_staged) {
                 if (!chunked || team.go.load() != 1 || he != hipSuccess) return;
-                auto up = [&](size_t off, size_t bytes) {
-                    if (bytes && he == hipSuccess) he = hipMemcpyAsync(team.d_in + off, hs + off, bytes, hipMemcpyHostToDevice, team.s2);
-                };
                 if (e_staged > e_up) {
-                    up(in.e_uvr + 12 * e_up, 12 * (e_staged - e_up));
-                    up(in.e_w + 4 * e_up, 4 * (e_staged - e_up));
-                    up(in.e_hub + 4 * e_up, 4 * (e_staged - e_up));
+                    up(din.e_uvr, hin.e_uvr, 3 * e_up, 3 * (e_staged - e_up));
+                    up(din.e_w, hin.e_w, e_up, e_staged - e_up);
+                    up(din.e_hub, hin.e_hub, e_up, e_staged - e_up);
                     e_up = e_staged;
                 }
                 if (l_staged > l_up) {
-                    up(in.points + 24 * l_up, 24 * (l_staged - l_up));
+                    up(din.points, hin.points, 3 * l_up, 3 * (l_staged - l_up));
                     l_up = l_staged;
                 }
             };
@@ -443,7 +485,7 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
             }
             for (size_t a = l0; a < l1 && team.go.load() != 2; a += LCH) {
                 const size_t b = std::min(l1, a + LCH);
-                memcpy(hs + in.points + 24 * a, pr->points + 3 * a, 24 * (b - a));
+                memcpy(hin.points + 3 * a, pr->points + 3 * a, 24 * (b - a));
                 flush(e1, b);
             }
             const bool last = team.staged.fetch_add(1) + 1 == W;
@@ -452,8 +494,8 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
             if (team.go.load() == 1) {
                 if (chunked) flush(e1, l1);
                 else if (last) {  // (every share is staged: fetch_add orders the others' writes before this thread's reads)
-                    const size_t offs[4] = {in.e_uvr, in.e_w, in.e_hub, in.points}, bytes[4] = {12 * (size_t)E, 4 * (size_t)E, 4 * (size_t)E, 24 * (size_t)L};
-                    for (int k = 0; k < 4 && he == hipSuccess; ++k) he = hipMemcpyAsync(team.d_in + offs[k], hs + offs[k], bytes[k], hipMemcpyHostToDevice, team.s2);
+                    up(din.e_uvr, hin.e_uvr, 0, din.e_uvr.n), up(din.e_w, hin.e_w, 0, din.e_w.n), up(din.e_hub, hin.e_hub, 0, din.e_hub.n);
+                    up(din.points, hin.points, 0, din.points.n);
                 }
             }
             team.err[q] = (int)he;
@@ -465,7 +507,7 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
         if (nth == 1) {
             if (team_sized) memcpy(points_out, pr->points, sizeof(double) * 3 * (size_t)L);  // (SVGPU_BA_HOST_THREADS=1)
             scan_range(0);
-            if (!bad[0]) memcpy(hs + in.points, pr->points, sizeof(double) * 3 * (size_t)L);
+            if (!bad[0]) memcpy(hin.points, pr->points, hin.points.bytes());
         }
         else {
             team.running = true;
@@ -508,7 +550,7 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
         if (!lm_major && team.running) {  // (rare at this size: the permuted copy below writes the whole staging image itself)
             team.go.store(2);
             team.join();
-            memcpy(hs + in.points, pr->points, sizeof(double) * 3 * (size_t)L);
+            memcpy(hin.points, pr->points, hin.points.bytes());
         }
     if (!lm_major) {
         for (int l = 0; l <= L; ++l) lm_off[l] = 0;
@@ -531,8 +573,8 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
         }
     }
     // (the pose -> edge lists and the robust-kernel flags are built on the device once the observations are there: sv_ba_build_pose_lists)
-    memcpy(hs + in.pose, pr->pose_cw, sizeof(double) * 12 * (size_t)P);
-    memcpy(hs + in.intr, pr->intrinsics, sizeof(double) * 5 * (size_t)P);
+    memcpy(hin.pose, pr->pose_cw, hin.pose.bytes());
+    memcpy(hin.intr, pr->intrinsics, hin.intr.bytes());
 
     lap("sort observations");
     // ---- solver choice (svgpu_ba_set_solver; SVGPU_BA_SOLVER overrides for experiments)
@@ -546,157 +588,34 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
         else if (!strcmp(ev, "envelope")) solver_opt = SV_BA_SOLVER_ENVELOPE;
     }
     // ---- device arena
-    const int nPmax = P, nmax = 6 * nPmax;
-    const int nb_lm = (8 * L + 255) / 256 /* k_ba_update / k_ba_chi2: 8 lanes per landmark */, nb_chi = nb_lm, nb_pose = (P + 255) / 256;
-    const size_t nb_cap = (size_t)P * (P + 1) / 2;
-    // worst-case pair storage: sum over landmarks of k(k+1)/2 (+ duplicates never exceed k^2)
-    size_t pair_cap = 0;
-    for (int l = 0; l < L; ++l) {
-        const size_t k = lm_off[l + 1] - lm_off[l];
-        pair_cap += k * k;
-    }
-    const size_t sc_part_blocks = pair_cap / 64 + nb_cap + 16;  // NB * nshare <= pairs / 64 + NB (a share holds at least 64 pairs: one trip of a wave)
-    const size_t xch_doubles = std::max(std::max((size_t)P, 4 * (size_t)L), nb_cap) + 8;
-    const size_t nparts_max = (size_t)(P + 3) / 4 + 1;
     // the dense matrix of the tiled LL^T (ba_dense_tiled.hip): on request, and as a candidate of AUTO for windows of 24 - 256 keyframes on one rank
     const bool want_dense = solver_opt == SV_BA_SOLVER_DENSE || (solver_opt == SV_BA_SOLVER_AUTO && !sharded && P >= 24 && P <= 256 && !std::getenv("SVGPU_BA_NO_DENSE_TILED"));
     // the solve's own landmark numbering (ba_pairs.hip): one stage, the host team's sizes, observations grouped by landmark
     // (a sharded solve renumbers the landmarks of ITS shard: the numbering is private to the rank's kernels, every landmark-sized exchange
     //  between ranks -- ownership marks, the final positions -- stays in the caller's numbering)
     const bool renumber = team.running && single_stage && !std::getenv("SVGPU_BA_NO_RENUMBER");
-    const bool chunk_units = renumber && pair_cap < ((size_t)1 << 31) && !std::getenv("SVGPU_BA_NO_UNITS");  // chunk-major units of the Schur kernel (ba_pairs.hip)
-    const size_t unit_cap = chunk_units ? sc_part_blocks : 0;
-    const size_t pair_scratch = std::max(std::max(std::max(sv_ba_pairs_scratch_bytes(pair_cap, E, nb_cap), sv_ba_pose_lists_scratch_bytes((size_t)E)), renumber ? sv_ba_renumber_scratch_bytes((size_t)L) : 0),
-                                         chunk_units ? sv_ba_units_scratch_bytes(pair_cap, unit_cap) : 0);
-    BaDev D;
-    memset(&D, 0, sizeof(D));
-    D.P = P;
-    D.L = L;
-    D.E = E;
-    D.world = world;
-    D.rank = rank;
     static const bool dbg_stamps = std::getenv("SVGPU_BA_DBG") != nullptr;
     static const bool dbg_schur = dbg_stamps && !strcmp(std::getenv("SVGPU_BA_DBG"), "schur");
     static const bool dbg_chol = dbg_stamps && !strcmp(std::getenv("SVGPU_BA_DBG"), "chol");
-    D.dbg_schur_on = dbg_schur ? 1 : (dbg_chol ? 2 : 0);
-    // ---- the device arena, described once: measured for sv_ensure_scratch, then placed
-    int *d_pose_slot, *d_slot_pose, *d_prow_off, *d_diag_blk, *d_pm_point, *d_blk_pair_l, *d_blk_off, *d_xs_idx;
-    uint8_t *d_pt_free, *d_lam_slot, *d_any_owner;
-    double *d_HB_full, *d_sc, *d_xch;
-    int2 *d_prow_ent, *d_blk_pairs, *d_blk_ab;
-    float *d_pm_uvr, *d_pm_w, *d_pm_hub;
-    char* d_pair_scratch;
-    // renumbered solve: the uploaded arrays (caller's order) are the sources, these the arrays the kernels read
-    int *rn_e_pose = nullptr, *rn_e_point = nullptr, *rn_src = nullptr, *rn_lm_off = nullptr, *rn_order = nullptr;
-    float *rn_uvr = nullptr, *rn_w = nullptr, *rn_hub = nullptr;
-    double* rn_pts = nullptr;
-    uint8_t* rn_pt_free_in = nullptr;
-    int4* d_unit_rec = nullptr;
-    int* d_blk_unit_off = nullptr;
-    double* d_rhs_unit = nullptr;
-    InBlock in_placed;
-    auto layout = [&](Arena& A) {
-        lay_in(A, in_placed);  // input block (same layout as the staging buffer)
-        OutBlock out_placed;
-        lay_out(A, out_placed);  // output block: control block | poses | points | outlier flags
-        D.pose_buf[1] = A.take<double>(12 * (size_t)P);
-        D.pt_buf[1] = A.take<double>(3 * (size_t)L);
-        D.e_level = A.take<uint8_t>(E);
-        D.e_chi = A.take<double>(E);
-        d_pose_slot = A.take<int>(P);
-        d_pt_free = A.take<uint8_t>(L);
-        d_slot_pose = A.take<int>(P);
-        D.W = A.take<double>(18 * (size_t)E);
-        D.lp_part = A.take<double>(27 * 16 * (size_t)P);
-        D.sc_part = A.take<double>(36 * sc_part_blocks);
-        D.rhs_part = A.take<double>(6 * 16 * (size_t)P);
-        D.Hll = A.take<double>(6 * (size_t)L);
-        D.bl = A.take<double>(3 * (size_t)L);
-        D.Hpp = A.take<double>(36 * (size_t)P);
-        D.bp = A.take<double>(6 * (size_t)P);
-        D.Sblk = A.take<double>(36 * nb_cap + 6 * (size_t)P + 8);
-        D.S = want_dense ? A.take<double>((size_t)(nmax + 1) * nmax + (size_t)(nmax / 48 + 1) * 48 * 48) : nullptr;  // (+ the inverted diagonal tiles of ba_dense_tiled.hip)
-        D.dp = A.take<double>(nmax);
-        D.red = A.take<double>(nb_chi + nb_lm + nb_pose + 8);
-        D.lm_max = A.take<double>(nb_lm);  // nb_lm == sv_ba_lm_blocks(L)
-        D.dbg = dbg_stamps ? A.take<unsigned long long>(8 * (dbg_schur ? sc_part_blocks + 64 : (size_t)nb_lm)) : nullptr;
-        d_HB_full = A.take<double>(42 * (size_t)P + (size_t)std::max(64, world));     // sharded: Hpp | bp summed over ranks | one slot per rank: its landmarks' largest diagonal (computeLambdaInit)
-        d_sc = A.take<double>(64 + (size_t)world);            // sharded: [0..3] per-trial sums, [8..8+world) lambda-init slots
-        d_xch = A.take<double>(xch_doubles);                  // sharded: pose-activity / block-presence / point exchange
-        d_prow_off = A.take<int>(P + 1);
-        d_prow_ent = A.take<int2>(2 * (nb_cap + 1));
-        d_diag_blk = A.take<int>(P);
-        D.pcg_Minv = A.take<double>(36 * (size_t)P);
-        D.pcg_rws = A.take<double>(6 * (size_t)nmax + 8);
-        D.pcg_own = A.take<double>(2 * (size_t)nmax + 8);
-        D.pcg_parts = A.take<double>(2 * 4 * nparts_max);
-        D.pcg_scal = A.take<double>(8);
-        d_pm_point = A.take<int>(E);
-        d_pm_uvr = A.take<float>(3 * (size_t)E);
-        d_pm_w = A.take<float>(E);
-        d_pm_hub = A.take<float>(E);
-        d_blk_pairs = A.take<int2>(pair_cap);
-        d_blk_pair_l = A.take<int>(pair_cap);
-        d_blk_ab = A.take<int2>(nb_cap);
-        d_blk_off = A.take<int>(nb_cap + 1);
-        d_pair_scratch = A.take<char>(pair_scratch);
-        d_xs_idx = A.take<int>(nb_cap + (size_t)P);  // keyframe-segment exchange: block / slot lists, damping owners
-        d_lam_slot = A.take<uint8_t>(P);
-        d_any_owner = A.take<uint8_t>(L);  // sharded: the landmark has observations on some rank
-        if (chunk_units) {
-            d_unit_rec = A.take<int4>(unit_cap);
-            d_blk_unit_off = A.take<int>(nb_cap + 2);
-            d_rhs_unit = A.take<double>(6 * unit_cap);
-        }
-        if (renumber) {
-            rn_e_pose = A.take<int>(E), rn_e_point = A.take<int>(E), rn_src = A.take<int>(E);
-            rn_uvr = A.take<float>(3 * (size_t)E), rn_w = A.take<float>(E), rn_hub = A.take<float>(E);
-            rn_lm_off = A.take<int>(L + 1), rn_order = A.take<int>(L);
-            rn_pts = A.take<double>(3 * (size_t)L);
-            rn_pt_free_in = A.take<uint8_t>(L);
-        }
-    };
-    int rc = sv_ensure_scratch(ctx, arena_measure(layout));
+    BaSizes Z = ba_sizes(P, L, E, world, lm_off, want_dense, renumber, /*units_wanted*/ !std::getenv("SVGPU_BA_NO_UNITS"), dbg_schur ? BA_DBG_SCHUR : (dbg_stamps ? BA_DBG_PER_LANDMARK : BA_DBG_OFF));
+    Z.pair_scratch = std::max(std::max(std::max(sv_ba_pairs_scratch_bytes(Z.pair_cap, E, Z.nb_cap), sv_ba_pose_lists_scratch_bytes((size_t)E)), renumber ? sv_ba_renumber_scratch_bytes((size_t)L) : 0),
+                              Z.chunk_units ? sv_ba_units_scratch_bytes(Z.pair_cap, Z.unit_cap()) : 0);
+    const size_t pair_cap = Z.pair_cap, nb_cap = Z.nb_cap, xch_doubles = Z.xch_doubles;
+    // ---- the device arena (ba_layout.h): measured for sv_ensure_scratch, then placed
+    const auto arena = [&](Arena& A) { ba_device_layout(A, Z, din, dout, dw); };
+    int rc = sv_ensure_scratch(ctx, arena_measure(arena));
     if (rc) return rc;
     Arena A(ctx->d_scratch, ctx->scratch_bytes);
-    layout(A);
-    if (in_placed.total != in.total) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_local_ba: internal layout mismatch");
+    arena(A);
     if (A.overflow) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_local_ba: internal arena overflow");
-    D.pose_buf[0] = d_pose0;
-    D.pt_buf[0] = d_pt0;
-    D.e_robust = d_e_robust;
-    D.ctl = d_ctl;
-    D.any_owner = d_any_owner;
-    char* const d_out = (char*)d_ctl;
-    D.e_pose = d_e_pose;
-    D.e_point = d_e_point;
-    D.e_uvr = d_e_uvr;
-    D.e_w = d_e_w;
-    D.e_huber = d_e_hub;
-    D.intr = d_intr;
-    D.any_equirect = 0;
+    if (ba_in_bytes(din, dout) != ba_in_bytes(hin, hout)) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_local_ba: internal layout mismatch");
+    BaDev D;
+    ba_bind(D, Z, din, dout, dw, sharded);
+    D.rank = rank;
+    D.dbg_schur_on = dbg_schur ? 1 : (dbg_chol ? 2 : 0);
     for (int p = 0; p < P; ++p)
         if (pr->intrinsics[5 * (size_t)p] == 0.0 && pr->intrinsics[5 * (size_t)p + 1] == 0.0) D.any_equirect = 1;
-    D.pose_slot = d_pose_slot;
-    D.pt_free = d_pt_free;
-    D.lm_off = d_lm_off;
-    D.pe_off = d_pe_off;
-    D.pe_idx = d_pe_idx;
-    D.slot_pose = d_slot_pose;
-    D.blk_pairs = d_blk_pairs;
-    D.blk_pair_l = d_blk_pair_l;
-    D.blk_ab = d_blk_ab;
-    D.blk_off = d_blk_off;
-    D.prow_off = d_prow_off;
-    D.prow_ent = d_prow_ent;
-    D.diag_blk = d_diag_blk;
-    D.maxslots = d_sc + 8;
-    D.xsum = sharded ? d_sc : nullptr;
-    D.red_chi_off = 0;
-    D.red_chi_n = nb_chi;
-    D.red_scale_off = nb_chi;
-    D.red_scale_n = nb_lm + nb_pose;
-    D.red_flag_off = nb_chi + nb_lm + nb_pose;
+    BaCopy cp{ctx, s};
     // page-locked block: the control block's read-back copy + the word the caller's stop flag is mirrored into for the device
     const size_t pinned_need = (sizeof(BaCtl) + 7) / 8 + 16;
     if (ctx->pinned_doubles < pinned_need) {
@@ -743,26 +662,24 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
         return wait_stream();
     };
 
-#define H2D(dst, src, bytes) SV_HIP(ctx, hipMemcpyAsync((void*)(dst), (src), (bytes), hipMemcpyHostToDevice, s))
     const void* sorted_edges = nullptr;  // the (pose, edge) records of sv_ba_prepare_lists, kept in the W buffer until the measurements are there
-    char* const d_in = (char*)D.pose_buf[0];
     {
         const size_t want = sv_ba_pose_lists_scratch_bytes((size_t)E);
-        const bool in_W = sizeof(double) * 18 * (size_t)E >= want;  // (the pair lists are built in the pair scratch: the records survive them only in W)
-        void* sc = in_W ? (void*)D.W : (void*)d_pair_scratch;
-        const size_t sc_bytes = in_W ? sizeof(double) * 18 * (size_t)E : pair_scratch;
+        const bool in_W = dw.W.bytes() >= want;  // (the pair lists are built in the pair scratch: the records survive them only in W)
+        void* sc = in_W ? (void*)D.W : (void*)dw.pair_scratch.p;
+        const size_t sc_bytes = in_W ? dw.W.bytes() : dw.pair_scratch.bytes();
         if (team.running && !in_W) {  // (cannot happen at these sizes; the team's work is then uploaded in one piece)
             team.go.store(2);
             team.join();
             copy_measurements(0, (size_t)E);
-            memcpy(hs + in.points, pr->points, sizeof(double) * 3 * (size_t)L);
+            memcpy(hin.points, pr->points, hin.points.bytes());
         }
         if (team.running) {
             if (!ctx->ba_copy_stream) SV_HIP(ctx, hipStreamCreateWithFlags(&ctx->ba_copy_stream, hipStreamNonBlocking));
             if (!ctx->ev_ba_copy) SV_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_ba_copy, hipEventDisableTiming));
-            H2D(d_in + in.pose, hs + in.pose, in.points - in.pose);          // poses
-            H2D(d_in + in.intr, hs + in.intr, in.e_uvr - in.intr);            // intrinsics | e_pose | e_point
-            H2D(d_in + in.lm_off, hs + in.lm_off, in.pe_off - in.lm_off);     // landmark offsets
+            if ((rc = cp.h2d_run(din.pose, din.points, hin.pose))) return rc;      // poses
+            if ((rc = cp.h2d_run(din.intr, din.e_uvr, hin.intr))) return rc;       // intrinsics | e_pose | e_point
+            if ((rc = cp.h2d_run(din.lm_off, din.pe_off, hin.lm_off))) return rc;  // landmark offsets
             // (the link is shared: the measurements queue behind the index arrays, which the structure kernels are waiting for)
             // SVGPU_BA_COPY_ON_MAIN: the measurements on the solve's own stream instead.  Measured over 150 config-5 calls: copy stream median
             // 7.50 ms, but 2 calls of 15 ms (the stream's first synchronisation arrives ~8 ms late: two DMA users of one process); own stream
@@ -772,24 +689,17 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
                 SV_HIP(ctx, hipEventRecord(ctx->ev_ba_copy, s));
                 SV_HIP(ctx, hipStreamWaitEvent(ctx->ba_copy_stream, ctx->ev_ba_copy, 0));
             }
-            team.d_in = d_in;
             team.s2 = copy_on_main ? s : ctx->ba_copy_stream;
             team.go.store(1);
         }
-        else H2D(d_in, hs, in.total);
-        if (renumber) {
-            const int rr = sv_ba_renumber_landmarks(ctx, s, d_lm_off, d_e_pose, L, P, E, d_pair_scratch, pair_scratch, rn_order, rn_lm_off, rn_e_pose, rn_e_point, rn_src);
+        else if ((rc = cp.h2d_run(din.pose, dout.ctl, hin.pose))) return rc;  // the whole input block
+        if (renumber) {  // (ba_bind has pointed the kernels at the rn_* arrays)
+            const int rr = sv_ba_renumber_landmarks(ctx, s, din.lm_off, din.e_pose, L, P, E, dw.pair_scratch, dw.pair_scratch.bytes(), dw.rn_order, dw.rn_lm_off, dw.rn_e_pose, dw.rn_e_point, dw.rn_src);
             if (rr) return rr;
-            D.e_pose = rn_e_pose, D.e_point = rn_e_point, D.lm_off = rn_lm_off;
-            D.e_uvr = rn_uvr, D.e_w = rn_w, D.e_huber = rn_hub;
-            D.pt_buf[0] = rn_pts;
-            D.lm_order = rn_order;
-            D.lm_off_caller = d_lm_off;
         }
         // pose -> edge lists on the device (they need the pose indices only)
-        const int rp = sv_ba_prepare_lists(ctx, s, D.e_pose, E, P, sc, sc_bytes, d_pe_off, D.e_level, D.e_chi, &sorted_edges);  // (also clears e_level / e_chi)
+        const int rp = sv_ba_prepare_lists(ctx, s, D.e_pose, E, P, sc, sc_bytes, din.pe_off, D.e_level, D.e_chi, &sorted_edges);  // (also clears e_level / e_chi)
         if (rp) return rp;
-        D.pm_point = d_pm_point, D.pm_uvr = d_pm_uvr, D.pm_w = d_pm_w, D.pm_hub = d_pm_hub;
     }
     // the measurements are on the device (pipelined: the stream waits for the copy stream) -> pose-major copies + robust flags
     auto finish_observations = [&]() -> int {
@@ -801,10 +711,10 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
             SV_HIP(ctx, hipStreamWaitEvent(s, ctx->ev_ba_copy, 0));
         }
         if (renumber) {  // measurements and positions into the solve's numbering
-            sv_ba_permute_measurements(s, rn_src, E, d_e_uvr, d_e_w, d_e_hub, rn_uvr, rn_w, rn_hub);
-            sv_ba_permute_points(s, rn_order, L, (const double*)(d_in + in.points), rn_pts);
+            sv_ba_permute_measurements(s, dw.rn_src, E, din.e_uvr, din.e_w, din.e_hub, dw.rn_uvr, dw.rn_w, dw.rn_hub);
+            sv_ba_permute_points(s, dw.rn_order, L, din.points, dw.rn_pts);
         }
-        const int rp = sv_ba_prepare_pose_major(ctx, s, sorted_edges, D.e_point, D.e_uvr, D.e_w, D.e_huber, E, d_pe_idx, D.e_robust, d_pm_point, d_pm_uvr, d_pm_w, d_pm_hub);
+        const int rp = sv_ba_prepare_pose_major(ctx, s, sorted_edges, D.e_point, D.e_uvr, D.e_w, D.e_huber, E, din.pe_idx, D.e_robust, dw.pm_point, dw.pm_uvr, dw.pm_w, dw.pm_hub);
         sorted_edges = nullptr;
         return rp;
     };
@@ -819,8 +729,8 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
     ctl0.gain_thr = pr->gain_threshold;
     ctl0.pcg_tol2 = ctx->pcg_tol * ctx->pcg_tol;
     ctl0.phase = 2;
-    H2D(D.ctl, &ctl0, sizeof(BaCtl));
-    SV_HIP(ctx, hipMemsetAsync(d_sc, 0, 8 * (64 + (size_t)world), s));
+    if ((rc = cp.h2d(dout.ctl, (const char*)&ctl0))) return rc;
+    SV_HIP(ctx, hipMemsetAsync(dw.sc, 0, dw.sc.bytes(), s));
 
     // ---- exchange helpers (sharded solve; no-ops otherwise)
     enum { XC_SETUP = 1, XC_POSE_BLOCKS = 2, XC_SYSTEM = 3, XC_SUMS = 6 };  // (4, 5: the separator / solution exchanges of ba_skyline.hip)
@@ -834,10 +744,9 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
     };
     std::vector<double> xch_host(sharded ? std::max((size_t)P, nb_cap) + 8 : 8);  // (the landmark-sized exchanges stay on the device)
     auto allreduce_host = [&](size_t n) -> int {  // xch_host[0..n) summed over the ranks (set-up steps only)
-        H2D(d_xch, xch_host.data(), 8 * n);
-        int r = allreduce_dev(d_xch, n, XC_SETUP);
-        if (r) return r;
-        SV_HIP(ctx, hipMemcpyAsync(xch_host.data(), d_xch, 8 * n, hipMemcpyDeviceToHost, s));
+        int r = cp.h2d(dw.xch, xch_host.data(), n);
+        if (r || (r = allreduce_dev(dw.xch, n, XC_SETUP))) return r;
+        if ((r = cp.d2h(xch_host.data(), dw.xch, n))) return r;
         SV_HIP(ctx, hipStreamSynchronize(s));
         return SVGPU_OK;
     };
@@ -850,12 +759,12 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
         // observations of (its landmark offsets are already there), the marks are summed, a landmark with two owners fails the call on
         // every rank; what comes back is two words.  The sum also says which landmarks have an owner at all (the final exchange of the
         // points leaves the others alone).
-        sv_ba_owned_mark(s, d_lm_off, L, d_xch, stop ? 1.0 : 0.0);
-        int r = allreduce_dev(d_xch, (size_t)L + 1, XC_SETUP);
+        sv_ba_owned_mark(s, din.lm_off, L, dw.xch, stop ? 1.0 : 0.0);
+        int r = allreduce_dev(dw.xch, (size_t)L + 1, XC_SETUP);
         if (r) return r;
-        sv_ba_owned_check(s, d_xch, L, d_any_owner, d_sc + 32);
+        sv_ba_owned_check(s, dw.xch, L, dw.any_owner, dw.sc + 32);
         double verdict[2] = {0.0, 0.0};
-        SV_HIP(ctx, hipMemcpyAsync(verdict, d_sc + 32, 16, hipMemcpyDeviceToHost, s));
+        SV_HIP(ctx, hipMemcpyAsync(verdict, dw.sc + 32, 16, hipMemcpyDeviceToHost, s));
         SV_HIP(ctx, hipStreamSynchronize(s));
         if (verdict[0] > 0.5) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_local_ba_sharded: observations must be sharded by landmark");
         stop_ptr_any = verdict[1] > 0.5;
@@ -869,13 +778,13 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
     std::vector<uint8_t> pose_active;
     int solver = SV_BA_SOLVER_CHOLESKY;
     auto upload_structure = [&]() -> int {
+        int r = SVGPU_OK;
         const std::vector<uint8_t>* pa_override = nullptr;
         if (sharded) {  // a pose is active if ANY rank holds an active observation of it
             for (int p = 0; p < P; ++p) xch_host[p] = 0;
             for (int e = 0; e < E; ++e)
                 if (!level[e]) xch_host[e_pose[e]] = 1;
-            int r = allreduce_host(P);
-            if (r) return r;
+            if ((r = allreduce_host(P))) return r;
             pose_active.assign(P, 0);
             for (int p = 0; p < P; ++p) pose_active[p] = xch_host[p] > 0.5;
             pa_override = &pose_active;
@@ -911,19 +820,19 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
             solver = SV_BA_SOLVER_CHOLESKY;
             D.chol_mfma = 1;
         }
-        D.Hpp_full = sharded ? d_HB_full : D.Hpp;
-        D.bp_full = sharded ? d_HB_full + 36 * (size_t)HS.nP : D.bp;
+        D.Hpp_full = sharded ? dw.HB_full.p : D.Hpp;
+        D.bp_full = sharded ? dw.HB_full + 36 * (size_t)HS.nP : D.bp;
         D.scale_pose = (!sharded || rank == 0) ? 1 : 0;
         D.add_lambda = (!sharded || rank == 0) ? 1 : 0;
-        memcpy(hs_struct + st_pt_free, HS.pt_free.data(), L);
+        memcpy(hst.pt_free, HS.pt_free.data(), hst.pt_free.bytes());
         if (renumber) {
-            H2D(rn_pt_free_in, hs_struct + st_pt_free, L);
-            sv_ba_permute_flags(s, rn_order, L, rn_pt_free_in, d_pt_free);
+            if ((r = cp.h2d(dw.rn_pt_free_in, hst.pt_free))) return r;
+            sv_ba_permute_flags(s, dw.rn_order, L, dw.rn_pt_free_in, dw.pt_free);
         }
-        else H2D(d_pt_free, hs_struct + st_pt_free, L);
+        else if ((r = cp.h2d(dw.pt_free, hst.pt_free))) return r;
         if (!reuse) {
-            memcpy(hs_struct + st_pose_slot, HS.pose_slot.data(), 4 * (size_t)P);
-            H2D(d_pose_slot, hs_struct + st_pose_slot, 4 * (size_t)P);
+            memcpy(hst.pose_slot, HS.pose_slot.data(), hst.pose_slot.bytes());
+            if ((r = cp.h2d(dw.pose_slot, hst.pose_slot))) return r;
             // The pair lists are built on the device.  A local-BA sized problem (<= 48 free poses; the count is the same on every rank of
             // a sharded solve) keeps EVERY upper block -- blocks without a pair are zero blocks, the solvers of that size are dense
             // anyway, and no union of block patterns has to be agreed between ranks -- so nothing has to come back: the pair total stays
@@ -932,14 +841,13 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
             const bool all_blocks = HS.nP <= 48;  // (the pair total stays on the device: the launches are sized for the capacity)
             std::vector<int> dense_off;
             if (all_blocks) {
-                int rp = sv_ba_build_pairs_async(ctx, s, D, d_pair_scratch, pair_scratch, pair_cap, -1, d_blk_pairs, d_blk_pair_l, d_blk_off);
+                int rp = sv_ba_build_pairs_async(ctx, s, D, dw.pair_scratch, dw.pair_scratch.bytes(), pair_cap, -1, (int2*)dw.blk_pairs.p, dw.blk_pair_l, dw.blk_off);
                 if (rp) return rp;
                 sub("pairs enqueued");
             }
             have_lists = true;
-            int* const h_slot_pose = (int*)(hs_struct + st_pe);
-            for (int sl = 0; sl < HS.nP; ++sl) h_slot_pose[sl] = HS.slot_pose[sl];
-            if (HS.nP > 0) H2D(d_slot_pose, h_slot_pose, 4 * (size_t)HS.nP);
+            for (int sl = 0; sl < HS.nP; ++sl) hst.slot_pose[sl] = HS.slot_pose[sl];
+            if (HS.nP > 0 && (r = cp.h2d(dw.slot_pose, hst.slot_pose, HS.nP))) return r;
             if (all_blocks) {
                 HS.blk_ab.clear();
                 for (int a = 0; a < HS.nP; ++a)
@@ -953,60 +861,29 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
                 HS.num_pairs = pair_cap;  // (an upper bound: sum over the landmarks of k^2; sizes the Schur shares)
             }
             else {
-                int rp = sv_ba_build_pairs(ctx, s, D, d_pair_scratch, pair_scratch, pair_cap, d_blk_pairs, d_blk_pair_l, dense_off);
+                int rp = sv_ba_build_pairs(ctx, s, D, dw.pair_scratch, dw.pair_scratch.bytes(), pair_cap, (int2*)dw.blk_pairs.p, dw.blk_pair_l, dense_off);
                 if (rp) return rp;
                 sub("device pairs");
                 std::vector<uint8_t> present(dense_off.size() ? dense_off.size() - 1 : 0, 0);
                 for (size_t k = 0; k < present.size(); ++k) present[k] = dense_off[k + 1] > dense_off[k];
                 if (sharded && !present.empty()) {  // the kept-block list must be the same on every rank: union of the local patterns
                     for (size_t k = 0; k < present.size(); ++k) xch_host[k] = present[k];
-                    int r = allreduce_host(present.size());
-                    if (r) return r;
+                    if ((r = allreduce_host(present.size()))) return r;
                     for (size_t k = 0; k < present.size(); ++k) present[k] = xch_host[k] > 0.5;
                 }
                 compact_blocks(dense_off, present, HS);
-                H2D(d_blk_off, HS.blk_off.data(), 4 * HS.blk_off.size());
+                if ((r = cp.h2d(dw.blk_off, HS.blk_off.data(), HS.blk_off.size()))) return r;
             }
             // block rows for the PCG: row a lists its kept blocks (a, b) and, transposed, (b, a)
             const int NB = (int)HS.blk_ab.size();
-            int2* const h_blk_ab = (int2*)(hs_struct + st_blk);
-            int* const h_prow_off = (int*)(h_blk_ab + NB);
-            int* const h_diag = h_prow_off + (HS.nP + 1);
-            int2* const h_prow_ent = (int2*)(hs_struct + st_prow);
-            for (int a = 0; a <= HS.nP; ++a) h_prow_off[a] = 0;
-            for (int k = 0; k < NB; ++k) {
-                const int2 ab = HS.blk_ab[k];
-                h_blk_ab[k] = ab;
-                h_prow_off[ab.x + 1]++;
-                if (ab.x != ab.y) h_prow_off[ab.y + 1]++;
-                else h_diag[ab.x] = k;
-            }
-            for (int a = 0; a < HS.nP; ++a) h_prow_off[a + 1] += h_prow_off[a];
-            {
-                // blk_ab is sorted by (a, b): filling row a with its transposed blocks (c, a), c < a, first (they arrive in c order)
-                // and its own blocks (a, b), b >= a, afterwards leaves every row sorted by column
-                std::vector<int> fill(h_prow_off, h_prow_off + HS.nP);
-                for (int k = 0; k < NB; ++k) {
-                    const int2 ab = HS.blk_ab[k];
-                    if (ab.x != ab.y) {
-                        int2 e2;
-                        e2.x = k | (1 << 30);
-                        e2.y = ab.x;
-                        h_prow_ent[fill[ab.y]++] = e2;
-                    }
-                }
-                for (int k = 0; k < NB; ++k) {
-                    const int2 ab = HS.blk_ab[k];
-                    int2 e1;
-                    e1.x = k;
-                    e1.y = ab.y;
-                    h_prow_ent[fill[ab.x]++] = e1;
-                }
-            }
-            if (NB > 0) H2D(d_blk_ab, h_blk_ab, 8 * (size_t)NB);
-            H2D(d_prow_off, h_prow_off, 4 * (size_t)(HS.nP + 1));
-            if (h_prow_off[HS.nP] > 0) H2D(d_prow_ent, h_prow_ent, 8 * (size_t)h_prow_off[HS.nP]);
-            if (HS.nP > 0) H2D(d_diag_blk, h_diag, 4 * (size_t)HS.nP);
+            if ((size_t)NB > hst.blk_ab.n) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_local_ba: more kept blocks than the upper triangle holds");
+            memcpy(hst.blk_ab, HS.blk_ab.data(), sizeof(int2) * (size_t)NB);
+            ba_block_rows(hst.blk_ab, NB, HS.nP, hst.prow_off, hst.diag, hst.prow_ent);
+            const int rows = hst.prow_off[HS.nP];
+            if (NB > 0 && (r = cp.h2d(dw.blk_ab, hst.blk_ab, NB))) return r;
+            if ((r = cp.h2d(dw.prow_off, hst.prow_off, HS.nP + 1))) return r;
+            if (rows > 0 && (r = cp.h2d(dw.prow_ent, hst.prow_ent, rows))) return r;
+            if (HS.nP > 0 && (r = cp.h2d(dw.diag_blk, hst.diag, HS.nP))) return r;
             sub("block rows");
         }
         else sv_ba_zero_inactive(s, D);
@@ -1035,17 +912,17 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
                 const char* ev = std::getenv("SVGPU_BA_UNITS_MIN");
                 return ev ? (size_t)std::max(1, std::atoi(ev)) : (size_t)8192;
             }();
-            if (chunk_units && HS.nP > 48 && (size_t)D.NB * D.nshare >= units_min && HS.num_pairs > 0) {
+            if (Z.chunk_units && HS.nP > 48 && (size_t)D.NB * D.nshare >= units_min && HS.num_pairs > 0) {
                 // ~0.5 MB of W records per chunk of consecutive landmark ranks (SVGPU_BA_CHUNK_SHIFT overrides: chunk = 2^shift landmarks).  Measured,
                 // Schur launch at config 5 / 9.6 M observations: 256 landmarks 125 / 930 us, 512: 122 / 880, 1 024: 132 / 882, 2 048: 158 / 973; arithmetic shares 144 / 1 537
                 int shift = 4;
                 while (((size_t)2 << shift) * 144 * ((size_t)E / (size_t)std::max(L, 1) + 1) <= ((size_t)1 << 19)) ++shift;
                 if (const char* ev = std::getenv("SVGPU_BA_CHUNK_SHIFT")) shift = std::max(0, std::min(30, std::atoi(ev)));
                 int U = 0;
-                const int ru = sv_ba_build_units(ctx, s, d_blk_off, D.NB, d_blk_pair_l, (int)HS.num_pairs, L, shift, (int)unit_cap, d_pair_scratch, pair_scratch, d_unit_rec, d_blk_unit_off, &U);
+                const int ru = sv_ba_build_units(ctx, s, dw.blk_off, D.NB, dw.blk_pair_l, (int)HS.num_pairs, L, shift, (int)Z.unit_cap(), dw.pair_scratch, dw.pair_scratch.bytes(), (int4*)dw.unit_rec.p, dw.blk_unit_off, &U);
                 if (ru) return ru;
                 if (U > 0) {
-                    D.unit_rec = d_unit_rec, D.blk_unit_off = d_blk_unit_off, D.rhs_unit = d_rhs_unit, D.num_units = U;
+                    D.unit_rec = (const int4*)dw.unit_rec.p, D.blk_unit_off = dw.blk_unit_off, D.rhs_unit = dw.rhs_unit, D.num_units = U;
                 }
                 if (trace) std::fprintf(stderr, "[ba]     chunk-major units: %d (chunks of %d landmarks)\n", U, 1 << shift);
                 sub("units");
@@ -1094,8 +971,7 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
                         if (sl >= 0 && (*job_of)[sl] >= 0 && (*owner)[(*job_of)[sl]] != rank) misplaced = 1.0;
                     }
                 xch_host[0] = misplaced;
-                int r = allreduce_host(1);
-                if (r) return r;
+                if ((r = allreduce_host(1))) return r;
                 std::vector<int> sep_slots;
                 if (candidate)
                     for (int sl = 0; sl < HS.nP; ++sl)
@@ -1104,16 +980,15 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
                     xs_on = true;
                     xs_nb = (int)sep_blocks->size();
                     xs_ns = (int)sep_slots.size();
-                    int* const h_idx = (int*)(hs_struct + st_blk);  // (the block-row image has been uploaded and the stream drained by the planner)
-                    uint8_t* const h_lam = (uint8_t*)(h_idx + xs_nb + xs_ns);
-                    SV_HIP(ctx, hipStreamSynchronize(s));
-                    for (int k = 0; k < xs_nb; ++k) h_idx[k] = (*sep_blocks)[k];
-                    for (int k = 0; k < xs_ns; ++k) h_idx[xs_nb + k] = sep_slots[k];
-                    for (int sl = 0; sl < HS.nP; ++sl) h_lam[sl] = (*job_of)[sl] >= 0 ? (*owner)[(*job_of)[sl]] == rank : rank == 0;
-                    H2D(d_xs_idx, h_idx, 4 * (size_t)(xs_nb + xs_ns));
-                    H2D(d_lam_slot, h_lam, (size_t)HS.nP);
-                    SV_HIP(ctx, hipStreamSynchronize(s));  // (the staging image is reused)
-                    D.lam_slot = d_lam_slot;
+                    if ((size_t)xs_nb + xs_ns > hst.xs_idx.n) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_local_ba: more separator blocks and rows than their index list holds");
+                    SV_HIP(ctx, hipStreamSynchronize(s));  // (an upload of an earlier structure may still be reading the lists' image)
+                    for (int k = 0; k < xs_nb; ++k) hst.xs_idx[k] = (*sep_blocks)[k];
+                    for (int k = 0; k < xs_ns; ++k) hst.xs_idx[xs_nb + k] = sep_slots[k];
+                    for (int sl = 0; sl < HS.nP; ++sl) hst.lam[sl] = (*job_of)[sl] >= 0 ? (*owner)[(*job_of)[sl]] == rank : rank == 0;
+                    if ((r = cp.h2d(dw.xs_idx, hst.xs_idx, xs_nb + xs_ns))) return r;
+                    if ((r = cp.h2d(dw.lam_slot, hst.lam, HS.nP))) return r;
+                    SV_HIP(ctx, hipStreamSynchronize(s));  // (the staging image is rewritten by the next structure)
+                    D.lam_slot = dw.lam_slot;
                 }
             }
             ctx->ba_xch[0] = !sharded ? 0 : (xs_on ? 2 : 1);
@@ -1129,8 +1004,8 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
     auto chi2_begin = [&](int store_cache) -> int {
         sv_ba_chi2(ctx, s, D, 0, store_cache, 0);
         if (sharded) {
-            sv_ba_fold(s, D, d_sc, 0);
-            return allreduce_dev(d_sc, 4, XC_SUMS);
+            sv_ba_fold(s, D, dw.sc, 0);
+            return allreduce_dev(dw.sc, 4, XC_SUMS);
         }
         return SVGPU_OK;
     };
@@ -1148,21 +1023,21 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
             // which k_ba_lin has just left in the control block -- rides behind the pose blocks.  The pose part of the maximum is taken from the
             // SUMMED blocks afterwards, identically on every rank; k_ba_prepare takes the largest of that and the slots.
             if (HS.nP > 0) {
-                SV_HIP(ctx, hipMemcpyAsync(d_HB_full, D.Hpp, 8 * 36 * (size_t)HS.nP, hipMemcpyDeviceToDevice, s));
-                SV_HIP(ctx, hipMemcpyAsync(d_HB_full + 36 * (size_t)HS.nP, D.bp, 8 * 6 * (size_t)HS.nP, hipMemcpyDeviceToDevice, s));
+                SV_HIP(ctx, hipMemcpyAsync(dw.HB_full, D.Hpp, 8 * 36 * (size_t)HS.nP, hipMemcpyDeviceToDevice, s));
+                SV_HIP(ctx, hipMemcpyAsync(dw.HB_full + 36 * (size_t)HS.nP, D.bp, 8 * 6 * (size_t)HS.nP, hipMemcpyDeviceToDevice, s));
             }
-            D.maxslots = d_HB_full + 42 * (size_t)HS.nP;
+            D.maxslots = dw.HB_full + 42 * (size_t)HS.nP;
             sv_ba_maxslot(s, D);
-            if ((r = allreduce_dev(d_HB_full, 42 * (size_t)HS.nP + (size_t)world, XC_POSE_BLOCKS))) return r;
+            if ((r = allreduce_dev(dw.HB_full, 42 * (size_t)HS.nP + (size_t)world, XC_POSE_BLOCKS))) return r;
             sv_ba_maxdiag(s, D);
             sv_ba_prepare(s, D);
         }
         sv_ba_reduce(ctx, s, D);
         if (HS.nP > 0) {
             if (xs_on) {  // keyframe-segment shards: only what touches two separator rows is shared between ranks
-                sv_ba_xs_move(s, D, d_xs_idx, xs_nb, d_xs_idx + xs_nb, xs_ns, d_xch, 0);
-                if ((r = allreduce_dev(d_xch, 36 * (size_t)xs_nb + 6 * (size_t)xs_ns, XC_SYSTEM))) return r;
-                sv_ba_xs_move(s, D, d_xs_idx, xs_nb, d_xs_idx + xs_nb, xs_ns, d_xch, 1);
+                sv_ba_xs_move(s, D, dw.xs_idx, xs_nb, dw.xs_idx + xs_nb, xs_ns, dw.xch, 0);
+                if ((r = allreduce_dev(dw.xch, 36 * (size_t)xs_nb + 6 * (size_t)xs_ns, XC_SYSTEM))) return r;
+                sv_ba_xs_move(s, D, dw.xs_idx, xs_nb, dw.xs_idx + xs_nb, xs_ns, dw.xch, 1);
             }
             else if ((r = allreduce_dev(D.Sblk, 36 * (size_t)D.NB + (size_t)D.n, XC_SYSTEM))) return r;
         }
@@ -1196,8 +1071,8 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
             sv_ba_chi2(ctx, s, D, 1, 0, 1);
         }
         if (sharded) {
-            sv_ba_fold(s, D, d_sc, 1);
-            if ((r = allreduce_dev(d_sc, 4, XC_SUMS))) return r;
+            sv_ba_fold(s, D, dw.sc, 1);
+            if ((r = allreduce_dev(dw.sc, 4, XC_SUMS))) return r;
         }
         sv_ba_decide(s, D);
         return SVGPU_OK;
@@ -1303,7 +1178,8 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
         std::fprintf(stderr, "\n");
     }
     if (D.dbg && !D.dbg_schur_on) {  // SVGPU_BA_DBG: where the time of the last fused tail went (100 MHz stamps, relative to the first workgroup's entry)
-        std::vector<unsigned long long> h(8 * (size_t)nb_lm);
+        const int nb_lm = Z.nb_lm;
+        std::vector<unsigned long long> h(dw.dbg.n);
         SV_HIP(ctx, hipMemcpyAsync(h.data(), D.dbg, 8 * h.size(), hipMemcpyDeviceToHost, s));
         SV_HIP(ctx, hipStreamSynchronize(s));
         unsigned long long t0 = ~0ull;
@@ -1337,7 +1213,7 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
         bool on_device = !sharded && E > 0 && HS.nP > 0 && HS.nP <= 48 && have_lists && !host_boundary;
         if (on_device) {
             sv_ba_gate(s, D, 1, nullptr);
-            sv_ba_activity(s, D, d_pt_free);
+            sv_ba_activity(s, D, dw.pt_free);
             rc = optimize(pr->num_second_iter, &it2, true);
             if (rc) return rc;
             st.num_gated = h_ctl->gated;
@@ -1365,23 +1241,23 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
         lap("stage 2");
     }
     // ---- outlier list, final chi2, read-back: ONE copy of the output block (control block | poses | points | outlier flags)
-    if (E > 0 && outlier_out) sv_ba_gate(s, D, 0, d_outlier);
+    if (E > 0 && outlier_out) sv_ba_gate(s, D, 0, dout.outlier);
     if ((rc = chi2_begin(0))) return rc;
     sv_ba_begin(s, D, 0, 0);  // folds the chi2 of the final estimate into the control block (phase 2: nothing else happens)
-    sv_ba_pack_out(s, D, d_state_out);
+    sv_ba_pack_out(s, D, dout.state);
     if (sharded) {  // every rank ends with every landmark: owners contribute their points, the rest zeros (an all-gather through the all-reduce), on the device
-        sv_ba_points_share(s, D, d_state_out + 12 * (size_t)P, d_xch, 0);
-        if ((rc = allreduce_dev(d_xch, 3 * (size_t)L, XC_SETUP))) return rc;
-        sv_ba_points_share(s, D, d_state_out + 12 * (size_t)P, d_xch, 1);
+        sv_ba_points_share(s, D, ba_out_points(dout, P), dw.xch, 0);
+        if ((rc = allreduce_dev(dw.xch, 3 * (size_t)L, XC_SETUP))) return rc;
+        sv_ba_points_share(s, D, ba_out_points(dout, P), dw.xch, 1);
     }
     // (a caller that takes no outlier flags -- global BA: 1.2 MB at config 5 -- gets the block without them)
-    SV_HIP(ctx, hipMemcpyAsync(hs_out, d_out, outlier_out ? out_total : out_outlier, hipMemcpyDeviceToHost, s));
+    SV_HIP(ctx, hipMemcpyAsync(hout.ctl, dout.ctl, ba_out_bytes(dout, outlier_out != nullptr), hipMemcpyDeviceToHost, s));
     if ((rc = wait_stream())) return rc;
-    memcpy(h_ctl, hs_out + out_ctl, sizeof(BaCtl));
-    memcpy(pose_out, hs_out + out_state, sizeof(double) * 12 * (size_t)P);
+    memcpy(h_ctl, hout.ctl, hout.ctl.bytes());
+    memcpy(pose_out, ba_out_poses(hout, P), ba_out_poses(hout, P).bytes());
     {
-        const char* const src = hs_out + out_state + sizeof(double) * 12 * (size_t)P;
-        const size_t bytes = sizeof(double) * 3 * (size_t)L;
+        const char* const src = (const char*)ba_out_points(hout, P).p;
+        const size_t bytes = ba_out_points(hout, P).bytes();
         if (bytes < ((size_t)16 << 20)) memcpy(points_out, src, bytes);
         else {  // (38 MB at 1.6 M landmarks: one core copies them in ~2 ms)
             const int nt = 4;
@@ -1402,7 +1278,7 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
             for (auto& t : th) t.join();
         }
     }
-    const uint8_t* const outl = (const uint8_t*)(hs_out + out_outlier);
+    const uint8_t* const outl = hout.outlier;
     if (outlier_out)
         for (int k = 0; k < E; ++k) outlier_out[perm.empty() ? k : perm[k]] = outl[k];
     st.chi2_final = h_ctl->chi_begin;
@@ -1414,7 +1290,6 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
     ctx->ba_xch[8] = st.lm_trials;
     ctx->ba_xch[9] = st.iters_stage1 + st.iters_stage2;
     if (stats) *stats = st;
-#undef H2D
     return SVGPU_OK;
 }
 

@@ -6,6 +6,7 @@
 #include <cstddef>
 #include <cstdio>
 #include <functional>
+#include <memory>
 #include <vector>
 
 #include "sv_arena.h"
@@ -42,10 +43,10 @@ void layout_check(const char* name, Layout&& layout, Table&& table, Extra&& extr
     CHECK(need % 256 == 0);
     for (const Row& r : table(M)) CHECK(r.p == nullptr && r.piece_bytes == r.touched);
 
-    std::vector<char> buf(need + 512);
-    const char* const base = buf.data();
+    const std::unique_ptr<char[]> buf(new char[need + 512]);  // (never touched: a global-BA sized arena costs address space only)
+    const char* const base = buf.get();
     Pieces Y{};
-    Arena A(buf.data(), need);
+    Arena A(buf.get(), need);
     layout(A, Y);
     CHECK(!A.overflow && A.off == need);
     Rows rows = table(Y);
@@ -59,7 +60,7 @@ void layout_check(const char* name, Layout&& layout, Table&& table, Extra&& extr
     }
     extra(Y, base, need);
     if (need > 0) {
-        Arena S(buf.data(), need - 1);
+        Arena S(buf.get(), need - 1);
         Pieces Z{};
         layout(S, Z);
         CHECK(S.overflow && S.off == need);

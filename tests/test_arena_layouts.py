@@ -1,10 +1,13 @@
 """The scratch arena (stella_vslam_amd/csrc/sv_arena.h) and the layouts of the entry points whose pieces carry their counts (pnp_layout.h,
-posegraph_layout.h, posegraph_envelope_layout.h, sim3opt_layout.h, poseopt_batch_layout.h, match_layout.h) are plain C++.  Each check program is built with
+posegraph_layout.h, posegraph_envelope_layout.h, sim3opt_layout.h, poseopt_batch_layout.h, match_layout.h, ba_layout.h) are plain C++.  Each check program is built with
 g++ against those headers alone.  arena_check.cpp checks the arena itself, the read-back range merge and the shared argument checks; the
-other six run tests/layout_check.h for the smallest and the largest shape of their GPU test: measuring hands out no pointer and keeps
+other seven run tests/layout_check.h for the smallest and the largest shape of their GPU test: measuring hands out no pointer and keeps
 every count, the measured size covers every piece the same layout places, the bytes per piece written out by hand in the program are the
 pieces' own, no two pieces overlap, and a capacity one byte short latches the overflow flag.  match_arena_check.cpp adds the prefix invariant
-of the two-pass matchers: every piece in front of the candidate lists keeps its offset whatever the lists' capacity."""
+of the two-pass matchers: every piece in front of the candidate lists keeps its offset whatever the lists' capacity.  ba_arena_check.cpp
+checks both placements of bundle adjustment (device arena and page-locked host image, under every flag combination), that their input
+blocks coincide piece by piece, that the output block is what the one-copy read-back takes it for, and ba_block_rows against a
+brute-force restatement."""
 import pytest
 
 from tests.host_check import ROOT, build_and_run
@@ -17,6 +20,7 @@ PROGRAMS = {
     "sim3opt_arena_check.cpp": "sim3opt arena ok",
     "poseopt_batch_arena_check.cpp": "poseopt batch arena ok",
     "match_arena_check.cpp": "match arena ok",
+    "ba_arena_check.cpp": "ba arena ok",
 }
 
 
