@@ -26,20 +26,7 @@ int sv_frame_reserve(svgpu_ctx* ctx, svgpu_frame* f, int n, int ncell) {
         if (f->slab) SV_HIP(ctx, hipFree(f->slab));
         f->slab = nullptr;
         f->cap = 0;
-        auto layout = [&](Arena& A) {
-            f->kps_raw = A.take<svgpu_keypoint>(cap);
-            f->desc = A.take<uint8_t>((size_t)cap * 32);
-            f->undist = A.take<svgpu_keypoint>(cap);
-            f->bearings = A.take<double>((size_t)cap * 3);
-            f->xright = A.take<float>(cap);
-            f->depth = A.take<float>(cap);
-            f->xy = A.take<float>((size_t)cap * 2);
-            f->octave = A.take<int32_t>(cap);
-            f->angle = A.take<float>(cap);
-            f->cell_of = A.take<int32_t>(cap);
-            f->cell_items = A.take<int32_t>(cap);
-            f->counts = A.take<int32_t>(1 + SV_MAX_LEVELS);
-        };
+        auto layout = [&](Arena& A) { frame_slab_layout(A, cap, *f); };
         const size_t bytes = arena_measure(layout);
         SV_HIP(ctx, hipMalloc((void**)&f->slab, bytes));
         f->slab_bytes = bytes;
@@ -58,8 +45,6 @@ int sv_frame_reserve(svgpu_ctx* ctx, svgpu_frame* f, int n, int ncell) {
     return SVGPU_OK;
 }
 namespace {
-inline int frame_reserve(svgpu_ctx* ctx, svgpu_frame* f, int n, int ncell) { return sv_frame_reserve(ctx, f, n, ncell); }
-
 // bins the frame's undistorted keypoints (f->xy, f->octave already in place) over the camera's image bounds
 void frame_bin(hipStream_t s, svgpu_frame* f, const svgpu_camera* cam, int grid_cols, int grid_rows) {
     f->grid_cols = grid_cols, f->grid_rows = grid_rows;
@@ -116,7 +101,7 @@ int svgpu_frame_adopt_extraction(svgpu_ctx* ctx, svgpu_frame* f, const svgpu_cam
     SV_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     const int n = ctx->last_extract_n;
-    int rc = frame_reserve(ctx, f, n, grid_cols * grid_rows);
+    int rc = sv_frame_reserve(ctx, f, n, grid_cols * grid_rows);
     if (rc) return rc;
     f->n = n;
     f->has_xright = false;
@@ -147,7 +132,7 @@ int svgpu_frame_upload(svgpu_ctx* ctx, svgpu_frame* f, const svgpu_camera* cam, 
     if (f->device != ctx->device) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_frame_upload: the frame lives on another device");
     SV_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    int rc = frame_reserve(ctx, f, n, grid_cols * grid_rows);
+    int rc = sv_frame_reserve(ctx, f, n, grid_cols * grid_rows);
     if (rc) return rc;
     f->n = n;
     f->has_xright = x_right != nullptr;

@@ -13,6 +13,7 @@
 #include "svgpu.h"
 #include "sv_arena.h"
 #include "orb_plan.h"  // ORB constants, OrbLevel / FastCell / DescBand / OrbConfig, the host planner
+#include "frame_layout.h"
 
 // Optional per-kernel timing with HIP events on the launch stream (svgpu_profile_select / _read / _read_class).
 // One accumulator per kernel class; the selection "*" brackets EVERY class, so that one timed region yields the mean launch time of
@@ -32,28 +33,16 @@ struct SvProf {
 // A frame observation resident on the device (include/svgpu.h svgpu_frame_*): what every projection-family matcher reads of a
 // data::frame / data::keyframe -- descriptors, undistorted keypoints split into the arrays the kernels take, stereo x_right, and the
 // keypoint grid of data::assign_keypoints_to_grid as CSR.  Plain device allocations (grow-only), usable from any context of the device.
-struct svgpu_frame {
+struct svgpu_frame : FrameSlab {
     int device = 0;
     int n = 0, cap = 0;
     int grid_cols = 0, grid_rows = 0, cells_cap = 0;
     float min_x = 0, max_x = 0, min_y = 0, max_y = 0;  // image bounds the grid was binned over
     bool has_xright = false;
-    // ONE device allocation (`slab`, `slab_bytes`), carved in this order, so that what the host wants back of a freshly extracted frame
-    // (kps_raw | desc | undist | bearings [| xright | depth for a stereo pair]) is one contiguous copy (svgpu_track_motion)
+    // ONE device allocation (`slab`, `slab_bytes`) holds the pieces of FrameSlab, carved by frame_slab_layout (frame_layout.h): the
+    // observation first, so that what the host wants back of a freshly extracted frame is one contiguous copy (svgpu_track_motion)
     char* slab = nullptr;
     size_t slab_bytes = 0;
-    svgpu_keypoint* kps_raw = nullptr;  // n distorted keypoints as the extractor wrote them (fused extraction only)
-    uint8_t* desc = nullptr;            // n x 32
-    svgpu_keypoint* undist = nullptr;   // n undistorted keypoint records
-    double* bearings = nullptr;         // n x 3
-    float* xy = nullptr;                // n x 2
-    int32_t* octave = nullptr;
-    float* angle = nullptr;
-    float* xright = nullptr;            // stereo_x_right_ (valid when has_xright)
-    float* depth = nullptr;             // depths_ (written by the fused stereo chain only: svgpu_track_motion_stereo)
-    int32_t* cell_of = nullptr;         // n
-    int32_t* cell_items = nullptr;      // n
-    int32_t* counts = nullptr;          // 1 + SV_MAX_LEVELS ints: the extractor's counts (fused extraction: [0] = n as the device knows it)
     int32_t* cell_off = nullptr;        // grid_cols * grid_rows + 1 (own allocation: sized by the grid)
     int32_t* dummy = nullptr;           // 1 int (the query-side scan of a grid build without queries)
 };

@@ -16,6 +16,7 @@
 #include "svgpu_internal.h"
 #include "ba_kernels.h"
 #include "track_kernels.h"
+#include "track_layout.h"
 
 struct svgpu_tracker {
     svgpu_ctx* ctx = nullptr;
@@ -23,44 +24,17 @@ struct svgpu_tracker {
     int map_device = 0;
     svgpu_camera cam{};
     svgpu_track_config cfg{};
-    // capacities
-    int cap_kp = 0;       // keypoints of the current frame
-    int cap_q = 0;        // queries (last frame's keypoints / local landmarks)
-    size_t cap_cand = 0;  // candidate-list entries BEHIND the per-query slots (lists longer than TRACK_SLOT)
-    size_t img_bytes = 0; // image part of the input block
-    // device
-    char* d_in = nullptr;    // input block: [image] | ids ...
-    size_t in_bytes = 0;
-    char* d_work = nullptr;  // everything the kernels hand to each other
-    size_t work_bytes = 0;
-    double* d_pose = nullptr;  // 12: the pose of the last optimisation
-    // page-locked host
-    char* h_in = nullptr;
-    size_t h_in_bytes = 0;
-    char* h_out = nullptr;   // small results written by the kernels + the read-back of a fresh observation
-    size_t h_out_bytes = 0;
-    // layout of d_work (set by reserve)
-    int32_t *cand_off = nullptr, *cand_cnt = nullptr, *match_q = nullptr, *num = nullptr, *who = nullptr, *kp_of = nullptr, *pred_level = nullptr;
-    uint32_t* dist = nullptr;
-    uint8_t *q_valid = nullptr, *q_blocks = nullptr, *occupied = nullptr, *visible = nullptr, *outlier_kp = nullptr, *po_outlier = nullptr, *po_level = nullptr,
-            *po_robust = nullptr;
-    double *reproj = nullptr, *po_pos = nullptr;
-    float *x_right = nullptr, *po_uvr = nullptr, *po_w = nullptr, *po_h = nullptr;
-    int* po_result = nullptr;
-    int32_t* cur_lm_motion = nullptr;  // chain 1's landmark ids per keypoint (chain 2's come with its input block)
-    int *g_owner = nullptr, *g_match = nullptr;  // tables of the replay's global-memory form (inputs beyond its LDS form)
-    // layout of h_out
-    int32_t *h_n = nullptr, *h_num = nullptr, *h_match = nullptr;
-    int* h_result = nullptr;
-    double* h_pose = nullptr;
-    uint8_t *h_outlier = nullptr, *h_visible = nullptr;
-    unsigned long long* h_stamps = nullptr;  // debug (SVGPU_TRACK_STAMPS): phase stamps of the last k_pose_opt
-    char* h_obs = nullptr;  // read-back of the fresh observation (prefix of the frame's slab)
-    size_t h_obs_bytes = 0;
+    TrackCaps caps;
+    // the four allocations and the layouts placed over them (track_layout.h; `in` over d_in and `hin` over h_in are the same layout)
+    char *d_in = nullptr, *d_work = nullptr, *h_in = nullptr, *h_out = nullptr;
+    TrackIn in, hin;
+    TrackWork w;
+    TrackOut out;
     int last_n_local = -1;
-    int obs_n = 0;          // the observation in h_obs (svgpu_tracker_observation)
-    size_t obs_off[6] = {0, 0, 0, 0, 0, 0};  // kps | desc | undist | bearings | x_right | depth inside h_obs
+    int obs_n = 0;          // the observation in out.h_obs (svgpu_tracker_observation): obs_n keypoints of a frame of capacity obs_cap,
+    int obs_cap = 0;        // laid out over h_obs as `obs` (with the stereo pieces when obs_stereo)
     bool obs_stereo = false;
+    FrameObs obs;
     long long launches = 0, syncs = 0;
     // the RIGHT camera of a stereo rig (svgpu_track_motion_stereo): its image goes through its own context and stream beside the left one's
     svgpu_ctx* right_ctx = nullptr;
@@ -134,59 +108,61 @@ void release(svgpu_tracker* t) {
     if (t->h_in) (void)hipHostFree(t->h_in);
     if (t->h_out) (void)hipHostFree(t->h_out);
     t->d_in = t->d_work = t->h_in = t->h_out = nullptr;
-    t->in_bytes = t->work_bytes = t->h_in_bytes = t->h_out_bytes = 0;
+    t->caps = TrackCaps{}, t->in = t->hin = TrackIn{}, t->w = TrackWork{}, t->out = TrackOut{}, t->obs = FrameObs{};
 }
 
-// (re)allocates the tracker's buffers for the given capacities (grow-only; the tracker is idle between its synchronous calls)
-int reserve(svgpu_tracker* t, int kp, int q, size_t cand, size_t img_bytes, size_t obs_bytes) {
+// lays the observation of a frame of capacity obs_cap out over out.h_obs, as the head of the frame's slab is laid out (like every piece,
+// h_obs owns its padding: the last take may end in it)
+bool place_observation(svgpu_tracker* t) {
+    Arena A(t->out.h_obs.p, pad(t->out.h_obs.n));
+    frame_obs_layout(A, (size_t)t->obs_cap, t->obs_stereo, t->obs);
+    return !A.overflow;
+}
+
+// (re)allocates the tracker's buffers for what a call wants (grow-only, track_caps; the tracker is idle between its synchronous calls)
+int reserve(svgpu_tracker* t, const TrackCaps& want) {
     svgpu_ctx* ctx = t->ctx;
-    const bool grow = kp > t->cap_kp || q > t->cap_q || cand > t->cap_cand || img_bytes > t->img_bytes || obs_bytes > t->h_obs_bytes;
-    if (!grow && t->d_work) return SVGPU_OK;
-    const int ckp = std::max(std::max(kp, t->cap_kp), 64), cq = std::max(std::max(q + q / 4, t->cap_q), 64);
-    const size_t cc = std::max(std::max(cand, t->cap_cand), (size_t)65536), ib = std::max(img_bytes, t->img_bytes), ob = std::max(obs_bytes, t->h_obs_bytes);
+    const TrackCaps c = track_caps(t->caps, want);
+    if (c == t->caps && t->d_work) return SVGPU_OK;
     double pose_keep[12] = {0};
     const bool had_pose = t->d_work != nullptr;
-    if (had_pose) SV_HIP(ctx, hipMemcpy(pose_keep, t->d_pose, sizeof pose_keep, hipMemcpyDeviceToHost));  // the last optimisation's pose survives a growth
+    if (had_pose) SV_HIP(ctx, hipMemcpy(pose_keep, t->w.pose, sizeof pose_keep, hipMemcpyDeviceToHost));  // the last optimisation's pose survives a growth
     std::vector<char> obs_keep;  // ... and so does the observation svgpu_tracker_observation hands out (a growth between an extraction and its matcher's re-run)
-    if (t->obs_n > 0 && t->h_obs) obs_keep.assign(t->h_obs, t->h_obs + t->h_obs_bytes);
+    if (t->obs_n > 0 && t->out.h_obs) obs_keep.assign(t->out.h_obs.p, t->out.h_obs.p + t->out.h_obs.n);
     release(t);
-    // input block: image | ids of the frame's keypoints (ckp) | ids of the queries (cq) | pose
-    t->in_bytes = pad(ib) + pad((size_t)ckp * 4) + pad((size_t)cq * 4) + 256;
-    SV_HIP(ctx, hipMalloc((void**)&t->d_in, t->in_bytes));
-    SV_HIP(ctx, hipHostMalloc((void**)&t->h_in, t->in_bytes, hipHostMallocDefault));
-    t->h_in_bytes = t->in_bytes;
-    auto work = [&](Arena& A) {
-        t->cand_off = A.take<int32_t>(cq + 1), t->cand_cnt = A.take<int32_t>(cq), t->match_q = A.take<int32_t>(cq), t->num = A.take<int32_t>(4);
-        t->who = A.take<int32_t>(ckp), t->kp_of = A.take<int32_t>(ckp), t->pred_level = A.take<int32_t>(cq), t->dist = A.take<uint32_t>((size_t)cq * TRACK_SLOT + cc);
-        t->q_valid = A.take<uint8_t>(cq), t->q_blocks = A.take<uint8_t>(cq), t->occupied = A.take<uint8_t>(ckp), t->visible = A.take<uint8_t>(cq);
-        t->outlier_kp = A.take<uint8_t>(ckp), t->po_outlier = A.take<uint8_t>(ckp), t->po_level = A.take<uint8_t>(ckp), t->po_robust = A.take<uint8_t>(ckp);
-        t->reproj = A.take<double>((size_t)cq * 2), t->po_pos = A.take<double>((size_t)ckp * 3), t->x_right = A.take<float>(cq), t->po_uvr = A.take<float>((size_t)ckp * 3);
-        t->po_w = A.take<float>(ckp), t->po_h = A.take<float>(ckp), t->po_result = A.take<int>(4), t->cur_lm_motion = A.take<int32_t>(ckp);
-        t->d_pose = A.take<double>(12);
-        t->g_owner = A.take<int>(ckp), t->g_match = A.take<int>(cq);
-    };
-    t->work_bytes = arena_measure(work);
-    SV_HIP(ctx, hipMalloc((void**)&t->d_work, t->work_bytes));
-    SV_HIP(ctx, hipMemset(t->d_work, 0, t->work_bytes));  // (the list allocation counter starts at zero; every chain leaves it at zero again)
-    Arena W(t->d_work, t->work_bytes);
-    work(W);
-    if (had_pose) SV_HIP(ctx, hipMemcpy(t->d_pose, pose_keep, sizeof pose_keep, hipMemcpyHostToDevice));
-    // host results
-    auto results = [&](Arena& A) {
-        t->h_stamps = A.take<unsigned long long>(64);
-        t->h_n = A.take<int32_t>(4), t->h_num = A.take<int32_t>(4), t->h_result = A.take<int>(4), t->h_pose = A.take<double>(12);
-        t->h_outlier = A.take<uint8_t>(ckp), t->h_match = A.take<int32_t>(cq), t->h_visible = A.take<uint8_t>(cq), t->h_obs = A.take<char>(ob);
-    };
-    t->h_out_bytes = arena_measure(results);
-    SV_HIP(ctx, hipHostMalloc((void**)&t->h_out, t->h_out_bytes, hipHostMallocDefault));
-    memset(t->h_out, 0, t->h_out_bytes);
-    Arena H(t->h_out, t->h_out_bytes);
-    results(H);
-    t->h_obs_bytes = ob;
-    t->cap_kp = ckp, t->cap_q = cq, t->cap_cand = cc, t->img_bytes = ib;
+    const size_t in_bytes = arena_measure([&](Arena& A) { track_in_layout(A, c, t->in); });
+    SV_HIP(ctx, hipMalloc((void**)&t->d_in, in_bytes));
+    SV_HIP(ctx, hipHostMalloc((void**)&t->h_in, in_bytes, hipHostMallocDefault));
+    Arena D(t->d_in, in_bytes), HI(t->h_in, in_bytes);
+    track_in_layout(D, c, t->in), track_in_layout(HI, c, t->hin);
+    const size_t work_bytes = arena_measure([&](Arena& A) { track_work_layout(A, c, TRACK_SLOT, t->w); });
+    SV_HIP(ctx, hipMalloc((void**)&t->d_work, work_bytes));
+    SV_HIP(ctx, hipMemset(t->d_work, 0, work_bytes));  // (the list allocation counter starts at zero; every chain leaves it at zero again)
+    Arena W(t->d_work, work_bytes);
+    track_work_layout(W, c, TRACK_SLOT, t->w);
+    if (had_pose) SV_HIP(ctx, hipMemcpy(t->w.pose, pose_keep, sizeof pose_keep, hipMemcpyHostToDevice));
+    const size_t out_bytes = arena_measure([&](Arena& A) { track_out_layout(A, c, t->out); });
+    SV_HIP(ctx, hipHostMalloc((void**)&t->h_out, out_bytes, hipHostMallocDefault));
+    memset(t->h_out, 0, out_bytes);
+    Arena H(t->h_out, out_bytes);
+    track_out_layout(H, c, t->out);
+    if (D.overflow || HI.overflow || W.overflow || H.overflow || (!obs_keep.empty() && !place_observation(t)))
+        return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_tracker: the buffers' layouts do not fit what was measured for them");
+    t->caps = c;
     t->last_n_local = -1;
-    if (!obs_keep.empty()) memcpy(t->h_obs, obs_keep.data(), std::min(obs_keep.size(), ob));
+    if (!obs_keep.empty()) memcpy(t->out.h_obs, obs_keep.data(), obs_keep.size());
     return SVGPU_OK;
+}
+
+// a count staged into or out of a piece, from element `at` on, may not exceed it
+template <class T>
+bool fits(const Piece<T>& p, size_t at, size_t n) { return at <= p.n && n <= p.n - at; }
+
+// `rows` rows of `row` bytes, `stride` apart, into the page-locked block at `pitch` (one copy where the two agree)
+void copy_rows(char* dst, size_t pitch, const void* src, size_t stride, size_t row, int rows) {
+    if (stride == pitch) memcpy(dst, src, pitch * rows);
+    else
+        for (int y = 0; y < rows; ++y) memcpy(dst + (size_t)y * pitch, (const char*)src + (size_t)y * stride, row);
 }
 
 void fill_reproj(const svgpu_tracker* t, ReprojProblem& R, const double* pose, float margin) {
@@ -206,7 +182,7 @@ void fill_reproj(const svgpu_tracker* t, ReprojProblem& R, const double* pose, f
 }
 
 void fill_cand_frame(TrackCandProblem& C, const svgpu_frame* f) {
-    C.tdesc = (const uint32_t*)f->desc;
+    C.tdesc = (const uint32_t*)f->desc.p;
     C.t_xy = f->xy;
     C.t_octave = f->octave;
     C.t_angle = f->angle;
@@ -234,72 +210,72 @@ int enqueue_match_and_optimize(svgpu_tracker* t, hipStream_t s, TrackCandProblem
     fill_cand_frame(C, cur);
     C.nt = nt;
     C.nt_dev = nt_dev;
-    C.occupied = t->occupied;
-    C.cand_off = t->cand_off;
-    C.counter = t->num + 2;  // (t->num: [0] matches, [2] the list allocation counter)
-    C.cand_cnt = t->cand_cnt;
-    C.dist = t->dist;
-    C.cap = (int)std::min<size_t>(t->cap_cand, 0x7FFFFFFF);
-    C.q_valid = t->q_valid;
-    C.q_blocks = t->q_blocks;
-    C.visible = t->visible;
-    C.reproj = t->reproj;
-    C.x_right = t->x_right;
-    C.pred_level = t->pred_level;
+    C.occupied = t->w.occupied;
+    C.cand_off = t->w.cand_off;
+    C.counter = t->w.num + 2;  // (t->w.num: [0] matches, [2] the list allocation counter)
+    C.cand_cnt = t->w.cand_cnt;
+    C.dist = t->w.dist;
+    C.cap = (int)std::min<size_t>(t->caps.cand, 0x7FFFFFFF);
+    C.q_valid = t->w.q_valid;
+    C.q_blocks = t->w.q_blocks;
+    C.visible = t->w.visible;
+    C.reproj = t->w.reproj;
+    C.x_right = t->w.x_right;
+    C.pred_level = t->w.pred_level;
     sv_launch_track_cand(ctx, s, C);
     CandProblem P{};
     P.t_octave = cur->octave;
     P.nq = nq;
     P.nt = nt;
     P.nt_dev = nt_dev;
-    P.cand_off = t->cand_off;
-    P.cand_cnt = t->cand_cnt;
-    P.cand_total = t->num + 2;
-    P.q_valid = t->q_valid;
-    P.occupied = C.cur_lm ? t->occupied : nullptr;
-    P.q_blocks = t->q_blocks;
+    P.cand_off = t->w.cand_off;
+    P.cand_cnt = t->w.cand_cnt;
+    P.cand_total = t->w.num + 2;
+    P.q_valid = t->w.q_valid;
+    P.occupied = C.cur_lm ? t->w.occupied : nullptr;
+    P.q_blocks = t->w.q_blocks;
     P.thr = thr;
     P.lowe_ratio = lowe_ratio;
     P.mode = mode;
-    P.dist = t->dist;
-    P.match_q = t->match_q;
-    P.num = t->num;
+    P.dist = t->w.dist;
+    P.match_q = t->w.match_q;
+    P.num = t->w.num;
     P.cap = C.cap;
-    P.match_host = t->h_match;
-    P.num_host = t->h_num;
+    P.match_host = t->out.h_match;
+    P.num_host = t->out.h_num;
     {
         SvProfScope ps(ctx, s, "k_cand");
-        sv_launch_cand_replay(ctx, s, P, t->g_owner, t->g_match);
+        sv_launch_cand_replay(ctx, s, P, t->w.g_owner, t->w.g_match);
     }
     PoseOptDev O;
     memset(&O, 0, sizeof O);
     O.n = 0;
-    O.pos_w = t->po_pos, O.uvr = t->po_uvr, O.inv_sigma_sq = t->po_w, O.huber = t->po_h;
+    O.pos_w = t->w.po_pos, O.uvr = t->w.po_uvr, O.inv_sigma_sq = t->w.po_w, O.huber = t->w.po_h;
     if (t->cam.model == SVGPU_CAM_EQUIRECTANGULAR) O.intr[0] = 0, O.intr[1] = 0, O.intr[2] = t->cam.cols, O.intr[3] = t->cam.rows, O.intr[4] = 0;
     else O.intr[0] = t->cam.fx, O.intr[1] = t->cam.fy, O.intr[2] = t->cam.cx, O.intr[3] = t->cam.cy, O.intr[4] = t->cam.focal_x_baseline;
     if (pose_by_value) memcpy(O.pose_in, pose_by_value, sizeof O.pose_in);
-    else O.pose_in_dev = t->d_pose;
+    else O.pose_in_dev = t->w.pose;
     O.num_trials_robust = t->cfg.po_num_trials_robust, O.num_trials = t->cfg.po_num_trials, O.num_each_iter = t->cfg.po_num_each_iter;
     O.reset_flag_each_round = t->cfg.po_reset_stop_flag_each_round;
     O.gain_thr = 1e-3;  // terminateAction->setGainThreshold(1e-3), pose_optimizer_g2o.cc:55
-    O.pose_out = t->d_pose;
-    O.outlier = t->po_outlier, O.result = t->po_result, O.level = t->po_level, O.robust = t->po_robust;
-    O.trk_overflow = t->num + 2, O.trk_overflow_cap = C.cap;
-    O.trk_match_q = t->match_q, O.trk_qid = q_ids, O.trk_nq = nq;
-    O.trk_cur_lm = cur_lm, O.trk_reset_cur = reset_cur, O.trk_who = t->who;
+    O.pose_out = t->w.pose;
+    O.outlier = t->w.po_outlier, O.result = t->w.po_result, O.level = t->w.po_level, O.robust = t->w.po_robust;
+    O.trk_overflow = t->w.num + 2, O.trk_overflow_cap = C.cap;
+    O.trk_match_q = t->w.match_q, O.trk_qid = q_ids, O.trk_nq = nq;
+    O.trk_cur_lm = cur_lm, O.trk_reset_cur = reset_cur, O.trk_who = t->w.who;
     O.trk_nt_dev = nt_dev, O.trk_nt = nt;
     O.trk_map = t->map->rec, O.trk_map_cap = t->map->cap;
     O.trk_xy = cur->xy, O.trk_octave = cur->octave, O.trk_xright = cur->has_xright ? cur->xright : nullptr;
     for (int l = 0; l < 16; ++l) O.trk_inv_sigma_sq[l] = l < t->cfg.num_levels ? t->cfg.inv_level_sigma_sq[l] : 0.f;
     constexpr float chi_sq_2D = 5.99146, chi_sq_3D = 7.81473;  // pose_optimizer_g2o.cc:74-79
     O.trk_huber = t->cfg.is_monocular ? std::sqrt(chi_sq_2D) : std::sqrt(chi_sq_3D);
-    O.trk_pos = t->po_pos, O.trk_uvr = t->po_uvr, O.trk_w = t->po_w, O.trk_h = t->po_h, O.trk_kp_of = t->kp_of;
-    O.trk_outlier_kp = t->outlier_kp, O.host_outlier_kp = t->h_outlier, O.host_pose = t->h_pose, O.host_result = t->h_result;
-    O.trk_counter_reset = t->num + 2;
+    O.trk_pos = t->w.po_pos, O.trk_uvr = t->w.po_uvr, O.trk_w = t->w.po_w, O.trk_h = t->w.po_h, O.trk_kp_of = t->w.kp_of;
+    O.trk_outlier_kp = t->w.outlier_kp, O.host_outlier_kp = t->out.h_outlier, O.host_pose = t->out.h_pose, O.host_result = t->out.h_result;
+    O.trk_counter_reset = t->w.num + 2;
     static const bool want_stamps = std::getenv("SVGPU_TRACK_STAMPS") != nullptr;
     if (want_stamps) {
-        O.stamps = t->h_stamps;
-        t->h_stamps[0] = 0;
+        O.stamps = t->out.h_stamps;
+        t->out.h_stamps[0] = 0;
     }
     sv_pose_opt(ctx, s, O);
     SV_HIP(ctx, hipGetLastError());
@@ -309,14 +285,14 @@ int enqueue_match_and_optimize(svgpu_tracker* t, hipStream_t s, TrackCandProblem
 
 void fill_result(const svgpu_tracker* t, int n_kp, svgpu_track_result* r) {
     r->n_keypoints = n_kp;
-    r->num_matches = t->h_num[0];
-    r->num_candidates = t->h_num[1];
-    r->replay_sweeps = t->h_num[2];
+    r->num_matches = t->out.h_num[0];
+    r->num_candidates = t->out.h_num[1];
+    r->replay_sweeps = t->out.h_num[2];
     r->reserved = 0;
-    r->num_valid = t->h_result[0];
-    r->lm_iterations = t->h_result[1];
-    r->num_observations = t->h_result[3];
-    memcpy(r->pose_cw, t->h_pose, sizeof r->pose_cw);
+    r->num_valid = t->out.h_result[0];
+    r->lm_iterations = t->out.h_result[1];
+    r->num_observations = t->out.h_result[3];
+    memcpy(r->pose_cw, t->out.h_pose, sizeof r->pose_cw);
 }
 }  // namespace
 
@@ -347,15 +323,15 @@ void svgpu_tracker_destroy(svgpu_tracker* t) {
 }
 
 int svgpu_tracker_observation(const svgpu_tracker* t, const svgpu_keypoint** kps, const uint8_t** desc, const svgpu_keypoint** undist_kps, const double** bearings) {
-    if (!t || !t->h_obs || t->obs_n <= 0) return 0;
-    if (kps) *kps = (const svgpu_keypoint*)(t->h_obs + t->obs_off[0]);
-    if (desc) *desc = (const uint8_t*)(t->h_obs + t->obs_off[1]);
-    if (undist_kps) *undist_kps = (const svgpu_keypoint*)(t->h_obs + t->obs_off[2]);
-    if (bearings) *bearings = (const double*)(t->h_obs + t->obs_off[3]);
+    if (!t || !t->obs.kps_raw || t->obs_n <= 0) return 0;
+    if (kps) *kps = t->obs.kps_raw;
+    if (desc) *desc = t->obs.desc;
+    if (undist_kps) *undist_kps = t->obs.undist;
+    if (bearings) *bearings = t->obs.bearings;
     return t->obs_n;
 }
 
-const unsigned long long* svgpu_tracker_debug_stamps(const svgpu_tracker* t) { return t ? t->h_stamps : nullptr; }
+const unsigned long long* svgpu_tracker_debug_stamps(const svgpu_tracker* t) { return t ? t->out.h_stamps : nullptr; }
 
 int svgpu_tracker_counters(const svgpu_tracker* t, long long* launches, long long* host_syncs) {
     if (!t) return SVGPU_ERR_INVALID;
@@ -419,15 +395,20 @@ int track_motion(svgpu_tracker* t, svgpu_ctx* ctx_right, svgpu_frame* cur, const
     const int row_l = ing_l ? C.width * ing_l->channels : C.width, pitch_l = ing_l ? row_l : pitch;
     const int row_r = ing_r ? C.width * ing_r->channels : C.width, pitch_r = ing_r ? row_r : pitch;
     const size_t img_bytes = img ? (size_t)pitch_l * C.height : 0, img_r_bytes = stereo ? (size_t)pitch_r * C.height : 0;
-    // what comes back of a fresh observation: the slab's prefix kps_raw | desc | undist | bearings
-    const size_t obs_bytes = !img ? 0 : (stereo || rgbd) ? (size_t)((char*)cur->depth - cur->slab) + (size_t)cur->cap * 4 : (size_t)((char*)cur->bearings - cur->slab) + (size_t)cur->cap * 24;
+    // what comes back of a fresh observation: the head of the slab, kps_raw | desc | undist | bearings [| xright | depth]
+    FrameObs fresh;
+    if (img) {
+        Arena measure;
+        frame_obs_layout(measure, (size_t)cur->cap, stereo || rgbd, fresh);
+    }
+    const size_t obs_bytes = frame_obs_bytes(fresh);
     const size_t depth_row = (size_t)C.width * (depth_type ? depth_es : sizeof(float));
     const size_t depth_bytes = rgbd ? depth_row * C.height : 0;
     if ((stereo || rgbd) && (rc = reserve_right(t, std::max(img_r_bytes, depth_bytes), nt_cap))) return rc;
     if (ing_l && (rc = reserve_ingest_buffer(t, (void**)&t->d_gray, &t->gray_bytes, gray_bytes))) return rc;
     if (ing_r && (rc = reserve_ingest_buffer(t, (void**)&t->d_gray_r, &t->gray_r_bytes, gray_bytes))) return rc;
     if (depth_type && (rc = reserve_ingest_buffer(t, (void**)&t->d_depth, &t->depth_bytes, (size_t)C.width * C.height * sizeof(float)))) return rc;
-    if ((rc = reserve(t, nt_cap, n_last, t->cap_cand, img_bytes, obs_bytes))) return rc;
+    if ((rc = reserve(t, TrackCaps{nt_cap, n_last, t->caps.cand, img_bytes, obs_bytes}))) return rc;
     // assume_forward / assume_backward (projection.cc:101-116)
     double Rg[9], tg[3], twc[3], tlc[3];
     for (int i = 0; i < 3; ++i) {
@@ -442,17 +423,15 @@ int track_motion(svgpu_tracker* t, svgpu_ctx* ctx_right, svgpu_frame* cur, const
     for (int attempt = 0; attempt < 2; ++attempt) {
         const bool extract = img && attempt == 0;
         // ---- input block: [image] | last frame's landmark ids, one copy
-        const size_t o_ids = pad(t->img_bytes);
-        if (extract) {
-            if (stride == pitch_l) memcpy(t->h_in, img, img_bytes);
-            else
-                for (int y = 0; y < C.height; ++y) memcpy(t->h_in + (size_t)y * pitch_l, img + (size_t)y * stride, row_l);
-        }
-        if (n_last > 0) memcpy(t->h_in + o_ids, last_lm_ids, (size_t)n_last * 4);
+        const TrackIn &in = t->in, &hin = t->hin;
+        if (!fits(in.ids, 0, n_last) || !fits(t->out.h_match, 0, n_last) || !fits(t->out.h_outlier, 0, nt_cap)
+            || (extract && (!fits(in.image, 0, img_bytes) || !fits(t->out.h_obs, 0, obs_bytes))))
+            return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_track_motion: internal count mismatch");
+        const size_t ids_bytes = (size_t)n_last * 4, o_ids = (size_t)((const char*)in.ids.p - in.image.p);
+        if (extract) copy_rows(hin.image, pitch_l, img, stride, row_l, C.height);
+        if (n_last > 0) memcpy(hin.ids, last_lm_ids, ids_bytes);
         if (extract && stereo) {  // the right image: its own copy, its own extraction, on the right context's stream -- beside everything below
-            if (stride_right == pitch_r) memcpy(t->h_in_r, img_right, img_r_bytes);
-            else
-                for (int y = 0; y < C.height; ++y) memcpy(t->h_in_r + (size_t)y * pitch_r, img_right + (size_t)y * stride_right, row_r);
+            copy_rows(t->h_in_r, pitch_r, img_right, stride_right, row_r, C.height);
             hipStream_t sr = ctx_right->stream;
             SV_HIP(ctx, hipMemcpyAsync(t->d_in_r, t->h_in_r, img_r_bytes, hipMemcpyHostToDevice, sr));
             const uint8_t* gray_r = (const uint8_t*)t->d_in_r;
@@ -475,23 +454,23 @@ int track_motion(svgpu_tracker* t, svgpu_ctx* ctx_right, svgpu_frame* cur, const
         }
         if (extract && rgbd) {  // the depth image rides down on the main stream behind the colour image (dense rows of C.width floats)
             const size_t ds = depth_type ? (size_t)depth_stride : (size_t)depth_stride * sizeof(float);  // (raw rows: the stride is in bytes)
-            for (int y = 0; y < C.height; ++y) memcpy(t->h_in_r + (size_t)y * depth_row, (const char*)depth_img + (size_t)y * ds, depth_row);
+            copy_rows(t->h_in_r, depth_row, depth_img, ds, depth_row, C.height);
         }
         std::unique_lock<std::mutex> lock(t->map->mtx);
         if (t->map->cap == 0) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_track_motion: the map is empty");
         SvMapReadScope reading(ctx, t->map, s);  // (declared behind the lock: every exit path records the read before the mutex is released)
         if ((rc = reading.begin())) return rc;
-        if (extract) SV_HIP(ctx, hipMemcpyAsync(t->d_in, t->h_in, o_ids + (size_t)n_last * 4, hipMemcpyHostToDevice, s));
-        else if (n_last > 0) SV_HIP(ctx, hipMemcpyAsync(t->d_in + o_ids, t->h_in + o_ids, (size_t)n_last * 4, hipMemcpyHostToDevice, s));
+        if (extract) SV_HIP(ctx, hipMemcpyAsync(in.image, hin.image, o_ids + ids_bytes, hipMemcpyHostToDevice, s));  // (the ids lie behind the image's padding)
+        else if (n_last > 0) SV_HIP(ctx, hipMemcpyAsync(in.ids, hin.ids, ids_bytes, hipMemcpyHostToDevice, s));
         t->launches += 1;
-        const int32_t* d_last_ids = (const int32_t*)(t->d_in + o_ids);
+        const int32_t* d_last_ids = in.ids;
         const int32_t* nt_dev = nullptr;
         if (img) {
             nt_dev = cur->counts;
             if (extract) {
-                const uint8_t* gray_l = (const uint8_t*)t->d_in;
+                const uint8_t* gray_l = (const uint8_t*)in.image.p;
                 if (ing_l) {  // raw frame -> grey, between the upload and the extraction
-                    if ((rc = svgpu_ingest_gray_batch_device(ctx, ing_l, (const uint8_t*)t->d_in, 1, img_bytes, pitch_l, t->d_gray, gray_bytes, pitch, s))) return rc;
+                    if ((rc = svgpu_ingest_gray_batch_device(ctx, ing_l, (const uint8_t*)in.image.p, 1, img_bytes, pitch_l, t->d_gray, gray_bytes, pitch, s))) return rc;
                     gray_l = t->d_gray;
                     t->launches += 1;
                 }
@@ -523,7 +502,7 @@ int track_motion(svgpu_tracker* t, svgpu_ctx* ctx_right, svgpu_frame* cur, const
                 F.G.cols = t->cfg.grid_cols;
                 F.G.rows = t->cfg.grid_rows;
                 F.G.cell_of = cur->cell_of, F.G.cell_off = cur->cell_off, F.G.cell_items = cur->cell_items;
-                F.n_host = t->h_n;
+                F.n_host = t->out.h_n;
                 if (rgbd) {
                     SV_HIP(ctx, hipMemcpyAsync(t->d_in_r, t->h_in_r, depth_bytes, hipMemcpyHostToDevice, s));
                     t->launches += 1;
@@ -543,7 +522,7 @@ int track_motion(svgpu_tracker* t, svgpu_ctx* ctx_right, svgpu_frame* cur, const
                 if (ctx->stream_aux) {
                     SV_HIP(ctx, hipEventRecord(ctx->ev_fork, s));
                     SV_HIP(ctx, hipStreamWaitEvent(ctx->stream_aux, ctx->ev_fork, 0));
-                    SV_HIP(ctx, hipMemcpyAsync(t->h_obs, cur->slab, obs_bytes, hipMemcpyDeviceToHost, ctx->stream_aux));
+                    SV_HIP(ctx, hipMemcpyAsync(t->out.h_obs, cur->kps_raw, obs_bytes, hipMemcpyDeviceToHost, ctx->stream_aux));
                     SV_HIP(ctx, hipEventRecord(ctx->ev_join, ctx->stream_aux));
                     t->launches += 1;
                 }
@@ -556,13 +535,13 @@ int track_motion(svgpu_tracker* t, svgpu_ctx* ctx_right, svgpu_frame* cur, const
         Cd.q_octave = last->octave;
         Cd.q_angle = last->angle;
         Cd.check_orientation = check_orientation;
-        rc = enqueue_match_and_optimize(t, s, Cd, cur, nt_cap, nt_dev, t->cur_lm_motion, 1, d_last_ids, n_last, 100u /* HAMMING_DIST_THR_HIGH */, 0.f,
+        rc = enqueue_match_and_optimize(t, s, Cd, cur, nt_cap, nt_dev, t->w.cur_lm_motion, 1, d_last_ids, n_last, 100u /* HAMMING_DIST_THR_HIGH */, 0.f,
                                         SVGPU_MATCH_BEST_ONLY, pose_guess_cw);
         if (rc) return rc;
         if (extract) {
             if (ctx->stream_aux) SV_HIP(ctx, hipStreamWaitEvent(s, ctx->ev_join, 0));
             else {
-                SV_HIP(ctx, hipMemcpyAsync(t->h_obs, cur->slab, obs_bytes, hipMemcpyDeviceToHost, s));
+                SV_HIP(ctx, hipMemcpyAsync(t->out.h_obs, cur->kps_raw, obs_bytes, hipMemcpyDeviceToHost, s));
                 t->launches += 1;
             }
         }
@@ -570,31 +549,27 @@ int track_motion(svgpu_tracker* t, svgpu_ctx* ctx_right, svgpu_frame* cur, const
         lock.unlock();
         SV_HIP(ctx, hipStreamSynchronize(s));
         t->syncs += 1;
-        if (extract) {  // host copies of the fresh observation (data::frame_observation), out of the slab prefix
-            cur->n = t->h_n[0];
-            t->obs_n = cur->n;
-            t->obs_off[0] = (size_t)((char*)cur->kps_raw - cur->slab), t->obs_off[1] = (size_t)((char*)cur->desc - cur->slab);
-            t->obs_off[2] = (size_t)((char*)cur->undist - cur->slab), t->obs_off[3] = (size_t)((char*)cur->bearings - cur->slab);
-            t->obs_off[4] = (size_t)((char*)cur->xright - cur->slab), t->obs_off[5] = (size_t)((char*)cur->depth - cur->slab);
-            t->obs_stereo = stereo || rgbd;
+        if (extract) {  // host copies of the fresh observation (data::frame_observation), out of the copy of the slab's head
+            cur->n = t->out.h_n[0];
+            t->obs_n = cur->n, t->obs_cap = cur->cap, t->obs_stereo = stereo || rgbd;
+            if (!place_observation(t)) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_track_motion: internal count mismatch");
             if (kps) {
                 const int m = std::min(cur->n, cap);
-                const char* o = t->h_obs;
-                memcpy(kps, o + t->obs_off[0], (size_t)m * sizeof(svgpu_keypoint));
-                memcpy(desc, o + t->obs_off[1], (size_t)m * 32);
-                memcpy(undist_kps, o + t->obs_off[2], (size_t)m * sizeof(svgpu_keypoint));
-                memcpy(bearings, o + t->obs_off[3], (size_t)m * 24);
+                memcpy(kps, t->obs.kps_raw, (size_t)m * sizeof(svgpu_keypoint));
+                memcpy(desc, t->obs.desc, (size_t)m * 32);
+                memcpy(undist_kps, t->obs.undist, (size_t)m * sizeof(svgpu_keypoint));
+                memcpy(bearings, t->obs.bearings, (size_t)m * 24);
             }
         }
-        if ((size_t)t->h_num[1] <= t->cap_cand) break;
+        if ((size_t)t->out.h_num[1] <= t->caps.cand) break;
         // the candidate lists did not fit the capacity: nothing ran behind the list kernel.  Grow (fresh buffers, counter at zero) and enqueue
         // the matcher again -- the extraction stands.
         if (attempt == 1) return sv_set_error(ctx, SVGPU_ERR_CAPACITY, "svgpu_track_motion: candidate lists keep overflowing");
-        if ((rc = reserve(t, nt_cap, n_last, (size_t)t->h_num[1] + (size_t)t->h_num[1] / 4 + 4096, t->img_bytes, t->h_obs_bytes))) return rc;
+        if ((rc = reserve(t, TrackCaps{nt_cap, n_last, (size_t)t->out.h_num[1] + (size_t)t->out.h_num[1] / 4 + 4096, t->caps.img_bytes, t->caps.obs_bytes}))) return rc;
     }
     const int n_kp = cur->n;
-    if (n_last > 0) memcpy(match_last, t->h_match, (size_t)n_last * 4);
-    memcpy(outlier, t->h_outlier, (size_t)(img ? std::min(n_kp, cap) : n_kp));
+    if (n_last > 0) memcpy(match_last, t->out.h_match, (size_t)n_last * 4);
+    memcpy(outlier, t->out.h_outlier, (size_t)(img ? std::min(n_kp, cap) : n_kp));
     fill_result(t, n_kp, result);
     if (img && n_kp > cap) return sv_set_error(ctx, SVGPU_ERR_CAPACITY, "svgpu_track_motion: more keypoints than cap");
     return SVGPU_OK;
@@ -646,9 +621,9 @@ int svgpu_tracker_set_ingest(svgpu_tracker* t, const svgpu_ingest* ingest_left, 
 }
 
 int svgpu_tracker_observation_stereo(const svgpu_tracker* t, const float** x_right, const float** depths) {
-    if (!t || !t->h_obs || t->obs_n <= 0 || !t->obs_stereo) return 0;
-    if (x_right) *x_right = (const float*)(t->h_obs + t->obs_off[4]);
-    if (depths) *depths = (const float*)(t->h_obs + t->obs_off[5]);
+    if (!t || !t->obs.depth || t->obs_n <= 0) return 0;
+    if (x_right) *x_right = t->obs.xright;
+    if (depths) *depths = t->obs.depth;
     return t->obs_n;
 }
 
@@ -668,40 +643,42 @@ int svgpu_track_local_map(svgpu_tracker* t, const svgpu_frame* cur, const int32_
     const int nt = cur->n;
     if (nt > 1024 * 8) return sv_set_error(ctx, SVGPU_ERR_CAPACITY, "svgpu_track_local_map: more than 8192 keypoints per frame");
     int rc;
-    if ((rc = reserve(t, nt, n_local, t->cap_cand, t->img_bytes, t->h_obs_bytes))) return rc;
+    if ((rc = reserve(t, TrackCaps{nt, n_local, t->caps.cand, t->caps.img_bytes, t->caps.obs_bytes}))) return rc;
     for (int attempt = 0; attempt < 2; ++attempt) {
         // ---- input block (behind the image area): the frame's landmark ids | the local landmarks' ids, one copy
-        const size_t o_cur = pad(t->img_bytes), o_loc = o_cur + pad((size_t)t->cap_kp * 4);
-        if (nt > 0) memcpy(t->h_in + o_cur, cur_lm_ids, (size_t)nt * 4);
-        if (n_local > 0) memcpy(t->h_in + o_loc, local_ids, (size_t)n_local * 4);
+        const TrackIn &in = t->in, &hin = t->hin;
+        if (nt > t->caps.kp || !fits(in.ids, in.loc_at, n_local) || !fits(t->out.h_match, 0, n_local) || !fits(t->out.h_visible, 0, n_local) || !fits(t->out.h_outlier, 0, nt))
+            return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_track_local_map: internal count mismatch");
+        if (nt > 0) memcpy(hin.ids, cur_lm_ids, (size_t)nt * 4);
+        if (n_local > 0) memcpy(hin.ids + in.loc_at, local_ids, (size_t)n_local * 4);
         std::unique_lock<std::mutex> lock(t->map->mtx);
         if (t->map->cap == 0) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_track_local_map: the map is empty");
         SvMapReadScope reading(ctx, t->map, s);
         if ((rc = reading.begin())) return rc;
-        SV_HIP(ctx, hipMemcpyAsync(t->d_in + o_cur, t->h_in + o_cur, (o_loc - o_cur) + (size_t)n_local * 4, hipMemcpyHostToDevice, s));
+        SV_HIP(ctx, hipMemcpyAsync(in.ids, hin.ids, (in.loc_at + (size_t)n_local) * 4, hipMemcpyHostToDevice, s));
         t->launches += 1;
         TrackCandProblem Cd{};
         fill_reproj(t, Cd.R, pose_cw, margin);
         Cd.R.ray_cos_thr = ray_cos_thr;
         Cd.R.dist_mode = 0, Cd.R.normal_mode = 0, Cd.R.center_mode = 0, Cd.R.window_mode = 0;
-        Cd.pose_dev = pose_cw ? nullptr : t->d_pose;
+        Cd.pose_dev = pose_cw ? nullptr : t->w.pose;
         Cd.mode = 1;
-        Cd.cur_lm = (const int32_t*)(t->d_in + o_cur);
-        Cd.visible_host = t->h_visible;
-        rc = enqueue_match_and_optimize(t, s, Cd, cur, nt, nullptr, (int32_t*)(t->d_in + o_cur), 0, (const int32_t*)(t->d_in + o_loc), n_local,
+        Cd.cur_lm = in.ids;
+        Cd.visible_host = t->out.h_visible;
+        rc = enqueue_match_and_optimize(t, s, Cd, cur, nt, nullptr, in.ids, 0, in.ids + in.loc_at, n_local,
                                         100u /* HAMMING_DIST_THR_HIGH */, lowe_ratio, SVGPU_MATCH_RATIO_SAME_OCTAVE, pose_cw);
         if (rc) return rc;
         if ((rc = reading.end())) return rc;
         lock.unlock();
         SV_HIP(ctx, hipStreamSynchronize(s));
         t->syncs += 1;
-        if ((size_t)t->h_num[1] <= t->cap_cand) break;
+        if ((size_t)t->out.h_num[1] <= t->caps.cand) break;
         if (attempt == 1) return sv_set_error(ctx, SVGPU_ERR_CAPACITY, "svgpu_track_local_map: candidate lists keep overflowing");
-        if ((rc = reserve(t, nt, n_local, (size_t)t->h_num[1] + (size_t)t->h_num[1] / 4 + 4096, t->img_bytes, t->h_obs_bytes))) return rc;  // (keeps the device pose)
+        if ((rc = reserve(t, TrackCaps{nt, n_local, (size_t)t->out.h_num[1] + (size_t)t->out.h_num[1] / 4 + 4096, t->caps.img_bytes, t->caps.obs_bytes}))) return rc;  // (keeps the device pose)
     }
-    if (n_local > 0) memcpy(match_local, t->h_match, (size_t)n_local * 4);
-    if (visible && n_local > 0) memcpy(visible, t->h_visible, n_local);
-    memcpy(outlier, t->h_outlier, nt);
+    if (n_local > 0) memcpy(match_local, t->out.h_match, (size_t)n_local * 4);
+    if (visible && n_local > 0) memcpy(visible, t->out.h_visible, n_local);
+    memcpy(outlier, t->out.h_outlier, nt);
     fill_result(t, nt, result);
     t->last_n_local = n_local;
     return SVGPU_OK;
@@ -713,9 +690,9 @@ int svgpu_track_local_map_observability(svgpu_tracker* t, int n_local, double* r
     if (n_local < 0 || n_local != t->last_n_local) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_track_local_map_observability: no matching svgpu_track_local_map call");
     if (n_local == 0) return SVGPU_OK;
     SV_HIP(ctx, hipSetDevice(ctx->device));
-    if (reproj) SV_HIP(ctx, hipMemcpyAsync(reproj, t->reproj, (size_t)n_local * 16, hipMemcpyDeviceToHost, ctx->stream));
-    if (x_right) SV_HIP(ctx, hipMemcpyAsync(x_right, t->x_right, (size_t)n_local * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (pred_scale_level) SV_HIP(ctx, hipMemcpyAsync(pred_scale_level, t->pred_level, (size_t)n_local * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (reproj) SV_HIP(ctx, hipMemcpyAsync(reproj, t->w.reproj, (size_t)n_local * 16, hipMemcpyDeviceToHost, ctx->stream));
+    if (x_right) SV_HIP(ctx, hipMemcpyAsync(x_right, t->w.x_right, (size_t)n_local * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (pred_scale_level) SV_HIP(ctx, hipMemcpyAsync(pred_scale_level, t->w.pred_level, (size_t)n_local * 4, hipMemcpyDeviceToHost, ctx->stream));
     SV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return SVGPU_OK;
 }

@@ -1,13 +1,18 @@
 """The scratch arena (stella_vslam_amd/csrc/sv_arena.h) and the layouts of the entry points whose pieces carry their counts (pnp_layout.h,
-posegraph_layout.h, posegraph_envelope_layout.h, sim3opt_layout.h, poseopt_batch_layout.h, match_layout.h, ba_layout.h) are plain C++.  Each check program is built with
+posegraph_layout.h, posegraph_envelope_layout.h, sim3opt_layout.h, poseopt_batch_layout.h, match_layout.h, ba_layout.h, track_layout.h,
+frame_layout.h) are plain C++.  Each check program is built with
 g++ against those headers alone.  arena_check.cpp checks the arena itself, the read-back range merge and the shared argument checks; the
-other seven run tests/layout_check.h for the smallest and the largest shape of their GPU test: measuring hands out no pointer and keeps
+other eight run tests/layout_check.h for the smallest and the largest shape of their GPU test: measuring hands out no pointer and keeps
 every count, the measured size covers every piece the same layout places, the bytes per piece written out by hand in the program are the
 pieces' own, no two pieces overlap, and a capacity one byte short latches the overflow flag.  match_arena_check.cpp adds the prefix invariant
 of the two-pass matchers: every piece in front of the candidate lists keeps its offset whatever the lists' capacity.  ba_arena_check.cpp
 checks both placements of bundle adjustment (device arena and page-locked host image, under every flag combination), that their input
 blocks coincide piece by piece, that the output block is what the one-copy read-back takes it for, and ba_block_rows against a
-brute-force restatement."""
+brute-force restatement.  track_arena_check.cpp checks the persistent buffers of the tracked-frame chain (track_layout.h) and the resident
+frame's slab (frame_layout.h, built with include/svgpu.h and orb_plan.h beside it): the input block's two id lists inside one piece (the
+second at a 256-byte boundary behind the keypoint capacity, both within the piece, the image adjacent in front), the observation's layout
+over a buffer of its own against the head of the slab, offset for offset and byte for byte with the expressions the tracker used to write
+out, and the growth policy track_caps (floors, never shrinking, idempotent, no re-allocation for a call repeated)."""
 import pytest
 
 from tests.host_check import ROOT, build_and_run
@@ -21,6 +26,7 @@ PROGRAMS = {
     "poseopt_batch_arena_check.cpp": "poseopt batch arena ok",
     "match_arena_check.cpp": "match arena ok",
     "ba_arena_check.cpp": "ba arena ok",
+    "track_arena_check.cpp": "track arena ok",
 }
 
 

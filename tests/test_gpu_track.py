@@ -436,6 +436,25 @@ def test_candidate_lists_beyond_the_first_capacity(ctx):
     assert np.array_equal(again["match_local"], got["match_local"]) and W.tracker.counters()[1] == 3
 
 
+def test_device_pose_survives_a_growth_of_the_candidate_lists(ctx):
+    """the second half reads the first half's pose on the device; its lists overflow, the buffers are re-allocated, and the re-run still
+    starts from that pose: equal, bit for bit, to a second tracker that is handed the same twelve doubles by value"""
+    from stella_vslam_amd import tracking
+    W = _World(ctx, 8, False, n_lm=6000, n_extra=2000)
+    first = W.tracker.track_motion(W.rf_cur, W.rf_last, W.last_ids, W.guess, W.pose_last, 20.0)
+    cur_lm = np.full(len(W.cur["xy"]), -1, np.int32)
+    local_ids = W.ids.copy()
+    syncs = W.tracker.counters()[1]
+    got = W.tracker.track_local_map(W.rf_cur, cur_lm, local_ids, 40.0, 0.8, 0.5, pose_cw=None)
+    assert got["result"]["num_candidates"] > 65536
+    assert W.tracker.counters()[1] == syncs + 2   # the attempt that overflowed + the one that fitted, behind the growth
+    T = W.T
+    other = tracking.tracker(ctx, W.table, W.cam, T["scale_factors"], T["inv_level_sigma_sq"], T["log_scale_factor"], is_monocular=True, true_baseline=0.11)
+    exp = other.track_local_map(W.rf_cur, cur_lm, local_ids, 40.0, 0.8, 0.5, pose_cw=first["result"]["pose_cw"])
+    assert np.array_equal(got["match_local"], exp["match_local"]) and np.array_equal(got["outlier"], exp["outlier"])
+    assert np.array_equal(got["result"]["pose_cw"], exp["result"]["pose_cw"])
+
+
 def test_landmark_table_upsert_erase_download(ctx):
     from stella_vslam_amd import tracking
     rng = np.random.default_rng(0)
