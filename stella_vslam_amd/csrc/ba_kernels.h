@@ -1,6 +1,9 @@
 // Kernel-argument struct and launchers of the local-BA kernels (internal).
 #pragma once
 #include <cstdint>
+#include <vector>
+
+#include "ba_plan.h"  // BaEnv, SV_BA_SOLVER_*
 
 // Levenberg-Marquardt control block, resident in device memory.  The whole damping loop of
 // OptimizationAlgorithmLevenberg::solve and the terminate_action hook run on the device (k_ba_begin / k_ba_prepare /
@@ -198,12 +201,46 @@ void sv_ba_update(svgpu_ctx* ctx, hipStream_t s, const BaDev& D);               
 // block-Jacobi PCG on the block-sparse reduced camera system (ba_pcg.hip)
 void sv_pcg_init(svgpu_ctx* ctx, hipStream_t s, const BaDev& D);
 void sv_pcg_iterate(svgpu_ctx* ctx, hipStream_t s, const BaDev& D, int first_it, int count);
-enum { SV_BA_SOLVER_AUTO = 0, SV_BA_SOLVER_CHOLESKY = 1, SV_BA_SOLVER_PCG = 2, SV_BA_SOLVER_DENSE = 3, SV_BA_SOLVER_PCG_MULTI = 4, SV_BA_SOLVER_PCG_LDS = 5 /* internal */,
-       SV_BA_SOLVER_ENVELOPE = 6, SV_BA_SOLVER_CHOLESKY_MFMA = 7 };
+void sv_ba_dense_tiled(hipStream_t s, const BaDev& D);  // ba_dense_tiled.hip: tiles of 48, panel + MFMA update per tile column
+// the remaining launchers of ba_kernels.hip
+void sv_ba_maxdiag(hipStream_t s, const BaDev& D);
+void sv_ba_maxslot(hipStream_t s, const BaDev& D);
+void sv_ba_owned_mark(hipStream_t s, const int* lm_off, int L, double* xch, double stop_vote);
+void sv_ba_owned_check(hipStream_t s, const double* xch, int L, uint8_t* any_owner, double* verdict);
+void sv_ba_points_share(hipStream_t s, const BaDev& D, double* points_out, double* xch, int dir);
+void sv_ba_xs_move(hipStream_t s, const BaDev& D, const int* blk_idx, int nb, const int* slot_idx, int ns, double* buf, int dir);
+void sv_ba_zero_inactive(hipStream_t s, const BaDev& D);
+// structure on the device (ba_pairs.hip): pair lists, pose lists, chunk-major units, the solve's own landmark numbering
+size_t sv_ba_pairs_scratch_bytes(size_t pair_cap, int E, size_t nb_cap);
+int sv_ba_build_pairs(svgpu_ctx* ctx, hipStream_t s, const BaDev& D, void* scratch, size_t scratch_bytes, size_t pair_cap, int2* pairs_out,
+                      int* pair_l_out, std::vector<int>& dense_off_host);
+int sv_ba_build_pairs_async(svgpu_ctx* ctx, hipStream_t s, const BaDev& D, void* scratch, size_t scratch_bytes, size_t pair_cap, int total,
+                            int2* pairs_out, int* pair_l_out, int* dense_off_dev);
+size_t sv_ba_pose_lists_scratch_bytes(size_t E);
+size_t sv_ba_units_scratch_bytes(size_t num_pairs, size_t unit_cap);
+int sv_ba_build_units(svgpu_ctx* ctx, hipStream_t s, const int* blk_off_dev, int NB, const int* pair_l_dev, int num_pairs, int L, int chunk_shift, int unit_cap, void* scratch,
+                      size_t scratch_bytes, int4* unit_rec_out, int* blk_unit_off_out, int* num_units_out);
+size_t sv_ba_renumber_scratch_bytes(size_t L);
+int sv_ba_renumber_landmarks(svgpu_ctx* ctx, hipStream_t s, const int* lm_off_old, const int* e_pose_old, int L, int P, int E, void* scratch, size_t scratch_bytes,
+                             int* order_out, int* lm_off_new, int* e_pose_new, int* e_point_new, int* src_edge);
+void sv_ba_permute_measurements(hipStream_t s, const int* src_edge, int E, const float* uvr_old, const float* w_old, const float* hub_old, float* uvr_new, float* w_new, float* hub_new);
+void sv_ba_permute_points(hipStream_t s, const int* order, int L, const double* pts_old, double* pts_new);
+void sv_ba_permute_flags(hipStream_t s, const int* order, int L, const uint8_t* old_flags, uint8_t* new_flags);
+int sv_ba_prepare_lists(svgpu_ctx* ctx, hipStream_t s, const int* e_pose_dev, int E, int P, void* scratch, size_t scratch_bytes, int* pe_off_dev, uint8_t* e_level_dev,
+                        double* e_chi_dev, const void** sorted_out);
+int sv_ba_prepare_pose_major(svgpu_ctx* ctx, hipStream_t s, const void* sorted, const int* e_point_dev, const float* e_uvr_dev, const float* e_w_dev, const float* e_huber_dev,
+                             int E, int* pe_idx_dev, uint8_t* robust_dev, int* pm_point, float* pm_uvr, float* pm_w, float* pm_hub);
+void sv_ba_build_pose_major(hipStream_t s, const int* pe_idx, const int* e_point, const float* e_uvr, const float* e_w, const float* e_hub, int E, int* pm_point,
+                            float* pm_uvr, float* pm_w, float* pm_hub);
+int sv_ba_build_pose_lists(svgpu_ctx* ctx, hipStream_t s, const int* e_pose_dev, const float* e_huber_dev, int E, int P, void* scratch, size_t scratch_bytes,
+                           int* pe_off_dev, int* pe_idx_dev, uint8_t* robust_dev);
+// The switches of this call (svgpu_ba.hip; ba_plan.h BaEnv): the only reader of the environment in the bundle-adjustment sources.  The
+// driver keeps the call's value in svgpu_ctx::ba_env, where the launchers and the envelope planner read it.
+BaEnv ba_env();
 // block envelope Cholesky of large reduced systems (ba_skyline.hip)
-#ifdef __cplusplus
-#include <vector>
 int sv_sky_plan(svgpu_ctx* ctx, hipStream_t s, int nP, const std::vector<int2>& blk_ab, size_t max_bytes, bool* usable, int rank, int world);
-#endif
+bool sv_sky_partition_roles(int nP, const std::vector<int2>& blk_ab, int world, const BaEnv& env, std::vector<int>& job_of, std::vector<int>& owner, int* ncuts, int* sep_blocks_n,
+                            long long* xch_doubles);
+bool sv_sky_current_roles(svgpu_ctx* ctx, const std::vector<int>** job_of, const std::vector<int>** owner, const std::vector<int>** sep_blocks);
 int sv_sky_solve(svgpu_ctx* ctx, hipStream_t s, const BaDev& D);
 void sv_sky_release(svgpu_ctx* ctx);

@@ -2632,7 +2632,7 @@ int sv_ba_lm_blocks(int L) { return (L * LM_LANES + 255) / 256; }
 void sv_ba_linearize(svgpu_ctx* ctx, hipStream_t s, const BaDev& D, int do_prepare) {
     SvProfScope ps(ctx, s, "ba_linearize");
     const int nb = nb_lm_blocks(D);
-    static const bool two_launches = std::getenv("SVGPU_BA_LIN_TWO_LAUNCHES") != nullptr;  // profiling aid: times the two sides apart
+    const bool two_launches = ctx->ba_env.proc.lin_two_launches;  // profiling aid: times the two sides apart
     const int np = D.nP * D.lin_split;
     auto launch = [&](int blocks, int blk0) {
         if (blocks <= 0) return;
@@ -2708,12 +2708,7 @@ void sv_ba_reduce(svgpu_ctx* ctx, hipStream_t s, const BaDev& D) {
     }
     if (D.nshare > RHS_SPLIT) return;  // (svgpu_ba.hip caps nshare at 16)
     const int n_schur = D.NB * D.nshare;
-    // A large system (more than one resident round of units): XCD-contiguous unit order, right-hand side summed by the shares of the diagonal
-    // blocks.  A small one (local BA) leaves the chip part-filled: the right-hand side runs beside the blocks as units of its own, which also
-    // leaves the observation arrays warm for the next linearisation (folded there: k_ba_schur_rhs 13.3 -> 13.6 us, k_ba_lin 11.8 -> 13.0 us).
-    int large = n_schur >= 8192;
-    const char* const order_env = std::getenv("SVGPU_BA_SCHUR_ORDER");  // tests / experiments: 0 = small-system form, 1 = large-system form
-    if (order_env) large = std::atoi(order_env) != 0;
+    const int large = ba_plan_schur_large(n_schur, ctx->ba_env);  // the large-system or the small-system form of the launch
     const int grid = large ? ((n_schur + 7) & ~7) : n_schur + D.nP * RHS_SPLIT;
     hipLaunchKernelGGL(k_ba_schur_rhs, dim3(grid), dim3(64 * SCH_WAVES), 0, s, D, D.nshare, D.rhs_part, large);
     hipLaunchKernelGGL(k_ba_sys_fin, dim3((D.NB * 36 + D.n + 255) / 256), dim3(256), 0, s, D, D.nshare, D.rhs_part, large ? D.nshare : RHS_SPLIT);
@@ -2739,8 +2734,7 @@ size_t sv_ba_chol_bytes(int n) { return sizeof(double) * (size_t)(n + 3) * (n | 
 void sv_ba_solve(svgpu_ctx* ctx, hipStream_t s, const BaDev& D) {
     if (D.nP <= 0) return;
     SvProfScope ps(ctx, s, "ba_solve");
-    static const bool force_mfma = std::getenv("SVGPU_BA_CHOL") && !strcmp(std::getenv("SVGPU_BA_CHOL"), "mfma");
-    if (D.n <= CM_MAX_N && (D.chol_mfma || force_mfma)) {
+    if (D.n <= CM_MAX_N && (D.chol_mfma || ctx->ba_env.proc.chol_mfma)) {
         const size_t lds = cm_lds_bytes(D.n);
         (void)sv_allow_dynamic_lds((const void*)k_ba_chol_mfma, lds);
         hipLaunchKernelGGL(k_ba_chol_mfma, dim3(1), dim3(CM_THREADS), lds, s, D);
@@ -2762,14 +2756,12 @@ void sv_ba_solve(svgpu_ctx* ctx, hipStream_t s, const BaDev& D) {
 // dense image in global memory + the one-workgroup LL^T on it (solver = dense: systems beyond the on-chip solver's 186 unknowns that are
 // to be factored densely all the same -- the default for those sizes is the block envelope Cholesky).  The library's own code throughout:
 // no vendor solver is loaded anywhere.
-void sv_ba_dense_tiled(hipStream_t s, const BaDev& D);
 void sv_ba_solve_dense(svgpu_ctx* ctx, hipStream_t s, const BaDev& D) {
     if (D.nP <= 0) return;
     SvProfScope ps(ctx, s, "ba_solve");
     (void)hipMemsetAsync(D.S, 0, sizeof(double) * (size_t)(D.n + 1) * D.n, s);
     hipLaunchKernelGGL(k_ba_expand_dense, dim3((D.NB * 36 + 255) / 256), dim3(256), 0, s, D);
-    static const bool one_wg = std::getenv("SVGPU_BA_DENSE_ONE_WG") != nullptr;  // A/B aid: the one-workgroup column-by-column form
-    if (one_wg || D.n > 1536) hipLaunchKernelGGL(k_ba_chol_global, dim3(1), dim3(1024), 0, s, D);  // (the tiled form keeps the right-hand side in LDS: n <= 1536)
+    if (ctx->ba_env.proc.dense_one_wg || D.n > 1536) hipLaunchKernelGGL(k_ba_chol_global, dim3(1), dim3(1024), 0, s, D);  // (the tiled form keeps the right-hand side in LDS: n <= 1536)
     else sv_ba_dense_tiled(s, D);  // ba_dense_tiled.hip: tiles of 48, panel + MFMA update per tile column
 }
 

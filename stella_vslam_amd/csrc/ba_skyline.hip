@@ -1021,7 +1021,8 @@ struct SkyPlan {
     std::vector<int> seg_job_of, seg_owner, seg_sep_blocks;
     // the block pattern the plan was made for: an unchanged pattern (the same window / map optimised again) keeps plan and device arrays
     unsigned long long pattern_hash = 0;
-    int pattern_nP = 0, pattern_rank = 0, pattern_world = 0, pattern_env = 0;
+    int pattern_nP = 0, pattern_rank = 0, pattern_world = 0;
+    unsigned long long pattern_env = 0;  // ba_plan_sky_env_key of the environment the plan was made under
     void* d_int = nullptr;
     size_t int_bytes = 0;
     void* d_val = nullptr;
@@ -1099,7 +1100,7 @@ void sv_sky_release(svgpu_ctx* ctx) {
 // two-sided elimination: dense among themselves after the elimination (their envelopes reach back to `sep`); with drop_sep their own
 // blocks are not assembled into this plan (the other plan holds them).
 static void host_sky(int nS, const std::vector<int>& order, const std::vector<std::vector<int>>& adj, const std::vector<int2>& blk_ab, int sep, bool drop_sep,
-                     size_t max_bytes, HostSky& H) {
+                     size_t max_bytes, const BaEnv& env, HostSky& H) {
     const int nP = (int)order.size();
     H = HostSky();
     H.nP = nP;
@@ -1114,8 +1115,7 @@ static void host_sky(int nS, const std::vector<int>& order, const std::vector<st
         if (i >= sep) f = std::min(f, sep);
         H.first[i] = f;
     }
-    // A non-decreasing first[] makes the rows of every column contiguous (the banded kernel); taking the suffix minimum only adds
-    // blocks, so it is kept when the envelope grows by less than a third and stays narrow.
+    // the suffix minimum of first[] makes the rows of every column contiguous: the banded kernel (ba_plan_sky_band says when it is kept)
     {
         std::vector<int> fm(H.first);
         for (int i = nP - 2; i >= 0; --i) fm[i] = std::min(fm[i], fm[i + 1]);
@@ -1126,7 +1126,7 @@ static void host_sky(int nS, const std::vector<int>& order, const std::vector<st
             n1 += (size_t)(i - fm[i] + 1);
             wmax = std::max(wmax, i - fm[i]);
         }
-        if (wmax <= SKY_BAND_W && 3 * n1 <= 4 * n0 && !std::getenv("SVGPU_SKY_NO_BAND")) {
+        if (ba_plan_sky_band(wmax, SKY_BAND_W, n0, n1, env)) {
             H.first = fm;
             H.band = true;
         }
@@ -1202,7 +1202,7 @@ static size_t band_lds_bytes(const HostSky& h) {
 // of half its length, while the stretch before the first cut (the arc through the start vertex) and the one behind the last stay whole: with
 // equal stretches those two jobs were twice as long as the other twelve (58 columns against 29) and set the time of the whole job launch.
 static void plan_segments(int nP, const std::vector<int>& order, const std::vector<std::vector<int>>& adj, const std::vector<int2>& blk_ab, int ncuts, int world,
-                          size_t max_bytes, HostSeg& G, bool cuts_only = false, bool ends_half = false) {
+                          size_t max_bytes, const BaEnv& env, HostSeg& G, bool cuts_only = false, bool ends_half = false) {
     G = HostSeg();
     if (ncuts < 1 || nP < 4) return;
     std::vector<int> pos0(nP);
@@ -1325,7 +1325,7 @@ static void plan_segments(int nP, const std::vector<int>& order, const std::vect
         G.nC[q] = n;
         G.ns[q] = (int)A.size();
         G.max_nC = std::max(G.max_nC, n);
-        host_sky(nP, ord, adj, blk_ab, n, true, max_bytes, G.job[q]);
+        host_sky(nP, ord, adj, blk_ab, n, true, max_bytes, env, G.job[q]);
         const HostSky& h = G.job[q];
         if (!h.ok || !h.band || h.max_m < 1 || h.max_m > SKY_BAND_W || (int)A.size() > h.max_m + 1 || band_lds_bytes(h) > 150 * 1024) return;
         for (size_t a = 0; a < A.size(); ++a)
@@ -1354,7 +1354,7 @@ static void plan_segments(int nP, const std::vector<int>& order, const std::vect
     }
     const int nsep = (int)G.sep_order.size();
     if (nsep > 0) {
-        host_sky(nP, G.sep_order, adj_sep, blk_ab, nsep, false, max_bytes, G.sep);
+        host_sky(nP, G.sep_order, adj_sep, blk_ab, nsep, false, max_bytes, env, G.sep);
         if (!G.sep.ok) return;
         std::vector<std::vector<int>> gb(G.sep.nblocks), gy(nsep);
         for (int q = 0; q < nj; ++q) {
@@ -1704,14 +1704,14 @@ static int seg_upload(svgpu_ctx* ctx, hipStream_t s, SkyPlan* P, int nP, const s
 // column-count model -- the longest job at ~3 us per column (jobs run side by side) + the separator system at ~3 us (banded kernel) or
 // ~6.5 us (general kernel) per column; `want` > 0 forces that many cuts.
 static bool choose_segments(int nP, const std::vector<int>& order, const std::vector<std::vector<int>>& adj, const std::vector<int2>& blk_ab, int want, int world,
-                            size_t max_bytes, HostSeg& G, SegLayout& LY) {
+                            size_t max_bytes, const BaEnv& env, HostSeg& G, SegLayout& LY) {
     G = HostSeg();
     // candidates ranked by the column-count model on their cuts alone (cheap), then planned in full in that order until one holds
     std::vector<std::pair<double, int>> cand;  // (model cost, cuts * 2 + ends_half)
     for (int nc = want > 0 ? want : 2; nc <= (want > 0 ? want : 8); ++nc)
         for (int eh = 0; eh < 2; ++eh) {
             HostSeg c;
-            plan_segments(nP, order, adj, blk_ab, nc, world, max_bytes, c, true, eh != 0);
+            plan_segments(nP, order, adj, blk_ab, nc, world, max_bytes, env, c, true, eh != 0);
             if (!c.ok || (int)c.nC.size() < world) continue;
             cand.push_back({3.0 * c.max_nC + 3.0 * c.nsep_rows + 15.0, 2 * nc + eh});
         }
@@ -1719,7 +1719,7 @@ static bool choose_segments(int nP, const std::vector<int>& order, const std::ve
     double best = 1e30;
     for (const auto& cn : cand) {
         HostSeg c;
-        plan_segments(nP, order, adj, blk_ab, cn.second >> 1, world, max_bytes, c, false, (cn.second & 1) != 0);
+        plan_segments(nP, order, adj, blk_ab, cn.second >> 1, world, max_bytes, env, c, false, (cn.second & 1) != 0);
         if (!c.ok) continue;
         const bool sep_band = c.sep.nP == 0 || (c.sep.band && c.sep.max_m <= SKY_BAND_W && band_lds_bytes(c.sep) <= 150 * 1024);
         const double cost = 3.0 * c.max_nC + (sep_band ? 3.0 : 6.5) * c.sep.nP + 15.0;
@@ -1738,7 +1738,7 @@ static bool choose_segments(int nP, const std::vector<int>& order, const std::ve
 // The front half of sv_sky_plan, free of the device: keyframe graph, RCM order, the one-piece plan H0 and -- when the band is long enough
 // and nothing switches it off -- the segmented plan.  Shared with the keyframe-segment partitioner of a sharded solve, which has to cut
 // the graph exactly where the solve will.
-static bool plan_front(int nP, const std::vector<int2>& blk_ab, int world, size_t max_bytes, std::vector<std::vector<int>>& adj, std::vector<int>& order,
+static bool plan_front(int nP, const std::vector<int2>& blk_ab, int world, size_t max_bytes, const BaEnv& env, std::vector<std::vector<int>>& adj, std::vector<int>& order,
                        HostSky& H0, HostSeg& G, SegLayout& LY) {
     adj.assign(nP, {});
     for (const int2& ab : blk_ab)
@@ -1747,23 +1747,22 @@ static bool plan_front(int nP, const std::vector<int2>& blk_ab, int world, size_
             adj[ab.y].push_back(ab.x);
         }
     order = rcm_order(nP, adj);
-    host_sky(nP, order, adj, blk_ab, nP, false, max_bytes, H0);
+    host_sky(nP, order, adj, blk_ab, nP, false, max_bytes, env, H0);
     if (!H0.ok) return false;
-    const char* ev = std::getenv("SVGPU_SKY_SEGMENTS");
-    const int want = ev ? std::atoi(ev) : -1;
-    if (want == 0 || std::getenv("SVGPU_SKY_ONE_SIDED") || !H0.band || H0.max_m < 1 || nP < 8 * (H0.max_m + 1)) return false;
-    return choose_segments(nP, order, adj, blk_ab, want, world, max_bytes, G, LY);
+    int want = -1;
+    if (!ba_plan_sky_segments(H0.band, H0.max_m, nP, env, &want)) return false;
+    return choose_segments(nP, order, adj, blk_ab, want, world, max_bytes, env, G, LY);
 }
 
 // Keyframe-segment roles of a block pattern, host only: slot -> job (-1 = separator row) and job -> owning rank, as the segmented plan of a
 // `world`-rank solve assigns them; false when that pattern gets no segmented plan.
-bool sv_sky_partition_roles(int nP, const std::vector<int2>& blk_ab, int world, std::vector<int>& job_of, std::vector<int>& owner, int* ncuts, int* sep_blocks_n, long long* xch_doubles) {
+bool sv_sky_partition_roles(int nP, const std::vector<int2>& blk_ab, int world, const BaEnv& env, std::vector<int>& job_of, std::vector<int>& owner, int* ncuts, int* sep_blocks_n, long long* xch_doubles) {
     std::vector<std::vector<int>> adj;
     std::vector<int> order, sep_blocks;
     HostSky H0;
     HostSeg G;
     SegLayout LY;
-    if (nP <= 0 || !plan_front(nP, blk_ab, world, (size_t)256 << 20, adj, order, H0, G, LY)) return false;
+    if (nP <= 0 || !plan_front(nP, blk_ab, world, (size_t)256 << 20, env, adj, order, H0, G, LY)) return false;
     seg_roles(nP, blk_ab, G, job_of, sep_blocks);
     owner = G.owner;
     if (ncuts) *ncuts = G.ncuts;
@@ -1788,10 +1787,10 @@ int sv_sky_plan(svgpu_ctx* ctx, hipStream_t s, int nP, const std::vector<int2>& 
         hsh = (hsh ^ (unsigned)ab.x) * 1099511628211ull;
         hsh = (hsh ^ (unsigned)ab.y) * 1099511628211ull;
     }
-    const char* env_seg = std::getenv("SVGPU_SKY_SEGMENTS");
-    const int env_code = (env_seg ? 1000 + std::atoi(env_seg) : 0) + (std::getenv("SVGPU_SKY_ONE_SIDED") ? 100000 : 0) + (std::getenv("SVGPU_SKY_NO_BAND") ? 200000 : 0);
+    const BaEnv& env = ctx->ba_env;
+    const unsigned long long env_key = ba_plan_sky_env_key(env);
     if (SkyPlan* Q = (SkyPlan*)ctx->ba_sky) {
-        if (Q->usable && Q->pattern_hash == hsh && Q->pattern_nP == nP && Q->pattern_rank == rank && Q->pattern_world == world && Q->pattern_env == env_code
+        if (Q->usable && Q->pattern_hash == hsh && Q->pattern_nP == nP && Q->pattern_rank == rank && Q->pattern_world == world && Q->pattern_env == env_key
             && Q->seg_NB * (Q->seg ? 1 : 0) == (Q->seg ? (int)blk_ab.size() : 0) && (Q->seg || Q->dev[0].NB == (int)blk_ab.size())) {
             *usable = true;  // (the epoch of the hand-over flags keeps counting)
             return SVGPU_OK;
@@ -1801,19 +1800,19 @@ int sv_sky_plan(svgpu_ctx* ctx, hipStream_t s, int nP, const std::vector<int2>& 
     struct Remember {  // records what the plan was made for when the function leaves with a usable plan
         svgpu_ctx* c;
         bool* ok;
-        unsigned long long h;
-        int nP, rank, world, env;
+        unsigned long long h, env;
+        int nP, rank, world;
         ~Remember() {
             SkyPlan* Q = (SkyPlan*)c->ba_sky;
             if (Q && *ok) Q->pattern_hash = h, Q->pattern_nP = nP, Q->pattern_rank = rank, Q->pattern_world = world, Q->pattern_env = env;
         }
-    } remember{ctx, usable, hsh, nP, rank, world, env_code};
+    } remember{ctx, usable, hsh, env_key, nP, rank, world};
     std::vector<std::vector<int>> adj;
     std::vector<int> order;  // position -> slot
     HostSky H[2];
     HostSeg G;
     SegLayout LY;
-    const bool segmented = plan_front(nP, blk_ab, world, max_bytes, adj, order, H[0], G, LY);
+    const bool segmented = plan_front(nP, blk_ab, world, max_bytes, env, adj, order, H[0], G, LY);
     if (!H[0].ok) return SVGPU_OK;
     SkyPlan* P = (SkyPlan*)ctx->ba_sky;
     if (!P) {
@@ -1828,7 +1827,7 @@ int sv_sky_plan(svgpu_ctx* ctx, hipStream_t s, int nP, const std::vector<int2>& 
         if (rs) return rs;
         P->seg_cuts = G.ncuts, P->seg_longest = G.max_nC, P->plan_rows = nP, P->plan_width = H[0].max_m;
         *usable = true;
-        if (std::getenv("SVGPU_BA_TRACE")) {
+        if (env.trace) {
             std::fprintf(stderr, "[ba]     envelope plan: %d block rows, segmented: %d cuts, %zu jobs (longest %d columns, %d on this rank), separator system %d rows%s\n", nP,
                          G.ncuts, G.job.size(), G.max_nC, P->seg_jobs_local, G.sep.nP, G.sep.band ? " (banded)" : "");
         }
@@ -1836,16 +1835,15 @@ int sv_sky_plan(svgpu_ctx* ctx, hipStream_t s, int nP, const std::vector<int2>& 
     }
     // two-sided elimination of a long band: T | S | B with S = as many rows as the band is wide (then no block couples T and B)
     int nplans = 1, tw_m = 0, tw_W = 0, tw_nB = 0;
-    // (the fallback when the segmented plan does not apply.  Its two workgroups wait for each other on flags, so both must be resident at
-    //  once: any device with at least two compute units -- a device restricted below that keeps the one-sided sweep.)
+    // (the fallback when the segmented plan does not apply: ba_plan_sky_two_sided)
     int cus = 0;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
-    if (cus >= 2 && H[0].band && H[0].max_m >= 1 && nP >= 8 * (H[0].max_m + 1) && !std::getenv("SVGPU_SKY_ONE_SIDED")) {
+    if (ba_plan_sky_two_sided(cus, H[0].band, H[0].max_m, nP, env)) {
         const int W = H[0].max_m, m = (nP - W) / 2, nB = nP - m - W;
         std::vector<int> o0(order.begin(), order.begin() + m + W), o1(order.rbegin(), order.rbegin() + nB + W);
         HostSky A, B;
-        host_sky(nP, o0, adj, blk_ab, m, false, max_bytes, A);
-        host_sky(nP, o1, adj, blk_ab, nB, true, max_bytes, B);
+        host_sky(nP, o0, adj, blk_ab, m, false, max_bytes, env, A);
+        host_sky(nP, o1, adj, blk_ab, nB, true, max_bytes, env, B);
         const int Ww = std::max(W, std::max(A.max_m, B.max_m));  // one window size, wide enough for all of S
         auto band_lds = [&](const HostSky& h) {
             return ((size_t)(Ww + 1) * (Ww + 1) * 36 + (size_t)Ww * 36 + (size_t)6 * h.nP) * sizeof(double) + 4 * ((size_t)3 * h.nP + 1 + 2 * h.colrows.size());
@@ -1948,7 +1946,7 @@ int sv_sky_plan(svgpu_ctx* ctx, hipStream_t s, int nP, const std::vector<int2>& 
     P->usable = true;
     P->plan_rows = nP, P->plan_width = H[0].max_m;
     *usable = true;
-    if (std::getenv("SVGPU_BA_TRACE"))
+    if (env.trace)
         std::fprintf(stderr, "[ba]     envelope plan: %d block rows, %zu blocks (%.1f MB), widest column %d rows%s%s\n", nP, H[0].nblocks + (nplans == 2 ? H[1].nblocks : 0),
                      (H[0].nblocks + (nplans == 2 ? H[1].nblocks : 0)) * 288.0 / 1048576.0, H[0].max_m, H[0].band ? ", banded" : "",
                      nplans == 2 ? ", two-sided elimination" : "");
@@ -2059,6 +2057,7 @@ extern "C" int svgpu_selftest_segmented_solve_rank(int nP, int NB, const int* bl
                                                   svgpu_allreduce_fn allreduce, void* allreduce_user, double* x, int* info) {
     if (world < 1 || rank < 0 || rank >= world) return -1;
     if (nP <= 0 || NB <= 0 || !blk_ab_in || !Sblk || !g || !x || !info) return -1;
+    const BaEnv env = ba_env();
     std::vector<int2> blk_ab(NB);
     std::vector<std::vector<int>> adj(nP);
     for (int k = 0; k < NB; ++k) {
@@ -2071,13 +2070,13 @@ extern "C" int svgpu_selftest_segmented_solve_rank(int nP, int NB, const int* bl
     }
     const std::vector<int> order = rcm_order(nP, adj);
     HostSky H0;
-    host_sky(nP, order, adj, blk_ab, nP, false, (size_t)256 << 20, H0);
+    host_sky(nP, order, adj, blk_ab, nP, false, (size_t)256 << 20, env, H0);
     for (int k = 0; k < 8; ++k) info[k] = 0;
     if (!H0.ok) return 1;
     info[7] = H0.max_m;
     HostSeg G;
     SegLayout LY;
-    if (!choose_segments(nP, order, adj, blk_ab, cuts, std::max(world, 1), (size_t)256 << 20, G, LY)) return 1;
+    if (!choose_segments(nP, order, adj, blk_ab, cuts, std::max(world, 1), (size_t)256 << 20, env, G, LY)) return 1;
     const int nj = (int)G.job.size(), nsep = (int)G.sep_order.size();
     info[0] = 1, info[1] = G.ncuts, info[2] = nj, info[3] = nsep, info[4] = G.max_nC, info[5] = G.sep.band ? 1 : 0;
     for (int q = 0; q < nj; ++q) info[6] = std::max(info[6], G.job[q].max_m);

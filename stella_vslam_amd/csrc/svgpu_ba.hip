@@ -21,38 +21,14 @@
 #include "sv_staged_call.h"
 #include "sv_validate.h"
 
-void sv_ba_maxdiag(hipStream_t s, const BaDev& D);
-void sv_ba_maxslot(hipStream_t s, const BaDev& D);
-void sv_ba_owned_mark(hipStream_t s, const int* lm_off, int L, double* xch, double stop_vote);
-void sv_ba_owned_check(hipStream_t s, const double* xch, int L, uint8_t* any_owner, double* verdict);
-void sv_ba_points_share(hipStream_t s, const BaDev& D, double* points_out, double* xch, int dir);
-void sv_ba_xs_move(hipStream_t s, const BaDev& D, const int* blk_idx, int nb, const int* slot_idx, int ns, double* buf, int dir);
-bool sv_sky_partition_roles(int nP, const std::vector<int2>& blk_ab, int world, std::vector<int>& job_of, std::vector<int>& owner, int* ncuts, int* sep_blocks_n, long long* xch_doubles);
-bool sv_sky_current_roles(svgpu_ctx* ctx, const std::vector<int>** job_of, const std::vector<int>** owner, const std::vector<int>** sep_blocks);
-void sv_ba_zero_inactive(hipStream_t s, const BaDev& D);
-size_t sv_ba_pairs_scratch_bytes(size_t pair_cap, int E, size_t nb_cap);
-int sv_ba_build_pairs(svgpu_ctx* ctx, hipStream_t s, const BaDev& D, void* scratch, size_t scratch_bytes, size_t pair_cap, int2* pairs_out,
-                      int* pair_l_out, std::vector<int>& dense_off_host);
-int sv_ba_build_pairs_async(svgpu_ctx* ctx, hipStream_t s, const BaDev& D, void* scratch, size_t scratch_bytes, size_t pair_cap, int total,
-                            int2* pairs_out, int* pair_l_out, int* dense_off_dev);
-size_t sv_ba_pose_lists_scratch_bytes(size_t E);
-size_t sv_ba_units_scratch_bytes(size_t num_pairs, size_t unit_cap);
-int sv_ba_build_units(svgpu_ctx* ctx, hipStream_t s, const int* blk_off_dev, int NB, const int* pair_l_dev, int num_pairs, int L, int chunk_shift, int unit_cap, void* scratch,
-                      size_t scratch_bytes, int4* unit_rec_out, int* blk_unit_off_out, int* num_units_out);
-size_t sv_ba_renumber_scratch_bytes(size_t L);
-int sv_ba_renumber_landmarks(svgpu_ctx* ctx, hipStream_t s, const int* lm_off_old, const int* e_pose_old, int L, int P, int E, void* scratch, size_t scratch_bytes,
-                             int* order_out, int* lm_off_new, int* e_pose_new, int* e_point_new, int* src_edge);
-void sv_ba_permute_measurements(hipStream_t s, const int* src_edge, int E, const float* uvr_old, const float* w_old, const float* hub_old, float* uvr_new, float* w_new, float* hub_new);
-void sv_ba_permute_points(hipStream_t s, const int* order, int L, const double* pts_old, double* pts_new);
-void sv_ba_permute_flags(hipStream_t s, const int* order, int L, const uint8_t* old_flags, uint8_t* new_flags);
-int sv_ba_prepare_lists(svgpu_ctx* ctx, hipStream_t s, const int* e_pose_dev, int E, int P, void* scratch, size_t scratch_bytes, int* pe_off_dev, uint8_t* e_level_dev,
-                        double* e_chi_dev, const void** sorted_out);
-int sv_ba_prepare_pose_major(svgpu_ctx* ctx, hipStream_t s, const void* sorted, const int* e_point_dev, const float* e_uvr_dev, const float* e_w_dev, const float* e_huber_dev,
-                             int E, int* pe_idx_dev, uint8_t* robust_dev, int* pm_point, float* pm_uvr, float* pm_w, float* pm_hub);
-void sv_ba_build_pose_major(hipStream_t s, const int* pe_idx, const int* e_point, const float* e_uvr, const float* e_w, const float* e_hub, int E, int* pm_point,
-                            float* pm_uvr, float* pm_w, float* pm_hub);
-int sv_ba_build_pose_lists(svgpu_ctx* ctx, hipStream_t s, const int* e_pose_dev, const float* e_huber_dev, int E, int P, void* scratch, size_t scratch_bytes,
-                           int* pe_off_dev, int* pe_idx_dev, uint8_t* robust_dev);
+// The switches of bundle adjustment as this call sees them (ba_plan.h).  The only reader of the environment in the bundle-adjustment
+// sources: every entry point calls it once, at its entry.  The process-wide switches keep the first value read.
+BaEnv ba_env() {
+    BaEnv env = ba_env_parse(std::getenv);
+    static const BaEnv::Process first = env.proc;
+    env.proc = first;
+    return env;
+}
 
 namespace {
 
@@ -265,13 +241,14 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
     if (sharded && (world < 1 || rank < 0 || rank >= world)) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_local_ba_sharded: bad rank/world");
     ctx->ba_ar_fn = allreduce;  // (the segmented envelope solve of ba_skyline.hip exchanges through the same all-reduce)
     ctx->ba_ar_user = ar_user;
+    const BaEnv env = ctx->ba_env = ba_env();  // (the launchers of ba_kernels.hip and the envelope planner read the context's copy)
     if (!sharded) {
         world = 1;
         rank = 0;
     }
     svgpu_ba_stats st;
     memset(&st, 0, sizeof(st));
-    const bool trace = std::getenv("SVGPU_BA_TRACE") != nullptr;
+    const bool trace = env.trace > 0;
     auto t_start = std::chrono::steady_clock::now();
     auto lap = [&](const char* what) {
         if (!trace) return;
@@ -281,11 +258,7 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
     };
     // (the outputs start as the inputs: every early return leaves the estimate untouched.  At global-BA sizes the copy of the landmark
     //  positions -- 38 MB at 1.6 M landmarks -- is left to the host team below)
-    const int team_min_obs = [] {  // (SVGPU_BA_TEAM_MIN_OBS, read per call: the tests take small problems through the team's set-up)
-        const char* ev = std::getenv("SVGPU_BA_TEAM_MIN_OBS");
-        return ev ? std::max(64, std::atoi(ev)) : 400000;
-    }();
-    const bool team_sized = E >= team_min_obs && !std::getenv("SVGPU_BA_ONE_THREAD");
+    const bool team_sized = ba_plan_team_sized(E, env);  // (the tests take small problems through the team's set-up)
     memcpy(pose_out, pr->pose_cw, sizeof(double) * 12 * (size_t)P);
     // (the flag is volatile and another thread raises it: ONE read decides both the copy and the return, so that no path leaves
     //  points_out unwritten -- ADVICE r5)
@@ -347,16 +320,11 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
     bool no_levels = true;  // until the first gate: every edge is at level 0
     // host threads of the staging pass at global-BA sizes (SVGPU_BA_HOST_THREADS overrides, 1 .. 16)
     const int nth = [&] {
-        if (!team_sized) return 1;
-        const char* ev = std::getenv("SVGPU_BA_HOST_THREADS");
-        const int v = ev ? std::atoi(ev) : 8;  // (config 5: 1.28 ms with 4 threads, 0.69 with 8, flat beyond)
-        // (the team spins at its barriers: never more threads than CPUs this process may run on -- the affinity mask, which is what a
-        //  container's cpuset leaves, not the machine's core count)
-        unsigned hw = std::thread::hardware_concurrency();
+        // (the CPUs this process may run on: the affinity mask, which is what a container's cpuset leaves, not the machine's core count)
+        unsigned hw = team_sized ? std::thread::hardware_concurrency() : 0;
         cpu_set_t cpus;
-        if (sched_getaffinity(0, sizeof(cpus), &cpus) == 0 && CPU_COUNT(&cpus) > 0) hw = hw == 0 ? (unsigned)CPU_COUNT(&cpus) : std::min(hw, (unsigned)CPU_COUNT(&cpus));
-        const int cap = hw == 0 ? 16 : (int)std::min(16u, hw);
-        return v < 1 ? 1 : (v > cap ? cap : v);
+        if (team_sized && sched_getaffinity(0, sizeof(cpus), &cpus) == 0 && CPU_COUNT(&cpus) > 0) hw = hw == 0 ? (unsigned)CPU_COUNT(&cpus) : std::min(hw, (unsigned)CPU_COUNT(&cpus));
+        return ba_plan_host_threads(team_sized, env, hw);
     }();
     // The host team of a global-BA sized call: nth threads (this one included) scan the observation indices -- range check, "already grouped
     // by landmark?" (the order local_bundle_adjuster_g2o.cc:168-227 and global_bundle_adjuster.cc:66-118 create their edges in) and,
@@ -578,26 +546,13 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
 
     lap("sort observations");
     // ---- solver choice (svgpu_ba_set_solver; SVGPU_BA_SOLVER overrides for experiments)
-    int solver_opt = ctx->ba_solver;
-    if (const char* ev = std::getenv("SVGPU_BA_SOLVER")) {
-        if (!strcmp(ev, "cholesky")) solver_opt = SV_BA_SOLVER_CHOLESKY;
-        else if (!strcmp(ev, "cholesky_mfma")) solver_opt = SV_BA_SOLVER_CHOLESKY_MFMA;
-        else if (!strcmp(ev, "pcg")) solver_opt = SV_BA_SOLVER_PCG;
-        else if (!strcmp(ev, "dense")) solver_opt = SV_BA_SOLVER_DENSE;
-        else if (!strcmp(ev, "pcg_multi")) solver_opt = SV_BA_SOLVER_PCG_MULTI;
-        else if (!strcmp(ev, "envelope")) solver_opt = SV_BA_SOLVER_ENVELOPE;
-    }
+    const int solver_opt = ba_plan_solver_option(ctx->ba_solver, env);
     // ---- device arena
-    // the dense matrix of the tiled LL^T (ba_dense_tiled.hip): on request, and as a candidate of AUTO for windows of 24 - 256 keyframes on one rank
-    const bool want_dense = solver_opt == SV_BA_SOLVER_DENSE || (solver_opt == SV_BA_SOLVER_AUTO && !sharded && P >= 24 && P <= 256 && !std::getenv("SVGPU_BA_NO_DENSE_TILED"));
-    // the solve's own landmark numbering (ba_pairs.hip): one stage, the host team's sizes, observations grouped by landmark
+    const bool want_dense = ba_plan_want_dense(solver_opt, sharded, P, env);
     // (a sharded solve renumbers the landmarks of ITS shard: the numbering is private to the rank's kernels, every landmark-sized exchange
     //  between ranks -- ownership marks, the final positions -- stays in the caller's numbering)
-    const bool renumber = team.running && single_stage && !std::getenv("SVGPU_BA_NO_RENUMBER");
-    static const bool dbg_stamps = std::getenv("SVGPU_BA_DBG") != nullptr;
-    static const bool dbg_schur = dbg_stamps && !strcmp(std::getenv("SVGPU_BA_DBG"), "schur");
-    static const bool dbg_chol = dbg_stamps && !strcmp(std::getenv("SVGPU_BA_DBG"), "chol");
-    BaSizes Z = ba_sizes(P, L, E, world, lm_off, want_dense, renumber, /*units_wanted*/ !std::getenv("SVGPU_BA_NO_UNITS"), dbg_schur ? BA_DBG_SCHUR : (dbg_stamps ? BA_DBG_PER_LANDMARK : BA_DBG_OFF));
+    const bool renumber = ba_plan_renumber(team.running, single_stage, env);
+    BaSizes Z = ba_sizes(P, L, E, world, lm_off, want_dense, renumber, /*units_wanted*/ !env.no_units, ba_plan_dbg_mode(env));
     Z.pair_scratch = std::max(std::max(std::max(sv_ba_pairs_scratch_bytes(Z.pair_cap, E, Z.nb_cap), sv_ba_pose_lists_scratch_bytes((size_t)E)), renumber ? sv_ba_renumber_scratch_bytes((size_t)L) : 0),
                               Z.chunk_units ? sv_ba_units_scratch_bytes(Z.pair_cap, Z.unit_cap()) : 0);
     const size_t pair_cap = Z.pair_cap, nb_cap = Z.nb_cap, xch_doubles = Z.xch_doubles;
@@ -612,7 +567,7 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
     BaDev D;
     ba_bind(D, Z, din, dout, dw, sharded);
     D.rank = rank;
-    D.dbg_schur_on = dbg_schur ? 1 : (dbg_chol ? 2 : 0);
+    D.dbg_schur_on = ba_plan_dbg_kernel(env);
     for (int p = 0; p < P; ++p)
         if (pr->intrinsics[5 * (size_t)p] == 0.0 && pr->intrinsics[5 * (size_t)p + 1] == 0.0) D.any_equirect = 1;
     BaCopy cp{ctx, s};
@@ -684,7 +639,7 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
             // SVGPU_BA_COPY_ON_MAIN: the measurements on the solve's own stream instead.  Measured over 150 config-5 calls: copy stream median
             // 7.50 ms, but 2 calls of 15 ms (the stream's first synchronisation arrives ~8 ms late: two DMA users of one process); own stream
             // 8.06 ms, no call above 8.9.  The default keeps the better mean (7.6 against 8.1); a caller that minds the tail sets the variable.
-            const bool copy_on_main = std::getenv("SVGPU_BA_COPY_ON_MAIN") != nullptr;
+            const bool copy_on_main = env.copy_on_main;
             if (!copy_on_main) {
                 SV_HIP(ctx, hipEventRecord(ctx->ev_ba_copy, s));
                 SV_HIP(ctx, hipStreamWaitEvent(ctx->ba_copy_stream, ctx->ev_ba_copy, 0));
@@ -814,12 +769,7 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
         D.n = 6 * HS.nP;
         D.lin_split = sv_ba_lin_split(E, HS.nP);
         D.chol_in_lds = D.n <= 186 && sv_ba_chol_bytes(D.n) <= 160 * 1024 - 12 * 1024;
-        solver = solver_opt;
-        D.chol_mfma = 0;
-        if (solver == SV_BA_SOLVER_CHOLESKY_MFMA) {  // the same dense on-chip solve, its MFMA form
-            solver = SV_BA_SOLVER_CHOLESKY;
-            D.chol_mfma = 1;
-        }
+        D.chol_mfma = solver_opt == SV_BA_SOLVER_CHOLESKY_MFMA ? 1 : 0;  // the same dense on-chip solve, its MFMA form
         D.Hpp_full = sharded ? dw.HB_full.p : D.Hpp;
         D.bp_full = sharded ? dw.HB_full + 36 * (size_t)HS.nP : D.bp;
         D.scale_pose = (!sharded || rank == 0) ? 1 : 0;
@@ -890,34 +840,12 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
         D.NB = (int)HS.blk_ab.size();
         D.g = D.Sblk + 36 * (size_t)D.NB;
         D.pcg_nparts = (HS.nP + 3) / 4;
-        // shares per block: ~192 pairs per wave (3 per lane); fewer, longer walks are slower (a lane's pairs are a chain of dependent
-        // loads), measured 2.30 / 2.31 / 2.43 / 2.90 / 3.79 ms per config-3 call at 96 / 192 / 384 / 768 / 1536 pairs per wave
-        static const size_t share_pairs = [] {
-            const char* e = std::getenv("SVGPU_BA_SHARE_PAIRS");  // tuning aid: pairs per share of a block of the reduced system
-            const long v = e ? std::atol(e) : 0;
-            return (size_t)(v >= 64 ? v : 192);  // (>= 64: the partial-sum buffer is sized for it)
-        }();
-        D.nshare = D.NB > 0 ? (int)std::min<size_t>(16, std::max<size_t>(1, (HS.num_pairs / (size_t)D.NB + share_pairs - 1) / share_pairs)) : 1;
-        if (D.NB > 0) {
-            // A small system does not fill the chip with ~192-pair shares (config 3: 136 blocks x 7 shares for 1 792 unit slots): its shares shrink
-            // down to one trip of a wave (64 pairs) while the units still fit one resident round -- 17.7 -> 13.4 us per launch there; a large
-            // system keeps the long shares (config 5 at 64 pairs per share: 314 us instead of 189)
-            const size_t avg = HS.num_pairs / (size_t)D.NB, ns_max = std::min<size_t>(16, std::max<size_t>(1, (avg + 63) / 64));
-            while ((size_t)D.nshare < ns_max && (size_t)D.NB * (D.nshare + 1) <= 2304) ++D.nshare;
-        }
+        D.nshare = ba_plan_nshare(HS.num_pairs, D.NB, env);  // shares per block
         if (!reuse) {
             D.unit_rec = nullptr;
             D.num_units = 0;
-            const size_t units_min = [] {  // (SVGPU_BA_UNITS_MIN, read per call: arithmetic shares below this many; the tests lower it)
-                const char* ev = std::getenv("SVGPU_BA_UNITS_MIN");
-                return ev ? (size_t)std::max(1, std::atoi(ev)) : (size_t)8192;
-            }();
-            if (Z.chunk_units && HS.nP > 48 && (size_t)D.NB * D.nshare >= units_min && HS.num_pairs > 0) {
-                // ~0.5 MB of W records per chunk of consecutive landmark ranks (SVGPU_BA_CHUNK_SHIFT overrides: chunk = 2^shift landmarks).  Measured,
-                // Schur launch at config 5 / 9.6 M observations: 256 landmarks 125 / 930 us, 512: 122 / 880, 1 024: 132 / 882, 2 048: 158 / 973; arithmetic shares 144 / 1 537
-                int shift = 4;
-                while (((size_t)2 << shift) * 144 * ((size_t)E / (size_t)std::max(L, 1) + 1) <= ((size_t)1 << 19)) ++shift;
-                if (const char* ev = std::getenv("SVGPU_BA_CHUNK_SHIFT")) shift = std::max(0, std::min(30, std::atoi(ev)));
+            if (ba_plan_units(Z.chunk_units, HS.nP, D.NB, D.nshare, HS.num_pairs, env)) {
+                const int shift = ba_plan_chunk_shift(E, L, env);  // a chunk = 2^shift consecutive landmark ranks
                 int U = 0;
                 const int ru = sv_ba_build_units(ctx, s, dw.blk_off, D.NB, dw.blk_pair_l, (int)HS.num_pairs, L, shift, (int)Z.unit_cap(), dw.pair_scratch, dw.pair_scratch.bytes(), (int4*)dw.unit_rec.p, dw.blk_unit_off, &U);
                 if (ru) return ru;
@@ -930,28 +858,15 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
         }
         // solver of this stage: PCG inside one workgroup's LDS when the blocks fit, else one launch per PCG iteration
         const bool lds_ok = sv_ba_pcg_lds_bytes(D) > 0;
-        // AUTO: dense LL^T in LDS while it fits (n <= ~135: 70 us per trial against 88 us for the LDS-resident PCG at n = 96), the
-        // LDS-resident PCG up to 512 unknowns / ~150 KB of blocks, the one-launch-per-iteration PCG beyond
-        if (solver == SV_BA_SOLVER_AUTO && D.chol_in_lds) solver = SV_BA_SOLVER_CHOLESKY;
-        if (solver == SV_BA_SOLVER_CHOLESKY && !D.chol_in_lds) solver = SV_BA_SOLVER_AUTO;
-        // beyond one workgroup's LDS, a window whose block pattern is close to full (every keyframe of a local window shares landmarks with
-        // most others): the tiled dense LL^T -- 2 launches per 48 columns, MFMA updates.  Measured per damping trial, auto before / tiled:
-        // see DESIGN section 6 (windows of 40 - 100 keyframes).
-        // (from where the register-tile solve no longer fits LDS -- n = 138: per trial 232 us at n = 156 against 386 for the LDS-resident PCG AUTO
-        //  took there and 282 for the envelope factorisation; at n = 132, where the register-tile solve still fits, the two tie at ~200 us)
-        if (solver == SV_BA_SOLVER_AUTO && D.S && !D.chol_in_lds && D.n <= 1536 && (size_t)D.NB * 5 >= (size_t)HS.nP * (HS.nP + 1)) solver = SV_BA_SOLVER_DENSE;  // >= 40 % of the upper blocks kept
-        // beyond the on-chip solvers: the direct envelope factorisation while the envelope of the ordered block graph is small (keyframe
-        // graphs are banded up to a few loop-closure rows), else -- or on request -- the PCG with one launch per iteration
-        if ((solver == SV_BA_SOLVER_AUTO && !lds_ok) || solver == SV_BA_SOLVER_ENVELOPE) {
-            if (!reuse) {
-                bool ok = false;
-                const int rs = sv_sky_plan(ctx, s, HS.nP, HS.blk_ab, (size_t)256 << 20, &ok, rank, world);
-                if (rs) return rs;
-                HS.envelope_ok = ok;
-            }
-            solver = HS.envelope_ok ? SV_BA_SOLVER_ENVELOPE : SV_BA_SOLVER_AUTO;
+        // (the cascade AUTO -> CHOLESKY / DENSE / ENVELOPE / PCG_LDS / PCG_MULTI: ba_plan.h)
+        const BaSolverFront front = ba_plan_solver_front(solver_opt, D.chol_in_lds != 0, D.S != nullptr, D.n, D.NB, HS.nP, lds_ok);
+        if (front.ask_envelope && !reuse) {
+            bool ok = false;
+            const int rs = sv_sky_plan(ctx, s, HS.nP, HS.blk_ab, (size_t)256 << 20, &ok, rank, world);
+            if (rs) return rs;
+            HS.envelope_ok = ok;
         }
-        if (solver == SV_BA_SOLVER_AUTO || solver == SV_BA_SOLVER_PCG) solver = lds_ok ? SV_BA_SOLVER_PCG_LDS : SV_BA_SOLVER_PCG_MULTI;
+        solver = ba_plan_solver_final(front, HS.envelope_ok, lds_ok);
         // Keyframe-segment exchange.  When the envelope solve is segmented and every observation this rank holds is of a keyframe in one of
         // ITS jobs' pieces (or of a separator keyframe) -- svgpu_ba_partition_keyframe_segments cuts shards that way -- the blocks and
         // right-hand side rows of a piece are complete on the rank that eliminates it and no other rank reads them: only the kept blocks
@@ -960,8 +875,7 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
             xs_on = false;
             D.lam_slot = nullptr;
             const std::vector<int>*job_of = nullptr, *owner = nullptr, *sep_blocks = nullptr;
-            const char* xe = std::getenv("SVGPU_BA_EXCHANGE");
-            const bool candidate = sharded && world > 1 && solver == SV_BA_SOLVER_ENVELOPE && !(xe && !strcmp(xe, "full")) && sv_sky_current_roles(ctx, &job_of, &owner, &sep_blocks);
+            const bool candidate = sharded && world > 1 && solver == SV_BA_SOLVER_ENVELOPE && !env.exchange_full && sv_sky_current_roles(ctx, &job_of, &owner, &sep_blocks);
             if (sharded && world > 1) {
                 double misplaced = candidate ? 0.0 : 1.0;
                 if (candidate)
@@ -1013,10 +927,9 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
     // one damping trial (preceded by the linearisation when the control block asks for one); everything is guarded by the control
     // block on the device, so a step enqueued behind a finished optimisation costs a dozen empty launches
     const int pcg_max_it = ctx->pcg_max_it > 0 ? ctx->pcg_max_it : 0;
-    static const bool no_fusion = std::getenv("SVGPU_BA_NO_FUSION") != nullptr;  // A/B aid: the separate kernels
     auto enqueue_step = [&](bool* finished_seen) -> int {
         int r;
-        const bool fused_tail = !no_fusion && !sharded && sv_ba_tail_ok(D);
+        const bool fused_tail = !env.proc.no_fusion &&!sharded && sv_ba_tail_ok(D);
         sv_ba_linearize(ctx, s, D, sharded ? 0 : 1);
         if (sharded) {  // pose blocks summed over the ranks before the damping is initialised from their diagonal
             // ONE collective (round 6; it was two): the rank's slot of the damping initialisation -- the largest diagonal entry of ITS landmarks,
@@ -1103,7 +1016,7 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
         // The steps of the whole stage are enqueued before the first read-back (the common case -- every first trial accepted --
         // costs ONE synchronisation per stage); rejected trials consume steps, so the loop tops up until the device reports phase 2.
         const int max_steps = 10 * std::max(iterations, 1);
-        const bool trace2 = trace && std::getenv("SVGPU_BA_TRACE")[0] == '2';  // one step per read-back, printed
+        const bool trace2 = env.trace == 2;  // one step per read-back, printed
         int steps = 0, todo = nothing ? 0 : (trace2 ? 1 : iterations);
         for (;;) {
             bool finished = false;
@@ -1209,8 +1122,7 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
         // The stage boundary stays on the device when nothing about it needs the host (one GPU, a reduced system whose blocks are all kept):
         // gate -> landmark activity + gated count + "did a pose lose its last edge" -> the second stage's kernels, enqueued without a
         // synchronisation; only a changed pose numbering (rare: a keyframe of the window left without a single inlier) comes back here.
-        const bool host_boundary = std::getenv("SVGPU_BA_HOST_BOUNDARY") != nullptr;  // A/B aid (read per call: the tests switch it)
-        bool on_device = !sharded && E > 0 && HS.nP > 0 && HS.nP <= 48 && have_lists && !host_boundary;
+        bool on_device = !sharded && E > 0 && HS.nP > 0 && HS.nP <= 48 && have_lists && !env.host_boundary;
         if (on_device) {
             sv_ba_gate(s, D, 1, nullptr);
             sv_ba_activity(s, D, dw.pt_free);
@@ -1506,6 +1418,7 @@ int svgpu_ba_last_exchange(svgpu_ctx* ctx, int64_t* info) {
 // keyframes a and b; every diagonal block), the cuts come from the solve's own planner (sv_sky_partition_roles).
 int svgpu_ba_partition_keyframe_segments(const svgpu_ba_problem* pr, int world, int32_t* landmark_rank, int32_t* info) {
     if (!pr || !landmark_rank || !info || world < 1) return SVGPU_ERR_INVALID;
+    const BaEnv env = ba_env();
     const int P = pr->num_poses, L = pr->num_points, E = pr->num_obs;
     for (int k = 0; k < 12; ++k) info[k] = 0;
     for (int l = 0; l < L; ++l) landmark_rank[l] = l % world;
@@ -1555,7 +1468,7 @@ int svgpu_ba_partition_keyframe_segments(const svgpu_ba_problem* pr, int world, 
     std::vector<int> job_of, owner;
     int ncuts = 0, sep_blocks_n = 0;
     long long xch_doubles = 0;
-    if (!sv_sky_partition_roles(nP, blk_ab, world, job_of, owner, &ncuts, &sep_blocks_n, &xch_doubles)) return SVGPU_OK;
+    if (!sv_sky_partition_roles(nP, blk_ab, world, env, job_of, owner, &ncuts, &sep_blocks_n, &xch_doubles)) return SVGPU_OK;
     // a landmark follows the piece of its keyframes.  (A FIXED landmark couples nothing and may be seen from two pieces: its observations
     // cannot be placed on one rank without feeding a foreign piece's pose blocks -- such a problem keeps l % world.)
     std::vector<int32_t> lr(L);

@@ -14,6 +14,7 @@
 #include "sv_arena.h"
 #include "orb_plan.h"  // ORB constants, OrbLevel / FastCell / DescBand / OrbConfig, the host planner
 #include "frame_layout.h"
+#include "ba_plan.h"  // BaEnv
 
 // Optional per-kernel timing with HIP events on the launch stream (svgpu_profile_select / _read / _read_class).
 // One accumulator per kernel class; the selection "*" brackets EVERY class, so that one timed region yields the mean launch time of
@@ -160,6 +161,7 @@ struct svgpu_ctx {
     void* ba_sky = nullptr;         // plan + buffers of the envelope Cholesky (ba_skyline.hip)
     svgpu_allreduce_fn ba_ar_fn = nullptr;  // the all-reduce of the sharded solve in progress (the segmented envelope solve exchanges through it); else null
     void* ba_ar_user = nullptr;
+    BaEnv ba_env;                   // the switches of the bundle-adjustment call in progress (ba_plan.h; local_ba_impl reads them at its entry)
     long long ba_xch[10] = {0};    // svgpu_ba_last_exchange: what the last sharded solve all-reduced (mode | bytes by category | calls | trials | linearisations)
     int comm_rank = 0, comm_world = 1;
 };

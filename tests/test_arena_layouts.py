@@ -12,7 +12,9 @@ brute-force restatement.  track_arena_check.cpp checks the persistent buffers of
 frame's slab (frame_layout.h, built with include/svgpu.h and orb_plan.h beside it): the input block's two id lists inside one piece (the
 second at a 256-byte boundary behind the keypoint capacity, both within the piece, the image adjacent in front), the observation's layout
 over a buffer of its own against the head of the slab, offset for offset and byte for byte with the expressions the tracker used to write
-out, and the growth policy track_caps (floors, never shrinking, idempotent, no re-allocation for a call repeated)."""
+out, and the growth policy track_caps (floors, never shrinking, idempotent, no re-allocation for a call repeated).  ba_plan_check.cpp checks
+the decisions of bundle adjustment (ba_plan.h, no arena in it): the environment switches parsed from a table, every plan function against
+the expression it replaced at the thresholds' neighbours and the bench shapes, and the key of the envelope plan cache."""
 import pytest
 
 from tests.host_check import ROOT, build_and_run
@@ -27,6 +29,7 @@ PROGRAMS = {
     "match_arena_check.cpp": "match arena ok",
     "ba_arena_check.cpp": "ba arena ok",
     "track_arena_check.cpp": "track arena ok",
+    "ba_plan_check.cpp": "ba plan ok",
 }
 
 
