@@ -858,6 +858,41 @@ int svgpu_bow_match(svgpu_ctx* ctx, const uint8_t* desc1, const float* angle1, c
                     const uint8_t* desc2, const float* angle2, const uint8_t* valid2, const int32_t* node2, int n2, const uint8_t* occupied2,
                     float lowe_ratio, int check_orientation, int32_t* match_1to2, int* num_matches);
 
+/* The bucketed matchers for ALL partners of a loop in one call: module::relocalizer's candidates (and their covisible neighbours) against
+ * the frame (module/relocalizer.cc:134-188), module::loop_detector's candidates against the current keyframe (module/loop_detector.cc:377),
+ * mapping_module::create_new_landmarks' neighbours against the current keyframe (mapping_module.cc:332-335).  A view is one side of
+ * svgpu_bow_match / svgpu_match_for_triangulation as host arrays.  `side1` has num_problems views, or ONE view that every problem uses
+ * when side1_shared != 0 (uploaded and ordered once); side2 likewise; both may be shared only when num_problems == 1.
+ *   match_1to2 / matched_2_in_1   the problems' results one after another in problem order: n1 of problem p entries each (num_problems * n1
+ *                                 with a shared side 1), a side-2 keypoint index of that problem's side 2 or -1
+ *   num_matches                   num_problems counts
+ * Problem p's result equals, element for element, what the single entry point returns for its two sides; it depends on nothing else in
+ * the batch.  A problem with n1 == 0 or n2 == 0 has no match.  num_problems == 0 succeeds and touches nothing.
+ * SVGPU_ERR_INVALID, before anything is staged or launched: a null required pointer; n < 0 or n2 >= 1 << 22; node ids on one side of a
+ * problem only (svgpu_bow_match_batch: missing on side 1); check_orientation without angles; for triangulation missing bearings or
+ * octaves, num_levels outside 1..16, an octave outside [0, num_levels); `occupied` on a side-1 view or on any view of the triangulation
+ * matcher; both sides shared with num_problems > 1; totals (rows, keypoints x 8, sum of n1 x n2) beyond int32.  Host in/out, synchronous. */
+typedef struct svgpu_match_view {
+    const uint8_t* desc;     /* n x 32 */
+    const float* angle;      /* n; required when check_orientation */
+    const uint8_t* valid;    /* nullable = all.  bow: "holds a live landmark" (side 1 always; side 2 for match_keyframes);
+                                triangulation: 1 = keypoint WITHOUT a landmark (robust.cc:47-50, 66-70) */
+    const int32_t* node;     /* BoW node id per keypoint, < 0 = none; null on BOTH sides of a problem = one bucket (robust::) */
+    const int32_t* octave;   /* side 1, triangulation only */
+    const double* bearings;  /* n x 3, triangulation only */
+    const float* xright;     /* nullable, triangulation only */
+    const uint8_t* occupied; /* side 2 of svgpu_bow_match_batch only, nullable: not matchable from the start */
+    int n;
+} svgpu_match_view;
+int svgpu_bow_match_batch(svgpu_ctx* ctx, int num_problems, const svgpu_match_view* side1, int side1_shared, const svgpu_match_view* side2,
+                          int side2_shared, float lowe_ratio, int check_orientation, int32_t* match_1to2, int32_t* num_matches);
+/* E_12: num_problems x 9, epipole_in_2: num_problems x 3, valid_epipole: num_problems; the remaining parameters as in
+ * svgpu_match_for_triangulation, shared by all problems. */
+int svgpu_match_for_triangulation_batch(svgpu_ctx* ctx, int num_problems, const svgpu_match_view* side1, int side1_shared,
+                                        const svgpu_match_view* side2, int side2_shared, const double* E_12, const double* epipole_in_2,
+                                        const int32_t* valid_epipole, const float* scale_factors, int num_levels, float residual_rad_thr,
+                                        float lowe_ratio, int check_orientation, int32_t* matched_2_in_1, int32_t* num_matches);
+
 /* ------------------------------------------------------------------------------ landmark refresh (batched)
  * data::landmark::compute_descriptor (data/landmark.cc:199-254) for n landmarks: the representative descriptor is the
  * observation whose row of the k x k Hamming matrix has the smallest lower median (sorted index (unsigned)(0.5 (k-1)); first

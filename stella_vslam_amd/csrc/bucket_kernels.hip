@@ -34,9 +34,8 @@ __global__ void k_bucket_keys(const int32_t* __restrict__ node, int n, unsigned*
 }
 
 // row r = r-th keypoint of side 1 in (node, index) order: its bucket [lo, hi) in the sorted side 2
-__global__ void k_bucket_rows(BucketProblem B) {
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= B.n1) return;
+// (the bodies below take one problem's view: the single call's kernels run them on the whole call, the batch's on record p of a table)
+__device__ __forceinline__ void bucket_row_body(const BucketProblem& B, const int r) {
     const int q = B.q_idx[r];
     const unsigned key = B.key1[r];
     bool live = !(B.valid1 && !B.valid1[q]) && key != 0xFFFFFFFFu;
@@ -61,11 +60,14 @@ __global__ void k_bucket_rows(BucketProblem B) {
     B.row_hi[r] = hi;
     B.q_valid[r] = live && lo < hi;
 }
+__global__ void k_bucket_rows(BucketProblem B) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= B.n1) return;
+    bucket_row_body(B, r);
+}
 
 template <bool FILL>
-__global__ __launch_bounds__(256) void k_bucket_scan(BucketProblem B) {
-    const int r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (r >= B.n1) return;
+__device__ __forceinline__ void bucket_scan_body(const BucketProblem& B, const int r, const int lane) {  // one wave per row
     int total = 0;
     if (B.q_valid[r]) {
         const int q = B.q_idx[r];
@@ -126,6 +128,12 @@ __global__ __launch_bounds__(256) void k_bucket_scan(BucketProblem B) {
     }
     if (!FILL && lane == 0) B.cand_off[r] = total;
 }
+template <bool FILL>
+__global__ __launch_bounds__(256) void k_bucket_scan(BucketProblem B) {
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (r >= B.n1) return;
+    bucket_scan_body<FILL>(B, r, lane);
+}
 
 __global__ void k_bucket_gather_rows(BucketProblem B, uint32_t* __restrict__ qdesc_rows, float* __restrict__ qangle_rows) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -167,6 +175,38 @@ __global__ __launch_bounds__(1024) void k_bucket_exscan(int32_t* __restrict__ da
         __syncthreads();
     }
     if (tid == 0) data[n] = s_carry;
+}
+
+// ---- the batch: K problems as records of a table in device memory; row_base[p] = first row of problem p among all rows
+__global__ __launch_bounds__(256) void k_bucket_rows_batch(const BucketProblem* __restrict__ tab, const int32_t* __restrict__ row_base, int num_problems) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= row_base[num_problems]) return;
+    const int p = sv_segment_of(row_base, num_problems, g);
+    bucket_row_body(tab[p], g - row_base[p]);
+}
+template <bool FILL>
+__global__ __launch_bounds__(256) void k_bucket_scan_batch(const BucketProblem* __restrict__ tab, const int32_t* __restrict__ row_base, int num_problems) {
+    const int g = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;  // one wave per (problem, row)
+    if (g >= row_base[num_problems]) return;
+    const int p = __builtin_amdgcn_readfirstlane(sv_segment_of(row_base, num_problems, g));
+    bucket_scan_body<FILL>(tab[p], g - row_base[p], lane);
+}
+// descriptors of every DISTINCT side 1 in row order (a shared side 1: once)
+__global__ __launch_bounds__(256) void k_bucket_gather_batch(const BucketBatchSide* __restrict__ sides, const int32_t* __restrict__ side_base, int num_sides) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= side_base[num_sides]) return;
+    const int u = sv_segment_of(side_base, num_sides, g), r = g - side_base[u];
+    const BucketBatchSide S = sides[u];
+    const int q = S.order[r];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) S.desc_rows[(size_t)r * 8 + k] = S.desc[(size_t)q * 8 + k];
+}
+__global__ __launch_bounds__(256) void k_bucket_scatter_batch(const BucketProblem* __restrict__ tab, const int32_t* __restrict__ row_base, int num_problems,
+                                                              const int32_t* __restrict__ match_rows, int32_t* __restrict__ match) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= row_base[num_problems]) return;
+    const int p = sv_segment_of(row_base, num_problems, g), b = row_base[p];
+    match[b + tab[p].q_idx[g - b]] = match_rows[g];
 }
 
 }  // namespace
@@ -237,4 +277,23 @@ void sv_bucket_gather_rows(hipStream_t s, const BucketProblem& B, uint32_t* qdes
 }
 void sv_bucket_scatter(hipStream_t s, const BucketProblem& B, const int32_t* match_rows, int32_t* match_q) {
     if (B.n1 > 0) hipLaunchKernelGGL(k_bucket_scatter, dim3((B.n1 + 255) / 256), dim3(256), 0, s, B, match_rows, match_q);
+}
+
+// ---- batch launches (rows = all problems' rows together)
+void sv_bucket_batch_rows_count(svgpu_ctx* ctx, hipStream_t s, const BucketProblem* tab, const int32_t* row_base, int num_problems, int rows, int32_t* cand_off,
+                                int* scan_scratch) {
+    if (rows <= 0) return;
+    hipLaunchKernelGGL(k_bucket_rows_batch, dim3((rows + 255) / 256), dim3(256), 0, s, tab, row_base, num_problems);
+    hipLaunchKernelGGL(k_bucket_scan_batch<false>, dim3((rows + 3) / 4), dim3(256), 0, s, tab, row_base, num_problems);
+    sv_scan_i32(s, cand_off, rows, scan_scratch);  // exclusive scan over all problems' rows: offsets into ONE pair of lists, the total in cand_off[rows]
+}
+void sv_bucket_batch_fill(hipStream_t s, const BucketProblem* tab, const int32_t* row_base, int num_problems, int rows) {
+    if (rows > 0) hipLaunchKernelGGL(k_bucket_scan_batch<true>, dim3((rows + 3) / 4), dim3(256), 0, s, tab, row_base, num_problems);
+}
+void sv_bucket_batch_gather(hipStream_t s, const BucketBatchSide* sides, const int32_t* side_base, int num_sides, int keypoints) {
+    if (keypoints > 0) hipLaunchKernelGGL(k_bucket_gather_batch, dim3((keypoints + 255) / 256), dim3(256), 0, s, sides, side_base, num_sides);
+}
+void sv_bucket_batch_scatter(hipStream_t s, const BucketProblem* tab, const int32_t* row_base, int num_problems, int rows, const int32_t* match_rows,
+                             int32_t* match) {
+    if (rows > 0) hipLaunchKernelGGL(k_bucket_scatter_batch, dim3((rows + 255) / 256), dim3(256), 0, s, tab, row_base, num_problems, match_rows, match);
 }

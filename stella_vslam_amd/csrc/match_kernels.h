@@ -93,6 +93,27 @@ struct CandProblem {
 void sv_launch_cand_replay(svgpu_ctx* ctx, hipStream_t s, const CandProblem& P, int* owner, int* match);  // the replay alone (lists + distances in place)
 int sv_cand_replay_form(int nq, int nt, bool with_cnt, int mode);  // host only: the form the launch code picks (see its definition)
 
+// last u in [0, count) with base[u] <= g (base[0] = 0, ascending): the problem of a row, the side of a keypoint (batch kernels)
+__device__ __forceinline__ int sv_segment_of(const int32_t* __restrict__ base, int count, int g) {
+    int a = 0, b = count;
+    while (b - a > 1) {
+        const int m = (a + b) >> 1;
+        if (base[m] <= g) a = m;
+        else b = m;
+    }
+    return a;
+}
+
+// The batch form: records of K problems in device memory, one replay workgroup per problem
+struct CandBatchReplay {
+    int K;       // sv_cand_replay_form of the problem: >= 0 staged entries per list (tables in LDS), -1 = tables in global memory
+    int* owner;  // K < 0: the problem's own nt / nq ints
+    int* match;
+};
+size_t sv_cand_lds_bytes(int nq, int nt, int K);  // dynamic LDS of the LDS-resident form
+void sv_launch_cand_batch(svgpu_ctx* ctx, hipStream_t s, const CandProblem* tab, const CandBatchReplay* form, const int32_t* row_base, int num_problems,
+                          int rows, size_t lds_bytes);
+
 // Device-side candidate lists: data::assign_keypoints_to_grid + data::get_keypoints_in_cell (data/common.cc:83-190)
 struct GridProblem {
     const float* t_xy;        // nt x 2 undistorted keypoint positions
@@ -198,3 +219,16 @@ void sv_bucket_count(hipStream_t s, const BucketProblem& B);
 void sv_bucket_fill(hipStream_t s, const BucketProblem& B);
 void sv_bucket_gather_rows(hipStream_t s, const BucketProblem& B, uint32_t* qdesc_rows, float* qangle_rows);
 void sv_bucket_scatter(hipStream_t s, const BucketProblem& B, const int32_t* match_rows, int32_t* match_q);
+
+// The batch (K problems as records in device memory, bucket_batch_layout.h): one side of the batch as the gather kernel sees it
+struct BucketBatchSide {
+    const uint32_t* desc;  // n x 8
+    const int* order;      // position in (node, index) order -> keypoint
+    uint32_t* desc_rows;   // side 1: descriptors in row order
+};
+void sv_bucket_batch_rows_count(svgpu_ctx* ctx, hipStream_t s, const BucketProblem* tab, const int32_t* row_base, int num_problems, int rows, int32_t* cand_off,
+                                int* scan_scratch);
+void sv_bucket_batch_fill(hipStream_t s, const BucketProblem* tab, const int32_t* row_base, int num_problems, int rows);
+void sv_bucket_batch_gather(hipStream_t s, const BucketBatchSide* sides, const int32_t* side_base, int num_sides, int keypoints);
+void sv_bucket_batch_scatter(hipStream_t s, const BucketProblem* tab, const int32_t* row_base, int num_problems, int rows, const int32_t* match_rows,
+                             int32_t* match);

@@ -844,9 +844,12 @@ __global__ __launch_bounds__(NT) void k_bf_replay(BfProblem P, int* __restrict__
 #define CAND_SORT_MAX 1024
 __device__ __forceinline__ int cand_total(const CandProblem& P) { return P.cand_total ? *P.cand_total : P.cand_off[P.nq]; }
 __device__ __forceinline__ bool cand_sorted(const CandProblem& P, int n) { return n <= CAND_SORT_MAX && P.mode != SVGPU_MATCH_TRIANGULATION && P.mode != SVGPU_MATCH_AREA; }
-__global__ void k_cand_dist(CandProblem P) {
+// (one implementation for the single call and the batch: the body over one problem's view, list q of P; 64 threads)
+// PT: how the problem travels -- by value for the single call (the kernel's own argument: its fields stay kernel-argument loads), by
+// reference to its record in global memory for the batch (a copy of the record would live in scratch memory)
+template <class PT>
+__device__ __forceinline__ void cand_dist_body(PT P, const int q) {
     if (P.cap > 0 && cand_total(P) > P.cap) return;  // the lists did not fit the guessed capacity: the host re-runs with the exact size
-    const int q = blockIdx.x;
     if (P.q_valid && !P.q_valid[q]) return;
     const int lo = P.cand_off[q], hi = P.cand_off[q + 1];
     __shared__ unsigned long long s_key[CAND_SORT_MAX];  // composites of a long list (more than one entry per lane)
@@ -939,6 +942,7 @@ __global__ void k_cand_dist(CandProblem P) {
         P.dist[lo + i] = key == ~0ull ? 0xFFFFFFFFu : ((uint32_t)(key >> 32) << 22) | (uint32_t)(key & 0x3FFFFFu);
     }
 }
+__global__ void k_cand_dist(CandProblem P) { cand_dist_body<const CandProblem>(P, blockIdx.x); }
 
 __device__ __forceinline__ int cand_verdict(const CandProblem& P, unsigned best, unsigned second, int best_lvl, int second_lvl, int best_idx);
 __device__ int cand_decide(const CandProblem& P, int q, const int* owner) {
@@ -1137,7 +1141,8 @@ __host__ __device__ inline size_t cand_lds_bytes(int nq, int nt, int K, bool wit
 // sweep over everything: 67 -> about 30 us at 2 400 - 4 800 queries.  The result is the serial loop's, as before: within a chunk the
 // iteration is the one described above, and across chunks the order is the serial order.
 #define CAND_CHUNK_QPT 1  // queries per thread and chunk
-__global__ __launch_bounds__(1024) void k_cand_replay_lds(CandProblem P, int K) {
+// (the body over one problem's view, run by one workgroup of 1024: the single call's kernel and the batch's instantiate it)
+__device__ __forceinline__ void cand_replay_lds_body(const CandProblem& P, const int K) {
     extern __shared__ int s_cand[];
     __shared__ int s_changed;
     if (P.cap > 0 && cand_total(P) > P.cap) {  // the lists did not fit: nothing was written, the host re-runs with the exact size
@@ -1234,8 +1239,9 @@ __global__ __launch_bounds__(1024) void k_cand_replay_lds(CandProblem P, int K) 
         if (P.num_host) P.num_host[0] = s_changed, P.num_host[1] = cand_total(P), P.num_host[2] = sweeps_total;
     }
 }
+__global__ __launch_bounds__(1024) void k_cand_replay_lds(CandProblem P, int K) { cand_replay_lds_body(P, K); }
 // the same replay with its tables in global memory (inputs beyond the LDS form)
-__global__ __launch_bounds__(1024) void k_cand_replay(CandProblem P, int* __restrict__ owner, int* __restrict__ match) {
+__device__ __forceinline__ void cand_replay_body(const CandProblem& __restrict__ P, int* __restrict__ owner, int* __restrict__ match) {
     __shared__ int s_changed;
     if (P.cap > 0 && cand_total(P) > P.cap) {
         if (P.num_host && threadIdx.x == 0) P.num_host[0] = 0, P.num_host[1] = cand_total(P);
@@ -1282,6 +1288,24 @@ __global__ __launch_bounds__(1024) void k_cand_replay(CandProblem P, int* __rest
         *P.num = s_changed;
         if (P.num_host) P.num_host[0] = s_changed, P.num_host[1] = cand_total(P);
     }
+}
+__global__ __launch_bounds__(1024) void k_cand_replay(CandProblem P, int* __restrict__ owner, int* __restrict__ match) { cand_replay_body(P, owner, match); }
+
+// The batch forms (bucket matcher, K problems in one call): the same bodies over record p of a table of problems in global memory.
+// Distances: one workgroup of 64 per (problem, row); row_base[p] = first row of problem p among all rows, row_base[K] = their number.
+__global__ __launch_bounds__(64) void k_cand_dist_batch(const CandProblem* __restrict__ tab, const int32_t* __restrict__ row_base, int num_problems) {
+    const int g = blockIdx.x;
+    if (g >= row_base[num_problems]) return;
+    const int p = sv_segment_of(row_base, num_problems, g);
+    cand_dist_body<const CandProblem&>(tab[p], g - row_base[p]);
+}
+// Replay: one persistent workgroup per problem, the form decided per problem on the host (sv_cand_replay_form): K >= 0 staged entries
+// per list with the tables in this workgroup's LDS, or -1 = the problem's own owner / match arrays in global memory.
+__global__ __launch_bounds__(1024) void k_cand_replay_batch(const CandProblem* __restrict__ tab, const CandBatchReplay* __restrict__ form) {
+    const int p = blockIdx.x;
+    const int K = form[p].K;
+    if (K >= 0) cand_replay_lds_body(tab[p], K);
+    else cand_replay_body(tab[p], form[p].owner, form[p].match);
 }
 
 // ------------------------------------------------------------------------------------------------ grid candidate lists
@@ -1852,6 +1876,17 @@ void sv_launch_cand(svgpu_ctx* ctx, hipStream_t s, const CandProblem& P, int* ow
     }
     sv_launch_cand_replay(ctx, s, P, owner, match);
 }
+// K problems (records of `tab` / `form` in device memory): distances for all rows, then one replay workgroup per problem.  `lds_bytes`
+// = the largest LDS-resident form among them (0: none takes it)
+void sv_launch_cand_batch(svgpu_ctx* ctx, hipStream_t s, const CandProblem* tab, const CandBatchReplay* form, const int32_t* row_base, int num_problems,
+                          int rows, size_t lds_bytes) {
+    SvProfScope ps(ctx, s, "k_cand_batch");
+    if (num_problems <= 0) return;
+    if (rows > 0) hipLaunchKernelGGL(k_cand_dist_batch, dim3(rows), dim3(64), 0, s, tab, row_base, num_problems);
+    (void)sv_allow_dynamic_lds((const void*)k_cand_replay_batch, CAND_LDS_BUDGET);
+    hipLaunchKernelGGL(k_cand_replay_batch, dim3(num_problems), dim3(1024), lds_bytes, s, tab, form);
+}
+size_t sv_cand_lds_bytes(int nq, int nt, int K) { return cand_lds_bytes(nq, nt, K, false); }
 void sv_launch_cand_replay(svgpu_ctx* ctx, hipStream_t s, const CandProblem& P0, int* owner, int* match) {
     CandProblem P = P0;
     static const int dbg = std::getenv("SVGPU_REPLAY_DBG") ? std::atoi(std::getenv("SVGPU_REPLAY_DBG")) : 0;

@@ -18,3 +18,12 @@ int sv_sort_pairs(hipStream_t s, unsigned* const keys[2], unsigned long long* co
 // n <= SV_SORT_SMALL_MAX (key, index) pairs sorted by (key, index) in ONE workgroup's LDS (bitonic network on the 64-bit composites)
 #define SV_SORT_SMALL_MAX 16384
 bool sv_sort_small(hipStream_t s, const unsigned* keys_in, const int* idx_in, int n, unsigned* keys_out, int* idx_out);  // false: not available on this device
+// the (node, index) order of several sides in ONE launch, one workgroup per side (the same network): side u sorts n keypoints by
+// (node id, index), node < 0 behind every bucket, node == null = identity; sides beyond SV_SORT_SMALL_MAX are skipped (the caller sorts them)
+struct SvSortSide {
+    const int32_t* node;
+    int n;
+    unsigned* keys_out;
+    int* idx_out;
+};
+bool sv_sort_small_sides(hipStream_t s, const SvSortSide* sides_dev, int count, int max_n);  // false: not available on this device

@@ -217,12 +217,13 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_scatter(const unsigned* __res
 }
 
 
-// (key, index) pairs of one small array: bitonic network over the 64-bit composites key << 32 | index in LDS
-__global__ __launch_bounds__(1024) void k_sort_small(const unsigned* __restrict__ keys_in, const int* __restrict__ idx_in, int n, int npow2, unsigned* __restrict__ keys_out,
-                                                    int* __restrict__ idx_out) {
+// (key, index) pairs of one small array: bitonic network over the 64-bit composites key << 32 | index in LDS.  `load(i)` gives composite i;
+// one workgroup of 1024 (the single sort and the sort of several sides at once instantiate it)
+template <class Load>
+__device__ __forceinline__ void sort_small_body(Load&& load, int n, int npow2, unsigned* __restrict__ keys_out, int* __restrict__ idx_out) {
     extern __shared__ unsigned long long s_v[];
     const int tid = threadIdx.x;
-    for (int i = tid; i < npow2; i += 1024) s_v[i] = i < n ? ((unsigned long long)keys_in[i] << 32) | (unsigned)idx_in[i] : ~0ull;
+    for (int i = tid; i < npow2; i += 1024) s_v[i] = i < n ? load(i) : ~0ull;
     __syncthreads();
     for (int k = 2; k <= npow2; k <<= 1)
         for (int j = k >> 1; j > 0; j >>= 1) {
@@ -243,6 +244,24 @@ __global__ __launch_bounds__(1024) void k_sort_small(const unsigned* __restrict_
         keys_out[i] = (unsigned)(s_v[i] >> 32);
         idx_out[i] = (int)(unsigned)s_v[i];
     }
+}
+__global__ __launch_bounds__(1024) void k_sort_small(const unsigned* __restrict__ keys_in, const int* __restrict__ idx_in, int n, int npow2, unsigned* __restrict__ keys_out,
+                                                    int* __restrict__ idx_out) {
+    sort_small_body([&](int i) { return ((unsigned long long)keys_in[i] << 32) | (unsigned)idx_in[i]; }, n, npow2, keys_out, idx_out);
+}
+// one workgroup per side: the (node, index) order of every side of at most SV_SORT_SMALL_MAX keypoints, keys formed on the way (a keypoint
+// without a node sorts behind every bucket; no node ids at all = one bucket, identity order).  Longer sides are left to the general sort.
+__global__ __launch_bounds__(1024) void k_sort_small_sides(const SvSortSide* __restrict__ sides) {
+    const SvSortSide S = sides[blockIdx.x];
+    if (S.n <= 0 || S.n > SV_SORT_SMALL_MAX) return;
+    if (!S.node) {
+        for (int i = threadIdx.x; i < S.n; i += 1024) S.keys_out[i] = 0u, S.idx_out[i] = i;
+        return;
+    }
+    int npow2 = 1;
+    while (npow2 < S.n) npow2 <<= 1;
+    const int32_t* __restrict__ node = S.node;
+    sort_small_body([&](int i) { return ((unsigned long long)(node[i] < 0 ? 0xFFFFFFFFu : (unsigned)node[i]) << 32) | (unsigned)i; }, S.n, npow2, S.keys_out, S.idx_out);
 }
 }  // namespace
 
@@ -280,5 +299,16 @@ bool sv_sort_small(hipStream_t s, const unsigned* keys_in, const int* idx_in, in
     const size_t lds = (size_t)npow2 * 8;
     if (lds > 48 * 1024 && sv_allow_dynamic_lds((const void*)k_sort_small, lds) != hipSuccess) return false;  // (per device, checked)
     hipLaunchKernelGGL(k_sort_small, dim3(1), dim3(1024), lds, s, keys_in, idx_in, n, npow2, keys_out, idx_out);
+    return hipGetLastError() == hipSuccess;
+}
+
+// the same for `count` sides described in device memory, in one launch; max_n = the largest n among those of at most SV_SORT_SMALL_MAX
+bool sv_sort_small_sides(hipStream_t s, const SvSortSide* sides_dev, int count, int max_n) {
+    if (count <= 0) return true;
+    int npow2 = 1;
+    while (npow2 < max_n) npow2 <<= 1;
+    const size_t lds = (size_t)npow2 * 8;
+    if (lds > 48 * 1024 && sv_allow_dynamic_lds((const void*)k_sort_small_sides, lds) != hipSuccess) return false;
+    hipLaunchKernelGGL(k_sort_small_sides, dim3(count), dim3(1024), lds, s, sides_dev);
     return hipGetLastError() == hipSuccess;
 }

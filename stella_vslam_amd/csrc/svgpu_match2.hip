@@ -5,6 +5,8 @@
 // Reprojection, grid lookup, pair gates, Hamming distances and the exact greedy replay all run on the device; the host only
 // stages the flat arrays and derives the handful of 3x3 quantities each method computes once per call.
 #include "svgpu_match_common.h"
+#include "bucket_batch_layout.h"
+#include "sv_sort.h"
 
 using namespace svm;
 
@@ -196,9 +198,215 @@ int bucket_match(svgpu_ctx* ctx, const char* who, const BucketSide& S1, const Bu
     return SVGPU_OK;
 }
 
+
+// K problems of the bucket matcher in one staged call (svgpu_bow_match_batch, svgpu_match_for_triangulation_batch): the same two passes
+// as bucket_match over the concatenation of all problems' rows.  A shared side is uploaded, ordered and (side 1) gathered once; every
+// kernel finds its problem's record in a table in device memory, and the replay runs one workgroup per problem.  Problem p's result
+// is what bucket_match returns for its two sides: its rows, buckets, lists, owner table and matches are its own.
+int bucket_match_batch(svgpu_ctx* ctx, const char* who, int K, const svgpu_match_view* side1, int shared1, const svgpu_match_view* side2, int shared2, int tri,
+                       const double* E12, const double* epipole, const int32_t* valid_epipole, const float* scale_factors, int num_levels,
+                       float residual_rad_thr, unsigned thr, float lowe_ratio, int check_orientation, int mode, int32_t* match_1to2, int32_t* num_matches) {
+    if (!ctx || K < 0) return sv_set_error(ctx, SVGPU_ERR_INVALID, who);
+    if (K == 0) return SVGPU_OK;
+    if (!side1 || !side2 || !num_matches || (shared1 && shared2 && K > 1)
+        || (tri && (!E12 || !epipole || !valid_epipole || !scale_factors || num_levels < 1 || num_levels > 16)))
+        return sv_set_error(ctx, SVGPU_ERR_INVALID, who);
+    BucketBatchShape S;
+    S.num_problems = K, S.shared1 = shared1 != 0, S.shared2 = shared2 != 0;
+    const size_t U1 = shared1 ? 1 : (size_t)K, U2 = shared2 ? 1 : (size_t)K;
+    size_t N1 = 0, N2 = 0, R = 0, pairs = 0;
+    for (size_t u = 0; u < U1; ++u) {
+        const svgpu_match_view& v = side1[u];
+        if (v.n < 0 || v.occupied || (v.n > 0 && (!v.desc || (check_orientation && !v.angle) || (tri && (!v.bearings || !v.octave)))))
+            return sv_set_error(ctx, SVGPU_ERR_INVALID, who);
+        if (tri)
+            for (int i = 0; i < v.n; ++i)
+                if (v.octave[i] < 0 || v.octave[i] >= num_levels) return sv_set_error(ctx, SVGPU_ERR_INVALID, who);
+        S.side1.push_back(BucketSide{v.desc, v.angle, v.valid, v.node, tri ? v.octave : nullptr, tri ? v.bearings : nullptr, tri ? v.xright : nullptr, v.n});
+        N1 += (size_t)v.n;
+    }
+    for (size_t u = 0; u < U2; ++u) {
+        const svgpu_match_view& v = side2[u];
+        if (v.n < 0 || v.n >= (1 << 22) || (tri && v.occupied) || (v.n > 0 && (!v.desc || (check_orientation && !v.angle) || (tri && !v.bearings))))
+            return sv_set_error(ctx, SVGPU_ERR_INVALID, who);
+        S.side2.push_back(BucketSide{v.desc, v.angle, v.valid, v.node, nullptr, tri ? v.bearings : nullptr, tri ? v.xright : nullptr, v.n});
+        S.occupied2.push_back(v.occupied);
+        N2 += (size_t)v.n;
+    }
+    bool work = false;
+    for (int p = 0; p < K; ++p) {
+        const BucketSide &a = S.s1(p), &b = S.s2(p);
+        if ((a.node == nullptr) != (b.node == nullptr)) return sv_set_error(ctx, SVGPU_ERR_INVALID, who);
+        R += (size_t)a.n;
+        pairs += (size_t)a.n * (size_t)b.n;  // (no list can hold more than its bucket: the lists' total stays below this)
+        work = work || (a.n > 0 && b.n > 0);
+    }
+    const size_t lim = (size_t)INT32_MAX;
+    if (R + (size_t)K > lim || N1 * 8 > lim || N2 * 8 > lim || pairs > lim || (R > 0 && !match_1to2))
+        return sv_set_error(ctx, SVGPU_ERR_INVALID, who);
+    for (int p = 0; p < K; ++p) num_matches[p] = 0;
+    for (size_t i = 0; i < R; ++i) match_1to2[i] = -1;
+    if (!work) return SVGPU_OK;
+
+    // the form of every problem's replay (sv_cand_replay_form decides), and the dynamic LDS of the one launch
+    std::vector<int> form((size_t)K);
+    S.global_form.assign((size_t)K, 0);
+    size_t lds_bytes = 0;
+    int max_small = 0;
+    for (int p = 0; p < K; ++p) {
+        const int n1 = S.s1(p).n, n2 = S.s2(p).n;
+        form[p] = sv_cand_replay_form(n1, n2, false, mode);
+        if (form[p] < 0) S.global_form[p] = 1;
+        else lds_bytes = std::max(lds_bytes, sv_cand_lds_bytes(n1, n2, form[p]));
+    }
+    for (const std::vector<BucketSide>* L : {&S.side1, &S.side2})
+        for (const BucketSide& b : *L) {
+            S.sortb = std::max(S.sortb, sv_bucket_sort_bytes(b.n));
+            if (b.n <= SV_SORT_SMALL_MAX) max_small = std::max(max_small, b.n);
+        }
+    S.scan_ints = sv_scan_scratch_ints(R);
+    S.side_rec = sizeof(SvSortSide), S.gather_rec = sizeof(BucketBatchSide), S.bucket_rec = sizeof(BucketProblem), S.cand_rec = sizeof(CandProblem);
+    S.replay_rec = sizeof(CandBatchReplay);
+
+    BucketBatchPieces Y;
+    std::vector<SvSortSide> sort_tab(U1 + U2);
+    std::vector<BucketBatchSide> gather_tab(U1);
+    std::vector<BucketProblem> bucket_tab((size_t)K);
+    std::vector<CandProblem> cand_tab((size_t)K);
+    std::vector<CandBatchReplay> replay_tab((size_t)K);
+    std::vector<int32_t> row_base((size_t)K + 1), side1_base(U1 + 1);
+    bool lists = false;
+    int32_t total = 0;
+    auto layout = [&](UploadArena& A) {
+        bucket_batch_layout(A, S, lists, (size_t)total, Y);
+        for (size_t u = 0; u < U1; ++u) {
+            const BucketSidePlace& a = Y.at1[u];
+            sort_tab[u] = SvSortSide{a.node, S.side1[u].n, a.key, a.order};
+            gather_tab[u] = BucketBatchSide{(const uint32_t*)a.desc, a.order, a.desc_rows};
+            side1_base[u] = (int32_t)a.first;
+        }
+        side1_base[U1] = (int32_t)N1;
+        for (size_t u = 0; u < U2; ++u) sort_tab[U1 + u] = SvSortSide{Y.at2[u].node, S.side2[u].n, Y.at2[u].key, Y.at2[u].order};
+        for (int p = 0; p < K; ++p) {
+            const BucketSidePlace &a = Y.at1[shared1 ? 0 : p], &b = Y.at2[shared2 ? 0 : p];
+            const size_t r0 = Y.row_first[p];
+            row_base[p] = (int32_t)r0;
+            BucketProblem& B = bucket_tab[p];
+            B = BucketProblem{};
+            B.n1 = S.s1(p).n, B.n2 = S.s2(p).n, B.check_orientation = check_orientation, B.tri = tri, B.thr = thr;
+            B.desc1 = (const uint32_t*)a.desc, B.desc2 = (const uint32_t*)b.desc;
+            B.angle1 = a.angle, B.angle2 = b.angle, B.valid1 = a.valid, B.valid2 = b.valid;
+            B.octave1 = a.octave, B.bearings1 = a.bearings, B.bearings2 = b.bearings, B.xright1 = a.xright, B.xright2 = b.xright;
+            if (tri) {
+                std::memcpy(B.E12, E12 + 9 * (size_t)p, sizeof B.E12);
+                std::memcpy(B.epipole, epipole + 3 * (size_t)p, sizeof B.epipole);
+                B.valid_epipole = valid_epipole[p];
+                for (int l = 0; l < num_levels; ++l) B.scale_factors[l] = scale_factors[l];
+                B.residual_rad_thr = residual_rad_thr;
+            }
+            B.key1 = a.key, B.q_idx = a.order, B.key2 = b.key, B.t_sorted = b.order;
+            // (the per-problem arrays: rows r0 .. of the concatenations; cand_off holds offsets into the ONE pair of lists, so a problem's
+            //  n1 + 1 entries end where the next problem's begin)
+            B.row_lo = Y.row_lo.p ? Y.row_lo.p + r0 : nullptr, B.row_hi = Y.row_hi.p ? Y.row_hi.p + r0 : nullptr;
+            B.q_valid = Y.q_valid.p ? Y.q_valid.p + r0 : nullptr, B.cand_off = Y.cand_off.p ? Y.cand_off.p + r0 : nullptr, B.cand_idx = Y.cand_idx;
+            CandProblem& P = cand_tab[p];
+            P = CandProblem{};
+            P.q_valid = B.q_valid, P.cand_off = B.cand_off, P.cand_idx = B.cand_idx;
+            P.qdesc = a.desc_rows, P.tdesc = B.desc2, P.nq = B.n1, P.nt = B.n2, P.occupied = b.occupied;
+            P.check_orientation = 0;  // gated in the scan
+            P.thr = thr, P.lowe_ratio = lowe_ratio, P.mode = mode;
+            P.dist = Y.dist, P.match_q = Y.match_rows.p ? Y.match_rows.p + r0 : nullptr, P.num = Y.num.p ? Y.num.p + p : nullptr;
+            replay_tab[p] = CandBatchReplay{form[p], form[p] < 0 && Y.owner.p ? Y.owner.p + Y.owner_first[p] : nullptr,
+                                            form[p] < 0 && Y.match_of_row.p ? Y.match_of_row.p + Y.mrow_first[p] : nullptr};
+        }
+        row_base[K] = (int32_t)R;
+    };
+    StagedCall C;
+    auto tables = [&]() {  // (after every layout: the records hold arena addresses)
+        C.up(Y.side_tab, (const char*)sort_tab.data(), Y.gather_tab, (const char*)gather_tab.data(), Y.bucket_tab, (const char*)bucket_tab.data());
+        C.up(Y.cand_tab, (const char*)cand_tab.data(), Y.replay_tab, (const char*)replay_tab.data());
+        C.up(Y.row_base, row_base.data(), Y.side1_base, side1_base.data());
+    };
+    auto count = [&]() -> int {  // uploads, orders, rows and the candidate count of all problems: pass 0, and again if the arena regrew for the lists
+        for (size_t u = 0; u < U1; ++u) {
+            const BucketSide& h = S.side1[u];
+            const BucketSidePlace& a = Y.at1[u];
+            const size_t n = (size_t)h.n;
+            C.up(a.desc, h.desc, n * 32), C.up(a.angle, h.angle, n), C.up(a.valid, h.valid, n), C.up(a.node, h.node, n);
+            C.up(a.octave, h.octave, n), C.up(a.bearings, h.bearings, n * 3), C.up(a.xright, h.xright, n);
+        }
+        for (size_t u = 0; u < U2; ++u) {
+            const BucketSide& h = S.side2[u];
+            const BucketSidePlace& b = Y.at2[u];
+            const size_t n = (size_t)h.n;
+            C.up(b.desc, h.desc, n * 32), C.up(b.angle, h.angle, n), C.up(b.valid, h.valid, n), C.up(b.node, h.node, n);
+            C.up(b.bearings, h.bearings, n * 3), C.up(b.xright, h.xright, n), C.up(b.occupied, S.occupied2[u], n);
+        }
+        tables();
+        int r = C.flush();
+        if (r) return r;
+        SvProfScope ps(ctx, C.s, "k_bucket_batch");
+        // every side of at most SV_SORT_SMALL_MAX keypoints in one launch, a workgroup each; longer ones one after another by the general sort
+        const bool small = sv_sort_small_sides(C.s, (const SvSortSide*)Y.side_tab.p, (int)(U1 + U2), max_small);
+        for (size_t u = 0; u < U1 + U2 && !r; ++u)
+            if (!small || sort_tab[u].n > SV_SORT_SMALL_MAX)
+                r = sv_bucket_sort(ctx, C.s, sort_tab[u].node, sort_tab[u].n, Y.sort_scratch, S.sortb, sort_tab[u].keys_out, sort_tab[u].idx_out);
+        if (r) return r;
+        sv_bucket_batch_rows_count(ctx, C.s, (const BucketProblem*)Y.bucket_tab.p, Y.row_base, K, (int)R, Y.cand_off, Y.scan_scratch);
+        return SVGPU_OK;
+    };
+    int rc = C.open(ctx, "bucket matcher batch: internal arena overflow", layout, false);
+    if (!rc) rc = count();
+    if (!rc) rc = C.read_now(&total, Y.cand_off.p + R);
+    if (rc || total == 0) return rc;
+    if (total < 0) return sv_set_error(ctx, SVGPU_ERR_INVALID, who);
+    bool survived = false;
+    lists = true;
+    if ((rc = C.reopen(layout, survived))) return rc;
+    if (!survived) {
+        if ((rc = count())) return rc;
+    }
+    else {
+        tables();  // the records now name the lists
+        if ((rc = C.flush())) return rc;
+    }
+    {
+        SvProfScope ps(ctx, C.s, "k_bucket_batch");
+        sv_bucket_batch_fill(C.s, (const BucketProblem*)Y.bucket_tab.p, Y.row_base, K, (int)R);
+        sv_bucket_batch_gather(C.s, (const BucketBatchSide*)Y.gather_tab.p, Y.side1_base, (int)U1, (int)N1);
+    }
+    sv_launch_cand_batch(ctx, C.s, (const CandProblem*)Y.cand_tab.p, (const CandBatchReplay*)Y.replay_tab.p, Y.row_base, K, (int)R, lds_bytes);
+    {  // (no memset of Y.match: a problem's rows are a permutation of its keypoints, the scatter writes all R entries)
+        SvProfScope ps(ctx, C.s, "k_bucket_batch");
+        sv_bucket_batch_scatter(C.s, (const BucketProblem*)Y.bucket_tab.p, Y.row_base, K, (int)R, Y.match_rows, Y.match);
+    }
+    C.down(match_1to2, Y.match);
+    C.down(num_matches, Y.num);
+    return C.finish();
+}
+
 }  // namespace
 
 extern "C" {
+
+int svgpu_bow_match_batch(svgpu_ctx* ctx, int num_problems, const svgpu_match_view* side1, int side1_shared, const svgpu_match_view* side2, int side2_shared,
+                          float lowe_ratio, int check_orientation, int32_t* match_1to2, int32_t* num_matches) {
+    const char* who = "svgpu_bow_match_batch: bad arguments";
+    if (num_problems > 0 && side1 && side2)  // node ids are required, as in svgpu_bow_match
+        for (int u = 0; u < (side1_shared ? 1 : num_problems); ++u)
+            if (!side1[u].node) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_bow_match_batch: node ids are required");
+    return bucket_match_batch(ctx, who, num_problems, side1, side1_shared, side2, side2_shared, 0, nullptr, nullptr, nullptr, nullptr, 0, 0.f, 50u, lowe_ratio,
+                              check_orientation, SVGPU_MATCH_RATIO, match_1to2, num_matches);
+}
+
+int svgpu_match_for_triangulation_batch(svgpu_ctx* ctx, int num_problems, const svgpu_match_view* side1, int side1_shared, const svgpu_match_view* side2,
+                                        int side2_shared, const double* E_12, const double* epipole_in_2, const int32_t* valid_epipole,
+                                        const float* scale_factors, int num_levels, float residual_rad_thr, float lowe_ratio, int check_orientation,
+                                        int32_t* matched_2_in_1, int32_t* num_matches) {
+    return bucket_match_batch(ctx, "svgpu_match_for_triangulation_batch: bad arguments", num_problems, side1, side1_shared, side2, side2_shared, 1, E_12,
+                              epipole_in_2, valid_epipole, scale_factors, num_levels, residual_rad_thr, 50u, lowe_ratio, check_orientation,
+                              SVGPU_MATCH_TRIANGULATION, matched_2_in_1, num_matches);
+}
 
 int svgpu_reproject_to_bearing(const svgpu_camera* cam, const double* rot_cw, const double* trans_cw, const double* pos_w, double* bearing, int* valid) {
     if (!cam || !rot_cw || !trans_cw || !pos_w || !bearing || !valid) return SVGPU_ERR_INVALID;

@@ -7,6 +7,7 @@
 #include <cstring>
 #include <map>
 #include <mutex>
+#include <stdexcept>
 #include <string>
 
 namespace stella_vslam {
@@ -425,6 +426,92 @@ unsigned tri_common(const kf_ptr& keyfrm_1, const kf_ptr& keyfrm_2, const Mat33_
     return (unsigned)num;
 }
 
+// one side of the batched bucket matchers: the flat arrays of a frame / keyframe and the view that points at them
+struct view_side {
+    kp_side kp;
+    std::vector<uint8_t> valid;
+    std::vector<int32_t> node;
+    svgpu_match_view view(bool tri) const {
+        svgpu_match_view v{};
+        v.desc = kp.desc.data(), v.angle = kp.angle.data(), v.valid = valid.empty() ? nullptr : valid.data();
+        v.node = node.empty() ? nullptr : node.data();
+        if (tri) v.octave = kp.octave.data(), v.bearings = kp.bearings.data(), v.xright = kp.xr();
+        v.n = kp.n;
+        return v;
+    }
+};
+// valid = "holds a live landmark" (bow_tree.cc:191-198, :286-294, :305-312)
+view_side bow_side(const data::frame_observation& obs, const data::bow_feature_vector& fv, const std::vector<lm_ptr>* lms) {
+    view_side s;
+    s.kp = flatten(obs);
+    s.node = node_ids(fv, s.kp.n);
+    if (s.kp.n == 0) s.node.assign(1, -1);  // (node ids are required: an empty side still names its array)
+    if (lms) {
+        s.valid.resize(s.kp.n);
+        for (int i = 0; i < s.kp.n; ++i) s.valid[i] = (lms->at(i) && !lms->at(i)->will_be_erased()) ? 1 : 0;
+    }
+    return s;
+}
+// valid = keypoint WITHOUT a landmark (robust.cc:47-50, 66-70)
+view_side tri_side(const kf_ptr& kf, bool with_nodes) {
+    view_side s;
+    s.kp = flatten(kf->frm_obs_, true);
+    const auto lms = kf->get_landmarks();
+    s.valid.resize(s.kp.n);
+    for (int i = 0; i < s.kp.n; ++i) s.valid[i] = lms.at(i) ? 0 : 1;
+    if (with_nodes) {
+        s.node = node_ids(kf->bow_feat_vec_, s.kp.n);
+        if (s.kp.n == 0) s.node.assign(1, -1);
+    }
+    return s;
+}
+
+std::vector<unsigned> tri_batch_common(const kf_ptr& keyfrm_1, const std::vector<kf_ptr>& keyfrms_2, const std::vector<Mat33_t>& E_12s,
+                                       std::vector<std::vector<std::pair<unsigned int, unsigned int>>>& matches_per_keyfrm_2, float residual_rad_thr,
+                                       float lowe_ratio, bool check_orientation, bool with_nodes) {
+    const size_t K = keyfrms_2.size();
+    matches_per_keyfrm_2.assign(K, {});
+    std::vector<unsigned> counts(K, 0);
+    if (K == 0) return counts;
+    if (E_12s.size() != K) throw std::invalid_argument("match_for_triangulation_batch: one E_12 per keyframe");
+    svgpu_ctx* ctx = hip::context();
+    double c1[3];
+    vec3(keyfrm_1->get_trans_wc(), c1);
+    std::vector<double> E(9 * K), epi(3 * K);
+    std::vector<int32_t> valid_epi(K);
+    const view_side s1 = tri_side(keyfrm_1, with_nodes);
+    std::vector<view_side> s2;
+    std::vector<svgpu_match_view> v2;
+    s2.reserve(K);
+    for (size_t k = 0; k < K; ++k) {  // epipole of keyframe 1 in keyframe k (robust.cc:22-27)
+        const svgpu_camera cam2 = hip::to_svgpu_camera(keyfrms_2[k]->camera_);
+        double R2[9], t2[3];
+        rot_rowmajor(keyfrms_2[k]->get_rot_cw(), R2);
+        vec3(keyfrms_2[k]->get_trans_cw(), t2);
+        int ve = 0;
+        hip::check(svgpu_reproject_to_bearing(&cam2, R2, t2, c1, &epi[3 * k], &ve), "svgpu_reproject_to_bearing");
+        valid_epi[k] = ve;
+        rot_rowmajor(E_12s[k], &E[9 * k]);
+        s2.push_back(tri_side(keyfrms_2[k], with_nodes));
+    }
+    for (const auto& s : s2) v2.push_back(s.view(true));
+    const svgpu_match_view v1 = s1.view(true);
+    const auto& sf = keyfrm_1->orb_params_->scale_factors_;
+    std::vector<int32_t> m((size_t)s1.kp.n * K + 1, -1), num(K, 0);
+    hip::check(svgpu_match_for_triangulation_batch(ctx, (int)K, &v1, 1, v2.data(), K == 1 ? 1 : 0, E.data(), epi.data(), valid_epi.data(), sf.data(),
+                                                   (int)sf.size(), residual_rad_thr, lowe_ratio, check_orientation ? 1 : 0, m.data(), num.data()),
+               "svgpu_match_for_triangulation_batch");
+    for (size_t k = 0; k < K; ++k) {
+        auto& pairs = matches_per_keyfrm_2[k];
+        pairs.reserve(num[k]);
+        const int32_t* mk = m.data() + (size_t)s1.kp.n * k;
+        for (int i = 0; i < s1.kp.n; ++i)
+            if (0 <= mk[i]) pairs.emplace_back(std::make_pair((unsigned)i, (unsigned)mk[i]));
+        counts[k] = (unsigned)num[k];
+    }
+    return counts;
+}
+
 }  // namespace
 
 namespace match {
@@ -540,6 +627,79 @@ unsigned int bow_tree::match_keyframes(const kf_ptr& keyfrm_1, const kf_ptr& key
     for (int i = 0; i < s1.n; ++i)
         if (0 <= m[i]) matched_lms_in_keyfrm_1.at(i) = lms_2.at(m[i]);  // :343
     return (unsigned)num;
+}
+
+std::vector<unsigned int> robust::match_for_triangulation_batch(const kf_ptr& keyfrm_1, const std::vector<kf_ptr>& keyfrms_2, const std::vector<Mat33_t>& E_12s,
+                                                                std::vector<std::vector<std::pair<unsigned int, unsigned int>>>& matches_per_keyfrm_2,
+                                                                const float residual_rad_thr) const {
+    return tri_batch_common(keyfrm_1, keyfrms_2, E_12s, matches_per_keyfrm_2, residual_rad_thr, lowe_ratio_, check_orientation_, false);
+}
+std::vector<unsigned int> bow_tree::match_for_triangulation_batch(const kf_ptr& keyfrm_1, const std::vector<kf_ptr>& keyfrms_2, const std::vector<Mat33_t>& E_12s,
+                                                                  std::vector<std::vector<std::pair<unsigned int, unsigned int>>>& matches_per_keyfrm_2,
+                                                                  const float residual_rad_thr) const {
+    return tri_batch_common(keyfrm_1, keyfrms_2, E_12s, matches_per_keyfrm_2, residual_rad_thr, lowe_ratio_, check_orientation_, true);
+}
+
+std::vector<unsigned int> bow_tree::match_frame_and_keyframe_batch(const std::vector<kf_ptr>& keyfrms, data::frame& frm,
+                                                                   std::vector<std::vector<lm_ptr>>& matched_lms_in_frm_per_keyfrm) const {
+    const size_t K = keyfrms.size();
+    const view_side s2 = bow_side(frm.frm_obs_, frm.bow_feat_vec_, nullptr);  // the frame: every keypoint is a candidate
+    matched_lms_in_frm_per_keyfrm.assign(K, std::vector<lm_ptr>(s2.kp.n, nullptr));
+    std::vector<unsigned int> counts(K, 0);
+    if (K == 0) return counts;
+    std::vector<std::vector<lm_ptr>> lms(K);
+    std::vector<view_side> s1;
+    std::vector<svgpu_match_view> v1;
+    s1.reserve(K);
+    size_t rows = 0;
+    for (size_t k = 0; k < K; ++k) {
+        lms[k] = keyfrms[k]->get_landmarks();
+        s1.push_back(bow_side(keyfrms[k]->frm_obs_, keyfrms[k]->bow_feat_vec_, &lms[k]));
+        rows += (size_t)s1.back().kp.n;
+    }
+    for (const auto& s : s1) v1.push_back(s.view(false));
+    const svgpu_match_view v2 = s2.view(false);
+    std::vector<int32_t> m(rows + 1, -1), num(K, 0);
+    check(svgpu_bow_match_batch(context(), (int)K, v1.data(), K == 1 ? 1 : 0, &v2, 1, lowe_ratio_, check_orientation_ ? 1 : 0, m.data(), num.data()),
+          "svgpu_bow_match_batch");
+    const int32_t* mk = m.data();
+    for (size_t k = 0; k < K; ++k) {
+        for (int i = 0; i < s1[k].kp.n; ++i)
+            if (0 <= mk[i]) matched_lms_in_frm_per_keyfrm[k].at(mk[i]) = lms[k].at(i);  // bow_tree.cc:235
+        mk += s1[k].kp.n;
+        counts[k] = (unsigned)num[k];
+    }
+    return counts;
+}
+
+std::vector<unsigned int> bow_tree::match_keyframes_batch(const kf_ptr& keyfrm_1, const std::vector<kf_ptr>& keyfrms_2,
+                                                          std::vector<std::vector<lm_ptr>>& matched_lms_per_keyfrm_2) const {
+    const size_t K = keyfrms_2.size();
+    const auto lms_1 = keyfrm_1->get_landmarks();
+    matched_lms_per_keyfrm_2.assign(K, std::vector<lm_ptr>(lms_1.size(), nullptr));
+    std::vector<unsigned int> counts(K, 0);
+    if (K == 0) return counts;
+    const view_side s1 = bow_side(keyfrm_1->frm_obs_, keyfrm_1->bow_feat_vec_, &lms_1);
+    std::vector<std::vector<lm_ptr>> lms_2(K);
+    std::vector<view_side> s2;
+    std::vector<svgpu_match_view> v2;
+    s2.reserve(K);
+    for (size_t k = 0; k < K; ++k) {
+        lms_2[k] = keyfrms_2[k]->get_landmarks();
+        s2.push_back(bow_side(keyfrms_2[k]->frm_obs_, keyfrms_2[k]->bow_feat_vec_, &lms_2[k]));
+    }
+    for (const auto& s : s2) v2.push_back(s.view(false));
+    const svgpu_match_view v1 = s1.view(false);
+    std::vector<int32_t> m((size_t)s1.kp.n * K + 1, -1), num(K, 0);
+    check(svgpu_bow_match_batch(context(), (int)K, &v1, 1, v2.data(), K == 1 ? 1 : 0, lowe_ratio_, check_orientation_ ? 1 : 0, m.data(), num.data()),
+          "svgpu_bow_match_batch");
+    for (size_t k = 0; k < K; ++k) {
+        const int32_t* mk = m.data() + (size_t)s1.kp.n * k;
+        for (int i = 0; i < s1.kp.n; ++i)
+            if (0 <= mk[i]) matched_lms_per_keyfrm_2[k].at(i) = lms_2[k].at(mk[i]);  // bow_tree.cc:343
+        counts[k] = (unsigned)num[k];
+    }
+    return counts;
 }
 
 // -------------------------------------------------------------------------------------------------------------------- projection

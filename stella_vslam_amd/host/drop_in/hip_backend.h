@@ -108,6 +108,12 @@ public:
                                          const float residual_rad_thr) const;
     unsigned int brute_force_match(const data::frame_observation& frm_obs, const std::shared_ptr<data::keyframe>& keyfrm,
                                    std::vector<std::pair<int, int>>& matches) const;
+    //! match_for_triangulation(keyfrm_1, keyfrms_2[k], E_12s[k], ...) for every k in ONE device call (svgpu_match_for_triangulation_batch:
+    //! the loop of mapping_module.cc:332-335); matches_per_keyfrm_2[k] and the returned counts are what the per-call method gives
+    std::vector<unsigned int> match_for_triangulation_batch(const std::shared_ptr<data::keyframe>& keyfrm_1,
+                                                            const std::vector<std::shared_ptr<data::keyframe>>& keyfrms_2, const std::vector<Mat33_t>& E_12s,
+                                                            std::vector<std::vector<std::pair<unsigned int, unsigned int>>>& matches_per_keyfrm_2,
+                                                            const float residual_rad_thr) const;
 };
 
 class bow_tree final : public base {  // match/bow_tree.h:18-44
@@ -120,6 +126,19 @@ public:
                                           std::vector<std::shared_ptr<data::landmark>>& matched_lms_in_frm) const;
     unsigned int match_keyframes(const std::shared_ptr<data::keyframe>& keyfrm_1, const std::shared_ptr<data::keyframe>& keyfrm_2,
                                  std::vector<std::shared_ptr<data::landmark>>& matched_lms_in_keyfrm_1) const;
+    // The same three for all partners in ONE device call (svgpu_bow_match_batch / svgpu_match_for_triangulation_batch): entry k of the
+    // outputs and of the returned counts is exactly what the per-call method fills for partner k.
+    //! match_frame_and_keyframe(keyfrms[k], frm, ...) for every k: the candidates (and neighbours) of module/relocalizer.cc:134-188
+    std::vector<unsigned int> match_frame_and_keyframe_batch(const std::vector<std::shared_ptr<data::keyframe>>& keyfrms, data::frame& frm,
+                                                             std::vector<std::vector<std::shared_ptr<data::landmark>>>& matched_lms_in_frm_per_keyfrm) const;
+    //! match_keyframes(keyfrm_1, keyfrms_2[k], ...) for every k: the candidates of module/loop_detector.cc:377
+    std::vector<unsigned int> match_keyframes_batch(const std::shared_ptr<data::keyframe>& keyfrm_1,
+                                                    const std::vector<std::shared_ptr<data::keyframe>>& keyfrms_2,
+                                                    std::vector<std::vector<std::shared_ptr<data::landmark>>>& matched_lms_per_keyfrm_2) const;
+    std::vector<unsigned int> match_for_triangulation_batch(const std::shared_ptr<data::keyframe>& keyfrm_1,
+                                                            const std::vector<std::shared_ptr<data::keyframe>>& keyfrms_2, const std::vector<Mat33_t>& E_12s,
+                                                            std::vector<std::vector<std::pair<unsigned int, unsigned int>>>& matches_per_keyfrm_2,
+                                                            const float residual_rad_thr) const;
 };
 
 class projection final : public base {  // match/projection.h:20-64

@@ -375,3 +375,69 @@ class bow_tree(base):
 
     def match_for_triangulation(self, **kw):
         return match_for_triangulation(self.ctx, self.lowe_ratio_, self.check_orientation_, **kw)
+
+    def match_batch(self, side1, side2):
+        """match / match_frame_and_keyframe / match_keyframes for all partners in ONE device call (svgpu_bow_match_batch).  `side1` and
+        `side2` are lists of dicts with the keyword names of match(): desc, angle, valid, node (+ occupied on side 2); ONE dict instead
+        of a list means that side is shared by every problem.  Returns (list of per-problem match arrays, counts)."""
+        return _match_batch(self.ctx, "svgpu_bow_match_batch", side1, side2, [], [self.lowe_ratio_, int(self.check_orientation_)])
+
+    def match_for_triangulation_batch(self, **kw):
+        return match_for_triangulation_batch(self.ctx, self.lowe_ratio_, self.check_orientation_, **kw)
+
+
+class svgpu_match_view(C.Structure):
+    """include/svgpu.h svgpu_match_view."""
+    _fields_ = [("desc", C.c_void_p), ("angle", C.c_void_p), ("valid", C.c_void_p), ("node", C.c_void_p), ("octave", C.c_void_p),
+                ("bearings", C.c_void_p), ("xright", C.c_void_p), ("occupied", C.c_void_p), ("n", C.c_int)]
+
+
+def _match_view(side, keep):
+    """One side as a dict: desc, angle, valid (or has_lm: inverted here, as svgpu_match_for_triangulation does), node, octave, bearings,
+    xright, occupied -- all but desc optional."""
+    valid = side.get("valid")
+    if valid is None and side.get("has_lm") is not None:
+        valid = (np.asarray(side["has_lm"]) == 0).astype(np.uint8)
+    a = [np.ascontiguousarray(side["desc"], np.uint8).reshape(-1, 32), _c(side.get("angle"), np.float32), _c(valid, np.uint8),
+         _c(side.get("node"), np.int32), _c(side.get("octave"), np.int32), _f64(side.get("bearings")), _c(side.get("xright"), np.float32),
+         _c(side.get("occupied"), np.uint8)]
+    keep.append(a)
+    v = svgpu_match_view()
+    v.desc, v.angle, v.valid, v.node, v.octave, v.bearings, v.xright, v.occupied = (None if x is None else x.ctypes.data for x in a)
+    v.n = len(a[0])
+    return v
+
+
+def _match_batch(ctx, fn_name, side1, side2, mid, tail):
+    shared1, shared2 = isinstance(side1, dict), isinstance(side2, dict)
+    l1, l2 = ([side1] if shared1 else list(side1)), ([side2] if shared2 else list(side2))
+    k = max(len(l1), len(l2)) if (shared1 or shared2) else len(l1)
+    if not shared1 and not shared2 and len(l1) != len(l2):
+        raise ValueError("side1 and side2 must name the same number of problems")
+    keep = []
+    v1 = (svgpu_match_view * max(len(l1), 1))(*[_match_view(s, keep) for s in l1])
+    v2 = (svgpu_match_view * max(len(l2), 1))(*[_match_view(s, keep) for s in l2])
+    n1 = [v1[0 if shared1 else p].n for p in range(k)]
+    out, num = np.full(max(sum(n1), 1), -1, np.int32), np.zeros(max(k, 1), np.int32)
+    ctx.check(getattr(lib(), fn_name)(ctx.handle, k, v1, int(shared1), v2, int(shared2), *mid, *tail, _p(out), _p(num)), fn_name)
+    off = np.concatenate([[0], np.cumsum(n1)]).astype(np.int64)
+    return [out[off[p]:off[p + 1]].copy() for p in range(k)], num[:k].copy()
+
+
+def match_for_triangulation_batch(ctx, lowe_ratio, check_orientation, side1, side2, E_12, epipole_in_2, valid_epipole, scale_factors, residual_rad_thr):
+    """match_for_triangulation for all neighbours in ONE device call (svgpu_match_for_triangulation_batch).  Sides as in bow_tree.match_batch
+    with desc, angle, octave (side 1), bearings, has_lm, xright, node; E_12 (K x 3 x 3), epipole_in_2 (K x 3), valid_epipole (K) per problem."""
+    sf = _c(scale_factors, np.float32)
+    E, ep, ve = _f64(E_12), _f64(epipole_in_2), _c(np.asarray(valid_epipole).astype(np.int32), np.int32)
+    return _match_batch(ctx, "svgpu_match_for_triangulation_batch", side1, side2, [_p(E), _p(ep), _p(ve), _p(sf), len(sf), residual_rad_thr],
+                        [lowe_ratio, int(check_orientation)])
+
+
+def triangulation_matches_to_batch(matched_2_in_1_per_neighbour):
+    """The (match_off, idx1, idx2) triangulate_two_views_batch takes, from the per-neighbour matched_2_in_1 arrays of
+    match_for_triangulation_batch: the matched pairs of neighbour k, in side-1 index order, are entries match_off[k] .. match_off[k + 1]."""
+    idx1 = [np.flatnonzero(np.asarray(m) >= 0).astype(np.int32) for m in matched_2_in_1_per_neighbour]
+    idx2 = [np.asarray(m, np.int32)[i] for m, i in zip(matched_2_in_1_per_neighbour, idx1)]
+    off = np.concatenate([[0], np.cumsum([len(i) for i in idx1])]).astype(np.int32)
+    cat = lambda xs: np.concatenate(xs).astype(np.int32) if xs else np.zeros(0, np.int32)  # noqa: E731
+    return off, cat(idx1), cat(idx2)
