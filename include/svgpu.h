@@ -1162,6 +1162,54 @@ int svgpu_pose_optimize_batch(svgpu_ctx* ctx, int num_problems, const int32_t* o
                               int num_trials_robust, int num_trials, int num_each_iter, int reset_stop_flag_each_round,
                               double* pose_out, uint8_t* outlier_flags, int32_t* num_valid, int32_t* lm_iterations);
 
+/* module::relocalizer::refine_pose (module/relocalizer.cc:236-297) for ALL candidates that survived optimize_pose, in one call: per
+ * candidate a chain of num_stages x (projection match of the candidate keyframe's landmarks into the frame from the current pose ->
+ * count test -> pose optimisation over every keypoint that holds a landmark); the pose, the new matches and the landmark bookkeeping
+ * move from step to step on the device.  The frame (keypoints, descriptors, grid) is uploaded and binned once and shared.
+ *   frame (shared)       cam, tdesc / t_xy / t_octave / t_angle / nt / grid as svgpu_match_frame_and_keyframe_projection; t_xright
+ *                        nullable (null = monocular camera: every edge monocular, Huber delta sqrt(5.99146); else the edge of keypoint t
+ *                        is stereo where t_xright[t] >= 0 and the delta is sqrt(7.81473), pose_optimizer_g2o.cc:86-109);
+ *                        inv_level_sigma_sq by octave; intrinsics and the trial counts as svgpu_pose_optimize_batch
+ *   per candidate p      active[p] (nullable = all); pose_cw[p] 12 doubles (the pose after relocalizer::optimize_pose);
+ *                        n_already_found[p] = already_found_landmarks.size(); frame_has_lm (K x nt bytes) and frame_lm_pos_w
+ *                        (K x nt x 3) = the frame's landmarks after optimize_pose's outlier rejection; the keyframe's landmark entries
+ *                        kf_off[p] .. kf_off[p + 1] of pos_w / valid / min_valid_dist / max_valid_dist / lm_desc / angle_kf with the
+ *                        meaning of the single call (valid = 0: null, will_be_erased or in already_found_landmarks; null = all valid)
+ *   stages               num_stages in 1..4, margin[s] and hamm_dist_thr[s] per stage (the relocaliser: {10, 3}, {100, 64}),
+ *                        min_num_valid_obs (50)
+ * Per candidate, with count = n_already_found, occupied = frame_has_lm, pose = pose_cw[p], for every stage s:
+ *   1. the single call's projection match of the still-valid entries from `pose` against the keypoints that are not occupied ->
+ *      num_found[p][s]; a matched entry is invalid for later stages, its keypoint becomes occupied and takes the entry's pos_w;
+ *   2. count + num_found[p][s] < min_num_valid_obs: status 1 + s, the candidate stops;
+ *   3. svgpu_pose_optimize over every keypoint that holds a landmark, in keypoint-index order -> pose, num_valid[p][s] = count
+ *      (outliers are NOT removed between stages);
+ *   after the last stage: count < min_num_valid_obs: status 1 + num_stages.
+ * Outputs: status (0 accepted, -1 inactive on input), pose_out (the pose of the last optimisation that ran; the input bit for bit if none
+ * ran), match_kf / match_stage per keyframe entry (frame keypoint and the stage that matched it, or -1), outlier (K x nt: the flags of
+ * the last optimisation that ran; 0 where the keypoint holds no landmark), num_found / num_valid (K x num_stages, 0 for a stage that was
+ * not reached), lm_iterations (K, of the last optimisation that ran; nullable).  Every output equals, bit for bit, the same chain made of
+ * svgpu_match_frame_and_keyframe_projection and svgpu_pose_optimize calls for that candidate alone.
+ * `stats` (nullable) receives what the call issued; none of the three depends on num_candidates.  One synchronisation per stage (the
+ * stage's candidate-list total) and one at the end; a call whose lists outgrow their capacity starts again with longer ones.
+ * SVGPU_ERR_INVALID before anything is launched or written: a null required pointer, kf_off[0] != 0 or non-monotone offsets, an octave
+ * outside [0, num_levels), num_stages outside 1..4, num_levels outside 1..16, nt >= 1 << 22, totals beyond int32.  num_candidates == 0
+ * succeeds whatever else is passed.  Host in/out, synchronous. */
+typedef struct svgpu_call_stats {
+    int32_t launches;          /* kernel launches */
+    int32_t copies;            /* runtime copies and memsets */
+    int32_t synchronisations;  /* stream synchronisations */
+} svgpu_call_stats;
+int svgpu_reloc_refine_batch(svgpu_ctx* ctx, const svgpu_camera* cam, const uint8_t* tdesc, const float* t_xy, const int32_t* t_octave,
+                             const float* t_angle, const float* t_xright, int nt, int grid_cols, int grid_rows, int num_levels,
+                             const float* scale_factors, const float* inv_level_sigma_sq, float log_scale_factor, const double* intrinsics,
+                             int num_trials_robust, int num_trials, int num_each_iter, int reset_stop_flag_each_round, int check_orientation,
+                             int num_candidates, const uint8_t* active, const double* pose_cw, const int32_t* n_already_found,
+                             const uint8_t* frame_has_lm, const double* frame_lm_pos_w, const int32_t* kf_off, const double* pos_w,
+                             const uint8_t* valid, const float* min_valid_dist, const float* max_valid_dist, const uint8_t* lm_desc,
+                             const float* angle_kf, int num_stages, const float* margin, const int32_t* hamm_dist_thr, int min_num_valid_obs,
+                             int32_t* status, double* pose_out, int32_t* match_kf, int32_t* match_stage, uint8_t* outlier, int32_t* num_found,
+                             int32_t* num_valid, int32_t* lm_iterations, svgpu_call_stats* stats);
+
 /* Global BA core (optimize/global_bundle_adjuster.cc:26-192, 279-412): the same graph over ALL keyframes (spanning root
  * fixed), ONE Levenberg-Marquardt run of problem->num_first_iter iterations with the terminate rule, optional Huber
  * (obs_huber_delta), no outlier gate (num_second_iter is ignored).  The caller applies the reference's post-conditions
