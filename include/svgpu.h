@@ -1102,6 +1102,26 @@ int svgpu_selftest_segmented_solve_rank(int nP, int NB, const int* blk_ab, const
  * permutation.  Either half is skipped when its output pointer is NULL.  Host in / out, synchronous. */
 int svgpu_selftest_scan_sort(svgpu_ctx* ctx, int n, const int32_t* values, int32_t* scan_out, const uint32_t* keys, int bits, int32_t* sorted_idx);
 
+/* Device self-test of the sort paths the entry above does not reach (csrc/sv_sort.hip, sv_bucket_sort of csrc/bucket_kernels.hip; NOT a
+ * product entry point).  Host in / out, synchronous; arguments a path does not name are ignored.  info: 4 ints.
+ *   SVGPU_SORT_PATH_RADIX_COUNT  sv_sort_pairs with the element count read ON THE DEVICE: keys[n] / idx[n] are the pairs (the 64-bit value
+ *                        of pair i is idx[i] with its complement in the high word), the launches are sized for n, `count` (0 .. n) is
+ *                        uploaded, the data starts in buffer set `start` (0 | 1).  keys_out / idx_out [count] = the sorted prefix, taken
+ *                        from the set the function returned; info[0] = that set, info[1] = 1 when every value came back whole.
+ *   SVGPU_SORT_PATH_SMALL        sv_sort_small on keys[n], idx[n] (any indices, 0 <= n <= 16384): keys_out / idx_out [n], info[0] = its bool.
+ *   SVGPU_SORT_PATH_SIDES        sv_sort_small_sides, ONE launch over n sides: sides[2 u] = keypoints of side u, sides[2 u + 1] != 0 when it
+ *                        has node ids; node = all sides' node ids one after another (a side without ids still occupies its stretch),
+ *                        keys_out / idx_out likewise.  Both outputs are filled with the byte 0xA5 before the launch: a side the
+ *                        launch skips keeps 0xA5A5A5A5.  info[0] = its bool, info[1] = the max_n passed (largest side <= 16384).
+ *   SVGPU_SORT_PATH_BUCKET       sv_bucket_sort on node[n] (or node == NULL: identity), scratch from sv_bucket_sort_bytes(n):
+ *                        keys_out / idx_out [n]; info[0] = 1 when n is beyond the one-workgroup sort (the radix fallback ran). */
+#define SVGPU_SORT_PATH_RADIX_COUNT 0
+#define SVGPU_SORT_PATH_SMALL 1
+#define SVGPU_SORT_PATH_SIDES 2
+#define SVGPU_SORT_PATH_BUCKET 3
+int svgpu_selftest_sort_paths(svgpu_ctx* ctx, int path, int n, int count, int start, int bits, const uint32_t* keys, const int32_t* idx,
+                              const int32_t* node, const int32_t* sides, uint32_t* keys_out, int32_t* idx_out, int32_t* info);
+
 /* Which form the replay of the candidate matcher takes for nq queries and nt targets (csrc/match_kernels.hip; NOT a product entry point:
  * the launch code calls the same function, tests assert with it that a problem reaches the form it was built for).  Host only, needs
  * no context and no device.  with_cnt != 0: the lists carry explicit counts (the tracked-frame chain).

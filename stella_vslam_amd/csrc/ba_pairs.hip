@@ -11,6 +11,7 @@
 #include <algorithm>
 #include "svgpu_internal.h"
 #include "ba_kernels.h"
+#include "match_kernels.h"  // sv_bucket_sort (svgpu_selftest_sort_paths)
 #include "sv_sort.h"
 
 namespace {
@@ -557,4 +558,145 @@ extern "C" int svgpu_selftest_scan_sort(svgpu_ctx* ctx, int n, const int32_t* va
     SV_HIP(ctx, hipGetLastError());
     SV_HIP(ctx, hipStreamSynchronize(s));
     return SVGPU_OK;
+}
+
+// ---- svgpu_selftest_sort_paths (include/svgpu.h): the device-count radix sort, the one-workgroup sorts and the bucket order on caller data
+namespace {
+__global__ void k_selftest_widen(const int* __restrict__ idx, int n, unsigned long long* __restrict__ out) {  // value = index | ~index << 32
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = (unsigned long long)(unsigned)idx[i] | ((unsigned long long)~(unsigned)idx[i] << 32);
+}
+}  // namespace
+extern "C" int svgpu_selftest_sort_paths(svgpu_ctx* ctx, int path, int n, int count, int start, int bits, const uint32_t* keys, const int32_t* idx,
+                                         const int32_t* node, const int32_t* sides, uint32_t* keys_out, int32_t* idx_out, int32_t* info) {
+    const char* const bad = "svgpu_selftest_sort_paths: bad arguments";
+    if (!ctx || !info || n < 0) return sv_set_error(ctx, SVGPU_ERR_INVALID, bad);
+    info[0] = info[1] = info[2] = info[3] = 0;
+    hipStream_t s = ctx->stream;
+    const size_t N = (size_t)n;
+    if (path == SVGPU_SORT_PATH_RADIX_COUNT) {
+        if (n < 1 || count < 0 || count > n || (start != 0 && start != 1) || bits < 1 || bits > 32 || !keys || !idx || (count > 0 && (!keys_out || !idx_out)))
+            return sv_set_error(ctx, SVGPU_ERR_INVALID, bad);
+        SortScratch S;
+        int *d_idx, *d_count;
+        int rc = sv_scratch_layout(ctx, "svgpu_selftest_sort_paths: internal arena overflow", [&](Arena& A) {
+            lay_sort(A, N, S);
+            d_idx = A.take<int>(N);
+            d_count = A.take<int>(1);
+        });
+        if (rc) return rc;
+        SV_HIP(ctx, hipMemcpyAsync(S.keys[start], keys, N * 4, hipMemcpyHostToDevice, s));
+        SV_HIP(ctx, hipMemcpyAsync(d_idx, idx, N * 4, hipMemcpyHostToDevice, s));
+        SV_HIP(ctx, hipMemcpyAsync(d_count, &count, 4, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_selftest_widen, dim3((n + 255) / 256), dim3(256), 0, s, d_idx, n, S.vals[start]);
+        const int r = sv_sort_pairs(s, S.keys, S.vals, start, n, bits, S.hist, d_count);
+        SV_HIP(ctx, hipGetLastError());
+        if (r != 0 && r != 1) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_selftest_sort_paths: sv_sort_pairs named no buffer set");
+        std::vector<unsigned long long> vals((size_t)count);
+        if (count > 0) {
+            SV_HIP(ctx, hipMemcpyAsync(keys_out, S.keys[r], (size_t)count * 4, hipMemcpyDeviceToHost, s));
+            SV_HIP(ctx, hipMemcpyAsync(vals.data(), S.vals[r], (size_t)count * 8, hipMemcpyDeviceToHost, s));
+        }
+        SV_HIP(ctx, hipStreamSynchronize(s));
+        info[0] = r, info[1] = 1;
+        for (int i = 0; i < count; ++i) {
+            idx_out[i] = (int32_t)(uint32_t)vals[i];
+            if ((uint32_t)(vals[i] >> 32) != ~(uint32_t)vals[i]) info[1] = 0;
+        }
+        return SVGPU_OK;
+    }
+    if (path == SVGPU_SORT_PATH_SMALL) {
+        if (n > SV_SORT_SMALL_MAX || (n > 0 && (!keys || !idx || !keys_out || !idx_out))) return sv_set_error(ctx, SVGPU_ERR_INVALID, bad);
+        unsigned *d_keys, *d_keys_out;
+        int *d_idx, *d_idx_out;
+        int rc = sv_scratch_layout(ctx, "svgpu_selftest_sort_paths: internal arena overflow", [&](Arena& A) {
+            d_keys = A.take<unsigned>(N + 1), d_keys_out = A.take<unsigned>(N + 1);
+            d_idx = A.take<int>(N + 1), d_idx_out = A.take<int>(N + 1);
+        });
+        if (rc) return rc;
+        if (n > 0) {
+            SV_HIP(ctx, hipMemcpyAsync(d_keys, keys, N * 4, hipMemcpyHostToDevice, s));
+            SV_HIP(ctx, hipMemcpyAsync(d_idx, idx, N * 4, hipMemcpyHostToDevice, s));
+            SV_HIP(ctx, hipMemsetAsync(d_keys_out, 0xA5, N * 4, s));
+            SV_HIP(ctx, hipMemsetAsync(d_idx_out, 0xA5, N * 4, s));
+        }
+        info[0] = sv_sort_small(s, d_keys, d_idx, n, d_keys_out, d_idx_out) ? 1 : 0;
+        if (n > 0) {
+            SV_HIP(ctx, hipMemcpyAsync(keys_out, d_keys_out, N * 4, hipMemcpyDeviceToHost, s));
+            SV_HIP(ctx, hipMemcpyAsync(idx_out, d_idx_out, N * 4, hipMemcpyDeviceToHost, s));
+        }
+        SV_HIP(ctx, hipStreamSynchronize(s));
+        return SVGPU_OK;
+    }
+    if (path == SVGPU_SORT_PATH_SIDES) {
+        if (n > 0 && !sides) return sv_set_error(ctx, SVGPU_ERR_INVALID, bad);
+        size_t total = 0;
+        int max_small = 0;
+        for (int u = 0; u < n; ++u) {
+            const int m = sides[2 * u];
+            if (m < 0 || m >= (1 << 22)) return sv_set_error(ctx, SVGPU_ERR_INVALID, bad);
+            total += (size_t)m;
+            if (m <= SV_SORT_SMALL_MAX) max_small = std::max(max_small, m);  // (as the batch of svgpu_match2.hip forms it)
+        }
+        if (total > 0 && (!node || !keys_out || !idx_out)) return sv_set_error(ctx, SVGPU_ERR_INVALID, bad);
+        int32_t* d_node;
+        unsigned* d_keys_out;
+        int* d_idx_out;
+        SvSortSide* d_tab;
+        int rc = sv_scratch_layout(ctx, "svgpu_selftest_sort_paths: internal arena overflow", [&](Arena& A) {
+            d_node = A.take<int32_t>(total + 1);
+            d_keys_out = A.take<unsigned>(total + 1), d_idx_out = A.take<int>(total + 1);
+            d_tab = A.take<SvSortSide>(N + 1);
+        });
+        if (rc) return rc;
+        std::vector<SvSortSide> tab(N);
+        size_t first = 0;
+        for (int u = 0; u < n; ++u) {
+            tab[u] = SvSortSide{sides[2 * u + 1] ? d_node + first : nullptr, sides[2 * u], d_keys_out + first, d_idx_out + first};
+            first += (size_t)sides[2 * u];
+        }
+        if (total > 0) {
+            SV_HIP(ctx, hipMemcpyAsync(d_node, node, total * 4, hipMemcpyHostToDevice, s));
+            SV_HIP(ctx, hipMemsetAsync(d_keys_out, 0xA5, total * 4, s));
+            SV_HIP(ctx, hipMemsetAsync(d_idx_out, 0xA5, total * 4, s));
+        }
+        if (n > 0) SV_HIP(ctx, hipMemcpyAsync(d_tab, tab.data(), N * sizeof(SvSortSide), hipMemcpyHostToDevice, s));
+        info[0] = sv_sort_small_sides(s, d_tab, n, max_small) ? 1 : 0;
+        info[1] = max_small;
+        if (total > 0) {
+            SV_HIP(ctx, hipMemcpyAsync(keys_out, d_keys_out, total * 4, hipMemcpyDeviceToHost, s));
+            SV_HIP(ctx, hipMemcpyAsync(idx_out, d_idx_out, total * 4, hipMemcpyDeviceToHost, s));
+        }
+        SV_HIP(ctx, hipStreamSynchronize(s));  // (also keeps `tab` alive until its copy has run)
+        return SVGPU_OK;
+    }
+    if (path == SVGPU_SORT_PATH_BUCKET) {
+        if (n >= (1 << 22) || (n > 0 && (!keys_out || !idx_out))) return sv_set_error(ctx, SVGPU_ERR_INVALID, bad);
+        const size_t sortb = sv_bucket_sort_bytes(n);
+        int32_t* d_node;
+        unsigned* d_keys_out;
+        int* d_idx_out;
+        char* d_scr;
+        int rc = sv_scratch_layout(ctx, "svgpu_selftest_sort_paths: internal arena overflow", [&](Arena& A) {
+            d_node = A.take<int32_t>(N + 1);
+            d_keys_out = A.take<unsigned>(N + 1), d_idx_out = A.take<int>(N + 1);
+            d_scr = A.take<char>(sortb);
+        });
+        if (rc) return rc;
+        if (n > 0) {
+            if (node) SV_HIP(ctx, hipMemcpyAsync(d_node, node, N * 4, hipMemcpyHostToDevice, s));
+            SV_HIP(ctx, hipMemsetAsync(d_keys_out, 0xA5, N * 4, s));
+            SV_HIP(ctx, hipMemsetAsync(d_idx_out, 0xA5, N * 4, s));
+        }
+        rc = sv_bucket_sort(ctx, s, node ? d_node : nullptr, n, d_scr, sortb, d_keys_out, d_idx_out);
+        if (rc) return rc;
+        if (n > 0) {
+            SV_HIP(ctx, hipMemcpyAsync(keys_out, d_keys_out, N * 4, hipMemcpyDeviceToHost, s));
+            SV_HIP(ctx, hipMemcpyAsync(idx_out, d_idx_out, N * 4, hipMemcpyDeviceToHost, s));
+        }
+        SV_HIP(ctx, hipStreamSynchronize(s));
+        info[0] = n > SV_SORT_SMALL_MAX ? 1 : 0;
+        return SVGPU_OK;
+    }
+    return sv_set_error(ctx, SVGPU_ERR_INVALID, bad);
 }

@@ -10,7 +10,7 @@ size_t sv_scan_scratch_ints(size_t n);
 void sv_scan_i32(hipStream_t s, int* data, int n, int* scratch);
 // stable least-significant-digit radix sort (6-bit digits) of n (u32 key, u64 value) pairs by the low `bits` key bits, ping-ponging between
 // the two buffer sets; `hist` = sv_sort_hist_ints(n) ints of scratch.  The data starts in set `start`; returns the set that holds the result
-// (start ^ (passes & 1)).
+// (start ^ (passes & 1)).  Key bits above `bits` travel with the key and order nothing: the last digit is cut where `bits` ends.
 int sv_sort_passes(int bits);
 size_t sv_sort_hist_ints(size_t n);
 // n_dev != null: the element count is read on the device (*n_dev <= n; n sizes the launches and the scratch)

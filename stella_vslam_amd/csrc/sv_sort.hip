@@ -23,9 +23,9 @@ __device__ __forceinline__ void scan_load_tile(const int* __restrict__ data, int
         for (int k = 0; k < SCAN_PER_THREAD; ++k) v[k] = i0 + k < n ? data[i0 + k] : 0;
     }
 }
-__global__ __launch_bounds__(1024) void k_scan_i32(int* __restrict__ data, const int* __restrict__ n_dev, int n_host) {
+__global__ __launch_bounds__(1024) void k_scan_i32(int* __restrict__ data, int n) {
     __shared__ int s_wave[2][17];  // [parity][exclusive prefix of the 16 wave totals | tile total]
-    const int n = n_dev ? *n_dev : n_host, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     constexpr int TILE = 1024 * SCAN_PER_THREAD;
     int carry = 0, par = 0;
     int v[SCAN_PER_THREAD], vn[SCAN_PER_THREAD];
@@ -145,8 +145,9 @@ __global__ __launch_bounds__(256) void k_scan_tiles(int* __restrict__ data, int 
 #define RS_ITEMS 8                         // per thread: a block owns RS_THREADS * RS_ITEMS consecutive elements
 #define RS_TILE (RS_THREADS * RS_ITEMS)
 
-// hist[digit * nblk + block] = elements of the block with that digit
-__global__ __launch_bounds__(RS_THREADS) void k_rs_hist(const unsigned* __restrict__ keys, const int* __restrict__ n_dev, int n_host, int shift, int nblk, int* __restrict__ hist) {
+// hist[digit * nblk + block] = elements of the block with that digit; `dmask` = the digit's bits that lie below the sort's `bits`
+// (RS_BINS - 1 but for a last pass that `bits` cuts short: key bits above `bits` must not order anything)
+__global__ __launch_bounds__(RS_THREADS) void k_rs_hist(const unsigned* __restrict__ keys, const int* __restrict__ n_dev, int n_host, int shift, unsigned dmask, int nblk, int* __restrict__ hist) {
     __shared__ int s_h[RS_BINS];
     const int n = n_dev ? *n_dev : n_host, tid = threadIdx.x, blk = blockIdx.x;
     if (tid < RS_BINS) s_h[tid] = 0;
@@ -154,7 +155,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_hist(const unsigned* __restri
     const int base = blk * RS_TILE;
     for (int k = 0; k < RS_ITEMS; ++k) {
         const int i = base + k * RS_THREADS + tid;
-        if (i < n) atomicAdd(&s_h[(keys[i] >> shift) & (RS_BINS - 1)], 1);
+        if (i < n) atomicAdd(&s_h[(keys[i] >> shift) & dmask], 1);
     }
     __syncthreads();
     if (tid < RS_BINS) hist[tid * nblk + blk] = s_h[tid];
@@ -165,7 +166,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_hist(const unsigned* __restri
 // (same digit in earlier rounds / waves: a prefix over the 32 (round, wave) counters per digit) + (same digit in lower lanes of its own
 // wave: six ballots narrow the wave down to the lanes that share the digit).
 __global__ __launch_bounds__(RS_THREADS) void k_rs_scatter(const unsigned* __restrict__ keys_in, const unsigned long long* __restrict__ vals_in, const int* __restrict__ n_dev,
-                                                           int n_host, int shift, int nblk, const int* __restrict__ hist_scanned, unsigned* __restrict__ keys_out,
+                                                           int n_host, int shift, unsigned dmask, int nblk, const int* __restrict__ hist_scanned, unsigned* __restrict__ keys_out,
                                                            unsigned long long* __restrict__ vals_out) {
     __shared__ int s_cnt[RS_ITEMS * (RS_THREADS / 64)][RS_BINS];  // [round * 4 + wave][digit]
     __shared__ int s_base[RS_BINS];
@@ -184,7 +185,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_scatter(const unsigned* __res
         const bool live = i < n;
         key[r] = live ? keys_in[i] : 0u;
         val[r] = live ? vals_in[i] : 0ull;
-        const unsigned d = (key[r] >> shift) & (RS_BINS - 1);
+        const unsigned d = (key[r] >> shift) & dmask;
         unsigned long long same = __ballot(live);
 #pragma unroll
         for (int b = 0; b < RS_BITS; ++b) {
@@ -208,7 +209,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_scatter(const unsigned* __res
     for (int r = 0; r < RS_ITEMS; ++r) {
         const int i = base + r * RS_THREADS + tid;
         if (i < n) {
-            const unsigned d = (key[r] >> shift) & (RS_BINS - 1);
+            const unsigned d = (key[r] >> shift) & dmask;
             const int o = s_base[d] + s_cnt[r * (RS_THREADS / 64) + wave][d] + rank[r];
             keys_out[o] = key[r];
             vals_out[o] = val[r];
@@ -268,12 +269,12 @@ __global__ __launch_bounds__(1024) void k_sort_small_sides(const SvSortSide* __r
 size_t sv_scan_scratch_ints(size_t n) { return n > SCAN_SINGLE_MAX ? (n + SCAN_TILE - 1) / SCAN_TILE + 8 : 0; }
 void sv_scan_i32(hipStream_t s, int* data, int n, int* scratch) {
     if (n <= SCAN_SINGLE_MAX) {
-        hipLaunchKernelGGL(k_scan_i32, dim3(1), dim3(1024), 0, s, data, (const int*)nullptr, n);
+        hipLaunchKernelGGL(k_scan_i32, dim3(1), dim3(1024), 0, s, data, n);
         return;
     }
     const int ntiles = (n + SCAN_TILE - 1) / SCAN_TILE;
     hipLaunchKernelGGL(k_scan_tile_sums, dim3(ntiles), dim3(256), 0, s, data, n, scratch);
-    hipLaunchKernelGGL(k_scan_i32, dim3(1), dim3(1024), 0, s, scratch, (const int*)nullptr, ntiles);  // scratch[ntiles] = the total
+    hipLaunchKernelGGL(k_scan_i32, dim3(1), dim3(1024), 0, s, scratch, ntiles);  // scratch[ntiles] = the total
     hipLaunchKernelGGL(k_scan_tiles, dim3(ntiles), dim3(256), 0, s, data, n, scratch, ntiles);
 }
 int sv_sort_passes(int bits) { return (bits + RS_BITS - 1) / RS_BITS; }
@@ -284,9 +285,11 @@ int sv_sort_pairs(hipStream_t s, unsigned* const keys[2], unsigned long long* co
     if (n <= 0) return cur ^ (sv_sort_passes(bits) & 1);
     const int nblk = (n + RS_TILE - 1) / RS_TILE, passes = sv_sort_passes(bits);
     for (int pass = 0; pass < passes; ++pass, cur ^= 1) {
-        hipLaunchKernelGGL(k_rs_hist, dim3(nblk), dim3(RS_THREADS), 0, s, keys[cur], n_dev, n, pass * RS_BITS, nblk, hist);
+        const int left = bits - pass * RS_BITS;  // key bits this pass still has to order
+        const unsigned dmask = left >= RS_BITS ? RS_BINS - 1 : (1u << left) - 1u;
+        hipLaunchKernelGGL(k_rs_hist, dim3(nblk), dim3(RS_THREADS), 0, s, keys[cur], n_dev, n, pass * RS_BITS, dmask, nblk, hist);
         sv_scan_i32(s, hist, RS_BINS * nblk, hist + hist_ints((size_t)n));
-        hipLaunchKernelGGL(k_rs_scatter, dim3(nblk), dim3(RS_THREADS), 0, s, keys[cur], vals[cur], n_dev, n, pass * RS_BITS, nblk, hist, keys[cur ^ 1], vals[cur ^ 1]);
+        hipLaunchKernelGGL(k_rs_scatter, dim3(nblk), dim3(RS_THREADS), 0, s, keys[cur], vals[cur], n_dev, n, pass * RS_BITS, dmask, nblk, hist, keys[cur ^ 1], vals[cur ^ 1]);
     }
     return cur;
 }

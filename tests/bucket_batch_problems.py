@@ -15,7 +15,8 @@ import numpy as np
 from oracle import oracle as O
 from tests import match_problems as MP
 
-CLASSES = ["reloc", "loop", "unshared", "tri_bow", "tri_robust", "planted_eq", "planted_lo", "planted_hi", "planted_tri", "spill", "many"]
+CLASSES = ["reloc", "loop", "unshared", "tri_bow", "tri_robust", "planted_eq", "planted_lo", "planted_hi", "planted_tri", "spill", "many", "long_sides",
+           "long_robust"]
 REGIME_BUCKETS = (64, 65, 1024, 1025)   # at most one entry per lane / the LDS sort / its limit / unsorted
 CHAIN = 1100                            # live queries whose claims chain across the replay's 1 024-query chunk
 
@@ -184,6 +185,8 @@ def acos_margin(b):
     for p in range(num_problems(b)):
         s1, s2 = sides(b, p)
         b1, b2 = np.asarray(s1["bearings"], np.float64), np.asarray(s2["bearings"], np.float64)
+        if len(b1) == 0 or len(b2) == 0:  # no pairs
+            continue
         e = b2 @ np.asarray(b["E_12"][p], np.float64).T                      # rows: E b2
         cosr = np.clip((b1 @ e.T) / np.linalg.norm(e, axis=1)[None, :], -1, 1)
         res = np.abs(np.pi / 2 - np.arccos(cosr))
@@ -351,3 +354,66 @@ def _many():
     """300 copies of one 64 x 64 problem: more problems than compute units."""
     s1, s2 = _small(np.random.default_rng(17))
     return dict(kind="bow", lowe_ratio=0.75, side1=[s1] * 300, side2=[s2] * 300, degenerate=())
+
+
+# ------------------------------------------------------------------------------------------------ sides beyond the one-workgroup sort
+SORT_SMALL_MAX = 16384                    # SV_SORT_SMALL_MAX of csrc/sv_sort.h: longer sides take the radix sort, n1 beyond it the long scan
+LONG_SHARED, LONG_OTHERS = 20000, (16385, 300, 16384, 0)
+LONG_NODES = 4000                         # distinct node ids: buckets of about 5, so that the Python-driven oracle stays fast
+
+
+def _long_nodes(rng, ids, n):
+    node = ids[rng.integers(0, len(ids), n)].astype(np.int32)
+    node[rng.uniform(0, 1, n) < 0.05] = -1
+    return node
+
+
+def _long_sides():
+    """ONE keyframe of 20 000 keypoints (side 1, shared) against candidates of 16 385, 300, 16 384 and 0 keypoints: sides on both sides of
+    the one-workgroup sort's limit in one batch, every single call with n1 beyond the short scan.  Node ids from 4 000 values, some -1;
+    planted pairs (a target = a query with a few bits flipped, in the query's node, at the query's angle) give every non-empty problem matches."""
+    rng = np.random.default_rng(18)
+    ids = rng.integers(0, 1 << 31, LONG_NODES, dtype=np.int64)
+    n1 = LONG_SHARED
+    q, node1 = _bits(rng, n1), _long_nodes(rng, ids, n1)
+    s1 = _side(q, angle=rng.uniform(0, 360, n1), node=node1, valid=(rng.uniform(0, 1, n1) < 0.9).astype(np.uint8))
+    with_node = np.flatnonzero(node1 >= 0)
+    cands = []
+    for n2 in LONG_OTHERS:
+        t, node2, angle2 = _bits(rng, n2), _long_nodes(rng, ids, n2), rng.uniform(0, 360, n2).astype(np.float32)
+        m = min(n2, 1200) // 3
+        for a, c in zip(rng.choice(with_node, m, replace=False), rng.choice(n2, m, replace=False) if n2 else []):
+            t[c] = _flip(q[a], int(rng.integers(0, 40)), rng)
+            node2[c], angle2[c] = node1[a], s1["angle"][a]
+        cands.append(_side(t, angle=angle2, node=node2, occupied=(rng.uniform(0, 1, n2) < 0.02).astype(np.uint8)))
+    return dict(kind="bow", lowe_ratio=0.75, side1=s1, side2=cands, degenerate=(3,))
+
+
+LONG_ROBUST_N1, LONG_ROBUST_OTHERS = 16385, (500, 0)
+
+
+def _long_robust():
+    """The triangulation matcher without node ids (match::robust: one bucket, identity order) with a shared side 1 of 16 385 keypoints: the
+    identity order beyond the one-workgroup sort and, in the single call, the long scan.  The geometry of planted_tri admits every pair
+    exactly, so the Hamming cut-off alone thins the 16 385 x 500 pairs; 150 planted pairs match."""
+    rng = np.random.default_rng(19)
+    n1 = LONG_ROBUST_N1
+    q = _bits(rng, n1)
+    s1 = _side(q, angle=rng.uniform(0, 360, n1), octave=np.zeros(n1, np.int32))
+    s1["node"] = None
+    cands = []
+    for n2 in LONG_ROBUST_OTHERS:
+        t, angle2 = _bits(rng, n2), rng.uniform(0, 360, n2).astype(np.float32)
+        m = n2 * 3 // 10
+        for a, c in zip(rng.choice(n1, m, replace=False), rng.choice(n2, m, replace=False) if n2 else []):
+            t[c] = _flip(q[a], int(rng.integers(0, 30)), rng)
+            angle2[c] = s1["angle"][a]
+        c2 = _side(t, angle=angle2)
+        c2["node"] = None
+        cands.append(c2)
+    for s in [s1] + cands:
+        s["bearings"] = np.tile(np.array([0.0, 0.0, 1.0]), (len(s["desc"]), 1))
+    k = len(cands)
+    E = np.array([[0.0, 0, 0], [0, 0, -1], [0, 1, 0]])
+    return dict(kind="tri", lowe_ratio=0.8, side1=s1, side2=cands, E_12=np.stack([E] * k), epipole_in_2=np.tile(np.array([1.0, 0, 0]), (k, 1)),
+                valid_epipole=np.zeros(k, np.int32), scale_factors=np.array([1.0, 1.2], np.float32), residual_rad_thr=0.01, degenerate=(1,))

@@ -51,6 +51,20 @@ def test_shapes():
     assert [len(x["desc"]) for x in s["side1"]] == [64, n, 64]
     assert (3 * n + 1) * 4 + 3 * ((n + 3) & ~3) + 16 > 150 * 1024  # cand_lds_bytes(n, n, 0) of match_kernels.hip: beyond the budget, the global-memory replay
     assert BP.num_problems(BP.batch("many")) == 300
+    # sides on both sides of the one-workgroup sort's limit (the radix fallback beyond it), and n1 beyond the short scan in every single call
+    lim = BP.SORT_SMALL_MAX
+    assert f"#define SV_SORT_SMALL_MAX {lim}" in (ROOT / "stella_vslam_amd" / "csrc" / "sv_sort.h").read_text()
+    ls = BP.batch("long_sides")
+    assert ls["kind"] == "bow" and isinstance(ls["side1"], dict) and len(ls["side1"]["desc"]) == 20000 > lim
+    assert [len(x["desc"]) for x in ls["side2"]] == [lim + 1, 300, lim, 0]
+    assert all(len(BP.sides(ls, p)[0]["desc"]) > lim for p in range(BP.num_problems(ls)))  # sv_bucket_count's long scan
+    for x in [ls["side1"]] + ls["side2"][:3]:
+        node = np.asarray(x["node"])
+        assert (node < 0).any() and np.bincount(np.unique(node[node >= 0], return_inverse=True)[1]).max() <= 40  # small buckets
+    assert 3000 < len(np.unique(ls["side1"]["node"])) <= BP.LONG_NODES + 1 and any(x["occupied"].any() for x in ls["side2"])
+    lr = BP.batch("long_robust")
+    assert lr["kind"] == "tri" and lr["side1"]["node"] is None and all(x["node"] is None for x in lr["side2"])
+    assert len(lr["side1"]["desc"]) == lim + 1 and [len(x["desc"]) for x in lr["side2"]] == [500, 0]
 
 
 # ---- the batched logic, restated: all sides ordered by (node, index); a row's bucket is the equal range of its node inside ITS

@@ -123,6 +123,28 @@ def test_matcher_grid_crowded_cells_outside_keypoints_and_large_frames(mods):
     check(rng.uniform(0, 1920, 9000), rng.uniform(0, 960, 9000))
 
 
+def test_matcher_grid_beyond_the_short_scan(mods):
+    """149 x 110 = 16 390 cells: the cell counters are scanned by k_exclusive_scan (match_kernels.hip grid_scan: beyond the 16 384 elements
+    of the shuffle-based scan).  3 000 keypoints, 300 of them outside the image bounds; the cell lists equal assign_keypoints_to_grid."""
+    cam_mod, data, feature, _ = mods
+    ctx = feature.Context(0)
+    cam = cam_mod.equirectangular("theta", "RGB", 1920, 960, 30.0, ctx=ctx)
+    bounds = cam.img_bounds_.as_tuple()
+    rng = np.random.default_rng(78)
+    cols, rows = 149, 110
+    assert cols * rows > 16384
+    x = np.concatenate([rng.uniform(0, 1920, 2700), rng.uniform(-60, -1, 100), rng.uniform(1921, 2000, 100), rng.uniform(0, 1920, 100)])
+    y = np.concatenate([rng.uniform(0, 960, 2700), rng.uniform(0, 960, 200), rng.uniform(961, 1100, 100)])
+    perm = rng.permutation(len(x))
+    k = np.zeros(len(x), O.KEYPOINT_DTYPE)
+    k["x"], k["y"], k["size"], k["class_id"] = x[perm].astype(np.float32), y[perm].astype(np.float32), 31.0, -1
+    obs = data.frame_observation(cam, k, np.zeros((len(k), 32), np.uint8), num_grid_cols=cols, num_grid_rows=rows)
+    off, items = O.assign_keypoints_to_grid(k["x"], k["y"], bounds, cols, rows)
+    assert len(off) == cols * rows + 1 and 2600 <= off[-1] <= 2700 and (np.diff(off) > 0).sum() > 2000  # keypoints all over the grid, the last cells included
+    assert off[16384] < off[-1] and np.diff(off)[16000:].sum() > 20  # also in the last partial round of 1 024 cells and beyond cell 16 384
+    assert np.array_equal(obs.cell_off_, off) and np.array_equal(obs.cell_items_, items)
+
+
 def test_wide_fisheye_bounds_and_reference_cell_vectors(mods):
     cam_mod, data, feature, _ = mods
     ctx = feature.Context(0)
