@@ -1079,6 +1079,11 @@ int svgpu_ba_set_solver(svgpu_ctx* ctx, int solver, double pcg_tolerance, int pc
  * 2 segmented, block rows, widest column; segmented: cuts, jobs, jobs on this rank, separator rows, longest job (columns)}. */
 int svgpu_ba_last_envelope_plan(svgpu_ctx* ctx, int* info);
 
+/* Which solver factored the reduced system in the last stage of the context's last bundle adjustment (diagnostics for tests): *solver =
+ * the svgpu_ba_solver value AUTO or the request resolved to -- CHOLESKY (both on-chip forms), DENSE, PCG_MULTI, ENVELOPE -- or 5, the PCG
+ * inside one workgroup's LDS; -1 before the first call. */
+int svgpu_ba_last_solver(svgpu_ctx* ctx, int* solver);
+
 /* Planner self-test of the segmented envelope factorisation (host arithmetic only, runs without a device; NOT a solver path: the
  * bundle adjusters never call it).  Plans the elimination of the 6x6-block SPD system {blk_ab[NB] upper blocks a <= b, Sblk NB x 36
  * row-major, g 6 nP} exactly as the global / sharded bundle adjusters do (RCM order, `cuts` separators or the planner's choice when

@@ -867,6 +867,7 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
             HS.envelope_ok = ok;
         }
         solver = ba_plan_solver_final(front, HS.envelope_ok, lds_ok);
+        ctx->ba_last_solver = solver;
         // Keyframe-segment exchange.  When the envelope solve is segmented and every observation this rank holds is of a keyframe in one of
         // ITS jobs' pieces (or of a separator keyframe) -- svgpu_ba_partition_keyframe_segments cuts shards that way -- the blocks and
         // right-hand side rows of a piece are complete on the rank that eliminates it and no other rank reads them: only the kept blocks
@@ -1411,6 +1412,12 @@ int svgpu_global_ba_sharded(svgpu_ctx* ctx, const svgpu_ba_problem* shard, int r
 int svgpu_ba_last_exchange(svgpu_ctx* ctx, int64_t* info) {
     if (!ctx || !info) return SVGPU_ERR_INVALID;
     for (int k = 0; k < 10; ++k) info[k] = ctx->ba_xch[k];
+    return SVGPU_OK;
+}
+
+int svgpu_ba_last_solver(svgpu_ctx* ctx, int* solver) {
+    if (!ctx || !solver) return SVGPU_ERR_INVALID;
+    *solver = ctx->ba_last_solver;
     return SVGPU_OK;
 }
 

@@ -162,6 +162,7 @@ struct svgpu_ctx {
     svgpu_allreduce_fn ba_ar_fn = nullptr;  // the all-reduce of the sharded solve in progress (the segmented envelope solve exchanges through it); else null
     void* ba_ar_user = nullptr;
     BaEnv ba_env;                   // the switches of the bundle-adjustment call in progress (ba_plan.h; local_ba_impl reads them at its entry)
+    int ba_last_solver = -1;        // svgpu_ba_last_solver: the solver the last stage's structure resolved to (ba_plan_solver_final)
     long long ba_xch[10] = {0};    // svgpu_ba_last_exchange: what the last sharded solve all-reduced (mode | bytes by category | calls | trials | linearisations)
     int comm_rank = 0, comm_world = 1;
 };

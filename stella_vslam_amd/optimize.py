@@ -78,6 +78,12 @@ class local_bundle_adjuster:
         return dict(kind=("one-sided", "two-sided", "segmented")[int(info[0])], rows=int(info[1]), widest_column=int(info[2]), cuts=int(info[3]),
                     jobs=int(info[4]), jobs_local=int(info[5]), separator_rows=int(info[6]), longest_job=int(info[7]))
 
+    def last_solver(self) -> str:
+        """Which solver the last stage of the context's last call resolved to (svgpu_ba_last_solver); "pcg_lds" is the PCG inside one workgroup's LDS."""
+        code = C.c_int(-1)
+        self.ctx.check(lib().svgpu_ba_last_solver(self.ctx.handle, C.byref(code)), "svgpu_ba_last_solver")
+        return {-1: "none", SOLVER_CHOLESKY: "cholesky", SOLVER_DENSE: "dense", SOLVER_PCG_MULTI: "pcg_multi", 5: "pcg_lds", SOLVER_ENVELOPE: "envelope"}[code.value]
+
     def last_exchange(self) -> dict:
         """What the context's last sharded solve all-reduced (svgpu_ba_last_exchange); bytes are payload per rank."""
         info = np.zeros(10, np.int64)
