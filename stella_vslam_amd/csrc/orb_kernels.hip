@@ -76,6 +76,45 @@ __device__ __forceinline__ void sv_glds16(unsigned long long base, uint32_t voff
                  : "memory");
 }
 
+// rows [y0, y0 + nrows) of an image (row pitch gp, any alignment) -> LDS at lds0 with row pitch 16 * cpr, by the `nwaves` waves of the workgroup
+// (k_describe_bands, level 0 of k_pyramid_lds).
+// An instruction carries `rpi` = 64 / cpr whole rows (lane = row_in_group * cpr + piece, so that LDS byte 16 * lane continues the linear
+// image; the lanes behind rpi * cpr rest): the lane's source offset is loop-invariant and the group's base address advances in scalar
+// registers -- no vector instruction per DMA.  Wave w takes the row groups w, w + nwaves, ...  (Rows wider than 1 KB: see db_stage_rows_wide.)
+__device__ __forceinline__ void db_stage_rows(const uint8_t* img, int gp, int y0, int nrows, int cpr, uint32_t lds0, int lane, int wave, int nwaves) {
+    const int rpi = 64 / cpr;                       // rows per instruction (>= 1: cpr <= 64)
+    const int rsub = lane / cpr, csub = lane - rsub * cpr;
+    const uint32_t voff = (uint32_t)(rsub * gp + csub * 16);
+    const int groups = (nrows + rpi - 1) / rpi;
+    const unsigned long long base = (unsigned long long)(uintptr_t)(img + (size_t)y0 * gp);
+    // (the last group may hold fewer than rpi rows: its surplus lanes stay out -- the rows behind a level's last one belong to somebody else, and
+    //  behind a caller's image to nobody)
+    if (rsub < rpi)
+        for (int g = wave; g < groups; g += nwaves)
+            if (g * rpi + rsub < nrows) sv_glds16(base + (unsigned long long)(g * rpi) * (unsigned)gp, voff, lds0 + (uint32_t)(g * rpi * cpr) * 16);
+}
+// the general form (pieces of a row spread over several instructions): piece q = row * cpr + c goes to LDS byte 16 q, instruction i covers
+// pieces [64 i, 64 i + 64)
+__device__ __forceinline__ void db_stage_rows_wide(const uint8_t* img, int gp, int y0, int nrows, int cpr, uint32_t lds0, int lane, int wave, int nwaves) {
+    const int total = nrows * cpr;
+    int q = wave * 64 + lane;
+    int row = q / cpr, c = q - row * cpr;
+    const int drow = (nwaves * 64) / cpr, dc = (nwaves * 64) - drow * cpr;
+    const unsigned long long base = (unsigned long long)(uintptr_t)(img + (size_t)y0 * gp);
+    uint32_t dst = lds0 + wave * 1024;
+    for (int i = wave * 64; i < total; i += nwaves * 64) {  // wave-uniform trip count
+        if (q < total) sv_glds16(base, (uint32_t)(row * gp + c * 16), dst);
+        q += nwaves * 64;
+        row += drow;
+        c += dc;
+        if (c >= cpr) {
+            c -= cpr;
+            ++row;
+        }
+        dst += nwaves * 1024;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ pyramid
 // OpenCV 8-bit bilinear: horizontal int32 with 11-bit coefficients, vertical
 // ((b0*(r0>>4))>>16) + ((b1*(r1>>4))>>16) + 2) >> 2.  Coefficient tables are built on the host (orb_plan.h).
@@ -202,12 +241,12 @@ __global__ __launch_bounds__(PYR_THREADS) void k_pyramid_lds(const OrbLevel* __r
         const int w0 = L[0].w, p0 = (w0 + 3) & ~3, lo0 = BR[0].x, n0 = BR[0].y - lo0;
         uint8_t* D0 = s_mem + s_img[0];
         if (((((size_t)I0) | (size_t)img0_pitch) & 15) == 0 && (p0 & 15) == 0) {
-            const int cpr = p0 >> 4, total = n0 * cpr;  // 16-byte chunks (the row pitch covers the rounded-up width)
-            const float inv = 1.0f / (float)cpr;
-            for (int i = tid; i < total; i += PYR_THREADS) {
-                const int r = (int)(((float)i + 0.5f) * inv), c = i - __mul24(r, cpr);
-                reinterpret_cast<uint4*>(D0)[i] = *reinterpret_cast<const uint4*>(I0 + (__umul24(lo0 + r, img0_pitch) + 16 * c));
-            }
+            // 16-byte pieces by LDS-DMA (the row pitch covers the rounded-up width): whole rows per instruction, the lane's source offset is
+            // loop-invariant and the row group's base advances in scalar registers -- no staging registers, no per-piece row / column arithmetic
+            const int cpr = p0 >> 4, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+            const uint32_t lds0 = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(const __attribute__((address_space(3))) uint8_t*)D0);
+            if (cpr <= 64) db_stage_rows(I0, img0_pitch, lo0, n0, cpr, lds0, tid & 63, wave, PYR_THREADS / 64);
+            else db_stage_rows_wide(I0, img0_pitch, lo0, n0, cpr, lds0, tid & 63, wave, PYR_THREADS / 64);
         }
         else if (((((size_t)I0) | (size_t)img0_pitch) & 3) == 0) {
             const int wpr = p0 >> 2, total = n0 * wpr;
@@ -232,6 +271,7 @@ __global__ __launch_bounds__(PYR_THREADS) void k_pyramid_lds(const OrbLevel* __r
             reinterpret_cast<short4*>(s_mem + s_yt[0])[i] = yrow[L[l].ytab_off + BR[l].x + r];
         }
     }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the wave's own DMA pieces have landed; the barrier publishes them to the other waves
     __syncthreads();
     uint8_t* P = pyr + (size_t)b * pyr_frame_bytes;
     for (int l = 1; l < num_levels; ++l) {
@@ -283,7 +323,9 @@ __global__ __launch_bounds__(PYR_THREADS) void k_pyramid_lds(const OrbLevel* __r
                 uint32_t v[4];
 #pragma unroll
                 for (int i = 0; i < 4; ++i) v[i] = (mul_hi_u24(b0, top[i]) + mul_hi_u24(b1, bot[i]) + 2u) >> 2;
-                const uint32_t packed = (v[0] & 255u) | ((v[1] & 255u) << 8) | ((v[2] & 255u) << 16) | (v[3] << 24);
+                // No result needs a mask: H <= 255 * (a0 + a1) and both coefficient pairs sum to at most 2049 (orb_plan_coef_sums_ok, verified by
+                // orb_plan_build), so (b0 * (H0 >> 4)) >> 16 + (b1 * (H1 >> 4)) >> 16 <= floor(2049 * 32655 / 65536) = 1020 and v <= (1020 + 2) >> 2 = 255.
+                const uint32_t packed = v[0] | (v[1] << 8) | (v[2] << 16) | (v[3] << 24);
                 *dl = packed;
                 if (dyo < own_n) *reinterpret_cast<uint32_t*>(Dg + goff) = packed;
                 dl += dpw;
@@ -748,10 +790,40 @@ __global__ __launch_bounds__(256) void k_fast(const OrbLevel* __restrict__ L, in
         p[15] = c[3 * FP - 1];
     };
 
+    // ---- what the cell loop keeps from cell to cell.  A thread stages the 16-byte pieces tid and tid + 256 of the ROI (piece q = row * 5 + piece-of-row;
+    //      pieces 256..349 belong to waves 0 and 1): their rows, columns and LDS destinations are the thread's own.  The level record, the source
+    //      base and pitch and the pieces' source offsets change with the cell's level; the staging predicates and the band masks of the quick test
+    //      with the cell's size.  Consecutive cells share both nearly always (only a level's last column and last row are smaller), and both
+    //      tests are wave-uniform.
+    const int pr0 = tid / 5, pc0 = 16 * (tid - 5 * pr0), pr1 = (tid + 256) / 5, pc1 = 16 * (tid + 256 - 5 * pr1);
+    const bool piece1 = wv < 2 && tid + 256 < SV_ROI_MAX * (FP / 16);
+    const uint32_t lds_raw = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(const __attribute__((address_space(3))) uint8_t*)s_raw) + (uint32_t)wv * 1024u;
+    int cur_lv = -1, cur_wh = -1;
+    OrbLevel lev = {};
+    const uint8_t* src = nullptr;
+    int spitch = 0;
+    uint32_t voff0 = 0, voff1 = 0;     // source byte offsets of the two pieces from the ROI's first fetched byte
+    bool fetch0 = false, fetch1 = false;
+    uint32_t band80[4] = {0, 0, 0, 0};  // per patch row: 0x80 per column of the patch inside the scored band, 0 for a row outside it
+
     const int c_first = grp * cpw, c_last = min(c_first + cpw, num_cells);
     for (int ci = c_first; ci < c_last; ++ci) {
-    const FastCell cell = cells[ci];
-    const OrbLevel lev = L[cell.lv];
+    static_assert(sizeof(FastCell) == 16, "a cell record is one 16-byte load");
+    const FastCell cell = __builtin_bit_cast(FastCell, reinterpret_cast<const uint4*>(cells)[ci]);  // one scalar load (the fields read one by one cost a vector load)
+    if (cell.lv != cur_lv) {
+        cur_lv = cell.lv;
+        lev = L[cell.lv];
+        if (cell.lv == 0) {
+            src = I0;
+            spitch = img0_pitch;
+        }
+        else {
+            src = PY + lev.pyr_off;
+            spitch = lev.pitch;
+        }
+        voff0 = (uint32_t)(__umul24(pr0, spitch) + pc0);
+        voff1 = (uint32_t)(__umul24(pr1, spitch) + pc1);
+    }
     auto masked = [&](int y, int x) -> bool {  // is_in_mask (orb_extractor.cc:168-170): (int)(y * scale), (int)(x * scale)
         int my = (int)((float)y * lev.scale), mx = (int)((float)x * lev.scale);
         my = min(my, mask_h - 1);
@@ -762,36 +834,33 @@ __global__ __launch_bounds__(256) void k_fast(const OrbLevel* __restrict__ L, in
         const int y0 = cell.min_y, y1 = cell.min_y + cell.h, xa = cell.min_x, xb = cell.min_x + cell.w;
         if (masked(y0, xa) || masked(y1, xa) || masked(y0, xb) || masked(y1, xb)) continue;
     }
-    const uint8_t* src;
-    int spitch;
-    if (cell.lv == 0) {
-        src = I0;
-        spitch = img0_pitch;
-    }
-    else {
-        src = PY + lev.pyr_off;
-        spitch = lev.pitch;
-    }
     const int w = cell.w, h = cell.h;
+    if (((w << 8) | h) != cur_wh) {  // (w, h <= 70)
+        cur_wh = (w << 8) | h;
+        fetch0 = pr0 < h && pc0 < w + 3;
+        fetch1 = piece1 && pr1 < h && pc1 < w + 3;
+        uint32_t cols = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) cols |= (x0 + j < w - 3) ? (0x80u << (8 * j)) : 0u;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) band80[g] = ly0 + g < h - 3 ? cols : 0u;
+    }
     if (ci != c_first) __syncthreads();  // the previous cell's flush has read s_key, its last pass s_a / s_raw
     // ROI -> LDS by LDS-DMA (round 6: global_load_lds_dwordx4, no staging registers, no ds_write pass, any source alignment -- the three
     // load variants of rounds 1-5 were one per alignment class).  The ROI starts at x = 19 + 64j, i.e. 3 bytes past a 16-byte boundary of an
     // aligned level: the pieces start 3 bytes early (real pixels of the border band) and the LDS copy is addressed with a +3 skew.  Piece q = row * 5 +
     // piece-of-row goes to LDS byte 16 q (the rows are FP = 80 bytes apart); a thread owns pieces tid and tid + 256, so its row and column are the same
-    // for every cell.  Rows past the cell and pieces past its width are NOT fetched: what the previous cell left there is never used (the quick test masks
+    // for every cell (set up in front of the cell loop).  Rows past the cell and pieces past its width are NOT fetched: what the previous cell left there is never used (the quick test masks
     // those positions, the arc score and the NMS only visit queued pixels, whose rings lie inside the cell).
     const uint8_t* rsrc = src + (size_t)cell.min_y * spitch + (cell.min_x - 3);
     {
         const unsigned long long rbase = (unsigned long long)(uintptr_t)rsrc;
-        const uint32_t lds_raw = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(const __attribute__((address_space(3))) uint8_t*)s_raw) + (uint32_t)wv * 1024u;
-#pragma unroll
-        for (int it = 0; it < 2; ++it) {
-            const int q = tid + 256 * it, r = q / 5, c = q - 5 * r;  // (compile-time divisor)
-            if (it == 0 || wv < 2) {                                   // pieces 256..349 belong to waves 0 and 1
-                if (q < SV_ROI_MAX * (FP / 16) && r < h && 16 * c < w + 3) sv_glds16(rbase, (uint32_t)(__umul24(r, spitch) + 16 * c), lds_raw + 4096u * it);
-            }
-            if (q < SV_ROI_MAX * (FP / 16)) reinterpret_cast<uint4*>(s_a)[q] = make_uint4(0, 0, 0, 0);
+        if (fetch0) sv_glds16(rbase, voff0, lds_raw);
+        if (wv < 2) {
+            if (fetch1) sv_glds16(rbase, voff1, lds_raw + 4096u);
         }
+        reinterpret_cast<uint4*>(s_a)[tid] = make_uint4(0, 0, 0, 0);
+        if (piece1) reinterpret_cast<uint4*>(s_a)[tid + 256] = make_uint4(0, 0, 0, 0);
     }
     if (tid == 0) {
         s_count = 0;
@@ -799,9 +868,6 @@ __global__ __launch_bounds__(256) void k_fast(const OrbLevel* __restrict__ L, in
     if (tid < FAST_KT * FAST_KT) s_key[tid] = 0ull;
     if (tid < w) s_gx[tid] = gtab[lev.gtab_x_off + cell.min_x + tid - SV_PATCH_RADIUS];
     else if (tid >= 128 && tid - 128 < h) s_gy[tid - 128] = gtab[lev.gtab_y_off + cell.min_y + (tid - 128) - SV_PATCH_RADIUS];
-    uint32_t band80 = 0;  // 0x80 per column of the patch inside the scored band
-#pragma unroll
-    for (int j = 0; j < 4; ++j) band80 |= (x0 + j < w - 3) ? (0x80u << (8 * j)) : 0u;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the wave's own DMA pieces have landed; the barrier publishes them to the other waves
     __syncthreads();
 
@@ -851,7 +917,7 @@ __global__ __launch_bounds__(256) void k_fast(const OrbLevel* __restrict__ L, in
             }
             // sign bytes of the four results -> one byte per pixel; a clear sign inside the band is a hit
             const uint32_t sgn = __builtin_amdgcn_perm(e2[1], e2[0], 0x07050301u);
-            m = (m >> 1) | (~sgn & (ly0 + g < h - 3 ? band80 : 0u));
+            m = (m >> 1) | (~sgn & band80[g]);
         }
         // Compaction, once per wave: exclusive prefix of the lanes' hit counts (row-scan adds), then every lane stores the hits of
         // its patch.  The queue order is patch by patch along a band of four rows -- neighbouring lanes of pass B then work on
@@ -1304,44 +1370,6 @@ __device__ __forceinline__ void sv_writelane8(uint32_t& lo, uint32_t& hi, const 
           "s"((uint32_t)m[3]), "s"((uint32_t)(m[3] >> 32)), "n"(LANE), "n"(LANE + 1), "n"(LANE + 2), "n"(LANE + 3));
 }
 
-// rows [y0, y0 + nrows) of an image (row pitch gp, any alignment) -> LDS at lds0 with row pitch 16 * cpr, by the whole workgroup.
-// An instruction carries `rpi` = 64 / cpr whole rows (lane = row_in_group * cpr + piece, so that LDS byte 16 * lane continues the linear
-// image; the lanes behind rpi * cpr rest): the lane's source offset is loop-invariant and the group's base address advances in scalar
-// registers -- no vector instruction per DMA.  Wave w takes the row groups w, w + 8, ...  (Rows wider than 1 KB: see db_stage_rows_wide.)
-__device__ __forceinline__ void db_stage_rows(const uint8_t* img, int gp, int y0, int nrows, int cpr, uint32_t lds0, int lane, int wave) {
-    const int rpi = 64 / cpr;                       // rows per instruction (>= 1: cpr <= 64)
-    const int rsub = lane / cpr, csub = lane - rsub * cpr;
-    const uint32_t voff = (uint32_t)(rsub * gp + csub * 16);
-    const int groups = (nrows + rpi - 1) / rpi;
-    const unsigned long long base = (unsigned long long)(uintptr_t)(img + (size_t)y0 * gp);
-    // (the last group may hold fewer than rpi rows: its surplus lanes stay out -- the rows behind a level's last one belong to somebody else, and
-    //  behind a caller's image to nobody)
-    if (rsub < rpi)
-        for (int g = wave; g < groups; g += DB_WAVES)
-            if (g * rpi + rsub < nrows) sv_glds16(base + (unsigned long long)(g * rpi) * (unsigned)gp, voff, lds0 + (uint32_t)(g * rpi * cpr) * 16);
-}
-// the general form (pieces of a row spread over several instructions): piece q = row * cpr + c goes to LDS byte 16 q, instruction i covers
-// pieces [64 i, 64 i + 64)
-__device__ __forceinline__ void db_stage_rows_wide(const uint8_t* img, int gp, int y0, int nrows, int cpr, uint32_t lds0, int lane, int wave) {
-    const int total = nrows * cpr;
-    int q = wave * 64 + lane;
-    int row = q / cpr, c = q - row * cpr;
-    const int drow = (DB_WAVES * 64) / cpr, dc = (DB_WAVES * 64) - drow * cpr;
-    const unsigned long long base = (unsigned long long)(uintptr_t)(img + (size_t)y0 * gp);
-    uint32_t dst = lds0 + wave * 1024;
-    for (int i = wave * 64; i < total; i += DB_WAVES * 64) {  // wave-uniform trip count
-        if (q < total) sv_glds16(base, (uint32_t)(row * gp + c * 16), dst);
-        q += DB_WAVES * 64;
-        row += drow;
-        c += dc;
-        if (c >= cpr) {
-            c -= cpr;
-            ++row;
-        }
-        dst += DB_WAVES * 1024;
-    }
-}
-
 __global__ __launch_bounds__(DB_THREADS) void k_describe_bands(const OrbLevel* __restrict__ L, int num_levels, const DescBand* __restrict__ bands, int num_bands,
                                                                const int4* __restrict__ sel, int total_grid, const int32_t* __restrict__ cellpos,
                                                                const int32_t* __restrict__ counts,
@@ -1390,8 +1418,8 @@ __global__ __launch_bounds__(DB_THREADS) void k_describe_bands(const OrbLevel* _
     {
         const uint8_t* img = lv == 0 ? img0 + (size_t)b * img0_frame_stride : pyr + (size_t)b * pyr_frame_bytes + L[lv].pyr_off;
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // the loads above are not counted against the DMA below
-        if (cpr <= 64) db_stage_rows(img, lv == 0 ? img0_pitch : L[lv].pitch, bd.yu0, bd.nru, cpr, lds0, lane, wave);
-        else db_stage_rows_wide(img, lv == 0 ? img0_pitch : L[lv].pitch, bd.yu0, bd.nru, cpr, lds0, lane, wave);
+        if (cpr <= 64) db_stage_rows(img, lv == 0 ? img0_pitch : L[lv].pitch, bd.yu0, bd.nru, cpr, lds0, lane, wave, DB_WAVES);
+        else db_stage_rows_wide(img, lv == 0 ? img0_pitch : L[lv].pitch, bd.yu0, bd.nru, cpr, lds0, lane, wave, DB_WAVES);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     __syncthreads();
@@ -1420,8 +1448,8 @@ __global__ __launch_bounds__(DB_THREADS) void k_describe_bands(const OrbLevel* _
     }
     __syncthreads();  // every wave is done with the un-blurred rows; the moments are in LDS
     // ---- phase A: blurred rows -> LDS (same region); meanwhile thread t: orientation, cos / sin and the record of keypoint t
-    if (cpr <= 64) db_stage_rows(blur + (size_t)b * blur_frame_bytes + L[lv].blur_off, L[lv].pitch, bd.yb0, bd.nrb, cpr, lds0, lane, wave);
-    else db_stage_rows_wide(blur + (size_t)b * blur_frame_bytes + L[lv].blur_off, L[lv].pitch, bd.yb0, bd.nrb, cpr, lds0, lane, wave);
+    if (cpr <= 64) db_stage_rows(blur + (size_t)b * blur_frame_bytes + L[lv].blur_off, L[lv].pitch, bd.yb0, bd.nrb, cpr, lds0, lane, wave, DB_WAVES);
+    else db_stage_rows_wide(blur + (size_t)b * blur_frame_bytes + L[lv].blur_off, L[lv].pitch, bd.yb0, bd.nrb, cpr, lds0, lane, wave, DB_WAVES);
     if (tid < nkp) {
         const int2 mm = s_aux[tid];
         const float angle = dev_fast_atan2((float)mm.y, (float)mm.x);

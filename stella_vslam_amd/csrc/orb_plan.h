@@ -271,6 +271,21 @@ inline bool orb_plan_pyramid_records(OrbConfig& C, int l, OrbTables& T) {
     return xg_ok;
 }
 
+// ---- every coefficient pair of the resize tables sums to at most SV_RESIZE_COEF_SUM_MAX (round(f * 2048) + round((1 - f) * 2048) is 2048,
+//      or 2049 when both halves round up).  k_pyramid_lds packs its four results of a row step without masking them to a byte: with
+//      a0 + a1 <= 2049 and b0 + b1 <= 2049 no result exceeds 255 (the argument stands at the pack).  Checked on the tables the kernels read --
+//      the plain pairs and their packed copies -- so a table that breaks it never reaches the device.
+#define SV_RESIZE_COEF_SUM_MAX 2049
+inline bool orb_plan_coef_sums_ok(const OrbTables& T) {
+    bool ok = true;
+    for (const OrbShort2& a : T.xa) ok = ok && (int)a.x + (int)a.y <= SV_RESIZE_COEF_SUM_MAX;
+    for (const OrbShort2& b : T.yb) ok = ok && (int)b.x + (int)b.y <= SV_RESIZE_COEF_SUM_MAX;
+    for (size_t r = 0; r + 8 <= T.xg.size(); r += 8)
+        for (int i = 2; i < 6; ++i) ok = ok && (T.xg[r + i] & 0xffffu) + (T.xg[r + i] >> 16) <= SV_RESIZE_COEF_SUM_MAX;
+    for (const OrbShort4& y : T.yrow) ok = ok && (int)y.z + (int)y.w <= SV_RESIZE_COEF_SUM_MAX;
+    return ok;
+}
+
 // ---- blur tiles and bands of level l
 inline void orb_plan_blur_items(OrbConfig& C, int l, int& btile_first, int& bband_first) {
     OrbLevel& L = C.levels[l];
@@ -517,6 +532,7 @@ inline const char* orb_plan_build(int width, int height, int max_batch, float sc
         orb_plan_blur_items(C, l, btile_first, bband_first);
         orb_plan_cells_and_grid(C, l, T, grid_first, grid_rows[l]);
     }
+    if (!orb_plan_coef_sums_ok(T)) return "resize coefficient pair sums to more than 2049";
     C.total_grid = grid_first;
     C.total_btiles = btile_first;
     C.total_bbands = bband_first;
