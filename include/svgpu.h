@@ -1235,6 +1235,63 @@ int svgpu_reloc_refine_batch(svgpu_ctx* ctx, const svgpu_camera* cam, const uint
                              int32_t* status, double* pose_out, int32_t* match_kf, int32_t* match_stage, uint8_t* outlier, int32_t* num_found,
                              int32_t* num_valid, int32_t* lm_iterations, svgpu_call_stats* stats);
 
+/* The middle of module::loop_detector::select_loop_candidate_via_Sim3 (module/loop_detector.cc:537-587) for ALL candidates that survived
+ * the pose refinement, in one call: per candidate the scale from the small-parallax landmark pairs (:540-573),
+ * projection::match_keyframes_mutually (:577; match/projection.cc:418-629), the edge gather of optimize::transform_optimizer::optimize
+ * (optimize/transform_optimizer.cc:64-94) and the optimisation itself (:581), with the decision of :585.  Keyframe 1 (the current
+ * keyframe) is uploaded and binned once; the candidates' keypoints are binned in one pass; both matcher passes of all candidates are one
+ * concatenation of queries; the edges go straight into the arrays the Sim3 optimiser reads.
+ *   keyframe 1 (shared)  cam1, pose_1w (12 doubles, rows of [rot_cw | trans_cw]), n1 keypoints: desc1 / xy1 (undistorted) / octave1, and
+ *                        one landmark slot per keypoint: pos_w1, has_lm1 (non-null and not will_be_erased), min_valid1 / max_valid1,
+ *                        lm_desc1; the ORB tables and the grid as svgpu_match_keyframes_mutually takes them, inv_level_sigma_sq by octave
+ *   per candidate p      cam2[p], pose_2w[p] (12), the entries kf2_off[p] .. kf2_off[p + 1] of desc2 / xy2 / octave2 / pos_w2 / has_lm2 /
+ *                        min_valid2 / max_valid2 / lm_desc2 (a candidate may have none); pose_1w_in_cand[p] (12, optimized_pose2, :537);
+ *                        rot_12[p] (9) and trans_12[p] (3) as :570-571 computes them; sim3_12[p] (8 doubles as
+ *                        svgpu_sim3_transform_optimize takes them; the scale entry is ignored); active[p] (nullable = all)
+ *   prior matches        curr_match_lms_observed_in_cand, each K x n1: prior_state 0 none, 1 present and alive, 2 present and
+ *                        will_be_erased; prior_idx2 = lm->get_index_in_keyframe(keyfrm_2), or -1 when negative or >= n2; prior_pos_w x 3
+ *   of the call          scale_12_in (nullable, K floats: the scale is taken from it and step 1 is skipped); margin (the reference: 7.5);
+ *                        chi_sq, fix_scale, num_iter as svgpu_sim3_transform_optimize; min_num_inliers (num_optimized_inliers_thr_)
+ * Per active candidate:
+ *   1. scale (:540-573): for every idx1 with has_lm1 and prior_state 1, pos_1_in_cand = R prior_pos_w + t from pose_1w_in_cand and
+ *      pos_1_in_curr from pose_1w and pos_w1; both norms in double, narrowed to float; cos_parallax = (float)(dot / (double)(n_cand *
+ *      n_curr)) with the product in float; kept iff 0.99996192306f < cos_parallax; ratio n_curr / n_cand in float; scale_12 = element
+ *      (count - 1) / 2 of the ratios in ascending order.  No ratio: status SVGPU_LOOP_NO_SCALE, nothing further runs for the candidate.
+ *   2. mutual match (projection.cc:418-629): is_already_matched_in_keyfrm_1 / 2 from prior_state != 0 && prior_idx2 >= 0 (:440-450); both
+ *      passes as svgpu_match_keyframes_mutually runs them (best only, HAMMING_DIST_THR_HIGH, level window +-1, the distance range with the
+ *      1.3 margins in double, keyframe 2's camera for the in-image test in BOTH passes), then the cross-check (:613-626).
+ *   3. edges (transform_optimizer.cc:64-94), idx1 ascending: has_lm1 and either a new mutual match (pos_w2[idx2]; it overwrites a prior
+ *      entry, :623) or a prior with prior_state 1 and prior_idx2 >= 0 (prior_pos_w).
+ *   4. svgpu_sim3_transform_optimize on those edges; status SVGPU_LOOP_FEW_INLIERS when num_inliers < min_num_inliers, else 0.
+ * Outputs: status (K; -1 = inactive on input), scale_12 (K; 0 where none was estimated), matched_2_in_1 (K x n1), matched_1_in_2
+ * (by kf2_off), mutual_2_in_1 (K x n1: the new mutual matches, else -1), num_mutual (K), edge_idx1 / edge_idx2 (K x n1, num_edges[p] valid
+ * entries per row, -1 behind them), edge_status (K x n1: the optimiser's status byte per edge, 0 behind them), sim3_12_out (K x 8: the
+ * input with the estimated scale if the optimiser returned early; the input itself for an inactive candidate or one without a scale),
+ * num_inliers (K), opt_stats (nullable, K; zero where the optimiser had nothing to do).  Every output equals, bit for bit, the chain
+ * of svgpu_match_keyframes_mutually and svgpu_sim3_transform_optimize for that candidate alone, whatever else the batch holds.
+ * `stats` (nullable) receives what the call issued; none of the three depends on num_candidates.  Two synchronisations: the candidate-list
+ * total and the end.  A call whose lists outgrow their first capacity (16 entries per row, at most 4 Mi entries) starts again with lists
+ * of the exact size: `stats` then holds the launches, copies and synchronisations of both attempts (3 synchronisations).
+ * SVGPU_ERR_INVALID before anything is launched or written: a null required pointer, kf2_off[0] != 0 or non-monotone offsets, an octave
+ * outside [0, num_levels), num_levels outside 1..16, n1 or an n2 >= 1 << 22, a prior_idx2 >= that candidate's n2, a camera model the Sim3
+ * edges do not cover, a non-unit quaternion, a non-positive chi_sq, inv_level_sigma_sq or scale_12_in, num_iter < 0, totals beyond int32.
+ * num_candidates == 0 succeeds whatever else is passed.  Host in/out, synchronous. */
+#define SVGPU_LOOP_NO_SCALE 1
+#define SVGPU_LOOP_FEW_INLIERS 2
+int svgpu_loop_sim3_batch(svgpu_ctx* ctx, const svgpu_camera* cam1, const double* pose_1w, int n1, const uint8_t* desc1, const float* xy1,
+                          const int32_t* octave1, const double* pos_w1, const uint8_t* has_lm1, const float* min_valid1,
+                          const float* max_valid1, const uint8_t* lm_desc1, int num_levels, const float* scale_factors,
+                          const float* inv_level_sigma_sq, float log_scale_factor, int grid_cols, int grid_rows, int num_candidates,
+                          const svgpu_camera* cam2, const double* pose_2w, const int32_t* kf2_off, const uint8_t* desc2, const float* xy2,
+                          const int32_t* octave2, const double* pos_w2, const uint8_t* has_lm2, const float* min_valid2,
+                          const float* max_valid2, const uint8_t* lm_desc2, const double* pose_1w_in_cand, const double* rot_12,
+                          const double* trans_12, const double* sim3_12, const uint8_t* active, const uint8_t* prior_state,
+                          const int32_t* prior_idx2, const double* prior_pos_w, const float* scale_12_in, float margin, float chi_sq,
+                          int fix_scale, int num_iter, int min_num_inliers, int32_t* status, float* scale_12, int32_t* matched_2_in_1,
+                          int32_t* matched_1_in_2, int32_t* mutual_2_in_1, int32_t* num_mutual, int32_t* edge_idx1, int32_t* edge_idx2,
+                          int32_t* num_edges, uint8_t* edge_status, double* sim3_12_out, int32_t* num_inliers,
+                          svgpu_sim3opt_stats* opt_stats, svgpu_call_stats* stats);
+
 /* Global BA core (optimize/global_bundle_adjuster.cc:26-192, 279-412): the same graph over ALL keyframes (spanning root
  * fixed), ONE Levenberg-Marquardt run of problem->num_first_iter iterations with the terminate rule, optional Huber
  * (obs_huber_delta), no outlier gate (num_second_iter is ignored).  The caller applies the reference's post-conditions

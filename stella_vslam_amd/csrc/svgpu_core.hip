@@ -108,7 +108,7 @@ static void prof_collect(SvProfClass& K) {
 extern "C" {
 
 const char* svgpu_profile_kernels(void) {
-    return "k_resize,k_blur,k_fast,k_select,k_describe,k_bf_binsort,k_bf_topk,k_bf_replay,k_cand,k_stereo,ba_linearize,ba_schur,ba_solve,ba_update,ba_chi2,k_pose_opt,k_pose_opt_batch,k_triangulate_two_views,k_ingest_gray,k_ingest_depth,k_pnp_pose,k_pnp_ransac,k_pnp_select,k_pg_linearize,k_pg_assemble,k_pg_solve,k_pg_trial,k_pg_correct_landmarks,k_sim3_opt,k_pg_env_assemble,k_pg_env_factor_solve,k_bucket_batch,k_cand_batch";
+    return "k_resize,k_blur,k_fast,k_select,k_describe,k_bf_binsort,k_bf_topk,k_bf_replay,k_cand,k_stereo,ba_linearize,ba_schur,ba_solve,ba_update,ba_chi2,k_pose_opt,k_pose_opt_batch,k_triangulate_two_views,k_ingest_gray,k_ingest_depth,k_pnp_pose,k_pnp_ransac,k_pnp_select,k_pg_linearize,k_pg_assemble,k_pg_solve,k_pg_trial,k_pg_correct_landmarks,k_sim3_opt,k_pg_env_assemble,k_pg_env_factor_solve,k_bucket_batch,k_cand_batch,k_loop_scale,k_loop_bin,k_loop_reproject,k_loop_walk,k_loop_edges";
 }
 
 int svgpu_profile_select(svgpu_ctx* ctx, const char* kernel_name) {

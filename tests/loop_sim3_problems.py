@@ -1,0 +1,430 @@
+"""Problems for svgpu_loop_sim3_batch (scale, mutual match and Sim3 of all loop candidates in one call), one per class of input the batch
+treats differently, and the yardstick `compose_single_calls`: the same chain per candidate -- a numpy restatement of the scale (float32 /
+float64 exactly as module/loop_detector.cc:540-573 has them), the mutual matcher given as a callable (svgpu_match_keyframes_mutually by
+default) with valid1 / valid2 derived here, the edge gather of transform_optimizer.cc:64-94 in numpy, and the Sim3 optimiser given as a
+callable (svgpu_sim3_transform_optimize).
+
+A problem is a dict of flat arrays named as the C ABI names them.  The scene: physical points in front of keyframe 1's camera; keyframe
+1's map is `drift` times larger than the candidates' (the scale a loop closes); candidate p sees part of the points from a camera a few
+centimetres away.  A candidate is described by a few knobs (`cand(...)`):
+  n2 / n_shared      its keypoints, and how many of them observe a point keyframe 1 observes too (the rest is clutter)
+  n_prior            prior matches (prior_state 1) with an index in keyframe 2: a ratio, an edge, and both keypoints blocked
+  n_erased           prior_state 2 with an index: blocks both keypoints, gives neither a ratio nor an edge
+  n_unindexed        prior_state 1 with prior_idx2 -1: a ratio, no edge, blocks nothing; a mutual match may overwrite it
+  n_parallax         prior matches whose landmark lies 3 degrees off: no ratio, still an edge
+  unrelated          the candidate's keypoint descriptors are random: no new match
+"""
+import numpy as np
+
+CAM_PERSPECTIVE, CAM_FISHEYE, CAM_EQUIRECTANGULAR = 0, 1, 2
+WIDTH, HEIGHT = 752, 480
+FX = FY = 458.654
+CX, CY = 367.215, 248.375
+NUM_LEVELS = 8
+NO_SCALE, FEW_INLIERS = 1, 2
+COS_THR = np.float32(0.99996192306)  # loop_detector.cc:559
+
+
+# the keyword arguments of stella_vslam_amd.loop_detector.validate_sim3_batch a problem carries
+KEYS = ("pose_1w", "desc1", "xy1", "octave1", "pos_w1", "has_lm1", "min_valid1", "max_valid1", "lm_desc1", "scale_factors", "inv_level_sigma_sq",
+        "log_scale_factor", "pose_2w", "kf2_off", "desc2", "xy2", "octave2", "pos_w2", "has_lm2", "min_valid2", "max_valid2", "lm_desc2", "pose_1w_in_cand",
+        "rot_12", "trans_12", "sim3_12", "prior_state", "prior_idx2", "prior_pos_w", "active", "scale_12_in", "margin", "chi_sq", "fix_scale", "num_iter",
+        "min_num_inliers", "grid_cols", "grid_rows")
+
+
+def oracle_camera(c):
+    """a camera dict as the oracle's Camera: laid out as svgpu_camera, the image bounds filled as the reference's constructors do"""
+    from oracle import oracle as O
+    return O.make_camera(c["model"], c["cols"], c["rows"], c["fx"], c["fy"], c["cx"], c["cy"], c["dist"], c["focal_x_baseline"])
+
+
+def orb_tables(scale_factor=1.2, num_levels=NUM_LEVELS):
+    """feature/orb_params.cc:41-71: the fp32 recurrences"""
+    sf = np.ones(num_levels, np.float32)
+    sig = np.ones(num_levels, np.float32)
+    for l in range(1, num_levels):
+        sf[l] = np.float32(sf[l - 1] * np.float32(scale_factor))
+        sig[l] = np.float32(sf[l] * sf[l])
+    return dict(scale_factors=sf, inv_level_sigma_sq=(np.float32(1.0) / sig).astype(np.float32),
+                log_scale_factor=float(np.float32(np.log(np.float32(scale_factor)))), num_levels=num_levels)
+
+
+def _rodrigues(w):
+    th = np.linalg.norm(w)
+    if th < 1e-12:
+        return np.eye(3)
+    k = w / th
+    K = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    return np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * (K @ K)
+
+
+def _quat(R):
+    """unit quaternion (x, y, z, w) of a rotation matrix"""
+    w = np.sqrt(max(0.0, 1.0 + R[0, 0] + R[1, 1] + R[2, 2])) / 2.0
+    q = np.array([(R[2, 1] - R[1, 2]) / (4 * w), (R[0, 2] - R[2, 0]) / (4 * w), (R[1, 0] - R[0, 1]) / (4 * w), w])
+    return q / np.linalg.norm(q)
+
+
+def _project(model, pc):
+    if model == CAM_EQUIRECTANGULAR:
+        b = pc / np.linalg.norm(pc, axis=1, keepdims=True)
+        return np.stack([WIDTH * (0.5 + np.arctan2(b[:, 0], b[:, 2]) / (2 * np.pi)), HEIGHT * (0.5 + np.arcsin(b[:, 1]) / np.pi)], 1)
+    return np.stack([FX * pc[:, 0] / pc[:, 2] + CX, FY * pc[:, 1] / pc[:, 2] + CY], 1)  # (undistorted keypoints: the pinhole form for fisheye too)
+
+
+def _cam(model):
+    return dict(model=model, cols=WIDTH, rows=HEIGHT, fx=FX, fy=FY, cx=CX, cy=CY, dist=(0, 0, 0, 0, 0), focal_x_baseline=0.0)
+
+
+def _flip(rng, desc, lo, hi):
+    out = desc.copy()
+    for k in range(len(out)):
+        bits = rng.choice(256, rng.integers(lo, hi), replace=False)
+        np.bitwise_xor.at(out[k], bits >> 3, (1 << (bits & 7)).astype(np.uint8))
+    return out
+
+
+def cand(n2=300, n_shared=200, n_prior=40, n_erased=0, n_unindexed=0, n_parallax=0, active=1, unrelated=False, model=None, seed=0):
+    return dict(n2=n2, n_shared=n_shared, n_prior=n_prior, n_erased=n_erased, n_unindexed=n_unindexed, n_parallax=n_parallax, active=active,
+                unrelated=unrelated, model=model, seed=seed)
+
+
+def make(name, cands, n1=320, model=CAM_PERSPECTIVE, seed=1, drift=1.05, use_scale_in=False, fix_scale=False, min_num_inliers=20, all_active_none=False,
+         clutter_div=5, p_lm=0.95):
+    """Keyframe 1 and len(cands) candidates over one set of physical points."""
+    rng = np.random.default_rng(seed)
+    T = orb_tables()
+    sf = T["scale_factors"]
+    n_obs = n1 - n1 // clutter_div  # keypoints of keyframe 1 that observe a point; the rest is clutter without a landmark
+    if model == CAM_EQUIRECTANGULAR:
+        d = rng.normal(0, 1, (n_obs, 3))
+        d[:, 1] *= 0.5
+        X1 = d / np.linalg.norm(d, axis=1, keepdims=True) * rng.uniform(4.0, 9.0, (n_obs, 1))
+    else:
+        X1 = np.stack([rng.uniform(-3.0, 3.0, n_obs), rng.uniform(-1.9, 1.9, n_obs), rng.uniform(4.5, 9.0, n_obs)], 1)
+    base_desc = rng.integers(0, 256, (n_obs, 32), dtype=np.uint8)
+    ref_oct = rng.integers(0, NUM_LEVELS - 2, n_obs)
+    R1w, t1w = _rodrigues(np.array([0.02, -0.3, 0.01])), np.array([0.4, -0.1, 0.7])
+    pose_1w = np.concatenate([R1w, t1w[:, None]], 1).reshape(12)
+
+    def keyframe(r, X, n, model_k, ids, scale, Rw, tw, unrelated=False):
+        """n keypoints, the first len(ids) observing the physical points `ids` at X (camera frame), the map `scale` times the physical size"""
+        m = len(ids)
+        oct_k = np.clip(ref_oct[ids] + r.integers(-1, 2, m), 0, NUM_LEVELS - 1)
+        xy = _project(model_k, X) + r.normal(0, 0.4, (m, 2)) * sf[oct_k][:, None]
+        n_cl = n - m
+        xy = np.concatenate([xy, np.stack([r.uniform(0, WIDTH, n_cl), r.uniform(0, HEIGHT, n_cl)], 1)]).astype(np.float32)
+        octave = np.concatenate([oct_k, r.integers(0, NUM_LEVELS, n_cl)]).astype(np.int32)
+        desc = np.concatenate([r.integers(0, 256, (m, 32), dtype=np.uint8) if unrelated else _flip(r, base_desc[ids], 0, 30), r.integers(0, 256, (n_cl, 32), dtype=np.uint8)])
+        lm_desc = np.concatenate([_flip(r, base_desc[ids], 0, 10), r.integers(0, 256, (n_cl, 32), dtype=np.uint8)])
+        pos = np.zeros((n, 3))
+        pos[:m] = (scale * X - tw) @ Rw  # R^T (x - t), row-wise
+        has = np.zeros(n, np.uint8)
+        has[:m] = r.uniform(0, 1, m) < p_lm
+        dist = np.linalg.norm(scale * X, axis=1)
+        maxv = np.ones(n, np.float32)
+        maxv[:m] = (dist * sf[ref_oct[ids]] * 0.9).astype(np.float32)
+        minv = (maxv / sf[NUM_LEVELS - 1] * 0.5).astype(np.float32)
+        perm = r.permutation(n)  # keypoint order is unrelated to point order
+        where = np.empty(n, np.int64)
+        where[perm] = np.arange(n)
+        return dict(xy=xy[perm], octave=octave[perm], desc=np.ascontiguousarray(desc[perm]), lm_desc=np.ascontiguousarray(lm_desc[perm]), pos_w=pos[perm],
+                    has_lm=has[perm], min_valid=minv[perm], max_valid=maxv[perm], kp_of=where[:m])
+
+    k1 = keyframe(rng, X1, n1, model, np.arange(n_obs), drift, R1w, t1w)
+    K = len(cands)
+    P = dict(pose_2w=np.zeros((K, 12)), pose_1w_in_cand=np.zeros((K, 12)), rot_12=np.zeros((K, 9)), trans_12=np.zeros((K, 3)), sim3_12=np.zeros((K, 8)),
+             prior_state=np.zeros((K, n1), np.uint8), prior_idx2=np.full((K, n1), -1, np.int32), prior_pos_w=np.zeros((K, n1, 3)))
+    parts = dict(desc2=[], xy2=[], octave2=[], pos_w2=[], has_lm2=[], min_valid2=[], max_valid2=[], lm_desc2=[])
+    kf2_off, cams2 = [0], []
+    for p, c in enumerate(cands):
+        r = np.random.default_rng(1000 * seed + 17 * p + c["seed"])
+        R21, t21 = _rodrigues(r.normal(0, 0.01, 3)), r.normal(0, 0.04, 3)
+        R2w, t2w = _rodrigues(r.normal(0, 0.3, 3)), r.normal(0, 1.0, 3)
+        m2 = c["model"] if c["model"] is not None else model
+        shared = r.permutation(n_obs)[:min(c["n_shared"], c["n2"], n_obs)]
+        X2_all = X1 @ R21.T + t21
+        k2 = keyframe(r, X2_all[shared], c["n2"], m2, shared, 1.0, R2w, t2w, c["unrelated"])
+        for k, src in (("desc2", "desc"), ("xy2", "xy"), ("octave2", "octave"), ("pos_w2", "pos_w"), ("has_lm2", "has_lm"), ("min_valid2", "min_valid"),
+                       ("max_valid2", "max_valid"), ("lm_desc2", "lm_desc")):
+            parts[k].append(k2[src])
+        kf2_off.append(kf2_off[-1] + c["n2"])
+        cams2.append(_cam(m2))
+        P["pose_2w"][p] = np.concatenate([R2w, t2w[:, None]], 1).reshape(12)
+        # camera 1 in the candidate's world: x1 = R12 x2 + t12 behind the candidate's pose, and what the pose optimisation left of it
+        R12, t12 = R21.T, -R21.T @ t21
+        dR = _rodrigues(r.normal(0, np.deg2rad(0.02), 3))
+        Rc, tc = dR @ R12 @ R2w, dR @ (R12 @ t2w + t12) + r.normal(0, 0.002, 3)
+        P["pose_1w_in_cand"][p] = np.concatenate([Rc, tc[:, None]], 1).reshape(12)
+        rot_12 = Rc @ R2w.T                       # loop_detector.cc:570-571
+        trans_12 = -rot_12 @ t2w + tc
+        P["rot_12"][p], P["trans_12"][p] = rot_12.reshape(9), trans_12
+        P["sim3_12"][p] = np.concatenate([_quat(rot_12), trans_12, [1.0]])
+        # the prior matches: keypoints of keyframe 1 whose point the candidate sees too, and whose slot holds a landmark
+        pw2_all = (X2_all - t2w) @ R2w  # every physical point in the candidate's world
+        order = [s for s in range(len(shared)) if k1["has_lm"][k1["kp_of"][shared[s]]]]
+        take = iter(order)
+        for kind, count in (("prior", c["n_prior"]), ("erased", c["n_erased"]), ("parallax", c["n_parallax"])):
+            for s in [s for _, s in zip(range(count), take)]:
+                i, j = k1["kp_of"][shared[s]], k2["kp_of"][s]
+                P["prior_state"][p, i] = 2 if kind == "erased" else 1
+                P["prior_idx2"][p, i] = j
+                pos = k2["pos_w"][j].copy()
+                if kind == "parallax":  # 3 degrees about camera 1's y axis, seen from camera 1
+                    pos = (_rodrigues(np.array([0.0, np.deg2rad(3.0), 0.0])) @ (Rc @ pos + tc) - tc) @ Rc
+                P["prior_pos_w"][p, i] = pos
+        rest = [g for g in range(n_obs) if k1["has_lm"][k1["kp_of"][g]] and P["prior_state"][p, k1["kp_of"][g]] == 0]
+        for g in rest[:c["n_unindexed"]]:
+            i = k1["kp_of"][g]
+            P["prior_state"][p, i], P["prior_pos_w"][p, i] = 1, pw2_all[g]
+    cat = lambda k, t, shape: np.ascontiguousarray(np.concatenate(parts[k]) if parts[k] else np.zeros(shape, t), t)
+    act = np.array([c["active"] for c in cands], np.uint8)
+    out = dict(name=name, cam1=_cam(model), cam2=cams2, pose_1w=pose_1w, n1=n1, desc1=k1["desc"], xy1=k1["xy"], octave1=k1["octave"], pos_w1=k1["pos_w"],
+               has_lm1=k1["has_lm"], min_valid1=k1["min_valid"], max_valid1=k1["max_valid"], lm_desc1=k1["lm_desc"], num_levels=NUM_LEVELS,
+               scale_factors=sf, inv_level_sigma_sq=T["inv_level_sigma_sq"], log_scale_factor=T["log_scale_factor"], grid_cols=64, grid_rows=48,
+               num_candidates=K, kf2_off=np.array(kf2_off, np.int32), desc2=cat("desc2", np.uint8, (0, 32)), xy2=cat("xy2", np.float32, (0, 2)),
+               octave2=cat("octave2", np.int32, 0), pos_w2=cat("pos_w2", np.float64, (0, 3)), has_lm2=cat("has_lm2", np.uint8, 0),
+               min_valid2=cat("min_valid2", np.float32, 0), max_valid2=cat("max_valid2", np.float32, 0), lm_desc2=cat("lm_desc2", np.uint8, (0, 32)),
+               active=None if all_active_none else act, scale_12_in=None, margin=7.5, chi_sq=10.0, fix_scale=int(fix_scale), num_iter=10,
+               min_num_inliers=min_num_inliers, knobs=list(cands), **P)
+    if use_scale_in:
+        out["scale_12_in"] = np.full(K, drift, np.float32)
+    return out
+
+
+PER_CAND = ("pose_2w", "pose_1w_in_cand", "rot_12", "trans_12", "sim3_12", "prior_state", "prior_idx2", "prior_pos_w")
+PER_KP2 = ("desc2", "xy2", "octave2", "pos_w2", "has_lm2", "min_valid2", "max_valid2", "lm_desc2")
+
+
+def rows_of(problem, keep):
+    off = problem["kf2_off"]
+    return np.concatenate([np.arange(off[p], off[p + 1]) for p in keep] + [np.zeros(0, np.int64)]).astype(np.int64)
+
+
+def sub(problem, keep):
+    """the problem with the candidates `keep` (indices, in that order) alone"""
+    keep = list(keep)
+    off, rows = problem["kf2_off"], rows_of(problem, keep)
+    q = dict(problem)
+    q["num_candidates"] = len(keep)
+    q["cam2"] = [problem["cam2"][p] for p in keep]
+    q["knobs"] = [problem["knobs"][p] for p in keep]
+    for k in PER_CAND:
+        q[k] = np.ascontiguousarray(problem[k][keep])
+    for k in ("active", "scale_12_in"):
+        q[k] = None if problem[k] is None else np.ascontiguousarray(problem[k][keep])
+    for k in PER_KP2:
+        q[k] = np.ascontiguousarray(problem[k][rows])
+    q["kf2_off"] = np.concatenate([[0], np.cumsum([off[p + 1] - off[p] for p in keep])]).astype(np.int32)
+    return q
+
+
+# ---------------------------------------------------------------------------------------------- the scale, restated
+def cos_and_ratio(pose_1w_in_cand, pose_1w, prior_pos_w, pos_w1):
+    """loop_detector.cc:553-564 for m pairs: (cos_parallax, ratio) as float32 arrays.  Eigen's 3-vector forms ((a0 b0 + a1 b1) + a2 b2),
+    both norms in double narrowed to float, the product of the norms in float, the quotient in double narrowed to float."""
+    T, Q = np.asarray(pose_1w_in_cand, np.float64).reshape(3, 4), np.asarray(pose_1w, np.float64).reshape(3, 4)
+    a, b = np.asarray(prior_pos_w, np.float64).reshape(-1, 3), np.asarray(pos_w1, np.float64).reshape(-1, 3)
+    c = [((T[r, 0] * a[:, 0] + T[r, 1] * a[:, 1]) + T[r, 2] * a[:, 2]) + T[r, 3] for r in range(3)]
+    u = [((Q[r, 0] * b[:, 0] + Q[r, 1] * b[:, 1]) + Q[r, 2] * b[:, 2]) + Q[r, 3] for r in range(3)]
+    n_cand = np.sqrt((c[0] * c[0] + c[1] * c[1]) + c[2] * c[2]).astype(np.float32)
+    n_curr = np.sqrt((u[0] * u[0] + u[1] * u[1]) + u[2] * u[2]).astype(np.float32)
+    dot = (c[0] * u[0] + c[1] * u[1]) + c[2] * u[2]
+    with np.errstate(all="ignore"):
+        cos = (dot / (n_cand * n_curr).astype(np.float64)).astype(np.float32)
+        ratio = (n_curr / n_cand).astype(np.float32)
+    return cos, ratio
+
+
+def scale_restatement(problem, p):
+    """(scale_12 or None, the kept ratios in idx1 order, their idx1) of candidate p"""
+    idx = np.flatnonzero((problem["has_lm1"] != 0) & (problem["prior_state"][p] == 1))
+    cos, ratio = cos_and_ratio(problem["pose_1w_in_cand"][p], problem["pose_1w"], problem["prior_pos_w"][p][idx], problem["pos_w1"][idx])
+    keep = COS_THR < cos  # strict; a NaN is not kept
+    kept = ratio[keep]
+    if len(kept) == 0:
+        return None, kept, idx[keep]
+    return np.sort(kept)[(len(kept) - 1) // 2], kept, idx[keep]
+
+
+# ---------------------------------------------------------------------------------------------- the chain of single calls
+def device_backend(ctx, make_camera):
+    """(mutual, optimise) on the EXISTING single entry points svgpu_match_keyframes_mutually and svgpu_sim3_transform_optimize"""
+    import types
+
+    from stella_vslam_amd import match, optimize
+    wrap = lambda c: types.SimpleNamespace(c_=make_camera(c))
+
+    def mutual(problem, p, s_12, kf1, kf2):
+        T1, T2 = problem["pose_1w"].reshape(3, 4), problem["pose_2w"][p].reshape(3, 4)
+        c = np.ascontiguousarray
+        return match.projection_flat(0.9, False, ctx).match_keyframes_mutually(
+            wrap(problem["cam1"]), wrap(problem["cam2"][p]), c(T1[:, :3]), c(T1[:, 3]), c(T2[:, :3]), c(T2[:, 3]), float(s_12), problem["rot_12"][p],
+            problem["trans_12"][p], kf1, kf2, problem["scale_factors"], problem["log_scale_factor"], float(problem["margin"]), problem["grid_cols"],
+            problem["grid_rows"])
+
+    def optimise(problem, p, obs1, obs2, w1, w2, pos1, pos2, sim3):
+        return optimize.sim3_transform_optimize(ctx, (problem["cam1"], problem["pose_1w"]), (problem["cam2"][p], problem["pose_2w"][p]), obs1, obs2, w1, w2,
+                                                pos1, pos2, sim3, chi_sq=float(problem["chi_sq"]), fix_scale=bool(problem["fix_scale"]),
+                                                num_iter=int(problem["num_iter"]))
+    return mutual, optimise
+
+
+STAT_KEYS = ("lm_iterations", "lm_trials", "early_return", "num_survivors", "first_chi2", "last_chi2", "lambda_final")
+STAT_SHAPES = dict(lm_iterations=(2,), lm_trials=(2,), early_return=(), num_survivors=(), first_chi2=(2,), last_chi2=(2,), lambda_final=())
+OUTPUTS = ("status", "scale_12", "matched_2_in_1", "matched_1_in_2", "mutual_2_in_1", "num_mutual", "edge_idx1", "edge_idx2", "num_edges", "edge_status",
+           "sim3_12_out", "num_inliers") + STAT_KEYS
+PER_CAND_OUT = tuple(k for k in OUTPUTS if k != "matched_1_in_2")
+
+
+def compose_single_calls(problem, backend):
+    """scale -> svgpu_match_keyframes_mutually -> gather -> svgpu_sim3_transform_optimize per candidate, as the host loop does it"""
+    mutual, optimise = backend
+    K, n1 = problem["num_candidates"], problem["n1"]
+    off = problem["kf2_off"]
+    N2 = int(off[-1])
+    out = dict(status=np.zeros(K, np.int32), scale_12=np.zeros(K, np.float32), matched_2_in_1=np.full((K, n1), -1, np.int32),
+               matched_1_in_2=np.full(N2, -1, np.int32), mutual_2_in_1=np.full((K, n1), -1, np.int32), num_mutual=np.zeros(K, np.int32),
+               edge_idx1=np.full((K, n1), -1, np.int32), edge_idx2=np.full((K, n1), -1, np.int32), num_edges=np.zeros(K, np.int32),
+               edge_status=np.zeros((K, n1), np.uint8), sim3_12_out=problem["sim3_12"].copy(), num_inliers=np.zeros(K, np.int32))
+    for k in STAT_KEYS:
+        out[k] = np.zeros((K,) + STAT_SHAPES[k], np.float64 if "chi2" in k or k == "lambda_final" else np.int32)
+    kf1 = dict(pos_w=problem["pos_w1"], min_valid_dist=problem["min_valid1"], max_valid_dist=problem["max_valid1"], lm_desc=problem["lm_desc1"],
+               desc=problem["desc1"], xy=problem["xy1"], octave=problem["octave1"])
+    w_of = problem["inv_level_sigma_sq"]
+    for p in range(K):
+        if problem["active"] is not None and not problem["active"][p]:
+            out["status"][p] = -1
+            continue
+        if problem["scale_12_in"] is not None:
+            s_12 = np.float32(problem["scale_12_in"][p])
+        else:
+            s_12 = scale_restatement(problem, p)[0]
+            if s_12 is None:
+                out["status"][p] = NO_SCALE
+                continue
+        out["scale_12"][p] = s_12
+        lo, hi = int(off[p]), int(off[p + 1])
+        state, pidx = problem["prior_state"][p], problem["prior_idx2"][p]
+        blocked1 = (state != 0) & (pidx >= 0)  # projection.cc:440-450
+        blocked2 = np.zeros(hi - lo, bool)
+        blocked2[pidx[blocked1]] = True
+        sl = lambda k: problem[k][lo:hi]
+        kf2 = dict(pos_w=sl("pos_w2"), valid=((sl("has_lm2") != 0) & ~blocked2).astype(np.uint8), min_valid_dist=sl("min_valid2"), max_valid_dist=sl("max_valid2"),
+                   lm_desc=sl("lm_desc2"), desc=sl("desc2"), xy=sl("xy2"), octave=sl("octave2"))
+        m21, m12, mut, num = mutual(problem, p, s_12, dict(kf1, valid=((problem["has_lm1"] != 0) & ~blocked1).astype(np.uint8)), kf2)
+        out["matched_2_in_1"][p], out["matched_1_in_2"][lo:hi], out["mutual_2_in_1"][p], out["num_mutual"][p] = m21, m12, mut, num
+        # transform_optimizer.cc:64-94 after projection.cc:623, idx1 ascending
+        new = mut >= 0
+        prior = ~new & (state == 1) & (pidx >= 0)
+        e1 = np.flatnonzero((problem["has_lm1"] != 0) & (new | prior))
+        e2 = np.where(new[e1], mut[e1], pidx[e1])
+        pos2 = np.where(new[e1][:, None], sl("pos_w2")[e2].reshape(-1, 3), problem["prior_pos_w"][p][e1])
+        sim3 = problem["sim3_12"][p].copy()
+        sim3[7] = float(s_12)
+        r = optimise(problem, p, problem["xy1"][e1].astype(np.float64), sl("xy2")[e2].astype(np.float64).reshape(-1, 2), w_of[problem["octave1"][e1]],
+                     w_of[sl("octave2")[e2]], problem["pos_w1"][e1], pos2, sim3)
+        n = len(e1)
+        out["num_edges"][p] = n
+        out["edge_idx1"][p, :n], out["edge_idx2"][p, :n], out["edge_status"][p, :n] = e1, e2, r["status"][:n]
+        out["sim3_12_out"][p], out["num_inliers"][p] = r["sim3"], r["num_inliers"]
+        for k in STAT_KEYS:
+            out[k][p] = r[k]
+        out["status"][p] = FEW_INLIERS if r["num_inliers"] < problem["min_num_inliers"] else 0
+    return out
+
+
+def same(a, b, keys=OUTPUTS):
+    """every output as raw bit patterns; returns the names that differ"""
+    bits = lambda k, v: np.ascontiguousarray(v, np.float64 if "chi2" in k or k in ("lambda_final", "sim3_12_out") else None).tobytes()
+    return [k for k in keys if np.shape(a[k]) != np.shape(b[k]) or bits(k, a[k]) != bits(k, np.asarray(b[k], np.asarray(a[k]).dtype))]
+
+
+# ---------------------------------------------------------------------------------------------- the classes
+def GOOD(seed=0, **kw):
+    return cand(seed=seed, **kw)
+
+
+def classes():
+    """name -> problem.  EXPECT[name] lists, per candidate, the status the class is named for."""
+    P = {}
+    P["all_accepted"] = make("all_accepted", [GOOD(1), GOOD(2, n2=380), GOOD(3, n2=220, n_shared=150)], seed=1)
+    P["each_status"] = make("each_status", [GOOD(1), cand(n_prior=0, seed=2), cand(n2=150, n_shared=14, n_prior=6, seed=3), GOOD(4, active=0)], seed=2)
+    P["unequal"] = make("unequal", [cand(n2=0, n_shared=0, n_prior=0, n_unindexed=30, seed=1), cand(n2=1, n_shared=1, n_prior=0, n_unindexed=30, seed=2),
+                                    cand(n2=150, n_shared=120, n_prior=30, seed=3), cand(n2=400, n_shared=250, n_prior=50, seed=4)], seed=3)
+    P["early_return"] = make("early_return", [cand(n2=200, n_shared=160, n_prior=6, unrelated=True, seed=1), GOOD(2)], seed=4)
+    P["no_new_matches"] = make("no_new_matches", [cand(n2=250, n_shared=200, n_prior=200, seed=1), cand(n2=160, n_shared=150, n_prior=150, seed=2)], seed=5)
+    P["no_priors"] = make("no_priors", [cand(n_prior=0, seed=1), cand(n_prior=0, n2=200, n_shared=180, seed=2)], seed=6, use_scale_in=True)
+    P["prior_erased"] = make("prior_erased", [cand(n_prior=30, n_erased=40, seed=1), cand(n_prior=0, n_erased=60, seed=2)], seed=7)
+    P["prior_unindexed"] = make("prior_unindexed", [cand(n_prior=0, n_unindexed=60, seed=1), cand(n_prior=20, n_unindexed=40, n_parallax=10, seed=2)], seed=8)
+    P["stereo_fix_scale"] = make("stereo_fix_scale", [GOOD(1), GOOD(2, n_prior=0)], seed=9, drift=1.0, use_scale_in=True, fix_scale=True)
+    P["fisheye"] = make("fisheye", [GOOD(1), GOOD(2, n2=180, n_shared=150)], model=CAM_FISHEYE, seed=10)
+    P["equirect"] = make("equirect", [GOOD(1), GOOD(2, n2=180, n_shared=150)], model=CAM_EQUIRECTANGULAR, seed=11)
+    P["mixed_models"] = make("mixed_models", [GOOD(1, model=CAM_EQUIRECTANGULAR), GOOD(2, model=CAM_FISHEYE), GOOD(3)], seed=12)
+    P["twins"] = sub(make("twins", [GOOD(1)], seed=13), [0, 0])
+    P["many_tiny"] = make("many_tiny", [cand(n2=10 + s % 21, n_shared=10 + s % 21, n_prior=4, seed=s) for s in range(40)], n1=150, seed=14, min_num_inliers=5)
+    for k, v in P.items():
+        v["name"] = k
+    return P
+
+
+def planted_kept(problem, p):
+    """the kept ratios the knobs plant for candidate p: every alive prior on a live slot, but the n_parallax ones"""
+    return int(((problem["prior_state"][p] == 1) & (problem["has_lm1"] != 0)).sum()) - problem["knobs"][p]["n_parallax"]
+
+
+EXPECT = dict(all_accepted=[0, 0, 0], each_status=[0, NO_SCALE, FEW_INLIERS, -1], unequal=[FEW_INLIERS, FEW_INLIERS, 0, 0], early_return=[FEW_INLIERS, 0],
+              no_new_matches=[0, 0], no_priors=[0, 0], prior_erased=[0, NO_SCALE], prior_unindexed=[0, 0], stereo_fix_scale=[0, 0], fisheye=[0, 0],
+              equirect=[0, 0], twins=[0, 0])
+
+
+# ---------------------------------------------------------------------------------------------- scale classes
+def _scale_base(n_kept, n1=150, seed=20):
+    """one candidate whose n_kept unindexed priors are the only pairs; a keyframe 2 of 20 keypoints"""
+    return make(f"scale_{n_kept}", [cand(n2=20, n_shared=20, n_prior=0, n_unindexed=n_kept, seed=1)], n1=n1, seed=seed, min_num_inliers=1, clutter_div=20,
+                p_lm=1.0)
+
+
+def boundary_positions(problem, i):
+    """For the pair at idx1 = i of candidate 0: two prior positions, found by search in the restatement, whose float cos_parallax is exactly
+    the threshold's float value (rejected: the test is strict) and the next float above it (kept).  The landmark is swung about an
+    axis at right angles to its ray by angles around 0.5 degrees, 1e-8 rad apart; one float step of the cosine is 7e-6 rad there."""
+    T = problem["pose_1w_in_cand"][0].reshape(3, 4)
+    Rc, tc = T[:, :3], T[:, 3]
+    Q = problem["pose_1w"].reshape(3, 4)
+    u = Q[:, :3] @ problem["pos_w1"][i] + Q[:, 3]
+    u = u / 1.05  # (about the candidate's scale; any length serves)
+    th = np.deg2rad(0.5) + np.arange(-4000, 4001) * 1e-8
+    k = np.cross(u, [0.0, 1.0, 0.0])
+    k /= np.linalg.norm(k)  # an axis at right angles to the ray: the swing is the parallax angle itself
+    swung = np.cos(th)[:, None] * u[None] + np.sin(th)[:, None] * np.cross(k, u)[None]
+    pos = (swung - tc) @ Rc
+    cos, _ = cos_and_ratio(problem["pose_1w_in_cand"][0], problem["pose_1w"], pos, np.repeat(problem["pos_w1"][i][None], len(th), 0))
+    at, above = np.flatnonzero(cos == COS_THR), np.flatnonzero(cos == np.nextafter(COS_THR, np.float32(2.0)))
+    assert len(at) and len(above), (len(at), len(above))
+    return pos[at[0]], pos[above[0]]
+
+
+def scale_classes():
+    S = {}
+    for n in (1, 2, 3):
+        S[f"kept_{n}"] = _scale_base(n)
+    S["kept_1025"] = _scale_base(1025, n1=1100, seed=21)  # more kept ratios than a workgroup has threads
+    t = _scale_base(9, seed=22)  # ties: the pairs 1.. are copies of pair 0 in both maps
+    idx = np.flatnonzero(t["prior_state"][0] == 1)
+    t["pos_w1"] = t["pos_w1"].copy()
+    t["pos_w1"][idx[1:6]] = t["pos_w1"][idx[0]]
+    t["prior_pos_w"][0, idx[1:6]] = t["prior_pos_w"][0, idx[0]]
+    t["name"] = "ties"
+    S["ties"] = t
+    b = _scale_base(5, seed=23)  # boundary: pair 0 exactly at the threshold, pair 1 one float above
+    idx = np.flatnonzero(b["prior_state"][0] == 1)
+    b["prior_pos_w"][0, idx[0]] = boundary_positions(b, idx[0])[0]
+    b["prior_pos_w"][0, idx[1]] = boundary_positions(b, idx[1])[1]
+    b["name"] = "boundary"
+    b["boundary_idx"] = (int(idx[0]), int(idx[1]))
+    S["boundary"] = b
+    return S
+
+
+SCALE_KEPT = dict(kept_1=1, kept_2=2, kept_3=3, kept_1025=1025, ties=9, boundary=4)

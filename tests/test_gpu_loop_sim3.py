@@ -1,0 +1,233 @@
+"""svgpu_loop_sim3_batch: every output of the batch equals, bit for bit, the chain composed of the numpy restatement of the scale and the
+existing single calls svgpu_match_keyframes_mutually and svgpu_sim3_transform_optimize, one candidate at a time (compose_single_calls of
+tests/loop_sim3_problems.py).  The yardstick of a class is computed once, shared by the tests and never changed."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from tests import loop_sim3_problems as LP
+
+pytestmark = pytest.mark.gpu
+CLASSES = ("all_accepted", "each_status", "unequal", "early_return", "no_new_matches", "no_priors", "prior_erased", "prior_unindexed", "stereo_fix_scale",
+           "fisheye", "equirect", "mixed_models", "twins", "many_tiny")
+SCALE_CLASSES = ("kept_1", "kept_2", "kept_3", "kept_1025", "ties", "boundary")
+KEYS = LP.KEYS
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    from stella_vslam_amd.feature import Context
+    return Context()
+
+
+@pytest.fixture(scope="module")
+def problems():
+    P = LP.classes()
+    P.update(LP.scale_classes())
+    return P
+
+
+_cam = LP.oracle_camera
+
+
+def _batch(ctx, problem, **over):
+    from stella_vslam_amd import loop_detector
+    kw = {k: problem[k] for k in KEYS}
+    kw.update(over)
+    return loop_detector.validate_sim3_batch(ctx, _cam(problem["cam1"]), [_cam(c) for c in problem["cam2"]], want_stats=True, **kw)
+
+
+_YARD = {}
+
+
+def _yardstick(ctx, problem, **over):
+    key = (problem["name"], tuple(sorted(over.items())))
+    if key not in _YARD:
+        _YARD[key] = LP.compose_single_calls(dict(problem, **over), LP.device_backend(ctx, _cam))
+    return _YARD[key]
+
+
+@pytest.mark.parametrize("name", CLASSES)
+def test_batch_equals_the_composed_single_calls(ctx, problems, name):
+    p = problems[name]
+    want, got = _yardstick(ctx, p), _batch(ctx, p)
+    print(name, "status", got["status"][:8], "scale", got["scale_12"][:4], "mutual", got["num_mutual"][:8], "edges", got["num_edges"][:8], "inliers", got["num_inliers"][:8])
+    assert LP.same(got, want) == [], (name, got["status"], want["status"], got["num_mutual"], want["num_mutual"], got["num_inliers"], want["num_inliers"])
+    if name in LP.EXPECT:
+        assert got["status"].tolist() == LP.EXPECT[name]
+    if name == "early_return":
+        assert got["early_return"][0] == 1 and got["num_survivors"][0] < 10
+        assert got["sim3_12_out"][0, 7] == float(got["scale_12"][0]) and np.array_equal(got["sim3_12_out"][0, :7], p["sim3_12"][0, :7])
+    if name == "no_new_matches":
+        assert (got["num_mutual"] == 0).all() and (got["num_edges"] > 100).all()
+    if name == "prior_erased":  # the erased rows block both keypoints and give no edge
+        e = np.flatnonzero(p["prior_state"][0] == 2)
+        assert (got["matched_2_in_1"][0, e] == -1).all() and not np.isin(e, got["edge_idx1"][0, :got["num_edges"][0]]).any()
+        assert (got["matched_1_in_2"][p["prior_idx2"][0, e]] == -1).all()
+    if name == "prior_unindexed":  # unindexed rows are offered to the matcher, and at least one is overwritten by a mutual match
+        u = np.flatnonzero((p["prior_state"][0] == 1) & (p["prior_idx2"][0] < 0))
+        assert (got["mutual_2_in_1"][0, u] >= 0).any()
+    if name == "mixed_models":
+        assert (got["num_mutual"] >= 0).all() and len({c["model"] for c in p["cam2"]}) == 3
+    if name == "twins":
+        for k in LP.PER_CAND_OUT:
+            assert np.ascontiguousarray(got[k][0]).tobytes() == np.ascontiguousarray(got[k][1]).tobytes(), k
+
+
+@pytest.mark.parametrize("name", CLASSES + SCALE_CLASSES)
+def test_scale_equals_the_numpy_restatement(ctx, problems, name):
+    p = problems[name]
+    if p["scale_12_in"] is not None:
+        got = _batch(ctx, p)
+        assert got["scale_12"].tobytes() == np.asarray(p["scale_12_in"], np.float32).tobytes()
+        return
+    got = _batch(ctx, p)
+    for c in range(p["num_candidates"]):
+        s = LP.scale_restatement(p, c)[0]
+        if p["active"] is not None and not p["active"][c]:
+            assert got["status"][c] == -1 and got["scale_12"][c] == 0
+        elif s is None:
+            assert got["status"][c] == LP.NO_SCALE and got["scale_12"][c] == 0
+        else:
+            print(name, c, float(s), float(got["scale_12"][c]))
+            assert np.float32(s).tobytes() == got["scale_12"][c].tobytes(), (name, c, s, got["scale_12"][c])
+    if name in LP.SCALE_KEPT:
+        assert len(LP.scale_restatement(p, 0)[1]) == LP.SCALE_KEPT[name]
+
+
+def test_boundary_pairs_decide_the_scale(ctx, problems):
+    """the pair exactly at the threshold is rejected and the pair one float above is kept: with either of them alone as the only pair, the
+    first gives NO_SCALE and the second its own ratio"""
+    p = problems["boundary"]
+    at, above = p["boundary_idx"]
+    for i, kept in ((at, False), (above, True)):
+        st = np.zeros_like(p["prior_state"])
+        st[0, i] = 1
+        got = _batch(ctx, p, prior_state=st)
+        cos, ratio = LP.cos_and_ratio(p["pose_1w_in_cand"][0], p["pose_1w"], p["prior_pos_w"][0, i], p["pos_w1"][i])
+        assert (cos[0] == LP.COS_THR) != kept and (not kept or cos[0] == np.nextafter(LP.COS_THR, np.float32(2.0)))
+        if kept:
+            assert got["status"][0] != LP.NO_SCALE and got["scale_12"][0].tobytes() == ratio[0].tobytes()
+        else:
+            assert got["status"][0] == LP.NO_SCALE
+
+
+@pytest.mark.parametrize("name", ("each_status", "unequal", "mixed_models"))
+def test_order_and_company_do_not_matter(ctx, problems, name):
+    p = problems[name]
+    K = p["num_candidates"]
+    full = _batch(ctx, p)
+    assert LP.same(_batch(ctx, p), full) == []  # the same call twice
+    rev = list(range(K))[::-1]
+    got = _batch(ctx, LP.sub(p, rev))
+    for k in LP.PER_CAND_OUT:
+        assert np.ascontiguousarray(got[k]).tobytes() == np.ascontiguousarray(full[k][rev]).tobytes(), (name, k)
+    assert np.array_equal(got["matched_1_in_2"], full["matched_1_in_2"][LP.rows_of(p, rev)])
+    for c in range(K):  # each candidate alone equals its row of the batch
+        one = _batch(ctx, LP.sub(p, [c]))
+        for k in LP.PER_CAND_OUT:
+            assert np.ascontiguousarray(one[k]).tobytes() == np.ascontiguousarray(full[k][c:c + 1]).tobytes(), (name, c, k)
+        assert np.array_equal(one["matched_1_in_2"], full["matched_1_in_2"][LP.rows_of(p, [c])])
+
+
+def test_launches_copies_and_synchronisations_do_not_depend_on_k(ctx, problems):
+    p = problems["all_accepted"]
+    s2, s6 = _batch(ctx, LP.sub(p, [0, 1]))["stats"], _batch(ctx, LP.sub(p, [0, 1, 2, 0, 1, 2]))["stats"]
+    assert s2 == s6, (s2, s6)
+    assert s2[2] == 2  # the candidate-list total, and the end
+
+
+def test_lists_that_outgrow_their_capacity_restart_the_call(ctx, problems):
+    """a window of 300 px x scale lists a good part of a keyframe per row, more than the 16 entries per row the lists are first sized for: the
+    call starts again with lists of the exact size (a third synchronisation) and still equals the yardstick"""
+    p = dict(problems["all_accepted"], name="wide_window", margin=300.0)
+    want, got = _yardstick(ctx, p), _batch(ctx, p)
+    assert LP.same(got, want) == []
+    assert got["stats"][2] == 3, got["stats"]
+
+
+def test_decision_boundary_planted_from_the_measured_inliers(ctx, problems):
+    p = LP.sub(problems["all_accepted"], [1])
+    p["name"] = "all_accepted_boundary"
+    n = int(_yardstick(ctx, p)["num_inliers"][0])
+    assert n >= 20
+    for m, st in ((n, 0), (n + 1, LP.FEW_INLIERS)):
+        got = _batch(ctx, p, min_num_inliers=m)
+        assert LP.same(got, _yardstick(ctx, p, min_num_inliers=m)) == []
+        assert got["status"][0] == st and got["num_inliers"][0] == n
+
+
+SENT = 77
+
+
+def _raw(ctx, p, small_outputs=False, **over):
+    """the C call itself with every output pre-filled with a sentinel; returns (status code, outputs)"""
+    from stella_vslam_amd._lib import lib, ptr
+    a = dict(p)
+    a.update(over)
+    K, n1 = a["num_candidates"], a["n1"]
+    Ko, n1o = (p["num_candidates"], p["n1"]) if small_outputs else (K, n1)  # (a call refused on its sizes writes nothing)
+    N2 = int(p["kf2_off"][-1])
+    E = Ko * n1o
+    outs = [np.full(Ko, SENT, np.int32), np.full(Ko, 7.5, np.float32), np.full(E, SENT, np.int32), np.full(N2, SENT, np.int32), np.full(E, SENT, np.int32),
+            np.full(Ko, SENT, np.int32), np.full(E, SENT, np.int32), np.full(E, SENT, np.int32), np.full(Ko, SENT, np.int32), np.full(E, SENT, np.uint8),
+            np.full((Ko, 8), 7.5), np.full(Ko, SENT, np.int32), np.full(Ko * 64, SENT, np.uint8), np.full(3, SENT, np.int32)]
+    c = lambda k, t: None if a[k] is None else np.ascontiguousarray(a[k], t)
+    cam1 = None if a["cam1"] is None else _cam(a["cam1"])
+    cams = None if a["cam2"] is None else (type(_cam(p["cam1"])) * max(len(a["cam2"]), 1))(*[_cam(x) for x in a["cam2"]])
+    if a.get("bad_model1"):
+        cam1.model = 9
+    if a.get("bad_model2") is not None:
+        cams[a["bad_model2"]].model = 9
+    f32, f64, u8, i32 = np.float32, np.float64, np.uint8, np.int32
+    rc = lib().svgpu_loop_sim3_batch(
+        ctx.handle, None if cam1 is None else C.byref(cam1), ptr(c("pose_1w", f64)), n1, ptr(c("desc1", u8)), ptr(c("xy1", f32)), ptr(c("octave1", i32)),
+        ptr(c("pos_w1", f64)), ptr(c("has_lm1", u8)), ptr(c("min_valid1", f32)), ptr(c("max_valid1", f32)), ptr(c("lm_desc1", u8)), a["num_levels"],
+        ptr(c("scale_factors", f32)), ptr(c("inv_level_sigma_sq", f32)), a["log_scale_factor"], a["grid_cols"], a["grid_rows"], K,
+        None if cams is None else C.cast(cams, C.c_void_p), ptr(c("pose_2w", f64)), ptr(c("kf2_off", i32)), ptr(c("desc2", u8)), ptr(c("xy2", f32)),
+        ptr(c("octave2", i32)), ptr(c("pos_w2", f64)), ptr(c("has_lm2", u8)), ptr(c("min_valid2", f32)), ptr(c("max_valid2", f32)), ptr(c("lm_desc2", u8)),
+        ptr(c("pose_1w_in_cand", f64)), ptr(c("rot_12", f64)), ptr(c("trans_12", f64)), ptr(c("sim3_12", f64)), ptr(c("active", u8)), ptr(c("prior_state", u8)),
+        ptr(c("prior_idx2", i32)), ptr(c("prior_pos_w", f64)), ptr(c("scale_12_in", f32)), a["margin"], a["chi_sq"], a["fix_scale"], a["num_iter"],
+        a["min_num_inliers"], *[ptr(o) for o in outs])
+    return rc, outs
+
+
+def test_invalid_arguments_launch_nothing_and_touch_nothing(ctx, problems):
+    p = problems["all_accepted"]
+    off = p["kf2_off"]
+    K, n1 = p["num_candidates"], p["n1"]
+
+    def changed(key, index, value):
+        v = np.array(p[key], copy=True)
+        v[index] = value
+        return {key: v}
+    cases = dict(
+        null_ctx_pose=dict(pose_1w=None), null_cam1=dict(cam1=None), null_cam2=dict(cam2=None), null_desc1=dict(desc1=None), null_has_lm1=dict(has_lm1=None),
+        null_offsets=dict(kf2_off=None), null_xy2=dict(xy2=None), null_pose_in_cand=dict(pose_1w_in_cand=None), null_rot=dict(rot_12=None),
+        null_trans=dict(trans_12=None), null_sim3=dict(sim3_12=None), null_prior_state=dict(prior_state=None), null_prior_idx=dict(prior_idx2=None),
+        null_prior_pos=dict(prior_pos_w=None), null_scale_factors=dict(scale_factors=None), null_sigma=dict(inv_level_sigma_sq=None),
+        first_offset=dict(kf2_off=off + np.int32(1) * (np.arange(len(off)) == 0)), non_monotone=dict(kf2_off=np.array([0, off[2], off[1], off[3]], np.int32)),
+        octave1_high=changed("octave1", 5, p["num_levels"]), octave1_negative=changed("octave1", 0, -1), octave2_high=changed("octave2", 7, p["num_levels"]),
+        octave2_negative=changed("octave2", 3, -1), no_level=dict(num_levels=0), seventeen_levels=dict(num_levels=17),
+        too_many_keypoints1=dict(n1=1 << 22, small_outputs=True), too_many_keypoints2=dict(num_candidates=1, kf2_off=np.array([0, 1 << 22], np.int32)),
+        prior_beyond_n2=changed("prior_idx2", (1, 4), int(off[2] - off[1])), camera1_model=dict(bad_model1=True), camera2_model=dict(bad_model2=1),
+        quaternion=changed("sim3_12", (2, 3), 0.5), chi_sq_zero=dict(chi_sq=0.0), chi_sq_negative=dict(chi_sq=-1.0), sigma_zero=changed("inv_level_sigma_sq", 2, 0.0),
+        scale_in_zero=dict(scale_12_in=np.array([1.0, 0.0, 1.0], np.float32)), scale_in_negative=dict(scale_12_in=np.array([1.0, 1.0, -2.0], np.float32)),
+        num_iter_negative=dict(num_iter=-1),
+        # totals that do not fit int32 (4000 candidates x 2^20 keypoint slots): refused on the sizes and the offsets alone
+        totals_beyond_int32=dict(num_candidates=4000, n1=1 << 20, kf2_off=np.zeros(4001, np.int32), small_outputs=True))
+    for name, over in cases.items():
+        rc, outs = _raw(ctx, p, **over)
+        assert rc == 1, (name, rc)  # SVGPU_ERR_INVALID
+        for o in outs:
+            assert (o == (7.5 if o.dtype.kind == "f" else SENT)).all(), name
+    rc, outs = _raw(ctx, p)  # and the same arrays unchanged are a valid call
+    assert rc == 0 and (outs[0] == 0).all()
+
+
+def test_no_candidate_succeeds_with_null_pointers(ctx):
+    from stella_vslam_amd._lib import lib
+    L = lib()
+    assert L.svgpu_loop_sim3_batch(ctx.handle, None, None, 0, *([None] * 8), 0, None, None, 0.0, 0, 0, 0, *([None] * 20), 0.0, 0.0, 0, 0, 0, *([None] * 14)) == 0
+    assert L.svgpu_loop_sim3_batch(ctx.handle, None, None, -5, *([None] * 8), 99, None, None, -1.0, -1, -1, 0, *([None] * 20), -1.0, -1.0, 0, -3, 0, *([None] * 14)) == 0
