@@ -194,7 +194,7 @@ __global__ __launch_bounds__(PYR_THREADS) void k_pyramid(const OrbLevel* __restr
 //     bilinear kernel is separable -- H(s) = S[s][sx] * a0 + S[s][sx + 1] * a1 per source row s, then the vertical blend of H(sy) and
 //     H(sy + 1) -- and consecutive output rows share a source row five times out of six at the 1 / 1.2 step, so the walk keeps H(sy + 1)
 //     in registers and forms ~1.3 instead of 2 horizontal rows per output row; the column record (window positions, byte selectors,
-//     coefficient pairs) is loop-invariant and lives in registers, read once per level straight from global memory.
+//     coefficient pairs) is loop-invariant and lives in registers, read from global memory one level ahead (PyrLevelLds below).
 //   Horizontal: two 8-byte windows per source row (ds_read2_b32), one v_perm_b32 per pixel lifts (S[sx], S[sx + 1]) into two 16-bit
 //   halves, one v_dot2_u32_u16 forms H.  Vertical: ((b0 * (H0 >> 4)) >> 16) + ((b1 * (H1 >> 4)) >> 16) as two v_mul_hi_u32_u24 of
 //   (b << 12) and (H & ~15): (b * 2^12) * ((H >> 4) * 2^4) >> 32 == (b * (H >> 4)) >> 16, both factors below 2^24.
@@ -206,14 +206,71 @@ __device__ __forceinline__ uint32_t mul_hi_u24(uint32_t a, uint32_t b) {  // (a 
     return d;
 }
 
+// What the level loop reads of one level, worked out once per workgroup (lane l of wave 0 for level l) and kept in static LDS: behind a
+// level barrier nothing is fetched from global memory -- the next level's entry and the thread's column record of that level are
+// read one level ahead, while the current level's rows are walked.
+struct PyrLevelLds {
+    int groups;        // column groups of 4 pixels = LDS row pitch in dwords
+    int rc, nrows;     // rows per chunk; rows [lo, lo + nrows) the band computes
+    int lo;
+    int dy0, own_n;    // lo - own_lo; rows the band owns (stores to global memory): own_lo <= row < own_lo + own_n
+    int pitch;         // row pitch of the stored level
+    int xg_off;
+    float inv_groups;  // 1 / groups
+    int yrow0;         // index of row lo in the row-record table
+    int pyr_lo, pyr_hi;  // OrbLevel::pyr_off
+};
+__device__ __forceinline__ int pyr_sgpr(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ PyrLevelLds pyr_level_scalars(const PyrLevelLds* p) {  // a workgroup-uniform entry -> scalar registers
+    const PyrLevelLds v = *p;
+    PyrLevelLds s;
+    s.groups = pyr_sgpr(v.groups);
+    s.rc = pyr_sgpr(v.rc);
+    s.nrows = pyr_sgpr(v.nrows);
+    s.lo = pyr_sgpr(v.lo);
+    s.dy0 = pyr_sgpr(v.dy0);
+    s.own_n = pyr_sgpr(v.own_n);
+    s.pitch = pyr_sgpr(v.pitch);
+    s.xg_off = pyr_sgpr(v.xg_off);
+    s.inv_groups = __int_as_float(pyr_sgpr(__float_as_int(v.inv_groups)));
+    s.yrow0 = 0;  // (only the staging of the row records reads it, per thread and straight from the table)
+    s.pyr_lo = pyr_sgpr(v.pyr_lo);
+    s.pyr_hi = pyr_sgpr(v.pyr_hi);
+    return s;
+}
+
 __global__ __launch_bounds__(PYR_THREADS) void k_pyramid_lds(const OrbLevel* __restrict__ L, int num_levels, const int2* __restrict__ band_rows,
                                                              int bands, const uint8_t* __restrict__ img0, size_t img0_frame_stride,
                                                              int img0_pitch, uint8_t* __restrict__ pyr, size_t pyr_frame_bytes,
                                                              const uint32_t* __restrict__ xg, const short4* __restrict__ yrow) {
     extern __shared__ __attribute__((aligned(16))) uint8_t s_mem[];
     __shared__ int s_img[SV_MAX_LEVELS], s_yt[SV_MAX_LEVELS + 1];
+    __shared__ __attribute__((aligned(16))) PyrLevelLds s_lev[SV_MAX_LEVELS];
     const int band = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
     const int2* BR = band_rows + (size_t)band * num_levels;
+    if (tid >= 64 && tid < 64 + num_levels) {  // (wave 1: wave 0's first lane walks the levels below)
+        const int l = tid - 64;
+        const int w = L[l].w, h = L[l].h;
+        const long long po = L[l].pyr_off;
+        const int2 br = BR[l];
+        const int own_lo = (int)((long long)band * h / bands), own_hi = (int)((long long)(band + 1) * h / bands);
+        PyrLevelLds v;
+        v.groups = (w + 3) >> 2;
+        v.nrows = br.y - br.x;
+        // thread -> (chunk of consecutive rows, column group): `chunks` chunks of rc rows
+        const int chunks = max(min(PYR_THREADS / v.groups, v.nrows), 1);
+        v.rc = (v.nrows + chunks - 1) / chunks;
+        v.lo = br.x;
+        v.dy0 = br.x - own_lo;
+        v.own_n = own_hi - own_lo;
+        v.pitch = L[l].pitch;
+        v.xg_off = L[l].xg_off;
+        v.inv_groups = 1.0f / (float)v.groups;
+        v.yrow0 = L[l].ytab_off + br.x;
+        v.pyr_lo = (int)(uint32_t)po;
+        v.pyr_hi = (int)(po >> 32);
+        s_lev[l] = v;
+    }
     if (tid == 0) {
         // level l is computed from level l - 1 only: two image regions alternate (odd levels in the first, even levels in the second),
         // each as large as its largest tenant
@@ -235,10 +292,31 @@ __global__ __launch_bounds__(PYR_THREADS) void k_pyramid_lds(const OrbLevel* __r
         s_yt[num_levels] = off;
     }
     __syncthreads();
+    // One level ahead: the level's table entry and, for a thread with rows at that level, its column record (6 dwords of xg).  The loads are
+    // issued before the current level's rows are walked (level 1's: before level 0 is staged) and consumed behind that level's barrier.
+    PyrLevelLds nxt = {};
+    int nxt_img = 0, nxt_yt = 0, nxt_g = 0, nxt_r0 = 0, nxt_r1 = 0;
+    uint4 nxt_e = make_uint4(0, 0, 0, 0);
+    uint2 nxt_e2 = make_uint2(0, 0);
+    auto prefetch = [&](int l) {
+        nxt = pyr_level_scalars(&s_lev[l]);
+        nxt_img = pyr_sgpr(s_img[l]);
+        nxt_yt = pyr_sgpr(s_yt[l]);
+        const int c = (int)(((float)tid + 0.5f) * nxt.inv_groups);
+        nxt_g = tid - __mul24(c, nxt.groups);
+        nxt_r0 = __mul24(c, nxt.rc);
+        nxt_r1 = min(nxt_r0 + nxt.rc, nxt.nrows);
+        if (nxt_r0 < nxt_r1) {
+            nxt_e = reinterpret_cast<const uint4*>(xg)[2 * (nxt.xg_off + nxt_g)];
+            nxt_e2 = reinterpret_cast<const uint2*>(xg)[4 * (nxt.xg_off + nxt_g) + 2];
+        }
+    };
+    if (num_levels > 1) prefetch(1);
     const uint8_t* I0 = img0 + (size_t)b * img0_frame_stride;
     {
         // ---- level-0 rows of the band -> LDS (pitch = w rounded up to 4), row records of the band's rows
-        const int w0 = L[0].w, p0 = (w0 + 3) & ~3, lo0 = BR[0].x, n0 = BR[0].y - lo0;
+        const PyrLevelLds lev0 = pyr_level_scalars(&s_lev[0]);
+        const int p0 = 4 * lev0.groups, lo0 = lev0.lo, n0 = lev0.nrows;
         uint8_t* D0 = s_mem + s_img[0];
         if (((((size_t)I0) | (size_t)img0_pitch) & 15) == 0 && (p0 & 15) == 0) {
             // 16-byte pieces by LDS-DMA (the row pitch covers the rounded-up width): whole rows per instruction, the lane's source offset is
@@ -257,7 +335,7 @@ __global__ __launch_bounds__(PYR_THREADS) void k_pyramid_lds(const OrbLevel* __r
             }
         }
         else {
-            const int total = n0 * p0;
+            const int w0 = L[0].w, total = n0 * p0;
             for (int i = tid; i < total; i += PYR_THREADS) {
                 const int r = i / p0, c = i - r * p0;
                 D0[i] = c < w0 ? I0[(size_t)(lo0 + r) * img0_pitch + c] : (uint8_t)0;
@@ -268,29 +346,27 @@ __global__ __launch_bounds__(PYR_THREADS) void k_pyramid_lds(const OrbLevel* __r
             int l = 1;
             while (l + 1 < num_levels && s_yt[0] + 8 * i >= s_yt[l + 1]) ++l;
             const int r = i - ((s_yt[l] - s_yt[0]) >> 3);
-            reinterpret_cast<short4*>(s_mem + s_yt[0])[i] = yrow[L[l].ytab_off + BR[l].x + r];
+            reinterpret_cast<short4*>(s_mem + s_yt[0])[i] = yrow[s_lev[l].yrow0 + r];
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the wave's own DMA pieces have landed; the barrier publishes them to the other waves
     __syncthreads();
     uint8_t* P = pyr + (size_t)b * pyr_frame_bytes;
+    int spw = pyr_sgpr(s_lev[0].groups), src_lo = pyr_sgpr(s_lev[0].lo), src_img = pyr_sgpr(s_img[0]);  // of the source level (pitch in dwords)
     for (int l = 1; l < num_levels; ++l) {
-        const OrbLevel lev = L[l];
-        const int spw = ((L[l - 1].w + 3) & ~3) >> 2, dpw = ((lev.w + 3) & ~3) >> 2;  // LDS pitches in dwords
-        const int src_lo = BR[l - 1].x, lo = BR[l].x, hi = BR[l].y;
-        const int own_lo = (int)((long long)band * lev.h / bands), own_hi = (int)((long long)(band + 1) * lev.h / bands);
-        const uint32_t* S = reinterpret_cast<const uint32_t*>(s_mem + s_img[l - 1]);
-        uint32_t* Dl = reinterpret_cast<uint32_t*>(s_mem + s_img[l]);
-        const short4* yt = reinterpret_cast<const short4*>(s_mem + s_yt[l]);
-        uint8_t* Dg = P + lev.pyr_off;
+        // this level: what the previous turn (or the prologue) fetched
+        const PyrLevelLds lev = nxt;
+        const int dpw = lev.groups, lo = lev.lo, img = nxt_img;
+        const uint32_t* S = reinterpret_cast<const uint32_t*>(s_mem + src_img);
+        uint32_t* Dl = reinterpret_cast<uint32_t*>(s_mem + img);
+        const short4* yt = reinterpret_cast<const short4*>(s_mem + nxt_yt);
+        uint8_t* Dg = P + (((long long)lev.pyr_hi << 32) | (uint32_t)lev.pyr_lo);
         // thread -> (chunk of consecutive rows, column group)
-        const int groups = (lev.w + 3) >> 2, nrows = hi - lo;
-        const int chunks = max(min(PYR_THREADS / groups, nrows), 1), rc = (nrows + chunks - 1) / chunks;
-        const int c = (int)(((float)tid + 0.5f) * (1.0f / (float)groups)), g = tid - __mul24(c, groups);
-        const int r0 = __mul24(c, rc), r1 = min(r0 + rc, nrows);
+        const int g = nxt_g, r0 = nxt_r0, r1 = nxt_r1;
+        const uint4 e = nxt_e;
+        const uint2 e2 = nxt_e2;
+        if (l + 1 < num_levels) prefetch(l + 1);  // the next level's, in flight while this level's rows are walked
         if (r0 < r1) {
-            const uint4 e = reinterpret_cast<const uint4*>(xg)[2 * (lev.xg_off + g)];
-            const uint2 e2 = reinterpret_cast<const uint2*>(xg)[4 * (lev.xg_off + g) + 2];
             const int i0 = e.x & 0xffff, i2 = e.x >> 16;
             const uint32_t coef[4] = {e.z, e.w, e2.x, e2.y};
             uint32_t sel[4];
@@ -309,8 +385,8 @@ __global__ __launch_bounds__(PYR_THREADS) void k_pyramid_lds(const OrbLevel* __r
             };
             uint32_t* dl = Dl + (__mul24(r0, dpw) + g);
             uint32_t goff = __umul24(lo + r0, lev.pitch) + 4 * g;  // byte offset of (row, group) in the level's global image
-            const uint32_t own_n = (uint32_t)(own_hi - own_lo);
-            uint32_t dyo = (uint32_t)(lo + r0 - own_lo);            // row - own_lo: owned <=> dyo < own_n (unsigned)
+            const uint32_t own_n = (uint32_t)lev.own_n;
+            uint32_t dyo = (uint32_t)(lev.dy0 + r0);                // row - own_lo: owned <=> dyo < own_n (unsigned)
             int prev = -1;                                           // the source row the bottom registers of the previous step hold
             // one output row: `top` already holds H(prev) -- reused when the row's first tap is that source row --, the second tap goes to `bot`;
             // the two register sets swap roles from row to row (the loop is unrolled by two), so the reuse costs no moves
@@ -341,6 +417,9 @@ __global__ __launch_bounds__(PYR_THREADS) void k_pyramid_lds(const OrbLevel* __r
             if (row < r1) step(row, hY, hX);
         }
         __syncthreads();
+        spw = dpw;
+        src_lo = lo;
+        src_img = img;
     }
 }
 
@@ -1382,14 +1461,24 @@ __global__ __launch_bounds__(DB_THREADS) void k_describe_bands(const OrbLevel* _
     xcd_frame_map(gridDim.x, gridDim.y, bi, b);
     const DescBand bd = bands[bi];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lv = bd.lv, lp = bd.lp, cpr = lp >> 4;
+    const uint32_t lds0 = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(const __attribute__((address_space(3))) uint8_t*)s_band);
+    // ---- phase U, first half: un-blurred rows -> LDS.  The copy is the longest wait of the prologue and needs the band and its level only,
+    // so it is issued first; the keypoint run, the selection entries and the tables below are fetched while it is in flight.
+    {
+        const uint8_t* img = lv == 0 ? img0 + (size_t)b * img0_frame_stride : pyr + (size_t)b * pyr_frame_bytes + L[lv].pyr_off;
+        if (cpr <= 64) db_stage_rows(img, lv == 0 ? img0_pitch : L[lv].pitch, bd.yu0, bd.nru, cpr, lds0, lane, wave, DB_WAVES);
+        else db_stage_rows_wide(img, lv == 0 ? img0_pitch : L[lv].pitch, bd.yu0, bd.nru, cpr, lds0, lane, wave, DB_WAVES);
+    }
     const int32_t* const P = cellpos + (size_t)b * (total_grid + 1);
     const int n = min(counts[b * (1 + num_levels)], cap);
     const int p0 = P[bd.cell0], nkp = min(P[bd.cell1], n) - p0;  // the band's keypoints: selection entries [p0, p0 + nkp)
-    if (nkp <= 0) return;
-    const int lv = bd.lv, lp = bd.lp, cpr = lp >> 4;
+    if (nkp <= 0) {  // (workgroup-uniform, in front of the first barrier) no keypoints: nothing to do but to let the copy land -- a wave must not
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // end with an LDS-DMA outstanding
+        return;
+    }
     int2* const s_xy = reinterpret_cast<int2*>(s_band + bd.img_bytes);  // (x, y) of keypoint j
     int2* const s_aux = s_xy + DB_MAX_KP;                               // (m10, m01), later (cos, sin) as float bits
-    const uint32_t lds0 = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(const __attribute__((address_space(3))) uint8_t*)s_band);
     const int4* const S = sel + (size_t)b * total_grid + p0;
     int4 sv = make_int4(0, 0, 0, 0);
     if (tid < nkp) {
@@ -1414,14 +1503,8 @@ __global__ __launch_bounds__(DB_THREADS) void k_describe_bands(const OrbLevel* _
         px1[r] = q.z;
         py1[r] = q.w;
     }
-    // ---- phase U: un-blurred rows -> LDS, moments (orb_impl.cc:68-91): m10 = SU - 15 S1, m01 = SV - 15 S1, exact integers
-    {
-        const uint8_t* img = lv == 0 ? img0 + (size_t)b * img0_frame_stride : pyr + (size_t)b * pyr_frame_bytes + L[lv].pyr_off;
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // the loads above are not counted against the DMA below
-        if (cpr <= 64) db_stage_rows(img, lv == 0 ? img0_pitch : L[lv].pitch, bd.yu0, bd.nru, cpr, lds0, lane, wave, DB_WAVES);
-        else db_stage_rows_wide(img, lv == 0 ? img0_pitch : L[lv].pitch, bd.yu0, bd.nru, cpr, lds0, lane, wave, DB_WAVES);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
+    // ---- phase U: moments on the un-blurred rows (orb_impl.cc:68-91): m10 = SU - 15 S1, m01 = SV - 15 S1, exact integers
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // one wait for the wave's pieces of the copy and for the loads behind it
     __syncthreads();
     {
         const int lane_off = (lane >> 3) * lp + 4 * (lane & 7), step = 8 * lp;
