@@ -4,19 +4,18 @@
 //   OptimizationAlgorithmLevenberg     g2o (pinned 20230223_git): lambda init 1e-5 * max diag, rho test, 10 trials
 //   terminate_action                   optimize/terminate_action.cc:36-76 (writes through the force-stop pointer)
 #include <algorithm>
-#include <atomic>
 #include <cfloat>
 #include <cmath>
 
 #include <chrono>
 #include <cstdlib>
 #include <dlfcn.h>
-#include <sched.h>
 #include <thread>
 
 #include "svgpu_internal.h"
 #include "ba_kernels.h"
 #include "ba_layout.h"
+#include "ba_stage.h"
 #include "poseopt_batch_layout.h"
 #include "sv_staged_call.h"
 #include "sv_validate.h"
@@ -224,6 +223,19 @@ struct BaCopy {
     }
 };
 
+// The device side of the host team (ba_stage.h): its workers upload what they staged, on the copy stream or, under SVGPU_BA_COPY_ON_MAIN,
+// on the solve's own (the caller has created the copy stream before it releases the team).
+struct BaTeamUpload {
+    svgpu_ctx* ctx;
+    bool copy_on_main;
+    int begin() const { return (int)hipSetDevice(ctx->device); }  // (the current device is a per-thread setting)
+    template <class T>
+    int operator()(Piece<T> dev, Piece<T> host, size_t first, size_t count) const {
+        return (int)hipMemcpyAsync(dev.p + first, host.p + first, count * sizeof(T), hipMemcpyHostToDevice, copy_on_main ? ctx->stream : ctx->ba_copy_stream);
+    }
+};
+static_assert(BA_STAGE_ERR_RANGE == (int)hipErrorInvalidValue, "ba_stage.h: a range error must read as hipErrorInvalidValue");
+
 }  // namespace
 
 static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single_stage, int rank, int world,
@@ -259,12 +271,27 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
     // (the outputs start as the inputs: every early return leaves the estimate untouched.  At global-BA sizes the copy of the landmark
     //  positions -- 38 MB at 1.6 M landmarks -- is left to the host team below)
     const bool team_sized = ba_plan_team_sized(E, env);  // (the tests take small problems through the team's set-up)
+    // host threads of the staging pass at global-BA sizes (SVGPU_BA_HOST_THREADS overrides, 1 .. 16)
+    const int nth = ba_plan_host_threads(team_sized, env, team_sized ? ba_stage_usable_cpus() : 0);
     memcpy(pose_out, pr->pose_cw, sizeof(double) * 12 * (size_t)P);
     // (the flag is volatile and another thread raises it: ONE read decides both the copy and the return, so that no path leaves
     //  points_out unwritten -- ADVICE r5)
     const bool stopped_at_entry = !sharded && stop && *stop;  // local_bundle_adjuster_g2o.cc:308-310
-    const bool team_copies_points = team_sized && !stopped_at_entry && E > 0 && P > 0 && L > 0;
-    if (!team_copies_points) memcpy(points_out, pr->points, sizeof(double) * 3 * (size_t)L);
+    // complete: points_out holds a full copy of pr->points, or will once the team, whose workers make the copy in shares, is joined.
+    // Every other copy is this one: here for a call without a team, on the way out for one that returns before its team has started
+    struct PointsOut {
+        double* out;
+        const double* in;
+        size_t bytes;
+        bool complete;
+        void restore() {
+            if (!complete) memcpy(out, in, bytes);
+            complete = true;
+        }
+        ~PointsOut() { restore(); }
+    } points_guard{points_out, pr->points, sizeof(double) * 3 * (size_t)L, false};
+    const bool team_copies_points = nth > 1 && !stopped_at_entry && E > 0 && P > 0 && L > 0;
+    if (!team_copies_points) points_guard.restore();
     if (E > 0 && outlier_out) memset(outlier_out, 0, E);
     if (stats) *stats = st;
     if (!sharded) {
@@ -272,13 +299,7 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
         if (E == 0 || P == 0 || L == 0) return SVGPU_OK;
     }
     else if (P == 0 || L == 0) return SVGPU_OK;  // same on every rank
-    {
-        const hipError_t e_dev = hipSetDevice(ctx->device);
-        if (e_dev != hipSuccess) {  // an early return before the team exists: the estimate leaves as it came
-            if (team_copies_points) memcpy(points_out, pr->points, sizeof(double) * 3 * (size_t)L);
-            SV_HIP(ctx, e_dev);
-        }
-    }
+    SV_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
 
     // ---- page-locked staging (ba_layout.h): input block | output block | structure block, the input block laid out exactly like the one at
@@ -292,254 +313,26 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
         const BaSizes shape = ba_sizes(P, L, E, world, nullptr, false, false, false, BA_DBG_OFF);  // (the landmark offsets are written into this image)
         const auto image = [&](Arena& A) { ba_host_layout(A, shape, hin, hout, hst); };
         const int r = sv_ensure_stage(ctx, arena_measure(image));
-        if (r) {
-            if (team_sized) memcpy(points_out, pr->points, sizeof(double) * 3 * (size_t)L);
-            return r;
-        }
+        if (r) return r;
         Arena A(ctx->h_stage, ctx->stage_bytes);
         image(A);
-        if (A.overflow) {
-            if (team_sized) memcpy(points_out, pr->points, sizeof(double) * 3 * (size_t)L);
-            return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_local_ba: internal staging overflow");
-        }
+        if (A.overflow) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_local_ba: internal staging overflow");
     }
     int* const lm_off = hin.lm_off;
     int* const e_pose = hin.e_pose;
     int* const e_point = hin.e_point;
-    float* const e_uvr = hin.e_uvr;
-    float* const e_w = hin.e_w;
-    float* const e_hub = hin.e_hub;
-    auto copy_measurements = [&](size_t a, size_t b) {
-        memcpy(e_uvr + 3 * a, pr->obs_uvr + 3 * a, 12 * (b - a));
-        memcpy(e_w + a, pr->obs_inv_sigma_sq + a, 4 * (b - a));
-        if (pr->obs_huber_delta) memcpy(e_hub + a, pr->obs_huber_delta + a, 4 * (b - a));
-        else memset(e_hub + a, 0, 4 * (b - a));
-    };
-    std::vector<int> perm;  // sorted position -> caller's observation index (empty = identity)
     std::vector<uint8_t> level((sharded || !single_stage) ? E : 0, 0);  // (host image of the edge levels: the stage boundary and the sharded set-up read it)
     bool no_levels = true;  // until the first gate: every edge is at level 0
-    // host threads of the staging pass at global-BA sizes (SVGPU_BA_HOST_THREADS overrides, 1 .. 16)
-    const int nth = [&] {
-        // (the CPUs this process may run on: the affinity mask, which is what a container's cpuset leaves, not the machine's core count)
-        unsigned hw = team_sized ? std::thread::hardware_concurrency() : 0;
-        cpu_set_t cpus;
-        if (team_sized && sched_getaffinity(0, sizeof(cpus), &cpus) == 0 && CPU_COUNT(&cpus) > 0) hw = hw == 0 ? (unsigned)CPU_COUNT(&cpus) : std::min(hw, (unsigned)CPU_COUNT(&cpus));
-        return ba_plan_host_threads(team_sized, env, hw);
-    }();
-    // The host team of a global-BA sized call: nth threads (this one included) scan the observation indices -- range check, "already grouped
-    // by landmark?" (the order local_bundle_adjuster_g2o.cc:168-227 and global_bundle_adjuster.cc:66-118 create their edges in) and,
-    // valid in that case, the landmark offsets -- and stage the two index arrays; the nth - 1 workers then go on staging the measurements
-    // and the landmark positions while this thread runs the device's structure work, and upload them on the copy stream once the arena
-    // is known (`go`).  One spawn per call; the phases of the scan are separated by spin barriers (a few microseconds each).
-    struct HostTeam {
-        std::vector<std::thread> th;
-        std::atomic<int> arrived{0};
-        std::atomic<int> gate{0};    // 0: the team is being created, 1: run, 2: creation failed, leave
-        std::atomic<int> staged{0};  // workers whose share of the measurements is in the staging image
-        std::atomic<int> go{0};  // 0: the arena is not known yet, 1: upload, 2: abandon (the caller returns early or stages the observations itself)
-        hipStream_t s2 = nullptr;
-        int err[16] = {0};
-        bool running = false;
-        void join() {
-            for (auto& t : th)
-                if (t.joinable()) t.join();
-            th.clear();
-            running = false;
-        }
-        void abandon_and_join() {
-            int z = 0;
-            go.compare_exchange_strong(z, 2);
-            join();
-        }
-    } team;
-    bool lm_major = true;
-    std::vector<uint8_t> pose_seen(P, 0);  // a pose with an observation (the pose half of the first stage's activity pass)
-    // (function scope: the workers run these closures until the team is joined -- TeamGuard below, declared behind them, goes first)
-        int bad[16] = {0}, unsorted[16] = {0};
-        std::vector<uint8_t> seen_q[16];
-        const int32_t* const op = pr->obs_pose;
-        const int32_t* const ol = pr->obs_point;
-        auto copy_range = [&](size_t a, size_t b, bool indices_only) {
-            memcpy(e_pose + a, pr->obs_pose + a, 4 * (b - a));
-            memcpy(e_point + a, pr->obs_point + a, 4 * (b - a));
-            if (indices_only) return;  // (the measurements follow in the team's second phase)
-            copy_measurements(a, b);
-        };
-        auto barrier = [&](int k) {  // the k-th barrier of the call (k = 1, 2, ...): every thread of the team arrives once
-            team.arrived.fetch_add(1);
-            for (int spins = 0; team.arrived.load() < k * nth; ++spins)
-                if (spins > 4000) std::this_thread::yield();
-        };
-        // Phase 1 of thread q: straight-line passes over its range (flag reductions the compiler vectorises), the landmark offsets as "end of
-        // landmark l = index behind its last observation", stored where a landmark's run ends and closed over the empty landmarks by a running
-        // maximum (shares of the offsets array, seeded by a backward look at the shares before)
-        auto scan_range = [&](int q) {
-            const size_t e0 = (size_t)E * q / nth, end = (size_t)E * (q + 1) / nth;
-            const size_t k0 = ((size_t)L + 1) * q / nth, k1 = ((size_t)L + 1) * (q + 1) / nth;
-            unsigned bd = 0, un = 0;
-            for (size_t e = e0; e < end; ++e) bd |= (unsigned)((unsigned)op[e] >= (unsigned)P) | (unsigned)((unsigned)ol[e] >= (unsigned)L);
-            for (size_t e = std::max<size_t>(e0, 1); e < end; ++e) un |= (unsigned)(ol[e] < ol[e - 1]);
-            bad[q] = bd != 0, unsorted[q] = un != 0;
-            if (!bd) {
-                std::vector<uint8_t>& seen = q == 0 ? pose_seen : seen_q[q];
-                if (q) seen.assign(P, 0);
-                uint8_t* const sn = seen.data();
-                for (size_t e = e0; e < end; ++e) sn[op[e]] = 1;
-                copy_range(e0, end, nth > 1);
-            }
-            for (size_t k = k0; k < k1; ++k) lm_off[k] = 0;
-            if (nth > 1) barrier(1);
-            int any_bad = 0, any_un = 0;
-            for (int t = 0; t < nth; ++t) any_bad |= bad[t], any_un |= unsorted[t];
-            const bool ok = !any_bad && !any_un;
-            if (ok && nth == 1)  // (one thread: stored unconditionally, the last observation of a landmark wins -- no branch to mispredict)
-                for (size_t e = e0; e < end; ++e) lm_off[ol[e] + 1] = (int)(e + 1);
-            else if (ok)
-                for (size_t e = e0; e < end; ++e) {
-                    const int l = ol[e], nxt = e + 1 < (size_t)E ? ol[e + 1] : -1;
-                    if (nxt != l) lm_off[l + 1] = (int)(e + 1);
-                }
-            if (nth > 1) barrier(2);
-            int v = 0;
-            if (ok)
-                for (size_t k = k0; k-- > 0;)
-                    if (lm_off[k]) {
-                        v = lm_off[k];
-                        break;
-                    }
-            if (nth > 1) barrier(3);
-            if (ok)
-                for (size_t k = k0; k < k1; ++k) {
-                    v = std::max(v, lm_off[k]);
-                    lm_off[k] = v;
-                }
-            if (nth > 1) barrier(4);
-        };
-        // Phase 2 of worker q (1 .. nth - 1): its share of the measurements and of the landmark positions into the staging image, chunk by
-        // chunk; a staged chunk is uploaded as soon as `go` says where to
-        auto stage_measurements = [&](int q) {
-            const int W = nth - 1, w = q - 1;
-            const size_t CH = (size_t)128 << 10;   // observations per chunk: 2.6 MB of measurements
-            const size_t LCH = (size_t)256 << 10;  // landmark positions: 6 MB per chunk
-            const size_t e0 = (size_t)E * w / W, e1 = (size_t)E * (w + 1) / W, l0 = (size_t)L * w / W, l1 = (size_t)L * (w + 1) / W;
-            memcpy(points_out + 3 * l0, pr->points + 3 * l0, 24 * (l1 - l0));  // (the caller's output starts as its input)
-            hipError_t he = hipSetDevice(ctx->device);  // (the current device is a per-thread setting)
-            size_t e_up = e0, l_up = l0;  // uploaded so far
-            // (every hipMemcpyAsync holds the runtime's lock for ~15 us, and this thread's launches queue behind it: below 4 M observations the
-            //  worker that finishes LAST uploads the whole image in four copies; beyond, every worker uploads its chunks as they are staged)
-            const bool chunked = E >= (4 << 20);
-            // elements [first, first + count) of a staged piece to the same elements of its device piece (placed before `go` said 1)
-            auto up = [&](auto dev, auto host, size_t first, size_t count) {
-                if (first + count > dev.n) he = hipErrorInvalidValue;
-                if (count && he == hipSuccess) he = hipMemcpyAsync(dev.p + first, host.p + first, count * sizeof(*dev.p), hipMemcpyHostToDevice, team.s2);
-            };
-            auto flush = [&](size_t e_staged, size_t l_staged) {
-                if (!chunked || team.go.load() != 1 || he != hipSuccess) return;
-                if (e_staged > e_up) {
-                    up(din.e_uvr, hin.e_uvr, 3 * e_up, 3 * (e_staged - e_up));
-                    up(din.e_w, hin.e_w, e_up, e_staged - e_up);
-                    up(din.e_hub, hin.e_hub, e_up, e_staged - e_up);
-                    e_up = e_staged;
-                }
-                if (l_staged > l_up) {
-                    up(din.points, hin.points, 3 * l_up, 3 * (l_staged - l_up));
-                    l_up = l_staged;
-                }
-            };
-            for (size_t a = e0; a < e1 && team.go.load() != 2; a += CH) {
-                const size_t b = std::min(e1, a + CH);
-                copy_measurements(a, b);
-                flush(b, l0);
-            }
-            for (size_t a = l0; a < l1 && team.go.load() != 2; a += LCH) {
-                const size_t b = std::min(l1, a + LCH);
-                memcpy(hin.points + 3 * a, pr->points + 3 * a, 24 * (b - a));
-                flush(e1, b);
-            }
-            const bool last = team.staged.fetch_add(1) + 1 == W;
-            for (int spins = 0; team.go.load() == 0; ++spins)
-                if (spins > 2000) std::this_thread::yield();
-            if (team.go.load() == 1) {
-                if (chunked) flush(e1, l1);
-                else if (last) {  // (every share is staged: fetch_add orders the others' writes before this thread's reads)
-                    up(din.e_uvr, hin.e_uvr, 0, din.e_uvr.n), up(din.e_w, hin.e_w, 0, din.e_w.n), up(din.e_hub, hin.e_hub, 0, din.e_hub.n);
-                    up(din.points, hin.points, 0, din.points.n);
-                }
-            }
-            team.err[q] = (int)he;
-        };
-        struct TeamGuard {
-            HostTeam& t;
-            ~TeamGuard() { t.abandon_and_join(); }
-        } team_guard{team};
-        if (nth == 1) {
-            if (team_sized) memcpy(points_out, pr->points, sizeof(double) * 3 * (size_t)L);  // (SVGPU_BA_HOST_THREADS=1)
-            scan_range(0);
-            if (!bad[0]) memcpy(hin.points, pr->points, hin.points.bytes());
-        }
-        else {
-            team.running = true;
-            // (the workers wait at a gate until the whole team exists: a thread the system refuses to create must not leave the others at a
-            //  barrier that counts nth arrivals -- the call fails instead, the caller's estimate untouched)
-            bool spawned = true;
-            try {
-                for (int q = 1; q < nth; ++q)
-                    team.th.emplace_back([&, q] {
-                        for (int spins = 0; team.gate.load() == 0; ++spins)
-                            if (spins > 2000) std::this_thread::yield();
-                        if (team.gate.load() != 1) return;
-                        scan_range(q);
-                        stage_measurements(q);
-                    });
-            } catch (...) {
-                spawned = false;
-            }
-            team.gate.store(spawned ? 1 : 2);
-            if (!spawned) {
-                team.join();
-                memcpy(points_out, pr->points, sizeof(double) * 3 * (size_t)L);
-                return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_global_ba: could not start the host threads of the set-up (SVGPU_BA_ONE_THREAD=1 runs it on the caller's thread)");
-            }
-            scan_range(0);  // (returns behind the last barrier: the whole scan is done)
-        }
-        int any_bad = 0, any_unsorted = 0;
-        for (int q = 0; q < nth; ++q) any_bad |= bad[q], any_unsorted |= unsorted[q];
-        if (any_bad) {
-            if (team_sized) {
-                team.go.store(2);
-                team.join();
-                memcpy(points_out, pr->points, sizeof(double) * 3 * (size_t)L);
-            }
-            return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_local_ba: observation index out of range");
-        }
-        for (int q = 1; q < nth; ++q)
-            for (int p = 0; p < P; ++p) pose_seen[p] |= seen_q[q][p];
-        lm_major = !any_unsorted;
-        if (!lm_major && team.running) {  // (rare at this size: the permuted copy below writes the whole staging image itself)
-            team.go.store(2);
-            team.join();
-            memcpy(hin.points, pr->points, hin.points.bytes());
-        }
-    if (!lm_major) {
-        for (int l = 0; l <= L; ++l) lm_off[l] = 0;
-        for (int e = 0; e < E; ++e) lm_off[pr->obs_point[e] + 1]++;
-        for (int l = 0; l < L; ++l) lm_off[l + 1] += lm_off[l];
-    }
-    if (!lm_major) {
-        perm.resize(E);
-        std::vector<int> fill(lm_off, lm_off + L);
-        for (int e = 0; e < E; ++e) perm[fill[pr->obs_point[e]]++] = e;
-        for (int k = 0; k < E; ++k) {
-            const int e = perm[k];
-            e_pose[k] = pr->obs_pose[e];
-            e_point[k] = pr->obs_point[e];
-            e_uvr[3 * k] = pr->obs_uvr[3 * e];
-            e_uvr[3 * k + 1] = pr->obs_uvr[3 * e + 1];
-            e_uvr[3 * k + 2] = pr->obs_uvr[3 * e + 2];
-            e_w[k] = pr->obs_inv_sigma_sq[e];
-            e_hub[k] = pr->obs_huber_delta ? pr->obs_huber_delta[e] : 0.f;
-        }
-    }
+    // ---- the staging pass (ba_stage.h): scan and index arrays on nth threads; from here until it is joined, a team stages and uploads the
+    //      measurements and copies points_out beside this thread's device work
+    BaStageTeam<BaTeamUpload> team(*pr, hin, points_out, nth, BA_STAGE_TUNING, BaTeamUpload{ctx, env.copy_on_main});
+    const BaStageResult staged = team.scan();
+    if (staged.no_threads)
+        return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_global_ba: could not start the host threads of the set-up (SVGPU_BA_ONE_THREAD=1 runs it on the caller's thread)");
+    points_guard.complete |= nth > 1;  // (a team that has started copies points_out, whatever becomes of it)
+    if (staged.bad_index) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_local_ba: observation index out of range");
+    const std::vector<int>& perm = staged.perm;  // sorted position -> caller's observation index (empty = identity)
+    const std::vector<uint8_t>& pose_seen = staged.pose_seen;
     // (the pose -> edge lists and the robust-kernel flags are built on the device once the observations are there: sv_ba_build_pose_lists)
     memcpy(hin.pose, pr->pose_cw, hin.pose.bytes());
     memcpy(hin.intr, pr->intrinsics, hin.intr.bytes());
@@ -551,7 +344,7 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
     const bool want_dense = ba_plan_want_dense(solver_opt, sharded, P, env);
     // (a sharded solve renumbers the landmarks of ITS shard: the numbering is private to the rank's kernels, every landmark-sized exchange
     //  between ranks -- ownership marks, the final positions -- stays in the caller's numbering)
-    const bool renumber = ba_plan_renumber(team.running, single_stage, env);
+    const bool renumber = ba_plan_renumber(team.running(), single_stage, env);
     BaSizes Z = ba_sizes(P, L, E, world, lm_off, want_dense, renumber, /*units_wanted*/ !env.no_units, ba_plan_dbg_mode(env));
     Z.pair_scratch = std::max(std::max(std::max(sv_ba_pairs_scratch_bytes(Z.pair_cap, E, Z.nb_cap), sv_ba_pose_lists_scratch_bytes((size_t)E)), renumber ? sv_ba_renumber_scratch_bytes((size_t)L) : 0),
                               Z.chunk_units ? sv_ba_units_scratch_bytes(Z.pair_cap, Z.unit_cap()) : 0);
@@ -623,13 +416,13 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
         const bool in_W = dw.W.bytes() >= want;  // (the pair lists are built in the pair scratch: the records survive them only in W)
         void* sc = in_W ? (void*)D.W : (void*)dw.pair_scratch.p;
         const size_t sc_bytes = in_W ? dw.W.bytes() : dw.pair_scratch.bytes();
-        if (team.running && !in_W) {  // (cannot happen at these sizes; the team's work is then uploaded in one piece)
-            team.go.store(2);
+        if (team.running() && !in_W) {  // (cannot happen at these sizes; the team's work is then uploaded in one piece)
+            team.abandon();
             team.join();
-            copy_measurements(0, (size_t)E);
+            ba_stage_measurements(*pr, hin, 0, (size_t)E);
             memcpy(hin.points, pr->points, hin.points.bytes());
         }
-        if (team.running) {
+        if (team.running()) {
             if (!ctx->ba_copy_stream) SV_HIP(ctx, hipStreamCreateWithFlags(&ctx->ba_copy_stream, hipStreamNonBlocking));
             if (!ctx->ev_ba_copy) SV_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_ba_copy, hipEventDisableTiming));
             if ((rc = cp.h2d_run(din.pose, din.points, hin.pose))) return rc;      // poses
@@ -639,13 +432,11 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
             // SVGPU_BA_COPY_ON_MAIN: the measurements on the solve's own stream instead.  Measured over 150 config-5 calls: copy stream median
             // 7.50 ms, but 2 calls of 15 ms (the stream's first synchronisation arrives ~8 ms late: two DMA users of one process); own stream
             // 8.06 ms, no call above 8.9.  The default keeps the better mean (7.6 against 8.1); a caller that minds the tail sets the variable.
-            const bool copy_on_main = env.copy_on_main;
-            if (!copy_on_main) {
+            if (!env.copy_on_main) {
                 SV_HIP(ctx, hipEventRecord(ctx->ev_ba_copy, s));
                 SV_HIP(ctx, hipStreamWaitEvent(ctx->ba_copy_stream, ctx->ev_ba_copy, 0));
             }
-            team.s2 = copy_on_main ? s : ctx->ba_copy_stream;
-            team.go.store(1);
+            team.release(din);  // (BaTeamUpload picks the stream)
         }
         else if ((rc = cp.h2d_run(din.pose, dout.ctl, hin.pose))) return rc;  // the whole input block
         if (renumber) {  // (ba_bind has pointed the kernels at the rn_* arrays)
@@ -658,10 +449,9 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
     }
     // the measurements are on the device (pipelined: the stream waits for the copy stream) -> pose-major copies + robust flags
     auto finish_observations = [&]() -> int {
-        if (team.running) {
-            team.join();
-            for (int q = 0; q < nth; ++q)
-                if (team.err[q]) return sv_set_error(ctx, SVGPU_ERR_HIP, "hipMemcpyAsync (measurements)", (hipError_t)team.err[q]);
+        if (team.running()) {
+            const int he = team.join();
+            if (he) return sv_set_error(ctx, SVGPU_ERR_HIP, "hipMemcpyAsync (measurements)", (hipError_t)he);
             SV_HIP(ctx, hipEventRecord(ctx->ev_ba_copy, ctx->ba_copy_stream));
             SV_HIP(ctx, hipStreamWaitEvent(s, ctx->ev_ba_copy, 0));
         }
@@ -674,7 +464,7 @@ static int local_ba_impl(svgpu_ctx* ctx, const svgpu_ba_problem* pr, bool single
         return rp;
     };
     bool observations_finished = false;
-    if (!team.running) {
+    if (!team.running()) {
         const int rp = finish_observations();
         if (rp) return rp;
         observations_finished = true;

@@ -14,7 +14,12 @@ second at a 256-byte boundary behind the keypoint capacity, both within the piec
 over a buffer of its own against the head of the slab, offset for offset and byte for byte with the expressions the tracker used to write
 out, and the growth policy track_caps (floors, never shrinking, idempotent, no re-allocation for a call repeated).  ba_plan_check.cpp checks
 the decisions of bundle adjustment (ba_plan.h, no arena in it): the environment switches parsed from a table, every plan function against
-the expression it replaced at the thresholds' neighbours and the bench shapes, and the key of the envelope plan cache."""
+the expression it replaced at the thresholds' neighbours and the bench shapes, and the key of the envelope plan cache.  ba_stage_check.cpp
+(built with -pthread) checks the observation staging of bundle adjustment (ba_stage.h, the only code of the library that starts threads):
+teams of 1, 2, 3, 5, 8 and 16 threads against a single-thread restatement on shapes that put every boundary of the shares to work --
+landmark offsets, the staged image byte for byte, the poses seen, the stable order of ungrouped observations, an index out of range in
+every share -- and, through a recording uploader over a fake device arena, that a released team uploads every element once, whole arrays
+or chunk by chunk, that an abandoned one uploads nothing, and that either way it joins with points_out holding the input points."""
 import pytest
 
 from tests.host_check import ROOT, build_and_run
@@ -30,12 +35,14 @@ PROGRAMS = {
     "ba_arena_check.cpp": "ba arena ok",
     "track_arena_check.cpp": "track arena ok",
     "ba_plan_check.cpp": "ba plan ok",
+    "ba_stage_check.cpp": "ba stage ok",
 }
+EXTRA_FLAGS = {"ba_stage_check.cpp": ("-pthread",)}  # the one program that starts threads
 
 
 @pytest.mark.parametrize("source", list(PROGRAMS))
 def test_measure_covers_what_the_layout_takes(source, tmp_path):
-    build_and_run(source, PROGRAMS[source], tmp_path)
+    build_and_run(source, PROGRAMS[source], tmp_path, EXTRA_FLAGS.get(source, ()))
 
 
 def test_the_checked_shapes_are_those_of_the_gpu_test():

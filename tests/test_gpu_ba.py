@@ -519,6 +519,47 @@ def test_global_ba_set_up_paths_agree(monkeypatch):
     assert np.array_equal(bad["points"], pts_before)
 
 
+def test_global_ba_host_team_agrees_with_one_thread_on_a_small_scene(monkeypatch):
+    """The host side of the set-up alone (csrc/ba_stage.h), on 36 keyframes / 400 landmarks / 1 600 observations taken through the team's
+    path with SVGPU_BA_TEAM_MIN_OBS, the caller's landmark numbering kept throughout so that nothing else differs: teams of 2, 3 and 16
+    threads (shares that split landmarks' runs, shares of a hundred observations) against the caller's thread alone, with the
+    observations grouped by landmark and shuffled (the team is abandoned, the stable sort stages everything); an index out of range in the
+    LAST observation, which only the last share's worker sees, fails the call and leaves the points as they came.  What the shares hold
+    is pinned on the host by tests/ba_stage_check.cpp; this is the same code with the device behind it."""
+    from stella_vslam_amd import optimize
+    monkeypatch.setenv("SVGPU_BA_TEAM_MIN_OBS", "64")
+    monkeypatch.setenv("SVGPU_BA_NO_RENUMBER", "1")
+    # (36 keyframes: on a ring of 30 no run of four neighbouring cameras sees one landmark, and the generator draws again for ever)
+    sc = S.ba_scene_large(num_kf=36, num_lm=400, obs_per_lm=4)
+    adj = optimize.local_bundle_adjuster()
+
+    def solve(scene, name, value):
+        with monkeypatch.context() as m:
+            m.setenv(name, value)
+            return adj.optimize_global_flat(scene, num_iter=10)
+
+    ref = solve(sc, "SVGPU_BA_ONE_THREAD", "1")
+    assert ref["stats"]["chi2_final"] < ref["stats"]["chi2_initial"]
+    def same(got):
+        assert got["stats"]["iters_stage1"] == ref["stats"]["iters_stage1"]
+        assert got["stats"]["chi2_final"] == pytest.approx(ref["stats"]["chi2_final"], rel=1e-12)
+        assert np.abs(got["pose_cw"] - ref["pose_cw"]).max() < 1e-10 and np.abs(got["points"] - ref["points"]).max() < 1e-10
+    perm = np.random.default_rng(7).permutation(len(sc["obs_pose"]))
+    shuffled = dict(sc)
+    for k in ("obs_pose", "obs_point", "obs_uvr", "obs_inv_sigma_sq", "obs_huber"):
+        shuffled[k] = np.ascontiguousarray(sc[k][perm])
+    bad = dict(sc)
+    bad["obs_point"] = sc["obs_point"].copy()
+    bad["obs_point"][-1] = len(sc["points"])
+    pts_before = bad["points"].copy()
+    for threads in ("2", "3", "16"):
+        same(solve(sc, "SVGPU_BA_HOST_THREADS", threads))
+        same(solve(shuffled, "SVGPU_BA_HOST_THREADS", threads))
+        with pytest.raises(Exception):
+            solve(bad, "SVGPU_BA_HOST_THREADS", threads)
+        assert np.array_equal(bad["points"], pts_before)
+
+
 def test_global_ba_two_sided_elimination_equals_one_sided(monkeypatch):
     """A long band can be eliminated from both ends by two workgroups (ba_skyline.hip: T | S | B, the Schur complements added on the
     separator) -- the fallback where the segmented plan does not apply, forced here with SVGPU_SKY_SEGMENTS=0; SVGPU_SKY_ONE_SIDED=1 keeps the
