@@ -1106,6 +1106,9 @@ int svgpu_selftest_segmented_solve_rank(int nP, int NB, const int* blk_ab, const
  * (n above 16384 takes the many-workgroup path).  keys[n] (low `bits` bits significant) are sorted stably: sorted_idx[n] receives the
  * permutation.  Either half is skipped when its output pointer is NULL.  Host in / out, synchronous. */
 int svgpu_selftest_scan_sort(svgpu_ctx* ctx, int n, const int32_t* values, int32_t* scan_out, const uint32_t* keys, int bits, int32_t* sorted_idx);
+/* The same scan without scratch, as the grid and bucket candidate lists call it: ONE launch of one workgroup that walks tiles of 16384
+ * elements, whatever n >= 0.  scan_out[n + 1].  Host in / out, synchronous. */
+int svgpu_selftest_scan_one_launch(svgpu_ctx* ctx, int n, const int32_t* values, int32_t* scan_out);
 
 /* Device self-test of the sort paths the entry above does not reach (csrc/sv_sort.hip, sv_bucket_sort of csrc/bucket_kernels.hip; NOT a
  * product entry point).  Host in / out, synchronous; arguments a path does not name are ignored.  info: 4 ints.

@@ -11,6 +11,7 @@
 
 #include "svgpu_internal.h"
 #include "ba_kernels.h"
+#include "sv_wave.h"
 
 namespace {
 
@@ -1283,19 +1284,8 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_opt_batch(PoseOptDev P) {
 
 // 64-lane sum of a double with DPP row scans (VALU only; __shfl_xor on a double is two ds_bpermute round trips per step).
 // Fixed order => bit-reproducible.  The total is returned in every lane.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double dpp_d(double v) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, ROW_MASK, 0xF, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, ROW_MASK, 0xF, false);
-    return __hiloint2double(hi, lo);
-}
 __device__ __forceinline__ double wave_sum_dpp(double v) {
-    v += dpp_d<0x111, 0xF>(v);  // row_shr:1
-    v += dpp_d<0x112, 0xF>(v);  // row_shr:2
-    v += dpp_d<0x114, 0xF>(v);  // row_shr:4
-    v += dpp_d<0x118, 0xF>(v);  // row_shr:8   -> lane 15 of every row holds the row sum
-    v += dpp_d<0x142, 0xA>(v);  // row_bcast:15 into rows 1 and 3
-    v += dpp_d<0x143, 0xC>(v);  // row_bcast:31 into rows 2 and 3 -> lane 63 holds the total
+    v = sv_wave_inclusive_sum(v);
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63), __builtin_amdgcn_readlane(__double2loint(v), 63));
 }
 

@@ -560,6 +560,22 @@ extern "C" int svgpu_selftest_scan_sort(svgpu_ctx* ctx, int n, const int32_t* va
     return SVGPU_OK;
 }
 
+// ---- svgpu_selftest_scan_one_launch (include/svgpu.h): sv_scan_i32 without scratch
+extern "C" int svgpu_selftest_scan_one_launch(svgpu_ctx* ctx, int n, const int32_t* values, int32_t* scan_out) {
+    if (!ctx || n < 0 || n > SV_SCAN_MAX || !scan_out || (n > 0 && !values)) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_selftest_scan_one_launch: bad arguments");
+    hipStream_t s = ctx->stream;
+    const size_t N = (size_t)n;
+    int* d_scan;
+    int rc = sv_scratch_layout(ctx, "svgpu_selftest_scan_one_launch: internal arena overflow", [&](Arena& A) { d_scan = A.take<int>(N + 1); });
+    if (rc) return rc;
+    if (n > 0) SV_HIP(ctx, hipMemcpyAsync(d_scan, values, N * 4, hipMemcpyHostToDevice, s));
+    if (sv_scan_i32(s, d_scan, n, nullptr) != 1) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_selftest_scan_one_launch: more than one launch");
+    SV_HIP(ctx, hipMemcpyAsync(scan_out, d_scan, (N + 1) * 4, hipMemcpyDeviceToHost, s));
+    SV_HIP(ctx, hipGetLastError());
+    SV_HIP(ctx, hipStreamSynchronize(s));
+    return SVGPU_OK;
+}
+
 // ---- svgpu_selftest_sort_paths (include/svgpu.h): the device-count radix sort, the one-workgroup sorts and the bucket order on caller data
 namespace {
 __global__ void k_selftest_widen(const int* __restrict__ idx, int n, unsigned long long* __restrict__ out) {  // value = index | ~index << 32

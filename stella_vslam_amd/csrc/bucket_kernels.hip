@@ -150,33 +150,6 @@ __global__ void k_bucket_scatter(BucketProblem B, const int32_t* __restrict__ ma
     match_q[B.q_idx[r]] = match_rows[r];
 }
 
-// same single-workgroup scan as k_exclusive_scan of match_kernels.hip (kept local: anonymous namespaces)
-__global__ __launch_bounds__(1024) void k_bucket_exscan(int32_t* __restrict__ data, int n) {
-    __shared__ int s_part[1024];
-    __shared__ int s_carry;
-    const int tid = threadIdx.x;
-    if (tid == 0) s_carry = 0;
-    __syncthreads();
-    for (int base = 0; base < n; base += 1024) {
-        const int i = base + tid;
-        const int v = i < n ? data[i] : 0;
-        s_part[tid] = v;
-        __syncthreads();
-        for (int off = 1; off < 1024; off <<= 1) {
-            const int add = tid >= off ? s_part[tid - off] : 0;
-            __syncthreads();
-            s_part[tid] += add;
-            __syncthreads();
-        }
-        const int carry = s_carry;
-        if (i < n) data[i] = carry + s_part[tid] - v;
-        __syncthreads();
-        if (tid == 1023) s_carry = carry + s_part[1023];
-        __syncthreads();
-    }
-    if (tid == 0) data[n] = s_carry;
-}
-
 // ---- the batch: K problems as records of a table in device memory; row_base[p] = first row of problem p among all rows
 __global__ __launch_bounds__(256) void k_bucket_rows_batch(const BucketProblem* __restrict__ tab, const int32_t* __restrict__ row_base, int num_problems) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
@@ -266,8 +239,7 @@ void sv_bucket_rows(hipStream_t s, const BucketProblem& B) {
 void sv_bucket_count(hipStream_t s, const BucketProblem& B) {  // cand_off = exclusive scan of the per-row counts, total in cand_off[n1]
     if (B.n1 <= 0) return;
     hipLaunchKernelGGL(k_bucket_scan<false>, dim3((B.n1 + 3) / 4), dim3(256), 0, s, B);
-    if (B.n1 <= 16384) sv_scan_i32(s, B.cand_off, B.n1, nullptr);  // (the shuffle-based one-workgroup scan; the kernel above beyond its size)
-    else hipLaunchKernelGGL(k_bucket_exscan, dim3(1), dim3(1024), 0, s, B.cand_off, B.n1);
+    sv_scan_i32(s, B.cand_off, B.n1, nullptr);  // (one launch whatever n1; cand_off starts an arena piece: the scan's alignment)
 }
 void sv_bucket_fill(hipStream_t s, const BucketProblem& B) {
     if (B.n1 > 0) hipLaunchKernelGGL(k_bucket_scan<true>, dim3((B.n1 + 3) / 4), dim3(256), 0, s, B);

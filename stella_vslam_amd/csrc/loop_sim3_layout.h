@@ -4,7 +4,7 @@
 //
 // Rows: the queries of both matcher passes are ONE concatenation, K x n1 rows of pass A (keyframe 1's landmarks under candidate p's
 // transform) followed by the N2 rows of pass B (every candidate's landmarks into keyframe 1).  Keypoint sets: the K candidates' keypoints
-// followed by keyframe 1's, binned in one pass with cell id = set x cells + cell.
+// followed by keyframe 1's, binned in one pass over ONE array of (K + 1) x cells counters (sv_launch_grid_sets).
 // The candidate lists are the LAST takes and nothing in front of them depends on their capacity: a call that has to repeat itself with
 // longer lists finds every other piece where it was.
 #pragma once
@@ -20,7 +20,7 @@ struct LoopSim3Shape {
     size_t ncell = 0;  // grid cells of one keyframe
     bool has_scale_in = false;
     size_t owner_ints = 0, mrow_ints = 0;  // tables of the candidates whose replay keeps them in global memory (sv_cand_replay_form < 0), else 0
-    size_t prob_rec = 0, reproj_rec = 0, cand_rec = 0, replay_rec = 0, geo_rec = 0, stats_rec = 0;  // sizeof of the records the tables hold
+    size_t prob_rec = 0, reproj_rec = 0, cand_rec = 0, replay_rec = 0, grid_rec = 0, stats_rec = 0;  // sizeof of the records the tables hold
     size_t cap = 0;    // capacity of the candidate lists, entries
 };
 
@@ -48,7 +48,8 @@ struct LoopSim3Pieces {
     Piece<uint8_t> active;                 // K
     Piece<float> scale_in;                 // K, optional
     Piece<char> prob;                      // K Sim3OptProblem: views and Sim3 from the host, scale and match range from the device
-    Piece<char> reproj_tab, geo_tab;       // K ReprojProblem (camera 2, modes, margin), K + 1 grid geometries
+    Piece<char> reproj_tab;                // K ReprojProblem (camera 2, modes, margin)
+    Piece<char> grid_tab;                  // 3K + 1 GridProblem: the K + 1 keypoint sets, then the rows of the 2K matcher problems
     Piece<char> cand_tab, replay_tab;      // 2K CandProblem / CandBatchReplay
     // ---- uploaded: the prior matches, K x n1
     Piece<uint8_t> prior_state;
@@ -118,7 +119,7 @@ void loop_sim3_layout(A& arena, const LoopSim3Shape& H, LoopSim3Pieces& Y) {
     Y.scale_in = optional_piece<float>(arena, H.has_scale_in, K);
     Y.prob = arena.template piece<char>(K * H.prob_rec);
     Y.reproj_tab = arena.template piece<char>(K * H.reproj_rec);
-    Y.geo_tab = arena.template piece<char>((K + 1) * H.geo_rec);
+    Y.grid_tab = arena.template piece<char>((3 * K + 1) * H.grid_rec);
     Y.cand_tab = arena.template piece<char>(2 * K * H.cand_rec);
     Y.replay_tab = arena.template piece<char>(2 * K * H.replay_rec);
     Y.prior_state = arena.template piece<uint8_t>(E);

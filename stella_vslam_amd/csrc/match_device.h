@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "match_kernels.h"
+#include "sv_wave.h"
 
 namespace svmd {
 
@@ -112,6 +113,91 @@ __device__ __forceinline__ void grid_frame_one(const GridProblem& G, const int n
         }
         __syncthreads();
     }
+}
+
+// ---- the grid lists of larger frames and of several keypoint sets at once: the bodies behind k_grid_assign / k_grid_place / k_grid_walk
+// and their _batch forms (match_kernels.hip).  data::assign_keypoints_to_grid (data/common.cc:83-108) and data::get_keypoints_in_cell
+// (:127-190): cells are x-major (col * rows + row), a cell lists its keypoints in index order, a query scans cells col-major inside its
+// window and keeps keypoints of the wanted levels strictly inside the margin square -- the reference's candidate ORDER, which decides
+// ties downstream.
+
+// the cell of keypoint i is counted (counts in cell_off; scanned in place afterwards) and noted as id_base + cell, -1 outside the grid;
+// id_base = 0 for one set, the set's first counter among all sets' for a batch
+__device__ __forceinline__ void grid_assign_one(const GridProblem& G, const int i, const int id_base) {
+    const int cx = (int)floor((double)(G.t_xy[2 * i] - G.min_x) * G.inv_w), cy = (int)floor((double)(G.t_xy[2 * i + 1] - G.min_y) * G.inv_h);
+    int c = -1;
+    if (0 <= cx && cx < G.cols && 0 <= cy && cy < G.rows) {
+        c = cx * G.rows + cy;
+        atomicAdd(&G.cell_off[c], 1);
+        c += id_base;
+    }
+    G.cell_of[i] = c;
+}
+// stable placement: the rank of keypoint i inside its cell = the number of keypoints in [first, i) with the same cell id `c`; the ids
+// stream through LDS tiles (whole workgroup of 256; n = the length of cell_of)
+__device__ __forceinline__ int grid_rank_in_cell(const int32_t* __restrict__ cell_of, const int n, const int first, const int i, const int c) {
+    __shared__ int s_cell[1024];
+    const int last = min((int)blockIdx.x * 256 + 255, n - 1);  // tiles beyond the block's last keypoint hold no earlier keypoint
+    int rank = 0;
+    for (int base = first; base <= last; base += 1024) {
+        __syncthreads();
+        for (int k = threadIdx.x; k < 1024; k += 256) s_cell[k] = base + k < n ? cell_of[base + k] : -2;
+        __syncthreads();
+        const int m = min(1024, i - base);  // earlier keypoints only
+        for (int k = 0; k < m; ++k) rank += s_cell[k] == c;
+    }
+    return rank;
+}
+// one wave per query q of G: the lanes take the cells of the window (column-major = the reference's scan order), count their keypoints
+// that pass the level and margin tests, and a wave prefix sum gives every cell its place in the query's list.  FILL = false leaves the
+// list's size in cand_off[q]; FILL = true writes the list behind cand_idx + cand_off[q]
+template <bool FILL>
+__device__ __forceinline__ void grid_walk_one(const GridProblem& G, const int q, const int lane) {
+    int total = 0;
+    const bool live = !G.q_valid || G.q_valid[q];
+    if (live) {
+        const float ref_x = G.q_xy[2 * q], ref_y = G.q_xy[2 * q + 1], margin = G.q_margin[q];
+        const int min_level = G.q_min_level ? G.q_min_level[q] : -1, max_level = G.q_max_level ? G.q_max_level[q] : -1;
+        int lo_x = (int)floor((double)(ref_x - G.min_x - margin) * G.inv_w), hi_x = (int)ceil((double)(ref_x - G.min_x + margin) * G.inv_w);
+        int lo_y = (int)floor((double)(ref_y - G.min_y - margin) * G.inv_h), hi_y = (int)ceil((double)(ref_y - G.min_y + margin) * G.inv_h);
+        lo_x = max(lo_x, 0);
+        lo_y = max(lo_y, 0);
+        hi_x = min(hi_x, G.cols - 1);
+        hi_y = min(hi_y, G.rows - 1);
+        if (lo_x < G.cols && 0 <= hi_x && lo_y < G.rows && 0 <= hi_y && lo_x <= hi_x && lo_y <= hi_y) {
+            const int ny = hi_y - lo_y + 1, ncell = (hi_x - lo_x + 1) * ny;
+            int32_t* out = FILL ? G.cand_idx + G.cand_off[q] : nullptr;
+            for (int base = 0; base < ncell; base += 64) {
+                const int k = base + lane;
+                int n = 0, c = 0;
+                if (k < ncell) {
+                    c = (lo_x + k / ny) * G.rows + lo_y + k % ny;
+                    for (int it = G.cell_off[c]; it < G.cell_off[c + 1]; ++it) {
+                        const int idx = G.cell_items[it];
+                        const int oct = G.t_octave[idx];
+                        if (0 <= min_level && oct < min_level) continue;
+                        if (0 <= max_level && max_level < oct) continue;
+                        const float dx = G.t_xy[2 * idx] - ref_x, dy = G.t_xy[2 * idx + 1] - ref_y;
+                        if (fabsf(dx) < margin && fabsf(dy) < margin) ++n;
+                    }
+                }
+                const int incl = sv_wave_inclusive_sum(n);
+                if (FILL && n > 0) {
+                    int o = total + incl - n;
+                    for (int it = G.cell_off[c]; it < G.cell_off[c + 1]; ++it) {
+                        const int idx = G.cell_items[it];
+                        const int oct = G.t_octave[idx];
+                        if (0 <= min_level && oct < min_level) continue;
+                        if (0 <= max_level && max_level < oct) continue;
+                        const float dx = G.t_xy[2 * idx] - ref_x, dy = G.t_xy[2 * idx + 1] - ref_y;
+                        if (fabsf(dx) < margin && fabsf(dy) < margin) out[o++] = idx;
+                    }
+                }
+                total += __builtin_amdgcn_readlane(incl, 63);
+            }
+        }
+    }
+    if (!FILL && lane == 0) G.cand_off[q] = total;
 }
 
 }  // namespace svmd

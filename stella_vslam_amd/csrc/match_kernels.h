@@ -111,8 +111,16 @@ struct CandBatchReplay {
     int* match;
 };
 size_t sv_cand_lds_bytes(int nq, int nt, int K);  // dynamic LDS of the LDS-resident form
-void sv_launch_cand_batch(svgpu_ctx* ctx, hipStream_t s, const CandProblem* tab, const CandBatchReplay* form, const int32_t* row_base, int num_problems,
-                          int rows, size_t lds_bytes);
+// what a launcher that chooses its own launch count issued: the callers that report svgpu_call_stats add these up
+struct SvIssued {
+    int launches = 0, copies = 0;  // kernel launches; memsets and memcpys
+    SvIssued& operator+=(const SvIssued& o) {
+        launches += o.launches, copies += o.copies;
+        return *this;
+    }
+};
+SvIssued sv_launch_cand_batch(svgpu_ctx* ctx, hipStream_t s, const CandProblem* tab, const CandBatchReplay* form, const int32_t* row_base, int num_problems,
+                              int rows, size_t lds_bytes);
 
 // Device-side candidate lists: data::assign_keypoints_to_grid + data::get_keypoints_in_cell (data/common.cc:83-190)
 struct GridProblem {
@@ -135,10 +143,19 @@ struct GridProblem {
     int32_t* cand_idx;        // filled by the second walk
     int cap;                  // > 0: capacity of cand_idx; the fill does nothing when the lists' total (cand_off[nq]) exceeds it (the host re-runs)
 };
-void sv_launch_grid_build(hipStream_t s, const GridProblem& G);                 // cell_of, cell_off, cell_items, cand_off (scanned)
-void sv_launch_grid_frame(hipStream_t s, const GridProblem& G);                 // ... the keypoint side alone (a resident frame is binned once)
-void sv_launch_grid_queries(hipStream_t s, const GridProblem& G);               // ... the query side over an already binned frame
-void sv_launch_grid_fill(hipStream_t s, const GridProblem& G);                  // cand_idx
+SvIssued sv_launch_grid_build(hipStream_t s, const GridProblem& G);             // cell_of, cell_off, cell_items, cand_off (scanned)
+SvIssued sv_launch_grid_frame(hipStream_t s, const GridProblem& G);             // ... the keypoint side alone (a resident frame is binned once)
+SvIssued sv_launch_grid_queries(hipStream_t s, const GridProblem& G);           // ... the query side over an already binned frame
+SvIssued sv_launch_grid_fill(hipStream_t s, const GridProblem& G);              // cand_idx
+// The same for records of GridProblems in device memory.  Keypoint sets (num_sets records, set u = keypoints [set_base[u], set_base[u + 1])
+// of the concatenation): all sets share ONE counter array `cell_cnt` (zero on entry, scanned once, the total behind its `counters`
+// entries) and record u's cell_off points at its own cells inside it; cell_of of record u = one array + set_base[u]; items are indices
+// inside the set and a cell lists them in index order.  Rows (num_problems records, problem p = rows [row_base[p], row_base[p + 1])):
+// a record's cell side is its set's, its q_* and cand_off pointers are one array + row_base[p] and cand_idx the one list itself, as
+// CandProblem records have them; the fill writes nothing when the total cand_off[rows] exceeds `cap`.
+SvIssued sv_launch_grid_sets(hipStream_t s, const GridProblem* tab, const int32_t* set_base, int num_sets, int keypoints, int32_t* cell_cnt, int counters);
+SvIssued sv_launch_grid_queries_batch(hipStream_t s, const GridProblem* tab, const int32_t* row_base, int num_problems, int rows, int32_t* cand_off);
+SvIssued sv_launch_grid_fill_batch(hipStream_t s, const GridProblem* tab, const int32_t* row_base, int num_problems, int rows, int cap);
 
 struct StereoProblem {
     const svgpu_keypoint* kl;

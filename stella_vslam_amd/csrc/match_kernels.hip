@@ -1310,61 +1310,38 @@ __global__ __launch_bounds__(1024) void k_cand_replay_batch(const CandProblem* _
 
 // ------------------------------------------------------------------------------------------------ grid candidate lists
 // data::assign_keypoints_to_grid (data/common.cc:83-108) and data::get_keypoints_in_cell (:127-190) on the device, so that the
-// projection-family matchers need no host-built CSR: cells are x-major (col * rows + row), a cell lists its keypoints in
-// index order, a query scans cells col-major inside its window and keeps keypoints of the wanted levels strictly inside
-// the margin square -- the reference's candidate ORDER, which decides ties downstream.
+// projection-family matchers need no host-built CSR.  The bodies are in match_device.h; a kernel here is a thin wrapper over one
+// GridProblem, its _batch twin the same body over a record of a table of GridProblems in device memory.
 __global__ void k_grid_assign(GridProblem G) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= G.nt) return;
-    const int cx = (int)floor((double)(G.t_xy[2 * i] - G.min_x) * G.inv_w), cy = (int)floor((double)(G.t_xy[2 * i + 1] - G.min_y) * G.inv_h);
-    int c = -1;
-    if (0 <= cx && cx < G.cols && 0 <= cy && cy < G.rows) {
-        c = cx * G.rows + cy;
-        atomicAdd(&G.cell_off[c], 1);  // counts; scanned in place afterwards
-    }
-    G.cell_of[i] = c;
+    if (i < G.nt) grid_assign_one(G, i, 0);
 }
-// in-place exclusive scan of data[0..n) with the total written to data[n]; single workgroup
-__global__ __launch_bounds__(1024) void k_exclusive_scan(int32_t* __restrict__ data, int n) {
-    __shared__ int s_part[1024];
-    __shared__ int s_carry;
-    const int tid = threadIdx.x;
-    if (tid == 0) s_carry = 0;
-    __syncthreads();
-    for (int base = 0; base < n; base += 1024) {
-        const int i = base + tid;
-        const int v = i < n ? data[i] : 0;
-        s_part[tid] = v;
-        __syncthreads();
-        for (int off = 1; off < 1024; off <<= 1) {  // Hillis-Steele inclusive scan
-            const int add = tid >= off ? s_part[tid - off] : 0;
-            __syncthreads();
-            s_part[tid] += add;
-            __syncthreads();
-        }
-        const int carry = s_carry;
-        if (i < n) data[i] = carry + s_part[tid] - v;
-        __syncthreads();
-        if (tid == 1023) s_carry = carry + s_part[1023];
-        __syncthreads();
-    }
-    if (tid == 0) data[n] = s_carry;
-}
-// stable placement: rank inside the cell = number of earlier keypoints of the same cell (cell ids stream through LDS tiles)
 __global__ __launch_bounds__(256) void k_grid_place(GridProblem G) {
-    __shared__ int s_cell[1024];
     const int i = blockIdx.x * 256 + threadIdx.x;
     const int c = i < G.nt ? G.cell_of[i] : -1;
-    const int last = min(blockIdx.x * 256 + 255, G.nt - 1);  // tiles beyond the block's last keypoint hold no earlier keypoint
-    int rank = 0;
-    for (int base = 0; base <= last; base += 1024) {
-        __syncthreads();
-        for (int k = threadIdx.x; k < 1024; k += 256) s_cell[k] = base + k < G.nt ? G.cell_of[base + k] : -2;
-        __syncthreads();
-        const int m = min(1024, i - base);  // earlier keypoints only
-        for (int k = 0; k < m; ++k) rank += s_cell[k] == c;
-    }
+    const int rank = grid_rank_in_cell(G.cell_of, G.nt, 0, i, c);
     if (c >= 0) G.cell_items[G.cell_off[c] + rank] = i;
+}
+// Several keypoint sets binned at once (sv_launch_grid_sets): keypoint g of all sets belongs to set u = sv_segment_of(set_base, .., g).
+// The sets' counters are ONE array (tab[0].cell_off its start, scanned once), their cell_of ONE array (tab[0].cell_of its start, set u's
+// part at set_base[u]); a cell's id is the index of its counter in that array, so keypoints of different sets never share an id.
+__global__ __launch_bounds__(256) void k_grid_assign_batch(const GridProblem* __restrict__ tab, const int32_t* __restrict__ set_base, int num_sets) {
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    if (g >= set_base[num_sets]) return;
+    const int u = sv_segment_of(set_base, num_sets, g);
+    grid_assign_one(tab[u], g - set_base[u], (int)(tab[u].cell_off - tab[0].cell_off));
+}
+// the workgroup's tiles start at the first keypoint of the set that holds the workgroup's first keypoint: earlier sets hold no keypoint
+// of these cells (the ids differ), the starting point only avoids walking them.  The item is the index inside the set.
+__global__ __launch_bounds__(256) void k_grid_place_batch(const GridProblem* __restrict__ tab, const int32_t* __restrict__ set_base, int num_sets) {
+    const int g = blockIdx.x * 256 + threadIdx.x, n = set_base[num_sets];
+    const int32_t* __restrict__ cell_of = tab[0].cell_of;
+    const int c = g < n ? cell_of[g] : -1;
+    const int first = set_base[sv_segment_of(set_base, num_sets, blockIdx.x * 256)];
+    const int rank = grid_rank_in_cell(cell_of, n, first, g, c);
+    if (c < 0) return;
+    const int u = sv_segment_of(set_base, num_sets, g);
+    tab[u].cell_items[tab[0].cell_off[c] + rank] = g - set_base[u];
 }
 // The keypoint side of the matcher grid in ONE launch of one workgroup (grids up to GRID_ONE_CELLS cells; the reference's is 64 x 48):
 // cell of every keypoint + its arrival number in the cell (LDS counters), exclusive scan of the counters (-> cell_off), unordered placement,
@@ -1374,65 +1351,24 @@ __global__ __launch_bounds__(256) void k_grid_place(GridProblem G) {
 __global__ __launch_bounds__(1024) void k_grid_frame_one(GridProblem G) {
     grid_frame_one(G, G.nt);
 }
-// one wave per query: the lanes take the cells of the window (column-major = the reference's scan order), count their
-// keypoints that pass the level and margin tests, and a wave prefix sum gives every cell its place in the query's list
 template <bool FILL>
 __global__ __launch_bounds__(256) void k_grid_walk(GridProblem G) {
     const int q = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;  // scalar: per-query data via scalar loads
     if (q >= G.nq) return;
     if (FILL && G.cap > 0 && G.cand_off[G.nq] > G.cap) return;  // capacity guess too small: nothing is written, the host re-runs
-    int total = 0;
-    const bool live = !G.q_valid || G.q_valid[q];
-    if (live) {
-        const float ref_x = G.q_xy[2 * q], ref_y = G.q_xy[2 * q + 1], margin = G.q_margin[q];
-        const int min_level = G.q_min_level ? G.q_min_level[q] : -1, max_level = G.q_max_level ? G.q_max_level[q] : -1;
-        int lo_x = (int)floor((double)(ref_x - G.min_x - margin) * G.inv_w), hi_x = (int)ceil((double)(ref_x - G.min_x + margin) * G.inv_w);
-        int lo_y = (int)floor((double)(ref_y - G.min_y - margin) * G.inv_h), hi_y = (int)ceil((double)(ref_y - G.min_y + margin) * G.inv_h);
-        lo_x = max(lo_x, 0);
-        lo_y = max(lo_y, 0);
-        hi_x = min(hi_x, G.cols - 1);
-        hi_y = min(hi_y, G.rows - 1);
-        if (lo_x < G.cols && 0 <= hi_x && lo_y < G.rows && 0 <= hi_y && lo_x <= hi_x && lo_y <= hi_y) {
-            const int ny = hi_y - lo_y + 1, ncell = (hi_x - lo_x + 1) * ny;
-            int32_t* out = FILL ? G.cand_idx + G.cand_off[q] : nullptr;
-            for (int base = 0; base < ncell; base += 64) {
-                const int k = base + lane;
-                int n = 0, c = 0;
-                if (k < ncell) {
-                    c = (lo_x + k / ny) * G.rows + lo_y + k % ny;
-                    for (int it = G.cell_off[c]; it < G.cell_off[c + 1]; ++it) {
-                        const int idx = G.cell_items[it];
-                        const int oct = G.t_octave[idx];
-                        if (0 <= min_level && oct < min_level) continue;
-                        if (0 <= max_level && max_level < oct) continue;
-                        const float dx = G.t_xy[2 * idx] - ref_x, dy = G.t_xy[2 * idx + 1] - ref_y;
-                        if (fabsf(dx) < margin && fabsf(dy) < margin) ++n;
-                    }
-                }
-                // inclusive prefix sum over the lanes: DPP row scans (VALU; six __shfl_up were six LDS-crossbar round trips on every query's chain)
-                int incl = n;
-                incl += __builtin_amdgcn_update_dpp(0, incl, 0x111, 0xF, 0xF, false);  // row_shr:1
-                incl += __builtin_amdgcn_update_dpp(0, incl, 0x112, 0xF, 0xF, false);  // row_shr:2
-                incl += __builtin_amdgcn_update_dpp(0, incl, 0x114, 0xF, 0xF, false);  // row_shr:4
-                incl += __builtin_amdgcn_update_dpp(0, incl, 0x118, 0xF, 0xF, false);  // row_shr:8: scans inside the four rows of 16
-                incl += __builtin_amdgcn_update_dpp(0, incl, 0x142, 0xA, 0xF, false);  // row_bcast:15 into rows 1 and 3
-                incl += __builtin_amdgcn_update_dpp(0, incl, 0x143, 0xC, 0xF, false);  // row_bcast:31 into rows 2 and 3
-                if (FILL && n > 0) {
-                    int o = total + incl - n;
-                    for (int it = G.cell_off[c]; it < G.cell_off[c + 1]; ++it) {
-                        const int idx = G.cell_items[it];
-                        const int oct = G.t_octave[idx];
-                        if (0 <= min_level && oct < min_level) continue;
-                        if (0 <= max_level && max_level < oct) continue;
-                        const float dx = G.t_xy[2 * idx] - ref_x, dy = G.t_xy[2 * idx + 1] - ref_y;
-                        if (fabsf(dx) < margin && fabsf(dy) < margin) out[o++] = idx;
-                    }
-                }
-                total += __builtin_amdgcn_readlane(incl, 63);
-            }
-        }
-    }
-    if (!FILL && lane == 0) G.cand_off[q] = total;
+    grid_walk_one<FILL>(G, q, lane);
+}
+// The queries of several problems as ONE concatenation of rows (sv_launch_grid_queries_batch / _fill_batch): row g is query g - row_base[p]
+// of record p.  The records' cand_off / cand_idx are offsets into ONE pair of lists (tab[0].cand_off its start), as CandProblem records
+// have them; the fill's capacity test reads the total behind the last row.
+template <bool FILL>
+__global__ __launch_bounds__(256) void k_grid_walk_batch(const GridProblem* __restrict__ tab, const int32_t* __restrict__ row_base, int num_problems, int cap) {
+    const int g = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int rows = row_base[num_problems];
+    if (g >= rows) return;
+    if (FILL && cap > 0 && tab[0].cand_off[rows] > cap) return;
+    const int p = __builtin_amdgcn_readfirstlane(sv_segment_of(row_base, num_problems, g));  // wave-uniform: the record through scalar loads
+    grid_walk_one<FILL>(tab[p], g - row_base[p], lane);
 }
 
 // area::match_in_consistent_area (match/area.cc:8-98) on the same CSR lists and distances (mode SVGPU_MATCH_AREA).
@@ -1827,33 +1763,55 @@ void sv_launch_bf(svgpu_ctx* ctx, hipStream_t s, const BfProblem& P0, int pairs,
         hipLaunchKernelGGL((k_bf_replay<4, 1024>), dim3(pairs), dim3(1024), lds, s, P, g_owner, g_match, use_lds, pool_rows);
     }
 }
-// exclusive scan of the grid's counters: the shuffle-based one-workgroup scan of sv_sort.hip (4.5 us) up to its 16 k elements, the
-// Hillis-Steele kernel above (9 us per 1 024 elements, needs no scratch) beyond
-static void grid_scan(hipStream_t s, int32_t* data, int n) {
-    if (n <= 16384) sv_scan_i32(s, data, n, nullptr);
-    else hipLaunchKernelGGL(k_exclusive_scan, dim3(1), dim3(1024), 0, s, data, n);
-}
-void sv_launch_grid_frame(hipStream_t s, const GridProblem& G) {  // the keypoint side: cell_of, cell_off, cell_items
+// The grid launchers report what they issued (SvIssued): the callers that tally a call's launches and copies add it up.  The scans are
+// sv_scan_i32 without scratch: one launch whatever the size; cell_off and cand_off start arena pieces, which gives the scan its alignment.
+SvIssued sv_launch_grid_frame(hipStream_t s, const GridProblem& G) {  // the keypoint side: cell_of, cell_off, cell_items
     const int nc = G.cols * G.rows;
+    SvIssued n;
     if (nc <= GRID_ONE_CELLS && G.nt <= 1024 * GRID_ONE_KPT_ROUNDS && !std::getenv("SVGPU_GRID_FOUR_LAUNCHES")) {
         hipLaunchKernelGGL(k_grid_frame_one, dim3(1), dim3(1024), 0, s, G);
-        return;
+        ++n.launches;
+        return n;
     }
     (void)hipMemsetAsync(G.cell_off, 0, (size_t)(nc + 1) * sizeof(int32_t), s);
+    ++n.copies;
     if (G.nt > 0) hipLaunchKernelGGL(k_grid_assign, dim3((G.nt + 255) / 256), dim3(256), 0, s, G);
-    grid_scan(s, G.cell_off, nc);
+    n.launches += sv_scan_i32(s, G.cell_off, nc, nullptr);
     if (G.nt > 0) hipLaunchKernelGGL(k_grid_place, dim3((G.nt + 255) / 256), dim3(256), 0, s, G);
+    n.launches += G.nt > 0 ? 2 : 0;
+    return n;
 }
-void sv_launch_grid_queries(hipStream_t s, const GridProblem& G) {  // the query side over a binned frame: list sizes + their scan
+SvIssued sv_launch_grid_queries(hipStream_t s, const GridProblem& G) {  // the query side over a binned frame: list sizes + their scan
+    SvIssued n;
     if (G.nq > 0) hipLaunchKernelGGL(k_grid_walk<false>, dim3((G.nq + 3) / 4), dim3(256), 0, s, G);
-    grid_scan(s, G.cand_off, G.nq);
+    n.launches = (G.nq > 0) + sv_scan_i32(s, G.cand_off, G.nq, nullptr);
+    return n;
 }
-void sv_launch_grid_build(hipStream_t s, const GridProblem& G) {
-    sv_launch_grid_frame(s, G);
-    sv_launch_grid_queries(s, G);
+SvIssued sv_launch_grid_build(hipStream_t s, const GridProblem& G) {
+    SvIssued n = sv_launch_grid_frame(s, G);
+    n += sv_launch_grid_queries(s, G);
+    return n;
 }
-void sv_launch_grid_fill(hipStream_t s, const GridProblem& G) {
+SvIssued sv_launch_grid_fill(hipStream_t s, const GridProblem& G) {
     if (G.nq > 0) hipLaunchKernelGGL(k_grid_walk<true>, dim3((G.nq + 3) / 4), dim3(256), 0, s, G);
+    return SvIssued{G.nq > 0, 0};
+}
+// The batch forms: records in device memory.  `keypoints` = set_base[num_sets], `rows` = row_base[num_problems], known to the host too.
+// The `counters` cell counters of all sets (cell_cnt = tab[0].cell_off) are zero on entry and scanned once; cell_cnt[counters] = the keypoints inside a grid
+SvIssued sv_launch_grid_sets(hipStream_t s, const GridProblem* tab, const int32_t* set_base, int num_sets, int keypoints, int32_t* cell_cnt, int counters) {
+    if (keypoints > 0) hipLaunchKernelGGL(k_grid_assign_batch, dim3((keypoints + 255) / 256), dim3(256), 0, s, tab, set_base, num_sets);
+    SvIssued n{sv_scan_i32(s, cell_cnt, counters, nullptr), 0};
+    if (keypoints > 0) hipLaunchKernelGGL(k_grid_place_batch, dim3((keypoints + 255) / 256), dim3(256), 0, s, tab, set_base, num_sets);
+    n.launches += keypoints > 0 ? 2 : 0;
+    return n;
+}
+SvIssued sv_launch_grid_queries_batch(hipStream_t s, const GridProblem* tab, const int32_t* row_base, int num_problems, int rows, int32_t* cand_off) {
+    if (rows > 0) hipLaunchKernelGGL(k_grid_walk_batch<false>, dim3((rows + 3) / 4), dim3(256), 0, s, tab, row_base, num_problems, 0);
+    return SvIssued{(rows > 0) + sv_scan_i32(s, cand_off, rows, nullptr), 0};
+}
+SvIssued sv_launch_grid_fill_batch(hipStream_t s, const GridProblem* tab, const int32_t* row_base, int num_problems, int rows, int cap) {
+    if (rows > 0) hipLaunchKernelGGL(k_grid_walk_batch<true>, dim3((rows + 3) / 4), dim3(256), 0, s, tab, row_base, num_problems, cap);
+    return SvIssued{rows > 0, 0};
 }
 // Which form the replay of (nq queries, nt targets) takes -- the one place that decides it (svgpu_selftest_cand_replay_form reports it).
 //   mode AREA: 1 = k_area_replay keeps holder / distance / match tables in LDS (up to 60 KiB), 0 = in global memory
@@ -1878,13 +1836,14 @@ void sv_launch_cand(svgpu_ctx* ctx, hipStream_t s, const CandProblem& P, int* ow
 }
 // K problems (records of `tab` / `form` in device memory): distances for all rows, then one replay workgroup per problem.  `lds_bytes`
 // = the largest LDS-resident form among them (0: none takes it)
-void sv_launch_cand_batch(svgpu_ctx* ctx, hipStream_t s, const CandProblem* tab, const CandBatchReplay* form, const int32_t* row_base, int num_problems,
-                          int rows, size_t lds_bytes) {
+SvIssued sv_launch_cand_batch(svgpu_ctx* ctx, hipStream_t s, const CandProblem* tab, const CandBatchReplay* form, const int32_t* row_base, int num_problems,
+                              int rows, size_t lds_bytes) {
     SvProfScope ps(ctx, s, "k_cand_batch");
-    if (num_problems <= 0) return;
+    if (num_problems <= 0) return SvIssued{};
     if (rows > 0) hipLaunchKernelGGL(k_cand_dist_batch, dim3(rows), dim3(64), 0, s, tab, row_base, num_problems);
     (void)sv_allow_dynamic_lds((const void*)k_cand_replay_batch, CAND_LDS_BUDGET);
     hipLaunchKernelGGL(k_cand_replay_batch, dim3(num_problems), dim3(1024), lds_bytes, s, tab, form);
+    return SvIssued{rows > 0 ? 2 : 1, 0};
 }
 size_t sv_cand_lds_bytes(int nq, int nt, int K) { return cand_lds_bytes(nq, nt, K, false); }
 void sv_launch_cand_replay(svgpu_ctx* ctx, hipStream_t s, const CandProblem& P0, int* owner, int* match) {

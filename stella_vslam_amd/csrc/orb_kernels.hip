@@ -11,6 +11,7 @@
 // operation order with contraction disabled (-ffp-contract=off, checked in the disassembly).
 #include "svgpu_internal.h"
 #include "sv_trig.h"
+#include "sv_wave.h"
 #include <utility>
 
 #pragma clang fp contract(off)
@@ -1002,13 +1003,7 @@ __global__ __launch_bounds__(256) void k_fast(const OrbLevel* __restrict__ L, in
         // its patch.  The queue order is patch by patch along a band of four rows -- neighbouring lanes of pass B then work on
         // neighbouring pixels, which its ring reads need (a queue in which a lane's entries were 16 rows apart cost +8 %).
         const int cnt = __popc(m);
-        int incl = cnt;
-        incl += __builtin_amdgcn_update_dpp(0, incl, 0x111, 0xF, 0xF, false);  // row_shr:1
-        incl += __builtin_amdgcn_update_dpp(0, incl, 0x112, 0xF, 0xF, false);  // row_shr:2
-        incl += __builtin_amdgcn_update_dpp(0, incl, 0x114, 0xF, 0xF, false);  // row_shr:4
-        incl += __builtin_amdgcn_update_dpp(0, incl, 0x118, 0xF, 0xF, false);  // row_shr:8
-        incl += __builtin_amdgcn_update_dpp(0, incl, 0x142, 0xA, 0xF, false);  // row_bcast:15
-        incl += __builtin_amdgcn_update_dpp(0, incl, 0x143, 0xC, 0xF, false);  // row_bcast:31
+        const int incl = sv_wave_inclusive_sum(cnt);
         wq = __builtin_amdgcn_readlane(incl, 63);
         int pos = incl - cnt;
         while (m) {
@@ -1163,13 +1158,7 @@ __device__ __forceinline__ float dev_util_sin(float v) { return sv_util_sin(v); 
 __device__ __forceinline__ int wave_sum(int v) {
     // row scans with DPP adds (one VALU instruction each, no LDS round trip), then the row totals across rows; the wave total
     // lands in lane 63 and is broadcast through a scalar register.  Integer adds: any order gives the same sum.
-    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, false);  // row_shr:1
-    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, false);  // row_shr:2
-    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, false);  // row_shr:4
-    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, false);  // row_shr:8   -> lane 15 of every row holds the row sum
-    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false);  // row_bcast:15 into rows 1 and 3
-    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false);  // row_bcast:31 into rows 2 and 3
-    return __builtin_amdgcn_readlane(v, 63);
+    return __builtin_amdgcn_readlane(sv_wave_inclusive_sum(v), 63);
 }
 
 // ---- orientation + descriptors.  One wave per keypoint, DESC_KPW keypoints per wave one after the other (the rBRIEF pattern

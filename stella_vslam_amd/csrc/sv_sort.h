@@ -1,13 +1,17 @@
-// Hand-written device sorts / scans shared by the BA structure builder (ba_pairs.hip) and the BoW merge-join (bucket_kernels.hip).
+// Hand-written device sorts / scans shared by the BA structure builder (ba_pairs.hip), the grid and bucket candidate lists
+// (match_kernels.hip, bucket_kernels.hip) and through them every matcher call.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstddef>
 #include <cstdint>
 
-// in-place exclusive scan of data[0 .. n), total to data[n] (data 16-byte aligned); `scratch` = sv_scan_scratch_ints(n) ints (0 for small n:
-// one workgroup; beyond that tile sums, their scan, and a scan of every tile behind its offset)
+// in-place exclusive scan of data[0 .. n), total to data[n]; 0 <= n <= SV_SCAN_MAX, data 16-byte aligned (the start of an arena piece is).
+// Returns the launches it issued.  scratch == nullptr: ONE launch of one workgroup that walks tiles of 16 k elements, correct for every n
+// (~9 us per tile: for callers that must not add launches or have no scratch).  With `scratch` = sv_scan_scratch_ints(n) ints (0 up to
+// 16 k elements, where the form is the same one launch): tile sums, their scan, and a scan of every tile behind its offset, 3 launches.
+#define SV_SCAN_MAX (INT32_MAX - 16384)  // (the one-workgroup kernel steps its int index a tile beyond n)
 size_t sv_scan_scratch_ints(size_t n);
-void sv_scan_i32(hipStream_t s, int* data, int n, int* scratch);
+int sv_scan_i32(hipStream_t s, int* data, int n, int* scratch);
 // stable least-significant-digit radix sort (6-bit digits) of n (u32 key, u64 value) pairs by the low `bits` key bits, ping-ponging between
 // the two buffer sets; `hist` = sv_sort_hist_ints(n) ints of scratch.  The data starts in set `start`; returns the set that holds the result
 // (start ^ (passes & 1)).  Key bits above `bits` travel with the key and order nothing: the last digit is cut where `bits` ends.

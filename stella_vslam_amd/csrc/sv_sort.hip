@@ -267,15 +267,16 @@ __global__ __launch_bounds__(1024) void k_sort_small_sides(const SvSortSide* __r
 }  // namespace
 
 size_t sv_scan_scratch_ints(size_t n) { return n > SCAN_SINGLE_MAX ? (n + SCAN_TILE - 1) / SCAN_TILE + 8 : 0; }
-void sv_scan_i32(hipStream_t s, int* data, int n, int* scratch) {
-    if (n <= SCAN_SINGLE_MAX) {
+int sv_scan_i32(hipStream_t s, int* data, int n, int* scratch) {
+    if (n <= SCAN_SINGLE_MAX || !scratch) {
         hipLaunchKernelGGL(k_scan_i32, dim3(1), dim3(1024), 0, s, data, n);
-        return;
+        return 1;
     }
     const int ntiles = (n + SCAN_TILE - 1) / SCAN_TILE;
     hipLaunchKernelGGL(k_scan_tile_sums, dim3(ntiles), dim3(256), 0, s, data, n, scratch);
     hipLaunchKernelGGL(k_scan_i32, dim3(1), dim3(1024), 0, s, scratch, ntiles);  // scratch[ntiles] = the total
     hipLaunchKernelGGL(k_scan_tiles, dim3(ntiles), dim3(256), 0, s, data, n, scratch, ntiles);
+    return 3;
 }
 int sv_sort_passes(int bits) { return (bits + RS_BITS - 1) / RS_BITS; }
 static inline size_t hist_ints(size_t n) { return ((size_t)RS_BINS * ((n + RS_TILE - 1) / RS_TILE + 1) + 1 + 3) & ~size_t(3); }  // the scan's scratch follows, 16-byte aligned

@@ -11,6 +11,7 @@
 #include "loop_sim3_layout.h"
 #include "sim3opt_kernels.h"
 #include "frame_device.h"
+#include "sv_sort.h"
 #include "sv_validate.h"
 
 using namespace svm;
@@ -19,15 +20,9 @@ namespace {
 
 #define LOOP_NO_RATIO 0xFFFFFFFFu  // ratio_bits of a pair that gives no ratio (no kept ratio has this pattern: it is a NaN's)
 
-struct LoopGeo {  // the grid of one keypoint set: data/common.cc:86-87 via camera::base
-    float min_x, min_y;
-    double inv_w, inv_h;
-};
-
 struct LoopDev {
-    int K, n1, N2, ncell, cols, rows;
+    int K, n1, N2;
     int rows_a, rows_all;  // K x n1, K x n1 + N2
-    int cap;               // capacity of the candidate lists
     float inv_level_sigma_sq[SV_MAX_LEVELS];
     double pose_1w[12];
     // keyframe 1
@@ -42,23 +37,21 @@ struct LoopDev {
     const double* pos_w2;
     const uint8_t* has_lm2;
     const float *min2, *max2;
-    const int32_t *kf2_off, *set_base;
+    const int32_t* kf2_off;
     const double *pose_in_cand, *pose_2w, *rot_12, *trans_12;
     const uint8_t* active;
     const float* scale_in;  // nullable
     Sim3OptProblem* prob;
     const ReprojProblem* reproj_tab;
-    const LoopGeo* geo;
     const uint8_t* prior_state;
     const int32_t* prior_idx2;
     const double* prior_pos_w;
     uint32_t* ratio_bits;
     double* xf;
     uint8_t *live, *already2;
-    int32_t *cell_cnt, *cell_of, *cell_items;
     uint8_t* visible;
     float *q_xy, *q_margin;
-    int32_t *q_min_level, *q_max_level, *cand_off, *cand_idx;
+    int32_t *q_min_level, *q_max_level;
     double *obs1, *obs2, *pos1, *pos2;
     float *w1, *w2;
     float* scale;
@@ -174,61 +167,6 @@ __global__ void __launch_bounds__(1024) k_loop_scale(LoopDev D) {
     }
 }
 
-// ---- the keypoint sets (the candidates' keyframes, then keyframe 1) are binned in one pass: cell id = set x cells + cell.
-// data::assign_keypoints_to_grid (data/common.cc:83-108) with the set's own image bounds.
-__device__ __forceinline__ const float* loop_set_xy(const LoopDev& D, int g) { return g < D.N2 ? D.xy2 + 2 * (size_t)g : D.xy1 + 2 * (size_t)(g - D.N2); }
-__global__ void __launch_bounds__(256) k_loop_bin_count(LoopDev D) {
-    const int g = blockIdx.x * 256 + threadIdx.x;
-    if (g >= D.N2 + D.n1) return;
-    const int u = sv_segment_of(D.set_base, D.K + 1, g);
-    const LoopGeo& G = D.geo[u];
-    const float* xy = loop_set_xy(D, g);
-    const int cx = (int)floor((double)(xy[0] - G.min_x) * G.inv_w), cy = (int)floor((double)(xy[1] - G.min_y) * G.inv_h);
-    int c = -1;
-    if (0 <= cx && cx < D.cols && 0 <= cy && cy < D.rows) {
-        c = u * D.ncell + cx * D.rows + cy;
-        atomicAdd(&D.cell_cnt[c], 1);  // counts; scanned in place afterwards
-    }
-    D.cell_of[g] = c;
-}
-// stable placement: rank inside the cell = number of earlier keypoints of the same set in the same cell, so a cell lists its keypoints in
-// index order (the reference's candidate order, which decides ties downstream); the item is the index inside the set
-__global__ void __launch_bounds__(256) k_loop_bin_place(LoopDev D) {
-    const int g = blockIdx.x * 256 + threadIdx.x;
-    if (g >= D.N2 + D.n1) return;
-    const int c = D.cell_of[g];
-    if (c < 0) return;
-    const int first = D.set_base[sv_segment_of(D.set_base, D.K + 1, g)];
-    int rank = 0;
-    for (int j = first; j < g; ++j) rank += D.cell_of[j] == c;
-    D.cell_items[D.cell_cnt[c] + rank] = g - first;
-}
-// in-place exclusive scan of data[0 .. n), total to data[n]: one workgroup, every thread a contiguous run, whatever n -- one launch
-__global__ void __launch_bounds__(1024) k_loop_scan(int32_t* __restrict__ data, int n) {
-    __shared__ int s_wsum[16];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int per = (int)(((long long)n + 1023) / 1024);
-    const int c0 = (int)min((long long)tid * per, (long long)n), c1 = (int)min((long long)c0 + per, (long long)n);  // (tid * per may pass 2^31 for n near it)
-    int run = 0;
-    for (int c = c0; c < c1; ++c) run += data[c];
-    int incl = run;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int v = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += v;
-    }
-    if (lane == 63) s_wsum[wave] = incl;
-    __syncthreads();
-    int base = incl - run;
-    for (int w = 0; w < wave; ++w) base += s_wsum[w];
-    for (int c = c0; c < c1; ++c) {
-        const int k = data[c];
-        data[c] = base;
-        base += k;
-    }
-    if (tid == 1023) data[n] = base;  // (the last thread's run ends at n or is empty: its base is the total either way)
-}
-
 // the row's candidate and pass: rows [0, K n1) are pass A (p = row / n1), the rest pass B (rows of candidate p from K n1 + kf2_off[p])
 struct LoopRow {
     int p, q;    // candidate, query index inside the problem
@@ -269,73 +207,6 @@ __global__ void __launch_bounds__(256) k_loop_reproject(LoopDev D) {
     svfd::reproject_one(R, X, X + 9, zero, offered, pw[0], pw[1], pw[2], 0.0, 0.0, 0.0, minv, maxv, 0, false, o);
     D.visible[g] = o.vis ? 1 : 0;
     svfd::reproject_window(R, o, D.q_xy[2 * (size_t)g], D.q_xy[2 * (size_t)g + 1], D.q_margin[g], D.q_min_level[g], D.q_max_level[g]);
-}
-
-// ---- data::get_keypoints_in_cell (data/common.cc:127-190) for every row: k_grid_walk's body (match_kernels.hip) over the row's own
-// keypoint set -- one wave per row, the lanes take the cells of the window in column-major order (the reference's scan order), count
-// their keypoints that pass the level and margin tests, and a wave prefix sum gives every cell its place in the row's list
-template <bool FILL>
-__global__ void __launch_bounds__(256) k_loop_walk(LoopDev D) {
-    const int g = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (g >= D.rows_all) return;
-    if (FILL && D.cand_off[D.rows_all] > D.cap) return;  // the lists outgrew their capacity: nothing is written, the host starts again
-    int total = 0;
-    if (D.visible[g]) {
-        const LoopRow r = loop_row(D, g);
-        const int u = r.a ? r.p : D.K;
-        const LoopGeo& G = D.geo[u];
-        const int32_t* __restrict__ cell_off = D.cell_cnt + (size_t)u * D.ncell;
-        const int32_t* __restrict__ cell_items = D.cell_items;
-        const float* __restrict__ t_xy = r.a ? D.xy2 + 2 * (size_t)D.kf2_off[r.p] : D.xy1;
-        const int32_t* __restrict__ t_octave = r.a ? D.octave2 + D.kf2_off[r.p] : D.octave1;
-        const float ref_x = D.q_xy[2 * (size_t)g], ref_y = D.q_xy[2 * (size_t)g + 1], margin = D.q_margin[g];
-        const int min_level = D.q_min_level[g], max_level = D.q_max_level[g];
-        int lo_x = (int)floor((double)(ref_x - G.min_x - margin) * G.inv_w), hi_x = (int)ceil((double)(ref_x - G.min_x + margin) * G.inv_w);
-        int lo_y = (int)floor((double)(ref_y - G.min_y - margin) * G.inv_h), hi_y = (int)ceil((double)(ref_y - G.min_y + margin) * G.inv_h);
-        lo_x = max(lo_x, 0);
-        lo_y = max(lo_y, 0);
-        hi_x = min(hi_x, D.cols - 1);
-        hi_y = min(hi_y, D.rows - 1);
-        if (lo_x < D.cols && 0 <= hi_x && lo_y < D.rows && 0 <= hi_y && lo_x <= hi_x && lo_y <= hi_y) {
-            const int ny = hi_y - lo_y + 1, ncell = (hi_x - lo_x + 1) * ny;
-            int32_t* out = FILL ? D.cand_idx + D.cand_off[g] : nullptr;
-            for (int base = 0; base < ncell; base += 64) {
-                const int k = base + lane;
-                int n = 0, c = 0;
-                if (k < ncell) {
-                    c = (lo_x + k / ny) * D.rows + lo_y + k % ny;
-                    for (int it = cell_off[c]; it < cell_off[c + 1]; ++it) {
-                        const int idx = cell_items[it];
-                        const int oct = t_octave[idx];
-                        if (0 <= min_level && oct < min_level) continue;
-                        if (0 <= max_level && max_level < oct) continue;
-                        const float dx = t_xy[2 * idx] - ref_x, dy = t_xy[2 * idx + 1] - ref_y;
-                        if (fabsf(dx) < margin && fabsf(dy) < margin) ++n;
-                    }
-                }
-                int incl = n;  // inclusive prefix sum over the lanes: DPP row scans
-                incl += __builtin_amdgcn_update_dpp(0, incl, 0x111, 0xF, 0xF, false);  // row_shr:1
-                incl += __builtin_amdgcn_update_dpp(0, incl, 0x112, 0xF, 0xF, false);  // row_shr:2
-                incl += __builtin_amdgcn_update_dpp(0, incl, 0x114, 0xF, 0xF, false);  // row_shr:4
-                incl += __builtin_amdgcn_update_dpp(0, incl, 0x118, 0xF, 0xF, false);  // row_shr:8
-                incl += __builtin_amdgcn_update_dpp(0, incl, 0x142, 0xA, 0xF, false);  // row_bcast:15 into rows 1 and 3
-                incl += __builtin_amdgcn_update_dpp(0, incl, 0x143, 0xC, 0xF, false);  // row_bcast:31 into rows 2 and 3
-                if (FILL && n > 0) {
-                    int o = total + incl - n;
-                    for (int it = cell_off[c]; it < cell_off[c + 1]; ++it) {
-                        const int idx = cell_items[it];
-                        const int oct = t_octave[idx];
-                        if (0 <= min_level && oct < min_level) continue;
-                        if (0 <= max_level && max_level < oct) continue;
-                        const float dx = t_xy[2 * idx] - ref_x, dy = t_xy[2 * idx + 1] - ref_y;
-                        if (fabsf(dx) < margin && fabsf(dy) < margin) out[o++] = idx;
-                    }
-                }
-                total += __builtin_amdgcn_readlane(incl, 63);
-            }
-        }
-    }
-    if (!FILL && lane == 0) D.cand_off[g] = total;
 }
 
 // ---- step 2's cross-check (projection.cc:613-626) and step 3, one workgroup per candidate: an ordered compaction of the edges in
@@ -417,10 +288,6 @@ bool loop_fill_view(const svgpu_camera& c, const double* pose_cw, Sim3OptView& o
 bool loop_camera_ok(const svgpu_camera& c) {
     return c.model >= SVGPU_CAM_PERSPECTIVE && c.model <= SVGPU_CAM_RADIAL_DIVISION && c.min_x < c.max_x && c.min_y < c.max_y;
 }
-LoopGeo loop_geo(const svgpu_camera& c, int cols, int rows) {
-    return LoopGeo{c.min_x, c.min_y, (double)cols / (c.max_x - c.min_x), (double)rows / (c.max_y - c.min_y)};  // float difference, double quotient
-}
-
 }  // namespace
 
 extern "C" int svgpu_loop_sim3_batch(svgpu_ctx* ctx, const svgpu_camera* cam1, const double* pose_1w, int n1, const uint8_t* desc1, const float* xy1,
@@ -458,7 +325,7 @@ extern "C" int svgpu_loop_sim3_batch(svgpu_ctx* ctx, const svgpu_camera* cam1, c
     const size_t ncell = (size_t)grid_cols * grid_rows;
     if (N2 > 0 && (!desc2 || !xy2 || !octave2 || !pos_w2 || !has_lm2 || !min_valid2 || !max_valid2 || !lm_desc2 || !matched_1_in_2))
         return sv_set_error(ctx, SVGPU_ERR_INVALID, bad);
-    if (E * 8 > lim || N2 * 8 > lim || R * 8 > lim || ((size_t)K + 1) * ncell + 1 > lim)
+    if (E * 8 > lim || N2 * 8 > lim || R * 8 > lim || ((size_t)K + 1) * ncell > (size_t)SV_SCAN_MAX)
         return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_loop_sim3_batch: totals do not fit int32");
     Sim3OptView view1;
     if (!loop_camera_ok(*cam1) || !loop_fill_view(*cam1, pose_1w, view1))
@@ -491,7 +358,7 @@ extern "C" int svgpu_loop_sim3_batch(svgpu_ctx* ctx, const svgpu_camera* cam1, c
     LoopSim3Shape H;
     H.K = (size_t)K, H.n1 = (size_t)n1, H.N2 = N2, H.ncell = ncell, H.has_scale_in = scale_12_in != nullptr;
     H.prob_rec = sizeof(Sim3OptProblem), H.reproj_rec = sizeof(ReprojProblem), H.cand_rec = sizeof(CandProblem), H.replay_rec = sizeof(CandBatchReplay);
-    H.geo_rec = sizeof(LoopGeo), H.stats_rec = sizeof(svgpu_sim3opt_stats);
+    H.grid_rec = sizeof(GridProblem), H.stats_rec = sizeof(svgpu_sim3opt_stats);
     // the 2K matcher problems: A_p = keyframe 1's landmarks into candidate p, B_p = candidate p's landmarks into keyframe 1.  The form of
     // every replay (sv_cand_replay_form decides, as for the single call), and the dynamic LDS of the one launch
     std::vector<int> form(2 * (size_t)K);
@@ -517,12 +384,13 @@ extern "C" int svgpu_loop_sim3_batch(svgpu_ctx* ctx, const svgpu_camera* cam1, c
     // (32 MB of arena and mirror) whatever R; lists beyond it start the call again, sized exactly
     H.cap = std::min<size_t>(std::max<size_t>(4096, R * 16), size_t(1) << 22);
     std::vector<ReprojProblem> reproj_tab((size_t)K);
-    std::vector<LoopGeo> geo_tab((size_t)K + 1);
+    std::vector<GridProblem> grid_tab(3 * (size_t)K + 1);  // the K + 1 keypoint sets (the candidates, then keyframe 1), then the 2K matcher problems' rows
     std::vector<CandProblem> cand_tab(2 * (size_t)K);
     std::vector<CandBatchReplay> replay_tab(2 * (size_t)K);
     std::vector<int32_t> code((size_t)K);
     struct Tally {  // what the call issues (svgpu_call_stats)
         int launches = 0, copies = 0, syncs = 0;
+        void add(const SvIssued& n) { launches += n.launches, copies += n.copies; }  // what a shared launcher says it issued
     } T;
     for (int attempt = 0; attempt < 3; ++attempt) {  // (lists that outgrow the capacity start the call again, once, sized exactly; the tally runs on: it reports what the call issued)
         LoopSim3Pieces Y{};
@@ -545,9 +413,20 @@ extern "C" int svgpu_loop_sim3_batch(svgpu_ctx* ctx, const svgpu_camera* cam1, c
             Q.ray_cos_thr = 0.5f, Q.num_levels = (unsigned)num_levels, Q.log_scale_factor = log_scale_factor, Q.margin = margin;
             for (int l = 0; l < num_levels; ++l) Q.scale_factors[l] = scale_factors[l];
             Q.dist_mode = 1, Q.normal_mode = 2, Q.center_mode = 1, Q.window_mode = 0;
-            geo_tab[p] = loop_geo(cam2[p], grid_cols, grid_rows);
         }
-        geo_tab[(size_t)K] = loop_geo(*cam1, grid_cols, grid_rows);
+        // the grid records (the conventions of sv_launch_grid_sets): set u's cells are cell_cnt + u x ncell of the ONE counter array, its
+        // cell_of the one array from set_base[u] on; every piece is offset by whole elements from its 256-byte aligned start, and the scans
+        // run over the pieces themselves (cell_cnt, cand_off), never over an offset part
+        for (int u = 0; u <= K; ++u) {
+            const svgpu_camera& c = u < K ? cam2[u] : *cam1;
+            const size_t o2 = u < K ? (size_t)kf2_off[u] : 0;
+            GridProblem& G = grid_tab[u];
+            G = GridProblem{};
+            G.t_xy = u < K ? Y.xy2.p + 2 * o2 : Y.xy1.p, G.t_octave = u < K ? Y.octave2.p + o2 : Y.octave1.p, G.nt = set_base[u + 1] - set_base[u];
+            G.min_x = c.min_x, G.min_y = c.min_y, G.cols = grid_cols, G.rows = grid_rows;
+            G.inv_w = (double)grid_cols / (c.max_x - c.min_x), G.inv_h = (double)grid_rows / (c.max_y - c.min_y);  // float difference, double quotient (data/common.cc:86-87 via camera::base)
+            G.cell_of = Y.cell_of.p + set_base[u], G.cell_off = Y.cell_cnt.p + (size_t)u * ncell, G.cell_items = Y.cell_items;
+        }
         for (int u = 0; u < 2 * K; ++u) {
             const int p = u < K ? u : u - K, n2 = kf2_off[p + 1] - kf2_off[p];
             const size_t o2 = (size_t)kf2_off[p], r0 = (size_t)row_base[u];
@@ -565,31 +444,34 @@ extern "C" int svgpu_loop_sim3_batch(svgpu_ctx* ctx, const svgpu_camera* cam1, c
             P.cand_off = Y.cand_off.p + r0, P.cand_idx = Y.cand_idx, P.q_valid = Y.visible.p + r0;
             P.check_orientation = 0, P.thr = 100u /* HAMMING_DIST_THR_HIGH */, P.lowe_ratio = 0.f, P.mode = SVGPU_MATCH_BEST_ONLY, P.no_claims = 1;
             P.dist = Y.dist, P.num = Y.num_ab.p + u;
+            GridProblem& G = grid_tab[(size_t)K + 1 + u] = grid_tab[u < K ? p : K];  // the rows of problem u walk the grid of their target set
+            G.q_xy = Y.q_xy.p + 2 * r0, G.q_margin = Y.q_margin.p + r0, G.q_min_level = Y.q_min_level.p + r0, G.q_max_level = Y.q_max_level.p + r0;
+            G.q_valid = P.q_valid, G.nq = P.nq, G.cand_off = Y.cand_off.p + r0, G.cand_idx = Y.cand_idx;
             replay_tab[u] = CandBatchReplay{form[u], form[u] < 0 ? Y.owner.p + owner_first[u] : nullptr, form[u] < 0 ? Y.match_of_row.p + mrow_first[u] : nullptr};
         }
-        C.up(Y.prob, (const char*)prob.data(), Y.reproj_tab, (const char*)reproj_tab.data(), Y.geo_tab, (const char*)geo_tab.data());
+        C.up(Y.prob, (const char*)prob.data(), Y.reproj_tab, (const char*)reproj_tab.data(), Y.grid_tab, (const char*)grid_tab.data());
         C.up(Y.cand_tab, (const char*)cand_tab.data(), Y.replay_tab, (const char*)replay_tab.data());
         if ((rc = C.flush())) return rc;
         ++T.copies;
 
         LoopDev D{};
-        D.K = K, D.n1 = n1, D.N2 = (int)N2, D.ncell = (int)ncell, D.cols = grid_cols, D.rows = grid_rows, D.rows_a = (int)E, D.rows_all = (int)R;
-        D.cap = (int)std::min(H.cap, lim);
+        D.K = K, D.n1 = n1, D.N2 = (int)N2, D.rows_a = (int)E, D.rows_all = (int)R;
         for (int l = 0; l < num_levels; ++l) D.inv_level_sigma_sq[l] = inv_level_sigma_sq[l];
         std::memcpy(D.pose_1w, pose_1w, sizeof D.pose_1w);
         D.xy1 = Y.xy1, D.octave1 = Y.octave1, D.pos_w1 = Y.pos_w1, D.has_lm1 = Y.has_lm1, D.min1 = Y.min1, D.max1 = Y.max1;
         D.xy2 = Y.xy2, D.octave2 = Y.octave2, D.pos_w2 = Y.pos_w2, D.has_lm2 = Y.has_lm2, D.min2 = Y.min2, D.max2 = Y.max2;
-        D.kf2_off = Y.kf2_off, D.set_base = Y.set_base, D.pose_in_cand = Y.pose_in_cand, D.pose_2w = Y.pose_2w, D.rot_12 = Y.rot_12, D.trans_12 = Y.trans_12;
+        D.kf2_off = Y.kf2_off, D.pose_in_cand = Y.pose_in_cand, D.pose_2w = Y.pose_2w, D.rot_12 = Y.rot_12, D.trans_12 = Y.trans_12;
         D.active = Y.active, D.scale_in = Y.scale_in, D.prob = (Sim3OptProblem*)Y.prob.p, D.reproj_tab = (const ReprojProblem*)Y.reproj_tab.p;
-        D.geo = (const LoopGeo*)Y.geo_tab.p, D.prior_state = Y.prior_state, D.prior_idx2 = Y.prior_idx2, D.prior_pos_w = Y.prior_pos_w;
-        D.ratio_bits = Y.ratio_bits, D.xf = Y.xf, D.live = Y.live, D.already2 = Y.already2, D.cell_cnt = Y.cell_cnt, D.cell_of = Y.cell_of;
-        D.cell_items = Y.cell_items, D.visible = Y.visible, D.q_xy = Y.q_xy, D.q_margin = Y.q_margin, D.q_min_level = Y.q_min_level;
-        D.q_max_level = Y.q_max_level, D.cand_off = Y.cand_off, D.cand_idx = Y.cand_idx;
+        D.prior_state = Y.prior_state, D.prior_idx2 = Y.prior_idx2, D.prior_pos_w = Y.prior_pos_w;
+        D.ratio_bits = Y.ratio_bits, D.xf = Y.xf, D.live = Y.live, D.already2 = Y.already2;
+        D.visible = Y.visible, D.q_xy = Y.q_xy, D.q_margin = Y.q_margin, D.q_min_level = Y.q_min_level, D.q_max_level = Y.q_max_level;
         D.obs1 = Y.obs1, D.obs2 = Y.obs2, D.pos1 = Y.pos1, D.pos2 = Y.pos2, D.w1 = Y.w1, D.w2 = Y.w2;
         D.scale = Y.scale, D.code = Y.code, D.match_a = Y.match_a, D.match_b = Y.match_b, D.mutual = Y.mutual, D.num_mutual = Y.num_mutual;
         D.num_edges = Y.num_edges, D.edge_idx1 = Y.edge_idx1, D.edge_idx2 = Y.edge_idx2, D.edge_status = Y.edge_status;
 
-        const unsigned keypoints = (unsigned)(N2 + (size_t)n1);
+        const int keypoints = (int)(N2 + (size_t)n1);
+        const GridProblem* const set_tab = (const GridProblem*)Y.grid_tab.p;
+        const GridProblem* const row_tab = set_tab + K + 1;
         bool again = false;
         SV_HIP(ctx, hipMemsetAsync(Y.cell_cnt.p, 0, Y.cell_cnt.bytes(), C.s));
         ++T.copies;
@@ -600,20 +482,16 @@ extern "C" int svgpu_loop_sim3_batch(svgpu_ctx* ctx, const svgpu_camera* cam1, c
         }
         if (keypoints > 0) {
             SvProfScope ps(ctx, C.s, "k_loop_bin");  // count, scan, place
-            hipLaunchKernelGGL(k_loop_bin_count, dim3((keypoints + 255) / 256), dim3(256), 0, C.s, D);
-            hipLaunchKernelGGL(k_loop_scan, dim3(1), dim3(1024), 0, C.s, Y.cell_cnt.p, (int)(((size_t)K + 1) * ncell));
-            hipLaunchKernelGGL(k_loop_bin_place, dim3((keypoints + 255) / 256), dim3(256), 0, C.s, D);
-            T.launches += 3;
+            T.add(sv_launch_grid_sets(C.s, set_tab, Y.set_base, K + 1, keypoints, Y.cell_cnt, (int)(((size_t)K + 1) * ncell)));
         }
         if (R > 0) {
             {
                 SvProfScope ps(ctx, C.s, "k_loop_reproject");
                 hipLaunchKernelGGL(k_loop_reproject, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, C.s, D);
+                ++T.launches;
             }
             SvProfScope ps(ctx, C.s, "k_loop_walk");  // list sizes and their scan here, the lists below
-            hipLaunchKernelGGL(k_loop_walk<false>, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, C.s, D);
-            hipLaunchKernelGGL(k_loop_scan, dim3(1), dim3(1024), 0, C.s, Y.cand_off.p, (int)R);
-            T.launches += 3;
+            T.add(sv_launch_grid_queries_batch(C.s, row_tab, Y.row_base, 2 * K, (int)R, Y.cand_off));
         }
         if (R > 0) {
             int32_t total = 0;
@@ -628,12 +506,10 @@ extern "C" int svgpu_loop_sim3_batch(svgpu_ctx* ctx, const svgpu_camera* cam1, c
         if (again) continue;  // (read_now synchronised: nothing enqueued still reads the arena the next attempt may replace)
         if (R > 0) {
             SvProfScope ps(ctx, C.s, "k_loop_walk");
-            hipLaunchKernelGGL(k_loop_walk<true>, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, C.s, D);
-            ++T.launches;
+            T.add(sv_launch_grid_fill_batch(C.s, row_tab, Y.row_base, 2 * K, (int)R, (int)std::min(H.cap, lim)));
         }
         // (without any row the replay workgroups still run: they leave every problem's count at 0)
-        sv_launch_cand_batch(ctx, C.s, (const CandProblem*)Y.cand_tab.p, (const CandBatchReplay*)Y.replay_tab.p, Y.row_base, 2 * K, (int)R, lds_bytes);
-        T.launches += R > 0 ? 2 : 1;
+        T.add(sv_launch_cand_batch(ctx, C.s, (const CandProblem*)Y.cand_tab.p, (const CandBatchReplay*)Y.replay_tab.p, Y.row_base, 2 * K, (int)R, lds_bytes));
         {
             SvProfScope ps(ctx, C.s, "k_loop_edges");
             hipLaunchKernelGGL(k_loop_edges, dim3(K), dim3(1024), 0, C.s, D);

@@ -8,7 +8,6 @@
 #include "reloc_refine_layout.h"
 #include "ba_kernels.h"
 #include "frame_device.h"
-#include "match_device.h"  // GRID_ONE_CELLS, GRID_ONE_KPT_ROUNDS: which form sv_launch_grid_frame takes (the launch count of the call)
 #include "sv_sort.h"
 #include "sv_validate.h"
 
@@ -136,6 +135,7 @@ __global__ void __launch_bounds__(256) k_reloc_decide(RelocDecide D) {
 
 struct Tally {  // what the call issues (svgpu_call_stats)
     int launches = 0, copies = 0, syncs = 0;
+    void add(const SvIssued& n) { launches += n.launches, copies += n.copies; }  // what a shared launcher says it issued
 };
 
 // A candidate's chain without a frame keypoint: nothing can match and nothing is optimised (fewer than 5 observations)
@@ -218,7 +218,6 @@ extern "C" int svgpu_reloc_refine_batch(svgpu_ctx* ctx, const svgpu_camera* cam,
     }
     constexpr float chi_sq_2D = 5.99146, chi_sq_3D = 7.81473;  // pose_optimizer_g2o.cc:98-105
     const float huber_delta = t_xright ? std::sqrt(chi_sq_3D) : std::sqrt(chi_sq_2D);
-    const bool grid_one = H.ncell <= GRID_ONE_CELLS && nt <= 1024 * GRID_ONE_KPT_ROUNDS && !std::getenv("SVGPU_GRID_FOUR_LAUNCHES");
 
     H.cap = std::max<size_t>(4096, N * 64);
     std::vector<CandProblem> cand_tab((size_t)S * K);
@@ -256,7 +255,8 @@ extern "C" int svgpu_reloc_refine_batch(svgpu_ctx* ctx, const svgpu_camera* cam,
                 P.qdesc = (const uint32_t*)Y.lm_desc.p + r0 * 8, P.tdesc = (const uint32_t*)Y.tdesc.p;
                 P.t_octave = Y.t_octave, P.t_xy = Y.t_xy;
                 P.nq = kf_off[p + 1] - kf_off[p], P.nt = nt;
-                // (offsets into the ONE pair of lists: a candidate's nq + 1 entries end where the next candidate's begin)
+                // (offsets into the ONE pair of lists: a candidate's nq + 1 entries end where the next candidate's begin; the scan runs over
+                // the whole piece, G.cand_off below, whose start is aligned -- an offset part need not be)
                 P.cand_off = Y.cand_off.p + r0, P.cand_idx = Y.cand_idx;
                 P.q_valid = Y.visible.p + r0, P.occupied = Y.occupied.p + (size_t)p * nt;
                 P.q_angle = Y.kf_angle.p ? Y.kf_angle.p + r0 : nullptr, P.t_angle = Y.t_angle;
@@ -287,9 +287,7 @@ extern "C" int svgpu_reloc_refine_batch(svgpu_ctx* ctx, const svgpu_camera* cam,
         G.cell_of = Y.cell_of, G.cell_off = Y.cell_off, G.cell_items = Y.cell_items;
         G.q_xy = Y.q_xy, G.q_margin = Y.q_margin, G.q_min_level = Y.q_min_level, G.q_max_level = Y.q_max_level, G.q_valid = Y.visible;
         G.cand_off = Y.cand_off, G.cand_idx = Y.cand_idx;
-        sv_launch_grid_frame(C.s, G);
-        if (grid_one) ++T.launches;
-        else T.launches += 3, ++T.copies;  // (memset, assign, scan, place)
+        T.add(sv_launch_grid_frame(C.s, G));  // (one launch, or a memset and three: the launcher decides and says)
 
         PoseOptDev D;
         memset(&D, 0, sizeof(D));
@@ -324,8 +322,7 @@ extern "C" int svgpu_reloc_refine_batch(svgpu_ctx* ctx, const svgpu_camera* cam,
                 ++T.launches;
             }
             if (N > 0) {
-                sv_launch_grid_queries(C.s, G);  // list sizes of all entries + their scan
-                T.launches += 2;
+                T.add(sv_launch_grid_queries(C.s, G));  // list sizes of all entries + their scan
                 int32_t total = 0;
                 if ((rc = C.read_now(&total, Y.cand_off.p + N))) return rc;
                 ++T.copies, ++T.syncs;
@@ -335,12 +332,10 @@ extern "C" int svgpu_reloc_refine_batch(svgpu_ctx* ctx, const svgpu_camera* cam,
                     again = true;
                     break;
                 }
-                sv_launch_grid_fill(C.s, G);
-                ++T.launches;
+                T.add(sv_launch_grid_fill(C.s, G));
             }
             // (without any entry the replay workgroups still run: they leave every candidate's num_found at 0)
-            sv_launch_cand_batch(ctx, C.s, (const CandProblem*)Y.cand_tab.p + (size_t)s * K, (const CandBatchReplay*)Y.replay_tab.p, Y.kf_off, K, (int)N, lds_bytes);
-            T.launches += N > 0 ? 2 : 1;
+            T.add(sv_launch_cand_batch(ctx, C.s, (const CandProblem*)Y.cand_tab.p + (size_t)s * K, (const CandBatchReplay*)Y.replay_tab.p, Y.kf_off, K, (int)N, lds_bytes));
             if (N > 0) {
                 RelocApply Ap{};
                 Ap.N = (int)N, Ap.K = K, Ap.nt = nt, Ap.stage = s, Ap.kf_off = Y.kf_off, Ap.match_q = Y.match_q, Ap.pos_w = Y.pos_w;

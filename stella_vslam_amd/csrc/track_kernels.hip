@@ -189,13 +189,7 @@ __global__ __launch_bounds__(256) void k_track_cand(TrackCandProblem P) {
                         }
                     }
                     // inclusive prefix sum over the lanes: DPP row scans
-                    int incl = n;
-                    incl += __builtin_amdgcn_update_dpp(0, incl, 0x111, 0xF, 0xF, false);  // row_shr:1
-                    incl += __builtin_amdgcn_update_dpp(0, incl, 0x112, 0xF, 0xF, false);  // row_shr:2
-                    incl += __builtin_amdgcn_update_dpp(0, incl, 0x114, 0xF, 0xF, false);  // row_shr:4
-                    incl += __builtin_amdgcn_update_dpp(0, incl, 0x118, 0xF, 0xF, false);  // row_shr:8
-                    incl += __builtin_amdgcn_update_dpp(0, incl, 0x142, 0xA, 0xF, false);  // row_bcast:15
-                    incl += __builtin_amdgcn_update_dpp(0, incl, 0x143, 0xC, 0xF, false);  // row_bcast:31
+                    const int incl = sv_wave_inclusive_sum(n);
                     int pos = done + incl - n;
                     if (n > 0 && n <= TRACK_CACHE) {
 #pragma unroll

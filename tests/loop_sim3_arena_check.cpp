@@ -7,14 +7,14 @@
 #include "layout_check.h"
 #include "loop_sim3_layout.h"
 
-static const size_t PROB = 344, REPROJ = 408, CAND = 312, REPLAY = 24, GEO = 24, STATS = 64, NCELL = 64 * 48;
+static const size_t PROB = 344, REPROJ = 408, CAND = 312, REPLAY = 24, GRID = 152, STATS = 64, NCELL = 64 * 48;
 
 static void check(size_t K, size_t n1, size_t N2, bool scale_in, size_t owner, size_t mrow, size_t cap) {
     char name[96];
     std::snprintf(name, sizeof name, "K %zu n1 %zu N2 %zu cap %zu", K, n1, N2, cap);
     LoopSim3Shape H;
     H.K = K, H.n1 = n1, H.N2 = N2, H.ncell = NCELL, H.has_scale_in = scale_in, H.owner_ints = owner, H.mrow_ints = mrow;
-    H.prob_rec = PROB, H.reproj_rec = REPROJ, H.cand_rec = CAND, H.replay_rec = REPLAY, H.geo_rec = GEO, H.stats_rec = STATS, H.cap = cap;
+    H.prob_rec = PROB, H.reproj_rec = REPROJ, H.cand_rec = CAND, H.replay_rec = REPLAY, H.grid_rec = GRID, H.stats_rec = STATS, H.cap = cap;
     const size_t E = K * n1, R = E + N2, T = N2 + n1;
     layout_check<LoopSim3Pieces>(
         name, [&](Arena& A, LoopSim3Pieces& Y) { loop_sim3_layout(A, H, Y); },
@@ -23,7 +23,7 @@ static void check(size_t K, size_t n1, size_t N2, bool scale_in, size_t owner, s
                         {Y.max1, n1 * 4}, {Y.desc2, N2 * 32}, {Y.lm_desc2, N2 * 32}, {Y.xy2, N2 * 8}, {Y.octave2, N2 * 4}, {Y.pos_w2, N2 * 24}, {Y.has_lm2, N2},
                         {Y.min2, N2 * 4}, {Y.max2, N2 * 4}, {Y.kf2_off, (K + 1) * 4}, {Y.set_base, (K + 2) * 4}, {Y.row_base, (2 * K + 1) * 4},
                         {Y.pose_in_cand, K * 96}, {Y.pose_2w, K * 96}, {Y.rot_12, K * 72}, {Y.trans_12, K * 24}, {Y.active, K}, {Y.scale_in, scale_in ? K * 4 : 0},
-                        {Y.prob, K * PROB}, {Y.reproj_tab, K * REPROJ}, {Y.geo_tab, (K + 1) * GEO}, {Y.cand_tab, 2 * K * CAND}, {Y.replay_tab, 2 * K * REPLAY},
+                        {Y.prob, K * PROB}, {Y.reproj_tab, K * REPROJ}, {Y.grid_tab, (3 * K + 1) * GRID}, {Y.cand_tab, 2 * K * CAND}, {Y.replay_tab, 2 * K * REPLAY},
                         {Y.prior_state, E}, {Y.prior_idx2, E * 4}, {Y.prior_pos_w, E * 24}, {Y.ratio_bits, E * 4}, {Y.xf, K * 192}, {Y.live, K}, {Y.already2, N2},
                         {Y.cell_cnt, ((K + 1) * NCELL + 1) * 4}, {Y.cell_of, T * 4}, {Y.cell_items, T * 4}, {Y.visible, R}, {Y.q_xy, R * 8}, {Y.q_margin, R * 4},
                         {Y.q_min_level, R * 4}, {Y.q_max_level, R * 4}, {Y.cand_off, (R + 1) * 4}, {Y.owner, owner * 4}, {Y.match_of_row, mrow * 4},

@@ -90,8 +90,8 @@ def cand(n2=300, n_shared=200, n_prior=40, n_erased=0, n_unindexed=0, n_parallax
 
 
 def make(name, cands, n1=320, model=CAM_PERSPECTIVE, seed=1, drift=1.05, use_scale_in=False, fix_scale=False, min_num_inliers=20, all_active_none=False,
-         clutter_div=5, p_lm=0.95):
-    """Keyframe 1 and len(cands) candidates over one set of physical points."""
+         clutter_div=5, p_lm=0.95, patch=None):
+    """Keyframe 1 and len(cands) candidates over one set of physical points (`patch`: all of them within that many metres of one point)."""
     rng = np.random.default_rng(seed)
     T = orb_tables()
     sf = T["scale_factors"]
@@ -100,6 +100,8 @@ def make(name, cands, n1=320, model=CAM_PERSPECTIVE, seed=1, drift=1.05, use_sca
         d = rng.normal(0, 1, (n_obs, 3))
         d[:, 1] *= 0.5
         X1 = d / np.linalg.norm(d, axis=1, keepdims=True) * rng.uniform(4.0, 9.0, (n_obs, 1))
+    elif patch is not None:
+        X1 = np.array([0.8, -0.5, 6.0]) + rng.uniform(-patch, patch, (n_obs, 3))
     else:
         X1 = np.stack([rng.uniform(-3.0, 3.0, n_obs), rng.uniform(-1.9, 1.9, n_obs), rng.uniform(4.5, 9.0, n_obs)], 1)
     base_desc = rng.integers(0, 256, (n_obs, 32), dtype=np.uint8)
@@ -340,6 +342,112 @@ def same(a, b, keys=OUTPUTS):
     return [k for k in keys if np.shape(a[k]) != np.shape(b[k]) or bits(k, a[k]) != bits(k, np.asarray(b[k], np.asarray(a[k]).dtype))]
 
 
+# ---------------------------------------------------------------------------------------------- the candidate lists, restated
+GRID_COLS, GRID_ROWS = 64, 48
+CELL_W, CELL_H = WIDTH / GRID_COLS, HEIGHT / GRID_ROWS  # a perspective camera without distortion: the image bounds are the image
+
+
+def window_lists(problem, p):
+    """Both passes of projection::match_keyframes_mutually for candidate p of a problem of perspective cameras without distortion, restated
+    in numpy up to the candidate lists: (A, B), A[i] = the keypoints of candidate p that data::get_keypoints_in_cell lists for landmark i of
+    keyframe 1, as (index, cell) pairs in the reference's order (cells column-major inside the window, a cell's keypoints in index order);
+    B[j] likewise for landmark j of the candidate into keyframe 1.  Rows that are not offered or not visible have no entry."""
+    f32, f64 = np.float32, np.float64
+    s = problem["scale_12_in"][p] if problem["scale_12_in"] is not None else scale_restatement(problem, p)[0]
+    if s is None:
+        return {}, {}
+    s = f64(f32(s))
+    rot_12, trans_12 = problem["rot_12"][p].reshape(3, 3), problem["trans_12"][p]
+    T1, T2 = problem["pose_1w"].reshape(3, 4), problem["pose_2w"][p].reshape(3, 4)
+    s_rot_12, s_rot_21 = s * rot_12, (1.0 / s) * rot_12.T
+    trans_21 = -s_rot_21 @ trans_12
+    lo, hi = int(problem["kf2_off"][p]), int(problem["kf2_off"][p + 1])
+    state, pidx = problem["prior_state"][p], problem["prior_idx2"][p]
+    blocked1 = (state != 0) & (pidx >= 0)
+    blocked2 = np.zeros(hi - lo, bool)
+    blocked2[pidx[blocked1]] = True
+    sf, lsf = problem["scale_factors"], f32(problem["log_scale_factor"])
+    inv_w, inv_h = f64(GRID_COLS) / f64(f32(WIDTH)), f64(GRID_ROWS) / f64(f32(HEIGHT))
+
+    def one_pass(R, t, pos, offered, minv, maxv, t_xy, t_oct):
+        cell = np.floor(t_xy[:, 0].astype(f64) * inv_w).astype(int) * GRID_ROWS + np.floor(t_xy[:, 1].astype(f64) * inv_h).astype(int)
+        out = {}
+        for i in np.flatnonzero(offered):
+            X = R @ pos[i] + t
+            if X[2] <= 0.0:
+                continue
+            rx, ry = FX * X[0] / X[2] + CX, FY * X[1] / X[2] + CY
+            dist = np.sqrt(X @ X)
+            if not (0.0 < rx < WIDTH and 0.0 < ry < HEIGHT) or dist < f64(minv[i]) / 1.3 or 1.3 * f64(maxv[i]) < dist:
+                continue
+            lv = int(np.clip(np.ceil(f32(np.log(f64(f32(maxv[i]) / f32(dist)))) / lsf), 0, NUM_LEVELS - 1))
+            qx, qy, m = f32(rx), f32(ry), f32(f32(problem["margin"]) * sf[lv])
+            lo_x, hi_x = max(int(np.floor(f64(qx - m) * inv_w)), 0), min(int(np.ceil(f64(qx + m) * inv_w)), GRID_COLS - 1)
+            lo_y, hi_y = max(int(np.floor(f64(qy - m) * inv_h)), 0), min(int(np.ceil(f64(qy + m) * inv_h)), GRID_ROWS - 1)
+            got = []
+            for cx in range(lo_x, hi_x + 1):
+                for cy in range(lo_y, hi_y + 1):
+                    for k in np.flatnonzero(cell == cx * GRID_ROWS + cy):
+                        if max(0, lv - 1) <= t_oct[k] <= min(NUM_LEVELS - 1, lv + 1) and abs(t_xy[k, 0] - qx) < m and abs(t_xy[k, 1] - qy) < m:
+                            got.append((int(k), cx * GRID_ROWS + cy))
+            out[int(i)] = got
+        return out
+
+    A = one_pass(s_rot_21 @ T1[:, :3], s_rot_21 @ T1[:, 3] + trans_21, problem["pos_w1"], (problem["has_lm1"] != 0) & ~blocked1, problem["min_valid1"],
+                 problem["max_valid1"], problem["xy2"][lo:hi], problem["octave2"][lo:hi])
+    B = one_pass(s_rot_12 @ T2[:, :3], s_rot_12 @ T2[:, 3] + trans_12, problem["pos_w2"][lo:hi], (problem["has_lm2"][lo:hi] != 0) & ~blocked2,
+                 problem["min_valid2"][lo:hi], problem["max_valid2"][lo:hi], problem["xy1"], problem["octave1"])
+    return A, B
+
+
+def best_distance_ties(lists, q_desc, t_desc):
+    """rows whose smallest Hamming distance is attained by two or more listed keypoints: (rows tied inside one cell, rows tied across cells)"""
+    inside, across = [], []
+    for i, got in lists.items():
+        if len(got) < 2:
+            continue
+        d = np.array([int(np.unpackbits(q_desc[i] ^ t_desc[k]).sum()) for k, _ in got])
+        cells = {c for (_, c), dk in zip(got, d) if dk == d.min()}
+        if (d == d.min()).sum() >= 2:
+            (inside if len(cells) == 1 else across).append(i)
+    return inside, across
+
+
+def cell_order():
+    """Every keyframe's keypoints in two adjacent cells of one row of cells, and every keypoint without a landmark a copy (descriptor and
+    octave) of one with a landmark, next to it in the same cell or just across the line between the two cells: a landmark that lists its
+    true match lists the copy too, at the same Hamming distance.  Which of the two is matched is decided by the order of the list alone --
+    index order inside a cell, column-major order across the two cells."""
+    p = make("cell_order", [cand(n2=40, n_shared=20, n_prior=4, seed=1), cand(n2=40, n_shared=20, n_prior=4, seed=2)], n1=64, seed=16, clutter_div=2,
+             p_lm=1.0, patch=0.07)
+
+    def cluster(xy, octave, desc, has):
+        xy = xy.copy()
+        own, copies = np.flatnonzero(has != 0), np.flatnonzero(has == 0)
+        centre = xy[own].astype(np.float64).mean(0)
+        line = round(centre[0] / CELL_W) * CELL_W                      # the line between the two cells
+        y0 = np.floor(centre[1] / CELL_H) * CELL_H
+        xy[own, 0] = np.clip(xy[own, 0], line - CELL_W + 0.5, line + CELL_W - 0.5)
+        xy[own, 1] = np.clip(xy[own, 1], y0 + 0.5, y0 + CELL_H - 0.5)
+        for n, (k, src) in enumerate(zip(copies, own)):
+            desc[k], octave[k] = desc[src], octave[src]
+            x, y = xy[src]
+            left = x < line
+            if n % 2 == 0:   # the same cell, 0.75 px away
+                xy[k] = (x - 0.75 if (x - 0.75 >= line) == (x >= line) and x - 0.75 > line - CELL_W else x + 0.75, y)
+                if (xy[k, 0] < line) != left:
+                    xy[k, 0] = x
+            else:            # just across the line
+                xy[k] = (line + 0.5 if left else line - 0.5, y)
+        return xy
+
+    p["xy1"] = cluster(p["xy1"], p["octave1"], p["desc1"], p["has_lm1"])
+    for c in range(2):
+        lo, hi = p["kf2_off"][c], p["kf2_off"][c + 1]
+        p["xy2"][lo:hi] = cluster(p["xy2"][lo:hi], p["octave2"][lo:hi], p["desc2"][lo:hi], p["has_lm2"][lo:hi])
+    return p
+
+
 # ---------------------------------------------------------------------------------------------- the classes
 def GOOD(seed=0, **kw):
     return cand(seed=seed, **kw)
@@ -363,6 +471,10 @@ def classes():
     P["mixed_models"] = make("mixed_models", [GOOD(1, model=CAM_EQUIRECTANGULAR), GOOD(2, model=CAM_FISHEYE), GOOD(3)], seed=12)
     P["twins"] = sub(make("twins", [GOOD(1)], seed=13), [0, 0])
     P["many_tiny"] = make("many_tiny", [cand(n2=10 + s % 21, n_shared=10 + s % 21, n_prior=4, seed=s) for s in range(40)], n1=150, seed=14, min_num_inliers=5)
+    # the keypoint sets of the binning are the candidates' keyframes, then keyframe 1: sets [0, 300), [300, 1 600), [1 600, 2 700).  The second
+    # starts inside a workgroup of 256 keypoints and is longer than a placement tile of 1 024; keyframe 1 starts inside a workgroup too
+    P["long_sets"] = make("long_sets", [cand(n2=300, n_shared=200, n_prior=40, seed=1), cand(n2=1300, n_shared=800, n_prior=40, seed=2)], n1=1100, seed=15)
+    P["cell_order"] = cell_order()
     for k, v in P.items():
         v["name"] = k
     return P
@@ -375,7 +487,7 @@ def planted_kept(problem, p):
 
 EXPECT = dict(all_accepted=[0, 0, 0], each_status=[0, NO_SCALE, FEW_INLIERS, -1], unequal=[FEW_INLIERS, FEW_INLIERS, 0, 0], early_return=[FEW_INLIERS, 0],
               no_new_matches=[0, 0], no_priors=[0, 0], prior_erased=[0, NO_SCALE], prior_unindexed=[0, 0], stereo_fix_scale=[0, 0], fisheye=[0, 0],
-              equirect=[0, 0], twins=[0, 0])
+              equirect=[0, 0], twins=[0, 0], long_sets=[0, 0])
 
 
 # ---------------------------------------------------------------------------------------------- scale classes

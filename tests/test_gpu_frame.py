@@ -124,8 +124,8 @@ def test_matcher_grid_crowded_cells_outside_keypoints_and_large_frames(mods):
 
 
 def test_matcher_grid_beyond_the_short_scan(mods):
-    """149 x 110 = 16 390 cells: the cell counters are scanned by k_exclusive_scan (match_kernels.hip grid_scan: beyond the 16 384 elements
-    of the shuffle-based scan).  3 000 keypoints, 300 of them outside the image bounds; the cell lists equal assign_keypoints_to_grid."""
+    """149 x 110 = 16 390 cells: the scan of the cell counters (sv_scan_i32 without scratch, one workgroup) walks a second tile of its
+    16 384 elements.  3 000 keypoints, 300 of them outside the image bounds; the cell lists equal assign_keypoints_to_grid."""
     cam_mod, data, feature, _ = mods
     ctx = feature.Context(0)
     cam = cam_mod.equirectangular("theta", "RGB", 1920, 960, 30.0, ctx=ctx)

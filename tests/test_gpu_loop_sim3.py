@@ -10,7 +10,7 @@ from tests import loop_sim3_problems as LP
 
 pytestmark = pytest.mark.gpu
 CLASSES = ("all_accepted", "each_status", "unequal", "early_return", "no_new_matches", "no_priors", "prior_erased", "prior_unindexed", "stereo_fix_scale",
-           "fisheye", "equirect", "mixed_models", "twins", "many_tiny")
+           "fisheye", "equirect", "mixed_models", "twins", "many_tiny", "long_sets", "cell_order")
 SCALE_CLASSES = ("kept_1", "kept_2", "kept_3", "kept_1025", "ties", "boundary")
 KEYS = LP.KEYS
 

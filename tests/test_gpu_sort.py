@@ -43,6 +43,29 @@ def test_radix_sort_is_stable(n, bits):
     assert np.array_equal(idx[:n], ref)
 
 
+def _scan_one_launch(gpu, values):
+    ctx, L = gpu
+    scan = np.full(len(values) + 1, -7, np.int32)
+    rc = L.svgpu_selftest_scan_one_launch(ctx.handle, len(values), C.c_void_p(values.ctypes.data), C.c_void_p(scan.ctypes.data))
+    ctx.check(rc, "svgpu_selftest_scan_one_launch")
+    return scan
+
+
+@pytest.mark.parametrize("n", [0, 1, 16383, 16384, 16385, 32767, 32768, 32769, 50000])
+def test_scan_without_scratch_walks_its_tiles(gpu, n):
+    """sv_scan_i32 without scratch (the grid and bucket lists' form): one workgroup over tiles of 16 384 elements -- either side of the first
+    and the second tile boundary, a last tile that is not full; the total behind the data."""
+    v = np.random.default_rng(n).integers(0, 30, n).astype(np.int32)
+    scan = _scan_one_launch(gpu, v)
+    assert np.array_equal(scan, np.concatenate([[0], np.cumsum(v, dtype=np.int64)]).astype(np.int32))
+    assert scan[n] == v.sum()
+
+
+def test_scan_without_scratch_of_zeros_over_three_tiles(gpu):
+    scan = _scan_one_launch(gpu, np.zeros(32769, np.int32))
+    assert scan.shape == (32770,) and not scan.any()
+
+
 # ---- the paths the two tests above do not reach (tests/sort_problems.py: key classes, sizes and the numpy references; its CPU test shows that
 # the classes tell an unstable sort, a sort by the full key and a sort that ignores the device count from the right one)
 RADIX_COUNT, SMALL, SIDES, BUCKET = 0, 1, 2, 3  # SVGPU_SORT_PATH_* of include/svgpu.h

@@ -15,7 +15,7 @@ def test_loop_sim3_arena_layout(tmp_path):
 
 
 def test_problem_and_stats_record_sizes_of_the_check_are_the_librarys(tmp_path):
-    """PROB and STATS of the check program against the library's own plain-C++ headers.  REPROJ, CAND, REPLAY and GEO are sizes of HIP-side
+    """PROB and STATS of the check program against the library's own plain-C++ headers.  REPROJ, CAND, REPLAY and GRID are sizes of HIP-side
     structs: they only scale pieces of the layout, the call itself passes sizeof, and here REPROJ is merely bounded below by the camera."""
     src = tmp_path / "sizes.cpp"
     src.write_text('#include <cstdio>\n#include "sim3opt_layout.h"\n#include "svgpu.h"\n'
@@ -25,6 +25,6 @@ def test_problem_and_stats_record_sizes_of_the_check_are_the_librarys(tmp_path):
     subprocess.check_call(["g++", "-std=c++17", "-I", str(ROOT / "stella_vslam_amd" / "csrc"), "-I", str(ROOT / "include"), str(src), "-o", str(exe)])
     prob, stats, cam = (int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split())
     chk = (ROOT / "tests" / "loop_sim3_arena_check.cpp").read_text()
-    m = re.search(r"PROB = (\d+), REPROJ = (\d+), CAND = (\d+), REPLAY = (\d+), GEO = (\d+), STATS = (\d+)", chk)
+    m = re.search(r"PROB = (\d+), REPROJ = (\d+), CAND = (\d+), REPLAY = (\d+), GRID = (\d+), STATS = (\d+)", chk)
     assert int(m.group(1)) == prob and int(m.group(6)) == stats
     assert int(m.group(2)) >= cam  # a ReprojProblem holds the camera

@@ -56,6 +56,9 @@ def test_shapes_are_what_the_gpu_test_relies_on(problems):
     m = problems["many_tiny"]
     assert m["num_candidates"] == 40 and np.diff(m["kf2_off"]).max() <= 30
     assert problems["each_status"]["active"].tolist() == [1, 1, 1, 0]
+    ls = problems["long_sets"]
+    sets = np.concatenate([ls["kf2_off"], [ls["kf2_off"][-1] + ls["n1"]]]).tolist()  # the binning's keypoint sets: the candidates, then keyframe 1
+    assert sets == [0, 300, 1600, 2700] and sets[1] % 256 and sets[2] % 256 and sets[2] - sets[1] > 1024
     assert {c["model"] for c in problems["mixed_models"]["cam2"]} == {0, 1, 2} and problems["mixed_models"]["cam1"]["model"] == 0
     t = problems["twins"]
     assert all(np.array_equal(t[k][0], t[k][1]) for k in LP.PER_CAND)
@@ -63,6 +66,61 @@ def test_shapes_are_what_the_gpu_test_relies_on(problems):
         assert (p["prior_idx2"] < np.diff(p["kf2_off"])[:, None]).all(), name
         q = p["sim3_12"][:, :4]
         assert np.abs((q * q).sum(1) - 1.0).max() < 1e-12, name
+
+
+def _first_best(lists, q_desc, t_desc, n):
+    """the matcher pass on restated lists: the first listed keypoint at the smallest Hamming distance, if within 100 bits"""
+    out = np.full(n, -1, np.int32)
+    for i, got in lists.items():
+        d = [int(np.unpackbits(q_desc[i] ^ t_desc[k]).sum()) for k, _ in got]
+        if d and min(d) <= 100:
+            out[i] = got[int(np.argmin(d))][0]
+    return out
+
+
+def test_cell_order_ties_are_decided_by_the_order_of_the_lists(problems):
+    """A condition on the inputs: in both passes at least 8 rows reach their best Hamming distance at two or more of the keypoints the
+    window lists, some of them inside one cell (index order decides) and some across the two cells (column-major order decides).  The
+    lists are the numpy restatement's (window_lists), which is itself held to the CPU oracle's matcher here."""
+    from oracle import oracle as O
+    p = problems["cell_order"]
+    assert p["num_candidates"] == 2 and p["n1"] == 64 and np.diff(p["kf2_off"]).tolist() == [40, 40]
+    cell = lambda xy: set((np.floor(xy[:, 0] / LP.CELL_W).astype(int) * LP.GRID_ROWS + np.floor(xy[:, 1] / LP.CELL_H).astype(int)).tolist())
+    cam1 = LP.oracle_camera(p["cam1"])
+    assert (cam1.min_x, cam1.max_x, cam1.min_y, cam1.max_y) == (0.0, LP.WIDTH, 0.0, LP.HEIGHT)  # what window_lists takes the grid's bounds to be
+    c1 = sorted(cell(p["xy1"]))
+    assert len(c1) == 2 and c1[1] - c1[0] == LP.GRID_ROWS  # two cells, neighbours in x
+    tied = dict(A_inside=0, A_across=0, B_inside=0, B_across=0)
+    for c in range(2):
+        lo, hi = int(p["kf2_off"][c]), int(p["kf2_off"][c + 1])
+        sl = lambda k: p[k][lo:hi]
+        c2 = sorted(cell(sl("xy2")))
+        assert len(c2) == 2 and c2[1] - c2[0] == LP.GRID_ROWS, c
+        A, B = LP.window_lists(p, c)
+        ia, aa = LP.best_distance_ties(A, p["lm_desc1"], sl("desc2"))
+        ib, ab = LP.best_distance_ties(B, sl("lm_desc2"), p["desc1"])
+        tied["A_inside"] += len(ia)
+        tied["A_across"] += len(aa)
+        tied["B_inside"] += len(ib)
+        tied["B_across"] += len(ab)
+        # the restated lists give the oracle's matches, ties included
+        state, pidx = p["prior_state"][c], p["prior_idx2"][c]
+        b1 = (state != 0) & (pidx >= 0)
+        b2 = np.zeros(hi - lo, bool)
+        b2[pidx[b1]] = True
+        kf1 = dict(pos_w=p["pos_w1"], valid=((p["has_lm1"] != 0) & ~b1).astype(np.uint8), min_valid_dist=p["min_valid1"], max_valid_dist=p["max_valid1"],
+                   lm_desc=p["lm_desc1"], desc=p["desc1"], xy=p["xy1"], octave=p["octave1"])
+        kf2 = dict(pos_w=sl("pos_w2"), valid=((sl("has_lm2") != 0) & ~b2).astype(np.uint8), min_valid_dist=sl("min_valid2"), max_valid_dist=sl("max_valid2"),
+                   lm_desc=sl("lm_desc2"), desc=sl("desc2"), xy=sl("xy2"), octave=sl("octave2"))
+        T1, T2, cc = p["pose_1w"].reshape(3, 4), p["pose_2w"][c].reshape(3, 4), np.ascontiguousarray
+        m21, m12, _, _ = O.match_keyframes_mutually(cam1, LP.oracle_camera(p["cam2"][c]), cc(T1[:, :3]), cc(T1[:, 3]), cc(T2[:, :3]), cc(T2[:, 3]),
+                                                    float(LP.scale_restatement(p, c)[0]), p["rot_12"][c], p["trans_12"][c], kf1, kf2, p["scale_factors"],
+                                                    p["log_scale_factor"], float(p["margin"]))
+        assert np.array_equal(_first_best(A, p["lm_desc1"], sl("desc2"), p["n1"]), m21), c
+        assert np.array_equal(_first_best(B, sl("lm_desc2"), p["desc1"], hi - lo), m12), c
+    print(tied)
+    assert tied["A_inside"] + tied["A_across"] >= 8 and tied["B_inside"] + tied["B_across"] >= 8, tied
+    assert min(tied.values()) >= 2, tied
 
 
 def test_scale_classes_count_tie_and_cross_the_workgroup(scale_problems):
