@@ -1295,6 +1295,40 @@ int svgpu_loop_sim3_batch(svgpu_ctx* ctx, const svgpu_camera* cam1, const double
                           int32_t* num_edges, uint8_t* edge_status, double* sim3_12_out, int32_t* num_inliers,
                           svgpu_sim3opt_stats* opt_stats, svgpu_call_stats* stats);
 
+/* The loop of mapping_module::create_new_landmarks (mapping_module.cc:275-341) for ALL neighbours in one call: per neighbour
+ * match_for_triangulation (:332-335), then two_view_triangulator::triangulate on its matches (:343-375).  The loop is sequential: a
+ * keypoint of the current keyframe that got a landmark at neighbour p (:364-367) is no query for neighbour p + 1 (robust.cc:47-50,
+ * bow_tree.cc likewise).  svgpu_match_for_triangulation_batch followed by svgpu_triangulate_two_views_batch treats the neighbours as
+ * independent and hands a keypoint that matches in two neighbours to both; this call carries the landmark state from neighbour to
+ * neighbour on the device.
+ *   side1 / view1       the current keyframe as the matcher and as the triangulator see it; side2[k] / neighbours[k] likewise for
+ *                       neighbour k.  The two views of a keyframe must agree in n and name the SAME octave / bearings / xright arrays
+ *                       (a side-2 match view may leave octave null); every array is uploaded once.
+ *   active              nullable = all; 0 = the neighbour is skipped (the baseline `continue` of :303-319, decided by the caller)
+ *   E_12, epipole_in_2, valid_epipole   per neighbour, as in svgpu_match_for_triangulation_batch; the remaining parameters as in
+ *                       svgpu_match_for_triangulation and svgpu_triangulate_two_views, shared by all neighbours
+ * With taken_0 = !side1->valid (null: nothing taken), for p = 0 .. num_neighbours - 1 in order:
+ *   inactive            row p of matched_2_in_1 is -1, of status SVGPU_TRI_SKIPPED, of pos_w zero, both counts 0; taken_{p+1} = taken_p
+ *   active              row p of matched_2_in_1 (num_neighbours x n1) equals, element for element, svgpu_match_for_triangulation with
+ *                       has_lm1 = taken_p against neighbour p; rows p of pos_w (x 3) and status equal, bit for bit,
+ *                       svgpu_triangulate_two_views on that row in its idx2 == NULL form;
+ *                       taken_{p+1} = taken_p | (status == SVGPU_TRI_ACCEPTED), and created_by[i] = p for those keypoints
+ *   created_by          n1: the neighbour whose match gave keypoint i its landmark, or -1
+ * `stats` (nullable) receives what the call issued.  Two synchronisations whatever num_neighbours is (the candidate-list total and
+ * the end; one when no neighbour has a candidate); launches = a constant + 2 per active neighbour (a replay and a triangulation
+ * launch, enqueued back to back); one read-back.
+ * SVGPU_ERR_INVALID before anything is staged or launched, the outputs untouched: a null required pointer; n < 0 or an n2 >= 1 << 22;
+ * node ids on one side only; check_orientation without angles; missing bearings, octaves or xy; num_levels outside 1..16; an octave of
+ * any keyframe outside [0, num_levels); `occupied` set on any view; a camera model out of range; a stereo keypoint of an equirectangular
+ * camera; the two views of a keyframe disagreeing; totals beyond int32.  num_neighbours == 0 succeeds and touches nothing.
+ * Host in/out, synchronous. */
+int svgpu_new_landmarks_batch(svgpu_ctx* ctx, const svgpu_match_view* side1, const svgpu_triangulate_view* view1, int num_neighbours,
+                              const svgpu_match_view* side2, const svgpu_triangulate_view* neighbours, const uint8_t* active, const double* E_12,
+                              const double* epipole_in_2, const int32_t* valid_epipole, const float* scale_factors, const float* level_sigma_sq,
+                              int num_levels, float residual_rad_thr, float lowe_ratio, int check_orientation, float rays_parallax_deg_thr,
+                              int32_t* matched_2_in_1, double* pos_w, uint8_t* status, int32_t* num_matches, int32_t* num_accepted,
+                              int32_t* created_by, svgpu_call_stats* stats);
+
 /* Global BA core (optimize/global_bundle_adjuster.cc:26-192, 279-412): the same graph over ALL keyframes (spanning root
  * fixed), ONE Levenberg-Marquardt run of problem->num_first_iter iterations with the terminate rule, optional Huber
  * (obs_huber_delta), no outlier gate (num_second_iter is ignored).  The caller applies the reference's post-conditions

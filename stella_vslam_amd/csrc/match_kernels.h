@@ -122,6 +122,33 @@ struct SvIssued {
 SvIssued sv_launch_cand_batch(svgpu_ctx* ctx, hipStream_t s, const CandProblem* tab, const CandBatchReplay* form, const int32_t* row_base, int num_problems,
                               int rows, size_t lds_bytes);
 
+// The new-landmark chain (k_newlm_replay / k_newlm_triangulate; svgpu_newlm.hip): the bucket matcher's batch tables for the ACTIVE neighbours, all with the
+// current keyframe as side 1 (problem p owns rows p * n1 ..), the triangulator's views, and the outputs in neighbour order
+struct TriView;  // triangulate_kernels.h
+struct NewLmChain {
+    int num_neighbours, n1;
+    const int32_t* prob_of_nb;     // per neighbour: its problem among the active ones, or -1 = inactive
+    const CandProblem* cand_tab;   // per active problem
+    const CandBatchReplay* form;
+    const int* q_idx;              // n1: row -> keypoint of the current keyframe (one order: side 1 is shared)
+    uint8_t* q_valid;              // problems x n1 rows, computed under taken_0
+    const int32_t* match_rows;     // problems x n1: the replay's result in row order
+    const TriView* views;          // num_neighbours + 1: the neighbours, then the current keyframe
+    float scale_factors[16];
+    float level_sigma_sq[16];
+    float cos_rays_parallax_thr;
+    uint8_t* taken;                // n1: taken_0 on entry, the keypoints that hold a landmark behind every neighbour
+    int32_t* match;                // num_neighbours x n1 (keypoint order)
+    double* pos_w;                 // num_neighbours x n1 x 3
+    uint8_t* status;               // num_neighbours x n1
+    int32_t* num_matches;          // num_neighbours
+    int32_t* num_accepted;         // num_neighbours
+    int32_t* created_by;           // n1
+};
+SvIssued sv_launch_cand_dist_batch(svgpu_ctx* ctx, hipStream_t s, const CandProblem* tab, const int32_t* row_base, int num_problems, int rows);
+// (`prob_of_nb`: the host copy of C.prob_of_nb; one init launch, then a replay and a triangulation launch per active neighbour, in order)
+SvIssued sv_launch_newlm_chain(svgpu_ctx* ctx, hipStream_t s, const NewLmChain& C, const int32_t* prob_of_nb, size_t lds_bytes);
+
 // Device-side candidate lists: data::assign_keypoints_to_grid + data::get_keypoints_in_cell (data/common.cc:83-190)
 struct GridProblem {
     const float* t_xy;        // nt x 2 undistorted keypoint positions

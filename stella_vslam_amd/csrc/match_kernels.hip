@@ -18,6 +18,7 @@
 #include "match_kernels.h"
 #include "sv_sort.h"
 #include "match_device.h"
+#include "triangulate_device.h"
 
 namespace {
 using namespace svmd;
@@ -1308,6 +1309,57 @@ __global__ __launch_bounds__(1024) void k_cand_replay_batch(const CandProblem* _
     else cand_replay_body(tab[p], form[p].owner, form[p].match);
 }
 
+// ------------------------------------------------------------------------------------------------ new-landmark chain
+// mapping_module::create_new_landmarks (mapping_module.cc:275-341): the neighbours in order.  Lists and distances of all active
+// neighbours were built beside each other under taken_0; what depends on the neighbours before it -- which keypoints of the current
+// keyframe are still queries -- is applied here, neighbour by neighbour, by two kernels enqueued back to back on the stream:
+//   k_newlm_replay       one workgroup: clears q_valid of the taken rows, then the replay (the bodies k_cand_replay_batch branches between)
+//   k_newlm_triangulate  one lane per ROW: the scatter to keypoint order and the triangulation of that keypoint's match (the body of
+//                        k_triangulate_two_views); an accepted keypoint is taken for every later neighbour
+// Rows are a permutation of the keypoints, so a row's lane owns its keypoint's outputs and no lane writes another's.  (One fused
+// kernel of 1 024 threads holds the triangulator's 128 VGPRs only with scratch: DESIGN section 20.)
+__global__ __launch_bounds__(256) void k_newlm_init(const NewLmChain C) {  // created_by, the counts, the rows of inactive neighbours (the `continue` of :303-319)
+    const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (g < (size_t)C.n1) C.created_by[g] = -1;
+    if (g < (size_t)C.num_neighbours) C.num_matches[g] = C.num_accepted[g] = 0;
+    if (g >= (size_t)C.num_neighbours * C.n1) return;
+    if (C.prob_of_nb[g / C.n1] >= 0) return;
+    C.match[g] = -1;
+    C.pos_w[3 * g] = C.pos_w[3 * g + 1] = C.pos_w[3 * g + 2] = 0.0;
+    C.status[g] = SV_TRI_SKIPPED;
+}
+__global__ __launch_bounds__(1024) void k_newlm_replay(const NewLmChain C, const int nb, const int p) {
+    const int tid = threadIdx.x;
+    uint8_t* const qv = C.q_valid + (size_t)p * C.n1;
+    for (int r = tid; r < C.n1; r += 1024)
+        if (C.taken[C.q_idx[r]]) qv[r] = 0;
+    __syncthreads();
+    const int K = C.form[p].K;
+    if (K >= 0) cand_replay_lds_body(C.cand_tab[p], K);
+    else cand_replay_body(C.cand_tab[p], C.form[p].owner, C.form[p].match);
+    if (tid == 0) C.num_matches[nb] = *C.cand_tab[p].num;  // (the bodies' thread 0 wrote it)
+}
+__global__ __launch_bounds__(256) void k_newlm_triangulate(const NewLmChain C, const int nb, const int p) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= C.n1) return;
+    const TriView& V1 = C.views[C.num_neighbours];
+    const TriView& V2 = C.views[nb];
+    const int i1 = C.q_idx[r], i2 = C.match_rows[(size_t)p * C.n1 + r];
+    double pwx = 0.0, pwy = 0.0, pwz = 0.0;
+    int st = SV_TRI_SKIPPED;
+    if (0 <= i2) st = svtri::triangulate_match(V1, V2, i1, i2, C.scale_factors, C.level_sigma_sq, C.cos_rays_parallax_thr, pwx, pwy, pwz);
+    const size_t o = (size_t)nb * C.n1 + i1;
+    C.match[o] = i2;
+    C.pos_w[3 * o] = pwx;
+    C.pos_w[3 * o + 1] = pwy;
+    C.pos_w[3 * o + 2] = pwz;
+    C.status[o] = (uint8_t)st;
+    if (st != SV_TRI_ACCEPTED) return;
+    C.taken[i1] = 1;
+    C.created_by[i1] = nb;
+    atomicAdd(C.num_accepted + nb, 1);
+}
+
 // ------------------------------------------------------------------------------------------------ grid candidate lists
 // data::assign_keypoints_to_grid (data/common.cc:83-108) and data::get_keypoints_in_cell (:127-190) on the device, so that the
 // projection-family matchers need no host-built CSR.  The bodies are in match_device.h; a kernel here is a thin wrapper over one
@@ -1844,6 +1896,29 @@ SvIssued sv_launch_cand_batch(svgpu_ctx* ctx, hipStream_t s, const CandProblem* 
     (void)sv_allow_dynamic_lds((const void*)k_cand_replay_batch, CAND_LDS_BUDGET);
     hipLaunchKernelGGL(k_cand_replay_batch, dim3(num_problems), dim3(1024), lds_bytes, s, tab, form);
     return SvIssued{rows > 0 ? 2 : 1, 0};
+}
+// The new-landmark call (svgpu_newlm.hip): the distances of all active neighbours' rows, then the chain -- one init launch and, per active
+// neighbour in order, a replay and a triangulation launch.  The three kernels are one profile class, "k_newlm_chain"
+SvIssued sv_launch_cand_dist_batch(svgpu_ctx* ctx, hipStream_t s, const CandProblem* tab, const int32_t* row_base, int num_problems, int rows) {
+    SvProfScope ps(ctx, s, "k_cand_batch");
+    if (num_problems <= 0 || rows <= 0) return SvIssued{};
+    hipLaunchKernelGGL(k_cand_dist_batch, dim3(rows), dim3(64), 0, s, tab, row_base, num_problems);
+    return SvIssued{1, 0};
+}
+SvIssued sv_launch_newlm_chain(svgpu_ctx* ctx, hipStream_t s, const NewLmChain& C, const int32_t* prob_of_nb, size_t lds_bytes) {
+    SvProfScope ps(ctx, s, "k_newlm_chain");
+    SvIssued n{1, 0};
+    const size_t cells = std::max<size_t>((size_t)C.num_neighbours * C.n1, (size_t)std::max(C.num_neighbours, C.n1));
+    hipLaunchKernelGGL(k_newlm_init, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, C);
+    (void)sv_allow_dynamic_lds((const void*)k_newlm_replay, CAND_LDS_BUDGET);
+    for (int nb = 0; nb < C.num_neighbours; ++nb) {  // (in order on the one stream: neighbour nb + 1 reads the `taken` neighbour nb left)
+        const int p = prob_of_nb[nb];
+        if (p < 0 || C.n1 <= 0) continue;
+        hipLaunchKernelGGL(k_newlm_replay, dim3(1), dim3(1024), lds_bytes, s, C, nb, p);
+        hipLaunchKernelGGL(k_newlm_triangulate, dim3((C.n1 + 255) / 256), dim3(256), 0, s, C, nb, p);
+        n.launches += 2;
+    }
+    return n;
 }
 size_t sv_cand_lds_bytes(int nq, int nt, int K) { return cand_lds_bytes(nq, nt, K, false); }
 void sv_launch_cand_replay(svgpu_ctx* ctx, hipStream_t s, const CandProblem& P0, int* owner, int* match) {

@@ -4,9 +4,8 @@ namespace stella_vslam {
 namespace module {
 namespace hip {
 
-namespace {
 // what two_view_triangulator::triangulate reads of a keyframe (module/two_view_triangulator.cc:8-31, 76-90)
-two_view_triangulator::side flatten(const std::shared_ptr<data::keyframe>& keyfrm) {
+two_view_triangulator::side two_view_triangulator::flatten(const std::shared_ptr<data::keyframe>& keyfrm) {
     two_view_triangulator::side s;
     s.cam = stella_vslam::hip::to_svgpu_camera(keyfrm->camera_);
     const Mat44_t pose_cw = keyfrm->get_pose_cw();
@@ -29,6 +28,7 @@ two_view_triangulator::side flatten(const std::shared_ptr<data::keyframe>& keyfr
     s.scale_factor = keyfrm->orb_params_->scale_factor_;
     return s;
 }
+namespace {
 const float* or_null(const std::vector<float>& v) { return v.empty() ? nullptr : v.data(); }
 }  // namespace
 

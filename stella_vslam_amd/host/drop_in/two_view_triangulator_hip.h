@@ -33,6 +33,8 @@ public:
         float scale_factor;
         int n;
     };
+    //! what triangulate reads of one keyframe (also used by new_landmark_creator, which flattens every keyframe once)
+    static side flatten(const std::shared_ptr<data::keyframe>& keyfrm);
     const side& side_1() const { return s1_; }
     const side& side_2() const { return s2_; }
 

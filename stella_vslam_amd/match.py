@@ -307,19 +307,22 @@ class svgpu_triangulate_view(C.Structure):
                 ("bearings", C.c_void_p), ("xright", C.c_void_p), ("depth", C.c_void_p), ("n", C.c_int32), ("scale_factor", C.c_float)]
 
 
-def _tri_view(view, keep):
+def _tri_arrays(view):
+    """The converted arrays of one triangulator view, by name."""
+    return dict(cam=getattr(view["cam"], "c_", view["cam"]), pose=np.ascontiguousarray(np.asarray(view["pose_cw"], np.float64)[:3, :4]),
+                xy=_c(view["xy"], np.float32), octave=_c(view["octave"], np.int32), bearings=_f64(view["bearings"]),
+                xright=_c(view.get("xright"), np.float32), depth=_c(view.get("depth"), np.float32))
+
+
+def _tri_view(view, keep, arrays=None):
     """One keyframe side of the triangulator as a dict: cam (a camera object or its svgpu_camera), pose_cw (3 x 4 or 4 x 4), true_baseline,
     xy (n x 2), octave, bearings (n x 3), xright / depth (optional), scale_factor.  `keep` holds the converted arrays alive."""
-    cam = getattr(view["cam"], "c_", view["cam"])
-    pose = np.ascontiguousarray(np.asarray(view["pose_cw"], np.float64)[:3, :4])
-    a = [cam, pose, _c(view["xy"], np.float32), _c(view["octave"], np.int32), _f64(view["bearings"]), _c(view.get("xright"), np.float32),
-         _c(view.get("depth"), np.float32)]
+    a = _tri_arrays(view) if arrays is None else arrays
     keep.append(a)
     v = svgpu_triangulate_view()
-    v.cam, v.pose_cw, v.true_baseline = C.addressof(cam), pose.ctypes.data, float(view.get("true_baseline", 0.0))
-    v.xy, v.octave, v.bearings = (None if x is None else x.ctypes.data for x in a[2:5])
-    v.xright, v.depth = (None if x is None else x.ctypes.data for x in a[5:7])
-    v.n, v.scale_factor = len(a[3]), float(view["scale_factor"])
+    v.cam, v.pose_cw, v.true_baseline = C.addressof(a["cam"]), a["pose"].ctypes.data, float(view.get("true_baseline", 0.0))
+    v.xy, v.octave, v.bearings, v.xright, v.depth = (None if a[k] is None else a[k].ctypes.data for k in ("xy", "octave", "bearings", "xright", "depth"))
+    v.n, v.scale_factor = len(a["octave"]), float(view["scale_factor"])
     return v
 
 
@@ -441,3 +444,48 @@ def triangulation_matches_to_batch(matched_2_in_1_per_neighbour):
     off = np.concatenate([[0], np.cumsum([len(i) for i in idx1])]).astype(np.int32)
     cat = lambda xs: np.concatenate(xs).astype(np.int32) if xs else np.zeros(0, np.int32)  # noqa: E731
     return off, cat(idx1), cat(idx2)
+
+
+def _view_pair(side, view, keep):
+    """The matcher's and the triangulator's view of ONE keyframe: octave, bearings and xright are the same arrays in both."""
+    a = _tri_arrays(view)
+    t = _tri_view(view, keep, a)
+    m = _match_view(dict(side, octave=a["octave"], bearings=a["bearings"], xright=a["xright"]), keep)
+    return m, t
+
+
+def new_landmarks_batch(ctx, lowe_ratio, check_orientation, side1, view1, side2, neighbours, E_12, epipole_in_2, valid_epipole, scale_factors,
+                        level_sigma_sq, residual_rad_thr, active=None, rays_parallax_deg_thr=1.0):
+    """The loop of mapping_module::create_new_landmarks for all neighbours in ONE device call (svgpu_new_landmarks_batch): per neighbour
+    match_for_triangulation and two_view_triangulator::triangulate, with the keypoints that got a landmark leaving the queries of every later
+    neighbour -- which match_for_triangulation_batch followed by triangulate_two_views_batch, two calls over independent neighbours, do not
+    reproduce.  `side1` / `side2[k]` are matcher sides (desc, angle, has_lm | valid, node, xright), `view1` / `neighbours[k]` the triangulator's
+    views of the same keyframes (cam, pose_cw, true_baseline, xy, octave, bearings, xright, depth, scale_factor); octave, bearings and xright are
+    taken from the triangulator's view for both.  Returns a dict: matched_2_in_1 (K x n1), pos_w (K x n1 x 3), status (K x n1, TRI_*),
+    num_matches, num_accepted (K each), created_by (n1: the neighbour that gave keypoint i its landmark, or -1), stats (launches, copies,
+    synchronisations)."""
+    from .relocalizer import call_stats
+    keep = []
+
+    def pair(side, view):
+        return _view_pair(side, view, keep)
+    m1, t1 = pair(side1, view1)
+    k = len(neighbours)
+    if len(side2) != k:
+        raise ValueError("side2 and neighbours must name the same keyframes")
+    both = [pair(s, v) for s, v in zip(side2, neighbours)]
+    m2 = (svgpu_match_view * max(k, 1))(*[b[0] for b in both])
+    t2 = (svgpu_triangulate_view * max(k, 1))(*[b[1] for b in both])
+    sf, sg = _c(scale_factors, np.float32), _c(level_sigma_sq, np.float32)
+    E, ep, ve = _f64(E_12), _f64(epipole_in_2), _c(np.asarray(valid_epipole).astype(np.int32), np.int32)
+    act = _c(active, np.uint8)
+    n1 = m1.n
+    out = dict(matched_2_in_1=np.full((k, n1), -1, np.int32), pos_w=np.zeros((k, n1, 3), np.float64), status=np.full((k, n1), TRI_SKIPPED, np.uint8),
+               num_matches=np.zeros(k, np.int32), num_accepted=np.zeros(k, np.int32), created_by=np.full(n1, -1, np.int32))
+    st = call_stats()
+    ctx.check(lib().svgpu_new_landmarks_batch(
+        ctx.handle, C.byref(m1), C.byref(t1), k, m2, t2, _p(act), _p(E), _p(ep), _p(ve), _p(sf), _p(sg), len(sf), residual_rad_thr, lowe_ratio,
+        int(check_orientation), rays_parallax_deg_thr, _p(out["matched_2_in_1"]), _p(out["pos_w"]), _p(out["status"]), _p(out["num_matches"]),
+        _p(out["num_accepted"]), _p(out["created_by"]), C.byref(st)), "svgpu_new_landmarks_batch")
+    out["stats"] = dict(launches=st.launches, copies=st.copies, synchronisations=st.synchronisations)
+    return out
