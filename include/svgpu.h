@@ -933,6 +933,41 @@ int svgpu_bow_transform(svgpu_ctx* ctx, const svgpu_vocabulary* vocab, const uin
  * files its feature under the code of the block it was found in.  k = the vocabulary's branching factor. */
 int svgpu_fbow_transform(svgpu_ctx* ctx, const svgpu_vocabulary* vocab, const uint8_t* desc, int n, int store_level, int k,
                          int32_t* word_id, float* weight, uint32_t* node_code);
+/* The WHOLE of compute_bow for num_frames descriptor sets in one call: the descent above and, built on the device, the two sparse maps of
+ * every frame as flat arrays in the iteration order of the reference's std::map.  Frame f is rows d_off[f] .. d_off[f + 1] of desc
+ * (d_off[0] = 0, offsets must not descend, empty frames anywhere).
+ *   form   SVGPU_BOW_FORM_DBOW2: `level` = node_level of svgpu_bow_transform (k ignored); features whose weight is not > 0 take part in
+ *          neither map; norm = the sum of fabs(v); if norm > 0 every weight is DIVIDED by it
+ *          SVGPU_BOW_FORM_FBOW:  `level` = store_level, k as in svgpu_fbow_transform (2 .. 65536); every feature takes part; norm = the sum of
+ *          v * v (the product rounded before the add); if norm > 0 every weight is MULTIPLIED by 1.0 / sqrt(norm), the reciprocal formed first
+ *   word_id, weight, node (nullable): d_off[B] entries, equal to the single calls on the same rows
+ *   vec_off (B + 1), vec_word / vec_weight: bow_vec of frame f at vec_off[f] .. vec_off[f + 1], word ids strictly ascending -- the form
+ *          svgpu_bowdb_add and svgpu_bowdb_acquire* take.  A word's weight is 0.0 + (double)weight[i0] + (double)weight[i1] + ... over its
+ *          features in ascending index; the norm adds the words one after another in ascending id.  No tree or wave reduction and no
+ *          floating-point atomic anywhere: the results equal data::bow_vocabulary_hip::compute_bow (host/camera.cpp) bit for bit.
+ *          (The Python bow_vocabulary.transform divides the FBoW form by sqrt(norm) instead, which differs in the last bit: this call
+ *          follows the C++ class.)
+ *   feat_off (B + 1), feat_key / feat_index: bow_feat_vec of frame f, entries in ascending key (node id, or FBoW path code), inside a key in
+ *          ascending feature index (an index inside its frame)
+ *   vec_* and feat_* arrays hold d_off[B] entries each (no frame has more words or kept features than descriptors); vec_off[B] and
+ *          feat_off[B] of them are written.
+ *   db (nullable) with slots (B): the B vectors are also appended to the database's pools, device to device and under its mutex, as
+ *          svgpu_bowdb_add_batch would append the returned vectors; slots as that call returns them.
+ * A frame of at most svgpu_bow_compute_lds_capacity() descriptors is ordered by one workgroup; longer ones take the radix sort, with the
+ * same results.  While every frame fits, the launches do not depend on B (they do on whether d_off[B] exceeds one scan tile of 16384).
+ * One synchronisation, two with a database (the B + 1 vector offsets come back first; a pool growth adds its own).  `stats` (nullable)
+ * receives what the call issued.  SVGPU_ERR_INVALID before anything is launched or written: a null required pointer, d_off[0] != 0 or
+ * descending offsets, num_frames < 0, level < 0, k out of range, an unknown form, d_off[B] > 1 << 26, a vocabulary or database of another
+ * device.  num_frames == 0 succeeds.  Host in/out, synchronous.  FBoW / DBoW2 parity stays unpinned, as above. */
+#define SVGPU_BOW_FORM_DBOW2 0
+#define SVGPU_BOW_FORM_FBOW 1
+struct svgpu_call_stats;
+struct svgpu_bowdb;
+int svgpu_bow_compute_batch(svgpu_ctx* ctx, const svgpu_vocabulary* vocab, int form, int level, int k, int num_frames, const int32_t* d_off,
+                            const uint8_t* desc, int32_t* word_id, float* weight, uint32_t* node, int32_t* vec_off, uint32_t* vec_word,
+                            double* vec_weight, int32_t* feat_off, uint32_t* feat_key, int32_t* feat_index, struct svgpu_bowdb* db, int32_t* slots,
+                            struct svgpu_call_stats* stats);
+int svgpu_bow_compute_lds_capacity(void);
 
 /* ------------------------------------------------------------------------------ keyframe BoW database
  * data::bow_database (data/bow_database.h:20-100, data/bow_database.cc:21-159): the candidates of module::relocalizer::relocalize
@@ -965,6 +1000,13 @@ int svgpu_bowdb_clear(svgpu_ctx* ctx, svgpu_bowdb* db);
 /* bow_database::add_keyframe (data/bow_database.cc:21-28).  *slot: the keyframe's number; slots are handed out in increasing order and not
  * reused before clear, so ascending slot order is insertion order.  Ids that do not ascend strictly: SVGPU_ERR_INVALID. */
 int svgpu_bowdb_add(svgpu_ctx* ctx, svgpu_bowdb* db, int n_words, const uint32_t* words, const double* weights, int32_t* slot);
+/* num_frames svgpu_bowdb_add calls as one submission (a loaded map registering every keyframe): vector f is entries off[f] .. off[f + 1] of
+ * words / weights (off[0] = 0); slots (num_frames) are handed out in order.  One pool growth check, one upload per pool span and one of
+ * the new slot records.  Afterwards slot numbers, svgpu_bowdb_size, pool capacity and fill, and every later acquire, score, erase and
+ * compaction are those after the single adds (num_growths counts one growth where the single adds may have doubled several times).  If
+ * the ids of ANY frame do not ascend strictly: SVGPU_ERR_INVALID and the database is untouched. */
+int svgpu_bowdb_add_batch(svgpu_ctx* ctx, svgpu_bowdb* db, int num_frames, const int32_t* off, const uint32_t* words, const double* weights,
+                          int32_t* slots);
 /* bow_database::erase_keyframe (data/bow_database.cc:30-50); an erased or unknown slot is ignored, as the reference ignores a keyframe it
  * does not hold.  Erased spans of the pools are reclaimed by a compaction once they exceed half of what the pools hold. */
 int svgpu_bowdb_erase(svgpu_ctx* ctx, svgpu_bowdb* db, int32_t slot);

@@ -107,6 +107,22 @@ __global__ void __launch_bounds__(256) k_fbow_descend(int n, const uint32_t* __r
 
 }  // namespace
 
+// the same two kernels over descriptors that already lie on the device (svgpu_bow_compute_batch, bow_compute_kernels.h)
+int sv_vocabulary_device(const svgpu_vocabulary* vocab) { return vocab->device; }
+void sv_launch_bow_descend(hipStream_t s, const svgpu_vocabulary* vocab, const uint32_t* desc, int n, int level, int fbow_k, int32_t* word, float* weight,
+                           int32_t* node) {
+    const dim3 grid((unsigned)(((size_t)n * 8 + 255) / 256));
+    if (fbow_k > 0) {
+        int nbits = 0;
+        while ((1 << nbits) < fbow_k) ++nbits;
+        hipLaunchKernelGGL(k_fbow_descend, grid, dim3(256), 0, s, n, desc, vocab->child_off, vocab->children, vocab->node_desc, vocab->node_weight,
+                           vocab->word_id, level, nbits, word, weight, reinterpret_cast<uint32_t*>(node));
+    }
+    else
+        hipLaunchKernelGGL(k_bow_descend, grid, dim3(256), 0, s, n, desc, vocab->child_off, vocab->children, vocab->node_desc, vocab->node_weight,
+                           vocab->word_id, level, word, weight, node);
+}
+
 extern "C" {
 
 int svgpu_bow_vocabulary_upload(svgpu_ctx* ctx, int n_nodes, const int32_t* child_off, const int32_t* children, const uint8_t* node_desc,

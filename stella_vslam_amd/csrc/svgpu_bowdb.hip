@@ -6,6 +6,7 @@
 
 #include "sv_staged_call.h"
 #include "bowdb_kernels.h"
+#include "bow_compute_kernels.h"
 
 struct svgpu_bowdb {
     int device = 0;
@@ -38,8 +39,8 @@ void release(svgpu_bowdb* db) {
     db->d_ids = nullptr, db->d_w = nullptr, db->d_slots = nullptr;
 }
 
-// room for `extra` more entries and one more slot (pool and table double until they fit; the stream is idle: every call synchronises)
-int reserve(svgpu_ctx* ctx, svgpu_bowdb* db, size_t extra) {
+// room for `extra` more entries and `new_slots` more slots (pool and table double until they fit; the stream is idle: every call synchronises)
+int reserve(svgpu_ctx* ctx, svgpu_bowdb* db, size_t extra, size_t new_slots = 1, int* syncs = nullptr) {
     hipStream_t s = ctx->stream;
     if (db->pool_used + extra > db->pool_cap) {
         size_t cap = std::max(db->pool_cap, POOL_INITIAL);
@@ -56,19 +57,22 @@ int reserve(svgpu_ctx* ctx, svgpu_bowdb* db, size_t extra) {
             SV_HIP(ctx, hipMemcpyAsync(ids, db->d_ids, db->pool_used * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
             SV_HIP(ctx, hipMemcpyAsync(w, db->d_w, db->pool_used * sizeof(double), hipMemcpyDeviceToDevice, s));
             SV_HIP(ctx, hipStreamSynchronize(s));
+            if (syncs) ++*syncs;
         }
         if (db->pool_cap) ++db->growths;
         (void)hipFree(db->d_ids);
         (void)hipFree(db->d_w);
         db->d_ids = ids, db->d_w = w, db->pool_cap = cap;
     }
-    if (db->slots.size() + 1 > db->slot_cap) {
-        const size_t cap = std::max(db->slot_cap * 2, SLOTS_INITIAL);
+    if (db->slots.size() + new_slots > db->slot_cap) {
+        size_t cap = std::max(db->slot_cap * 2, SLOTS_INITIAL);
+        while (db->slots.size() + new_slots > cap) cap *= 2;
         BowSlot* t = nullptr;
         SV_HIP(ctx, hipMalloc(&t, cap * sizeof(BowSlot)));
         if (!db->slots.empty()) {
             SV_HIP(ctx, hipMemcpyAsync(t, db->slots.data(), db->slots.size() * sizeof(BowSlot), hipMemcpyHostToDevice, s));
             SV_HIP(ctx, hipStreamSynchronize(s));
+            if (syncs) ++*syncs;
         }
         (void)hipFree(db->d_slots);
         db->d_slots = t, db->slot_cap = cap;
@@ -210,7 +214,72 @@ int query_core(svgpu_ctx* ctx, svgpu_bowdb* db, const char* who, int Q, const in
 
 }  // namespace
 
+// ---- B keyframes as one submission (bow_compute_kernels.h): one growth check for the whole batch, one copy per pool span, one upload of
+// the new slot records.  The pools end where B single adds leave them: both double from the same capacity until the same fill fits.
+int sv_bowdb_device(const svgpu_bowdb* db) { return db->device; }
+struct SvBowdbAppendState {
+    std::unique_lock<std::mutex> lock;
+    std::vector<BowSlot> recs;
+    size_t entries = 0;
+};
+SvBowdbAppend::SvBowdbAppend() = default;
+SvBowdbAppend::~SvBowdbAppend() = default;
+int SvBowdbAppend::begin(svgpu_ctx* ctx, svgpu_bowdb* db_, int num, const int32_t* off, const uint32_t* words, const double* weights, bool on_device) {
+    state.reset(new SvBowdbAppendState);
+    SvBowdbAppendState* st = state.get();
+    st->lock = std::unique_lock<std::mutex>(db_->mtx);
+    db = db_;
+    if (db->slots.size() + (size_t)num > 0x7FFFFFFFull) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_bowdb_add_batch: out of slot numbers");
+    SV_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const size_t total = (size_t)off[num];
+    int rc;
+    if ((rc = reserve(ctx, db, total, (size_t)num, &syncs))) return rc;
+    st->recs.resize((size_t)num);
+    for (int f = 0; f < num; ++f) st->recs[f] = BowSlot{(uint32_t)(db->pool_used + (size_t)off[f]), (uint32_t)(off[f + 1] - off[f]), 1u, 0u};
+    st->entries = total;
+    if (total) {
+        const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+        SV_HIP(ctx, hipMemcpyAsync(db->d_ids + db->pool_used, words, total * sizeof(uint32_t), kind, s));
+        SV_HIP(ctx, hipMemcpyAsync(db->d_w + db->pool_used, weights, total * sizeof(double), kind, s));
+        copies += 2;
+    }
+    if (num) {  // (the records live in `state` until the caller has synchronised)
+        SV_HIP(ctx, hipMemcpyAsync(db->d_slots + db->slots.size(), st->recs.data(), (size_t)num * sizeof(BowSlot), hipMemcpyHostToDevice, s));
+        ++copies;
+    }
+    return SVGPU_OK;
+}
+void SvBowdbAppend::commit(int32_t* slots) {
+    SvBowdbAppendState* st = state.get();
+    for (size_t f = 0; f < st->recs.size(); ++f) {
+        slots[f] = (int32_t)db->slots.size();
+        db->slots.push_back(st->recs[f]);
+    }
+    db->pool_used += st->entries;
+    db->live_keyframes += (int)st->recs.size();
+    db->live_entries += (long long)st->entries;
+}
+
 extern "C" {
+
+int svgpu_bowdb_add_batch(svgpu_ctx* ctx, svgpu_bowdb* db, int num_frames, const int32_t* off, const uint32_t* words, const double* weights,
+                          int32_t* slots) {
+    const char* who = "svgpu_bowdb_add_batch: bad arguments (offsets must not descend, word ids must ascend strictly inside a frame)";
+    if (!ctx || !db || num_frames < 0) return sv_set_error(ctx, SVGPU_ERR_INVALID, who);
+    if (num_frames == 0) return SVGPU_OK;
+    if (!off || off[0] != 0 || !slots) return sv_set_error(ctx, SVGPU_ERR_INVALID, who);
+    for (int f = 0; f < num_frames; ++f) {
+        const int n = off[f + 1] - off[f];
+        if (off[f + 1] < off[f] || (n && (!words || !weights)) || !ascending(words + off[f], n)) return sv_set_error(ctx, SVGPU_ERR_INVALID, who);
+    }
+    SvBowdbAppend app;
+    int rc = app.begin(ctx, db, num_frames, off, words, weights, false);
+    if (rc) return rc;
+    SV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    app.commit(slots);
+    return SVGPU_OK;
+}
 
 int svgpu_bowdb_query_stage_capacity(void) { return SV_BOWDB_STAGE; }
 

@@ -192,6 +192,55 @@ class bow_vocabulary:
             bow_vec = {k: v / norm for k, v in bow_vec.items()}
         return dict(sorted(bow_vec.items())), dict(sorted(feat.items()))
 
+    def compute_bow_batch(self, descriptor_sets, levels_up: int = 4, db: "bow_database | None" = None) -> dict:
+        """svgpu_bow_compute_batch: compute_bow of every descriptor set in ONE device call, the two maps built on the device.  -> the flat
+        arrays of include/svgpu.h: d_off, word, weight, node (per descriptor), vec_off / vec_word / vec_weight, feat_off / feat_key /
+        feat_index, `stats` (launches, copies, synchronisations) and, with `db`, the `slots` the vectors were registered under.
+        The arithmetic is that of the C++ class data::bow_vocabulary_hip::compute_bow: the FBoW form multiplies by 1.0 / sqrt(norm), where
+        transform() divides by sqrt(norm) -- the two may differ in the last bit."""
+        sets = [np.ascontiguousarray(d, np.uint8).reshape(-1, 32) for d in descriptor_sets]
+        b = len(sets)
+        off = np.zeros(b + 1, np.int32)
+        off[1:] = np.cumsum([len(d) for d in sets])
+        n = int(off[-1])
+        desc = np.ascontiguousarray(np.concatenate(sets)) if n else np.zeros((0, 32), np.uint8)
+        fbow = self.framework_ == "fbow"
+        level = int(levels_up) if fbow else max(self.depth_ - int(levels_up), 0)
+        out = dict(d_off=off, word=np.zeros(n, np.int32), weight=np.zeros(n, np.float32), node=np.zeros(n, np.uint32),
+                   vec_off=np.zeros(b + 1, np.int32), vec_word=np.zeros(n, np.uint32), vec_weight=np.zeros(n, np.float64),
+                   feat_off=np.zeros(b + 1, np.int32), feat_key=np.zeros(n, np.uint32), feat_index=np.zeros(n, np.int32))
+        slots = np.full(b, -1, np.int32) if db is not None else None
+        stats = np.zeros(3, np.int32)
+        self.ctx.check(lib().svgpu_bow_compute_batch(self.ctx.handle, self._h, 1 if fbow else 0, level, self.k_, b, _p(off), _p(desc), _p(out["word"]),
+                                                     _p(out["weight"]), _p(out["node"]), _p(out["vec_off"]), _p(out["vec_word"]), _p(out["vec_weight"]),
+                                                     _p(out["feat_off"]), _p(out["feat_key"]), _p(out["feat_index"]),
+                                                     db._h if db is not None else None, _p(slots) if db is not None else None, _p(stats)),
+                       "svgpu_bow_compute_batch")
+        nv, nf = int(out["vec_off"][-1]), int(out["feat_off"][-1])
+        for key in ("vec_word", "vec_weight"):
+            out[key] = out[key][:nv]
+        for key in ("feat_key", "feat_index"):
+            out[key] = out[key][:nf]
+        out["stats"] = dict(launches=int(stats[0]), copies=int(stats[1]), synchronisations=int(stats[2]))
+        if db is not None:
+            out["slots"] = slots
+        return out
+
+    def transform_batch(self, descriptor_sets, levels_up: int = 4, db: "bow_database | None" = None):
+        """compute_bow for a list of descriptor arrays in one device call -> a list of (bow_vec, bow_feat_vec) as transform() returns them
+        (see compute_bow_batch for the one difference in the FBoW form's last bit).  With `db` the vectors are registered in the database on
+        the way, device to device: -> (that list, slots)."""
+        r = self.compute_bow_batch(descriptor_sets, levels_up, db)
+        res = []
+        for f in range(len(r["d_off"]) - 1):
+            v0, v1, f0, f1 = r["vec_off"][f], r["vec_off"][f + 1], r["feat_off"][f], r["feat_off"][f + 1]
+            bow_vec = {int(w): float(x) for w, x in zip(r["vec_word"][v0:v1], r["vec_weight"][v0:v1])}
+            feat = {}
+            for key, i in zip(r["feat_key"][f0:f1], r["feat_index"][f0:f1]):
+                feat.setdefault(int(key), []).append(int(i))
+            res.append((bow_vec, feat))
+        return (res, [int(s) for s in r["slots"]]) if db is not None else res
+
     def close(self):
         if self._h:
             lib().svgpu_bow_vocabulary_free(self._h)
@@ -236,6 +285,21 @@ class bow_database:
         slot = C.c_int32(-1)
         self.ctx.check(lib().svgpu_bowdb_add(self.ctx.handle, self._h, len(w), _p(w), _p(v), C.byref(slot)), "svgpu_bowdb_add")
         return slot.value
+
+    def add_keyframes(self, bow_vecs) -> list:
+        """svgpu_bowdb_add_batch: every vector of the list registered in one submission -> their slots, in order.  The database ends as
+        after add_keyframe on each; if any vector's ids do not ascend strictly nothing is added."""
+        arrs = [_bow_arrays(b) for b in bow_vecs]
+        b = len(arrs)
+        if b == 0:
+            return []
+        off = np.zeros(b + 1, np.int32)
+        off[1:] = np.cumsum([len(w) for w, _ in arrs])
+        w = np.ascontiguousarray(np.concatenate([a for a, _ in arrs]), np.uint32)
+        v = np.ascontiguousarray(np.concatenate([a for _, a in arrs]), np.float64)
+        slots = np.full(b, -1, np.int32)
+        self.ctx.check(lib().svgpu_bowdb_add_batch(self.ctx.handle, self._h, b, _p(off), _p(w), _p(v), _p(slots)), "svgpu_bowdb_add_batch")
+        return [int(s) for s in slots]
 
     def erase_keyframe(self, slot: int):
         self.ctx.check(lib().svgpu_bowdb_erase(self.ctx.handle, self._h, int(slot)), "svgpu_bowdb_erase")

@@ -157,5 +157,43 @@ void bow_vocabulary_hip::compute_bow(const cv::Mat& descriptors, std::map<unsign
     if (norm > 0.0)
         for (auto& kv : bow_vec) kv.second /= norm;
 }
+
+void bow_vocabulary_hip::compute_bow_batch(const std::vector<cv::Mat>& descriptors, std::vector<std::map<unsigned int, double>>& bow_vecs,
+                                           std::vector<std::map<unsigned int, std::vector<unsigned int>>>& bow_feat_vecs, int levels_up, svgpu_bowdb* db,
+                                           std::vector<int32_t>* slots) const {
+    const int B = (int)descriptors.size();
+    bow_vecs.assign((size_t)B, {});
+    bow_feat_vecs.assign((size_t)B, {});
+    if (db && !slots) throw std::runtime_error("bow_vocabulary_hip::compute_bow_batch: a database needs `slots`");
+    if (slots) slots->assign((size_t)B, -1);
+    if (B == 0) return;
+    if (!db && B < min_frames_for_batch_) {
+        for (int f = 0; f < B; ++f) compute_bow(descriptors[(size_t)f], bow_vecs[(size_t)f], bow_feat_vecs[(size_t)f], levels_up);
+        return;
+    }
+    std::vector<int32_t> d_off((size_t)B + 1, 0);
+    for (int f = 0; f < B; ++f) d_off[(size_t)f + 1] = d_off[(size_t)f] + descriptors[(size_t)f].rows;
+    const size_t N = (size_t)d_off[(size_t)B];
+    std::vector<uint8_t> packed(N * 32);
+    for (int f = 0; f < B; ++f)
+        for (int i = 0; i < descriptors[(size_t)f].rows; ++i) std::memcpy(&packed[((size_t)d_off[(size_t)f] + (size_t)i) * 32], descriptors[(size_t)f].ptr(i), 32);
+    std::vector<int32_t> vec_off((size_t)B + 1), feat_off((size_t)B + 1), feat_index(N);
+    std::vector<uint32_t> vec_word(N), feat_key(N);
+    std::vector<double> vec_weight(N);
+    const bool fbow = fbow_k_ > 0;
+    const int rc = svgpu_bow_compute_batch(ctx_, vocab_, fbow ? SVGPU_BOW_FORM_FBOW : SVGPU_BOW_FORM_DBOW2, fbow ? levels_up : std::max(depth_ - levels_up, 0),
+                                           fbow_k_, B, d_off.data(), packed.data(), nullptr, nullptr, nullptr, vec_off.data(), vec_word.data(),
+                                           vec_weight.data(), feat_off.data(), feat_key.data(), feat_index.data(), db, db ? slots->data() : nullptr, nullptr);
+    if (rc != SVGPU_OK) throw std::runtime_error(std::string("svgpu_bow_compute_batch: ") + svgpu_last_error(ctx_));
+    for (int f = 0; f < B; ++f) {  // both ranges ascend by key: every insertion goes to the end of its map
+        auto& bv = bow_vecs[(size_t)f];
+        for (int32_t j = vec_off[(size_t)f]; j < vec_off[(size_t)f + 1]; ++j) bv.emplace_hint(bv.end(), vec_word[(size_t)j], vec_weight[(size_t)j]);
+        auto& fv = bow_feat_vecs[(size_t)f];
+        for (int32_t j = feat_off[(size_t)f]; j < feat_off[(size_t)f + 1]; ++j) {
+            if (fv.empty() || fv.rbegin()->first != feat_key[(size_t)j]) fv.emplace_hint(fv.end(), feat_key[(size_t)j], std::vector<unsigned int>());
+            fv.rbegin()->second.push_back((unsigned int)feat_index[(size_t)j]);
+        }
+    }
+}
 }  // namespace data
 }  // namespace stella_vslam_hip

@@ -126,6 +126,15 @@ public:
     bow_vocabulary_hip& operator=(const bow_vocabulary_hip&) = delete;
     void compute_bow(const cv::Mat& descriptors, std::map<unsigned int, double>& bow_vec,
                      std::map<unsigned int, std::vector<unsigned int>>& bow_feat_vec, int levels_up = 4) const;
+    //! compute_bow of every descriptor set: from min_frames_for_batch_ sets on ONE svgpu_bow_compute_batch call, which builds both maps on
+    //! the device (bit for bit what the loop over compute_bow gives), below it that loop.  With `db` the batch call is always taken and
+    //! the vectors are also appended to the database device to device; `slots` (required then) receives their slot numbers.
+    void compute_bow_batch(const std::vector<cv::Mat>& descriptors, std::vector<std::map<unsigned int, double>>& bow_vecs,
+                           std::vector<std::map<unsigned int, std::vector<unsigned int>>>& bow_feat_vecs, int levels_up = 4, svgpu_bowdb* db = nullptr,
+                           std::vector<int32_t>* slots = nullptr) const;
+    //! the smallest number of sets the batch call is taken for (DESIGN section 21 states the measurement behind the default)
+    int min_frames_for_batch_ = 1;
+    svgpu_ctx* context() const { return ctx_; }
 
 private:
     svgpu_ctx* ctx_;

@@ -1,5 +1,7 @@
 #include "bow_database_hip.h"
 
+#include <algorithm>
+
 namespace stella_vslam {
 namespace data {
 namespace hip {
@@ -32,6 +34,51 @@ void bow_database::add_keyframe(const std::shared_ptr<keyframe>& keyfrm) {
     stella_vslam::hip::check(svgpu_bowdb_add(stella_vslam::hip::context(), db_, (int)words.size(), words.data(), weights.data(), &slot), "svgpu_bowdb_add");
     slot_of_id_[keyfrm->id_] = slot;
     keyfrm_of_slot_[slot] = keyfrm;
+}
+
+void bow_database::add_keyframes(const std::vector<std::shared_ptr<keyframe>>& keyfrms) {
+    std::lock_guard<std::mutex> lock(mtx_);
+    std::vector<std::shared_ptr<keyframe>> fresh;
+    std::vector<int32_t> off{0};
+    std::vector<uint32_t> words;
+    std::vector<double> weights;
+    for (const auto& keyfrm : keyfrms) {
+        if (slot_of_id_.count(keyfrm->id_) || std::any_of(fresh.begin(), fresh.end(), [&](const auto& k) { return k->id_ == keyfrm->id_; })) continue;
+        fresh.push_back(keyfrm);
+        for (const auto& word_and_weight : keyfrm->bow_vec_) {
+            words.push_back((uint32_t)word_and_weight.first);
+            weights.push_back((double)word_and_weight.second);
+        }
+        off.push_back((int32_t)words.size());
+    }
+    std::vector<int32_t> slots(fresh.size(), -1);
+    stella_vslam::hip::check(svgpu_bowdb_add_batch(stella_vslam::hip::context(), db_, (int)fresh.size(), off.data(), words.data(), weights.data(), slots.data()),
+                             "svgpu_bowdb_add_batch");
+    for (size_t i = 0; i < fresh.size(); ++i) {
+        slot_of_id_[fresh[i]->id_] = slots[i];
+        keyfrm_of_slot_[slots[i]] = fresh[i];
+    }
+}
+
+void bow_database::add_keyframes(const std::vector<std::shared_ptr<keyframe>>& keyfrms, const stella_vslam_hip::data::bow_vocabulary_hip& vocab, int levels_up) {
+    std::lock_guard<std::mutex> lock(mtx_);
+    std::vector<std::shared_ptr<keyframe>> fresh;
+    std::vector<cv::Mat> descriptors;
+    for (const auto& keyfrm : keyfrms) {
+        if (slot_of_id_.count(keyfrm->id_) || std::any_of(fresh.begin(), fresh.end(), [&](const auto& k) { return k->id_ == keyfrm->id_; })) continue;
+        fresh.push_back(keyfrm);
+        descriptors.push_back(keyfrm->frm_obs_.descriptors_);
+    }
+    std::vector<bow_vector> bow_vecs;
+    std::vector<bow_feature_vector> bow_feat_vecs;
+    std::vector<int32_t> slots;
+    vocab.compute_bow_batch(descriptors, bow_vecs, bow_feat_vecs, levels_up, db_, &slots);
+    for (size_t i = 0; i < fresh.size(); ++i) {
+        fresh[i]->bow_vec_.swap(bow_vecs[i]);
+        fresh[i]->bow_feat_vec_.swap(bow_feat_vecs[i]);
+        slot_of_id_[fresh[i]->id_] = slots[i];
+        keyfrm_of_slot_[slots[i]] = fresh[i];
+    }
 }
 
 void bow_database::erase_keyframe(const std::shared_ptr<keyframe>& keyfrm) {

@@ -6,6 +6,7 @@
 #include <mutex>
 #include <unordered_map>
 
+#include "camera.h"
 #include "hip_backend.h"
 
 namespace stella_vslam {
@@ -26,6 +27,12 @@ public:
     bow_database& operator=(const bow_database&) = delete;
 
     void add_keyframe(const std::shared_ptr<keyframe>& keyfrm);
+    //! add_keyframe for every keyframe of the list, in order, as ONE svgpu_bowdb_add_batch (map load: io/map_database_io_*.cc register
+    //! every keyframe); keyframes the database already holds are passed over
+    void add_keyframes(const std::vector<std::shared_ptr<keyframe>>& keyfrms);
+    //! the same for keyframes that have descriptors but no BoW yet (data/keyframe.cc:244, data/map_database.cc:399): compute_bow of all
+    //! of them in one svgpu_bow_compute_batch, which fills bow_vec_ / bow_feat_vec_ and appends the vectors to the database device to device
+    void add_keyframes(const std::vector<std::shared_ptr<keyframe>>& keyfrms, const stella_vslam_hip::data::bow_vocabulary_hip& vocab, int levels_up = 4);
     void erase_keyframe(const std::shared_ptr<keyframe>& keyfrm);
     void clear();
     std::vector<std::shared_ptr<keyframe>> acquire_keyframes(const bow_vector& bow_vec, const float min_score = 0.0f,
