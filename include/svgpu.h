@@ -1280,6 +1280,60 @@ int svgpu_reloc_refine_batch(svgpu_ctx* ctx, const svgpu_camera* cam, const uint
                              int32_t* status, double* pose_out, int32_t* match_kf, int32_t* match_stage, uint8_t* outlier, int32_t* num_found,
                              int32_t* num_valid, int32_t* lm_iterations, svgpu_call_stats* stats);
 
+/* module::relocalizer::reloc_by_candidate (module/relocalizer.cc:93-132) behind the BoW matcher, for ALL candidates in one call: per
+ * candidate relocalize_by_pnp_solver's RANSAC (:191-197; solve/pnp_solver.cc:44-124) -> relocalizer::optimize_pose (:211-234) -> the
+ * bookkeeping of :103-123 -> refine_pose (:236-297), i.e. the chain svgpu_pnp_ransac -> svgpu_pose_optimize -> svgpu_reloc_refine_batch
+ * with the host steps between them done on the device.  The frame, its bearings and the keyframe entries are uploaded once; which
+ * problems PnP and the first optimisation run is decided on the device, from the flags the kernel before wrote.
+ *   frame (shared)       as svgpu_reloc_refine_batch, plus t_bearings (nt x 3 doubles, frm_obs_.bearings_)
+ *   per candidate p      active[p] (nullable = all) and its 2D-3D matches, the entries match_off[p] .. match_off[p + 1] of
+ *     m_keypt            frame keypoint index, strictly ascending inside a candidate (extract_valid_indices order, :391-405)
+ *     m_pos_w            3 doubles, the landmark's position
+ *     m_kf_entry         index of the landmark among the candidate's keyframe entries (relative to kf_off[p]), or -1 when it is none of
+ *                        them (it came from a neighbour keyframe); the values >= 0 are distinct inside a candidate
+ *                        octave, observation, weight and Huber delta of a match are derived on the device from t_octave / t_xy /
+ *                        t_xright / inv_level_sigma_sq as svgpu_reloc_refine_batch derives them (pose_optimizer_g2o.cc:86-109)
+ *   PnP                  min_num_inliers, num_iter, samples (num_candidates x num_iter x 4, local indices), recompute,
+ *                        gauss_newton_num_iter: as svgpu_pnp_ransac_batch
+ *   min_num_opt_valid_obs   the threshold of optimize_pose: the reference tests its count against min_num_bow_matches_ / 2 (:220), a
+ *                        number of its own beside the min_num_valid_obs of refine_pose
+ *   keyframe entries, stages   kf_off, pos_w, valid, min_valid_dist, max_valid_dist, lm_desc, angle_kf, num_stages, margin, hamm_dist_thr,
+ *                        min_num_valid_obs: as svgpu_reloc_refine_batch
+ * Per candidate, in order:
+ *   1. svgpu_pnp_ransac over its matches; not valid: status SVGPU_RELOC_PNP_FAILED, the candidate stops.  A candidate with fewer than 4 or
+ *      fewer than min_num_inliers matches is not valid and launches nothing for itself.
+ *   2. svgpu_pose_optimize from the PnP pose over the inlier matches, in entry order; the pose goes on whatever follows (:218);
+ *      num_valid < min_num_opt_valid_obs: status SVGPU_RELOC_OPTIMIZE_FAILED, the candidate stops.
+ *   3. a keypoint holds a landmark where its match is an inlier of 1 and no outlier of 2, frame_lm_pos_w is that match's m_pos_w,
+ *      n_already_found the number of such matches, and every keyframe entry such a match names becomes invalid;
+ *   4. the stages of svgpu_reloc_refine_batch from that state.
+ * Outputs: status (0 accepted, -1 inactive on input, the two codes above, else the refine call's 1 + s unchanged); of step 1 pnp_valid /
+ * pnp_pose_cw / best_iter per candidate and is_inlier per match entry, as svgpu_pnp_ransac returns them; of step 2 opt_pose,
+ * opt_num_valid per candidate and opt_outlier per match entry (0 for a non-inlier); every output of svgpu_reloc_refine_batch.  Every
+ * output of candidate p equals, bit for bit, that chain of calls for the candidate alone, whatever else the batch holds; outputs of a
+ * step a candidate did not reach carry what the refine call documents for a stage not reached (pose = the last pose that exists -- zero
+ * after an invalid PnP --, counts 0, flags 0, matches -1).
+ * `stats` (nullable): launches, copies and synchronisations do not depend on num_candidates, and the synchronisations are those of
+ * svgpu_reloc_refine_batch for the same num_stages.
+ * SVGPU_ERR_INVALID before anything is launched or written: what svgpu_reloc_refine_batch refuses; offsets that do not start at 0 or are
+ * not monotone; m_keypt outside [0, nt) or not strictly ascending; m_kf_entry outside [-1, kf_off[p + 1] - kf_off[p]) or repeated; a
+ * sample index outside its problem or repeated within a sample (of a problem that runs).  num_candidates == 0 succeeds whatever else is
+ * passed.  Host in/out, synchronous. */
+#define SVGPU_RELOC_PNP_FAILED (-2)
+#define SVGPU_RELOC_OPTIMIZE_FAILED (-3)
+int svgpu_reloc_solve_batch(svgpu_ctx* ctx, const svgpu_camera* cam, const uint8_t* tdesc, const float* t_xy, const int32_t* t_octave,
+                            const float* t_angle, const float* t_xright, const double* t_bearings, int nt, int grid_cols, int grid_rows,
+                            int num_levels, const float* scale_factors, const float* inv_level_sigma_sq, float log_scale_factor,
+                            const double* intrinsics, int num_trials_robust, int num_trials, int num_each_iter, int reset_stop_flag_each_round,
+                            int check_orientation, int num_candidates, const uint8_t* active, const int32_t* match_off, const int32_t* m_keypt,
+                            const double* m_pos_w, const int32_t* m_kf_entry, int min_num_inliers, int num_iter, const uint32_t* samples,
+                            int recompute, int gauss_newton_num_iter, int min_num_opt_valid_obs, const int32_t* kf_off, const double* pos_w,
+                            const uint8_t* valid, const float* min_valid_dist, const float* max_valid_dist, const uint8_t* lm_desc, const float* angle_kf,
+                            int num_stages, const float* margin, const int32_t* hamm_dist_thr, int min_num_valid_obs, int32_t* status,
+                            uint8_t* pnp_valid, double* pnp_pose_cw, uint8_t* is_inlier, int32_t* best_iter, double* opt_pose,
+                            uint8_t* opt_outlier, int32_t* opt_num_valid, double* pose_out, int32_t* match_kf, int32_t* match_stage,
+                            uint8_t* outlier, int32_t* num_found, int32_t* num_valid, int32_t* lm_iterations, svgpu_call_stats* stats);
+
 /* The middle of module::loop_detector::select_loop_candidate_via_Sim3 (module/loop_detector.cc:537-587) for ALL candidates that survived
  * the pose refinement, in one call: per candidate the scale from the small-parallax landmark pairs (:540-573),
  * projection::match_keyframes_mutually (:577; match/projection.cc:418-629), the edge gather of optimize::transform_optimizer::optimize

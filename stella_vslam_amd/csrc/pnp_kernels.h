@@ -53,3 +53,14 @@ struct PnpRansacProblem {
 void sv_launch_pnp_pose(hipStream_t s, const PnpPoseProblem& P);
 void sv_launch_pnp_ransac(hipStream_t s, const PnpRansacProblem& P);
 void sv_launch_pnp_select(hipStream_t s, const PnpRansacProblem& P);
+
+// ---- the host side of find_via_ransac in the form a call takes that has its matches on the device already (svgpu_pnp.hip):
+// max_cos_errors_ of one scale factor (:27-32), the check of one problem's num_iter x 4 sample table against its np matches (null, or what
+// is wrong with it), and the launches of svgpu_pnp_ransac_batch over placed pieces (pnp_layout.h) -- hypotheses, selection and, with
+// `recompute`, the pose over the winner's inliers.  Returns the launches it issued.
+struct svgpu_ctx;
+struct PnpRansacPieces;
+float sv_pnp_max_cos(float scale_factor);
+const char* sv_pnp_check_samples(const uint32_t* samples, int num_iter, unsigned np);
+int sv_pnp_ransac_enqueue(svgpu_ctx* ctx, hipStream_t s, const PnpRansacPieces& Y, int num_problems, int num_active, int num_iter, int gn_iter,
+                          int min_num_inliers, int recompute);

@@ -69,8 +69,10 @@ struct RelocRefinePieces {
     Piece<uint32_t> dist;
 };
 
+// The layout in two halves, so that a call that runs something in front of the stages (svgpu_reloc_solve_batch, reloc_solve_layout.h) can
+// put its own results right in front of these: `front` is everything up to the matcher state, `back` the results and the lists.
 template <class A>
-void reloc_refine_layout(A& arena, const RelocRefineShape& H, RelocRefinePieces& Y) {
+void reloc_refine_layout_front(A& arena, const RelocRefineShape& H, RelocRefinePieces& Y) {
     const size_t K = H.K, nt = H.nt, N = H.N, S = H.S, E = K * nt;
     Y.tdesc = arena.template piece<uint8_t>(nt * 32);
     Y.t_xy = arena.template piece<float>(nt * 2);
@@ -115,6 +117,11 @@ void reloc_refine_layout(A& arena, const RelocRefineShape& H, RelocRefinePieces&
     Y.match_q = arena.template piece<int32_t>(N);
     Y.owner = optional_piece<int>(arena, H.global_replay, E);
     Y.match_of_row = optional_piece<int>(arena, H.global_replay, N);
+}
+
+template <class A>
+void reloc_refine_layout_back(A& arena, const RelocRefineShape& H, RelocRefinePieces& Y) {
+    const size_t K = H.K, nt = H.nt, N = H.N, S = H.S, E = K * nt;
     Y.status = arena.template piece<int32_t>(K);
     Y.pose_stage = arena.template piece<double>(S * K * 12);
     Y.match_kf = arena.template piece<int32_t>(N);
@@ -124,4 +131,10 @@ void reloc_refine_layout(A& arena, const RelocRefineShape& H, RelocRefinePieces&
     Y.flags = arena.template piece<uint8_t>(S * E);
     Y.cand_idx = arena.template piece<int32_t>(H.cap);  // the lists: last
     Y.dist = arena.template piece<uint32_t>(H.cap);
+}
+
+template <class A>
+void reloc_refine_layout(A& arena, const RelocRefineShape& H, RelocRefinePieces& Y) {
+    reloc_refine_layout_front(arena, H, Y);
+    reloc_refine_layout_back(arena, H, Y);
 }

@@ -8,6 +8,52 @@
 #include "pnp_layout.h"
 #include "sv_trig.h"
 
+// ---- what svgpu_reloc_solve_batch (svgpu_reloc.hip) shares with the entry points of this file
+float sv_pnp_max_cos(float scale_factor) {
+    constexpr double max_rad_error = 1.0 * M_PI / 180.0;
+    return sv_util_cos((float)(scale_factor * max_rad_error));
+}
+
+const char* sv_pnp_check_samples(const uint32_t* samples, int num_iter, unsigned np) {
+    for (int it = 0; it < num_iter; ++it) {
+        const uint32_t* s = samples + 4 * (size_t)it;
+        for (int a = 0; a < 4; ++a) {
+            if (s[a] >= np) return "svgpu_pnp_ransac: sample index outside its problem";
+            for (int b = 0; b < a; ++b)
+                if (s[a] == s[b]) return "svgpu_pnp_ransac: index repeated within a sample";
+        }
+    }
+    return nullptr;
+}
+
+int sv_pnp_ransac_enqueue(svgpu_ctx* ctx, hipStream_t s, const PnpRansacPieces& Y, int P, int num_active, int I, int gn_iter, int min_num_inliers,
+                          int recompute) {
+    if (num_active <= 0) return 0;
+    PnpRansacProblem R{};
+    R.bearings = Y.bearings, R.pos_w = Y.pos_w, R.max_cos = Y.max_cos, R.match_off = Y.match_off, R.samples = Y.samples, R.active = Y.active;
+    R.num_problems = P, R.num_active = num_active, R.num_iter = I, R.gn_iter = gn_iter;
+    R.min_num_inliers = (unsigned)min_num_inliers;
+    R.recompute = recompute != 0;
+    R.hyp_pose = Y.hyp_pose, R.hyp_num_inliers = Y.hyp_num_inliers, R.hyp_cost = Y.hyp_cost, R.hyp_inlier = Y.hyp_inlier;
+    R.valid = Y.valid, R.pose = Y.pose, R.is_inlier = Y.is_inlier, R.best_iter = Y.best_iter, R.inl_idx = Y.inl_idx, R.inl_count = Y.inl_count;
+    {
+        SvProfScope prof(ctx, s, "k_pnp_ransac");
+        sv_launch_pnp_ransac(s, R);
+    }
+    {
+        SvProfScope prof(ctx, s, "k_pnp_select");
+        sv_launch_pnp_select(s, R);
+    }
+    if (recompute) {  // (:109-123) over the winner's inliers; an invalid problem keeps what k_pnp_select wrote
+        PnpPoseProblem Q{};
+        Q.bearings = Y.bearings, Q.pos_w = Y.pos_w, Q.off = Y.match_off, Q.idx = Y.inl_idx, Q.count = Y.inl_count, Q.enable = Y.valid;
+        Q.sets = Y.active, Q.num_launch = num_active, Q.pose = Y.pose, Q.err = nullptr, Q.num_sets = P, Q.gn_iter = gn_iter, Q.keep_on_failure = 1;
+        SvProfScope prof(ctx, s, "k_pnp_pose");
+        sv_launch_pnp_pose(s, Q);
+    }
+    return (I > 0 ? 1 : 0) + 1 + (recompute ? 1 : 0);  // launches
+}
+
 namespace {
 
 int ransac_core(svgpu_ctx* ctx, const char* who, int num_problems, const int32_t* match_off, const double* bearings, const double* pos_w,
@@ -21,11 +67,10 @@ int ransac_core(svgpu_ctx* ctx, const char* who, int num_problems, const int32_t
     const int P = num_problems, I = num_iter, n = match_off[P];
     if (n > 0 && (!bearings || !pos_w || !octaves || !is_inlier)) return sv_set_error(ctx, SVGPU_ERR_INVALID, who);
     // max_cos_errors_ (:27-32): `scale_factors.at(octaves.at(i)) * max_rad_error` is a double, util::cos takes and returns a float
-    constexpr double max_rad_error = 1.0 * M_PI / 180.0;
     std::vector<float> max_cos(n);
     for (int i = 0; i < n; ++i) {
         if (octaves[i] < 0 || octaves[i] >= num_levels) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_pnp_ransac: octave out of range");
-        max_cos[i] = sv_util_cos((float)(scale_factors[octaves[i]] * max_rad_error));
+        max_cos[i] = sv_pnp_max_cos(scale_factors[octaves[i]]);
     }
     // the problems that run (:49-52), and every index their hypotheses dereference
     std::vector<int32_t> active;
@@ -34,14 +79,7 @@ int ransac_core(svgpu_ctx* ctx, const char* who, int num_problems, const int32_t
         if (np < 4u || np < (unsigned)min_num_inliers) continue;
         active.push_back(p);
         if (I > 0 && !samples) return sv_set_error(ctx, SVGPU_ERR_INVALID, who);
-        for (int it = 0; it < I; ++it) {
-            const uint32_t* s = samples + 4 * ((size_t)p * I + it);
-            for (int a = 0; a < 4; ++a) {
-                if (s[a] >= np) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_pnp_ransac: sample index outside its problem");
-                for (int b = 0; b < a; ++b)
-                    if (s[a] == s[b]) return sv_set_error(ctx, SVGPU_ERR_INVALID, "svgpu_pnp_ransac: index repeated within a sample");
-            }
-        }
+        if (const char* what = sv_pnp_check_samples(samples + 4 * (size_t)p * I, I, np)) return sv_set_error(ctx, SVGPU_ERR_INVALID, what);
     }
     const int num_active = (int)active.size();
     if (num_active > 0) {
@@ -55,28 +93,7 @@ int ransac_core(svgpu_ctx* ctx, const char* who, int num_problems, const int32_t
         C.up(Y.bearings, bearings), C.up(Y.pos_w, pos_w), C.up(Y.max_cos, max_cos.data());
         C.up(Y.match_off, match_off), C.up(Y.samples, samples), C.up(Y.active, active.data());
         if ((rc = C.flush())) return rc;
-        PnpRansacProblem R{};
-        R.bearings = Y.bearings, R.pos_w = Y.pos_w, R.max_cos = Y.max_cos, R.match_off = Y.match_off, R.samples = Y.samples, R.active = Y.active;
-        R.num_problems = P, R.num_active = num_active, R.num_iter = I, R.gn_iter = gn_iter;
-        R.min_num_inliers = (unsigned)min_num_inliers;
-        R.recompute = recompute != 0;
-        R.hyp_pose = Y.hyp_pose, R.hyp_num_inliers = Y.hyp_num_inliers, R.hyp_cost = Y.hyp_cost, R.hyp_inlier = Y.hyp_inlier;
-        R.valid = Y.valid, R.pose = Y.pose, R.is_inlier = Y.is_inlier, R.best_iter = Y.best_iter, R.inl_idx = Y.inl_idx, R.inl_count = Y.inl_count;
-        {
-            SvProfScope prof(ctx, s, "k_pnp_ransac");
-            sv_launch_pnp_ransac(s, R);
-        }
-        {
-            SvProfScope prof(ctx, s, "k_pnp_select");
-            sv_launch_pnp_select(s, R);
-        }
-        if (recompute) {  // (:109-123) over the winner's inliers; an invalid problem keeps what k_pnp_select wrote
-            PnpPoseProblem Q{};
-            Q.bearings = Y.bearings, Q.pos_w = Y.pos_w, Q.off = Y.match_off, Q.idx = Y.inl_idx, Q.count = Y.inl_count, Q.enable = Y.valid;
-            Q.sets = Y.active, Q.num_launch = num_active, Q.pose = Y.pose, Q.err = nullptr, Q.num_sets = P, Q.gn_iter = gn_iter, Q.keep_on_failure = 1;
-            SvProfScope prof(ctx, s, "k_pnp_pose");
-            sv_launch_pnp_pose(s, Q);
-        }
+        sv_pnp_ransac_enqueue(ctx, s, Y, P, num_active, I, gn_iter, min_num_inliers, recompute);
         C.down(valid, Y.valid), C.down(pose_cw, Y.pose), C.down(is_inlier, Y.is_inlier), C.down(best_iter, Y.best_iter);
         C.down(hyp_pose, Y.hyp_pose), C.down(hyp_num_inliers, Y.hyp_num_inliers), C.down(hyp_cost, Y.hyp_cost);  // optional: null is no request
         if ((rc = C.finish())) return rc;
