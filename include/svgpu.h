@@ -1425,6 +1425,99 @@ int svgpu_new_landmarks_batch(svgpu_ctx* ctx, const svgpu_match_view* side1, con
                               int32_t* matched_2_in_1, double* pos_w, uint8_t* status, int32_t* num_matches, int32_t* num_accepted,
                               int32_t* created_by, svgpu_call_stats* stats);
 
+/* ------------------------------------------------------------------------------ landmark fusion of a new keyframe
+ * mapping_module::fuse_landmark_duplication (mapping_module.cc:417-537) for all fuse targets in ONE staged call: per target
+ * fuse::detect_duplication of the current keyframe's landmarks, then the replace / connect_to_keyframe / compute_descriptor /
+ * update_mean_normal_and_obs_scale_variance bookkeeping (:436-467) that decides the next target's inputs, and at the end the
+ * backward pass into the current keyframe (:471-536).  The landmark state travels from target to target on the device.
+ *
+ * keyframes   num_targets + 1 records: slot 0 the current keyframe, slots 1.. the targets in the caller's order.  desc / xy / octave /
+ *             xright (nullable) as svgpu_fuse_detect_duplication takes them; `observer` = the keyframe's index in the observer table;
+ *             kp_lm (in/out, n entries) = landmark slot per keypoint, -1 = none.  The ORB tables are the call's (one extractor per map).
+ * observers   every keyframe that observes a landmark of the table: observer_rank = its place in the order of landmark::observations_t
+ *             (data/landmark.h:29: id_less, i.e. ascending keyframe id; ranks are distinct), observer_trans_wc its camera centre.
+ * table       num_landmarks slots.  pos_w, ref_trans_wc / ref_scale_factor (the reference keyframe's camera centre and
+ *             scale_factors_[octave of its keypoint]; a survivor keeps its reference keyframe), obs_off / obs_cap are inputs; alive,
+ *             descriptor, mean_normal, the distance limits, the two "has" flags, obs_cnt and the observation entries at
+ *             obs_off[l] .. obs_off[l] + obs_cnt[l] (rank order; observer, keypoint, its 32-byte descriptor, and the weight the
+ *             observation adds to num_observations(): 2 for a keypoint with stereo x_right >= 0, else 1, data/landmark.cc:116-121)
+ *             are in/out; replaced_by (out) = the survivor a dead landmark was replaced by, -1 otherwise.
+ * fwd_list    n_fwd slots (-1 allowed): cur_keyfrm_->get_landmarks() as copied before the loop (:426).
+ * bwd_list    n_bwd distinct slots: the landmarks of the targets in the order the caller wants them checked (the reference iterates an
+ *             unordered_set); entries that are dead after the forward loop are no candidates.
+ * For k = 1 .. num_targets: valid = slot >= 0, alive, no observation by target k; gates, window, greedy claims in list order and
+ * best <= HAMMING_DIST_THR_LOW as svgpu_fuse_detect_duplication on the CURRENT table; then the hits in ascending list index, the
+ * duplicates (:436-456) before the new connections (:458-467):
+ *   duplicate (the keypoint's kp_lm at detection time is alive)   same slot: SVGPU_FUSE_SAME_ID.  Otherwise the one with fewer
+ *       num_observations() loses (the checked one at equality survives); its observations move to the survivor where the survivor
+ *       has none by that observer, kp_lm of a table keyframe is rewritten (landmark::replace, prepare_for_erasing), the loser dies,
+ *       replaced_by[loser] = survivor, and the survivor's descriptor / geometry are refreshed if their flag is down.
+ *       SVGPU_FUSE_DUP_SURVIVED / SVGPU_FUSE_DUP_LOST speak of the checked landmark.  A pair one of whose members died earlier in the
+ *       same target (possible only when kp_lm and the observation lists disagree on entry) is SVGPU_FUSE_SKIPPED.
+ *   new connection (the keypoint holds no landmark)   replaced_by is followed from the checked landmark (:461-463), the observation is
+ *       inserted (an existing one by that observer is overwritten and its weight added, as observations_[keyfrm] = idx does),
+ *       kp_lm is set, both refreshes run.  SVGPU_FUSE_NEW_CONNECTION.
+ * Then once for bwd_list into slot 0.  best (num_targets + 1 rows: fwd rows of n_fwd, then one row of n_bwd, concatenated) and event
+ * per checked entry; num_fused per pass (num_targets + 1).
+ * Every float output equals, bit for bit, the chain of svgpu_fuse_detect_duplication, svgpu_landmarks_compute_descriptor and
+ * svgpu_landmarks_update_geometry calls with that bookkeeping done on the host between them.
+ * SVGPU_ERR_INVALID before anything is staged or launched: a null required pointer, an index out of its range (kp_lm, lists, observation
+ * entries, observers), obs_cnt > obs_cap, overlapping observation ranges, an octave outside [0, num_levels), duplicate ranks, two keyframe
+ * slots with one observer, a keyframe of more than 8192 keypoints or a grid of more than 4096 cells, an obs_cap above 4096, an observation
+ * weight outside {1, 2}, a list that is not in rank order, the same (observer, keypoint) held by two landmarks, a slot twice in bwd_list.
+ * num_targets == 0 succeeds, reports zero stats and touches nothing else.
+ * SVGPU_FUSE_OVERFLOW: an observation list would have outgrown obs_cap, or a candidate list the capacity sized from the snapshot
+ * (fuse_layout.h); every in/out and output array is then untouched and the caller takes the chain of single calls.
+ * `stats`: two synchronisations whatever num_targets is; launches and copies affine in num_targets (a call whose arena regrows for the
+ * lists stages and bins a second time: a larger constant, the same slope).  Host in/out, synchronous. */
+#define SVGPU_FUSE_OVERFLOW 100
+#define SVGPU_FUSE_NONE 0
+#define SVGPU_FUSE_NEW_CONNECTION 1
+#define SVGPU_FUSE_DUP_SURVIVED 2
+#define SVGPU_FUSE_DUP_LOST 3
+#define SVGPU_FUSE_SAME_ID 4
+#define SVGPU_FUSE_SKIPPED 5
+typedef struct svgpu_fuse_keyframe {
+    const svgpu_camera* cam;
+    const double* rot_cw;   /* 9, row-major */
+    const double* trans_cw; /* 3 */
+    const uint8_t* desc;    /* n x 32 */
+    const float* xy;        /* n x 2 undistorted */
+    const int32_t* octave;  /* n */
+    const float* xright;    /* n, nullable */
+    int32_t* kp_lm;         /* n, in/out */
+    int32_t n;
+    int32_t observer;
+    int32_t grid_cols, grid_rows;
+} svgpu_fuse_keyframe;
+typedef struct svgpu_fuse_table {
+    int32_t num_landmarks;
+    int32_t num_entries;     /* length of the observation arrays: every obs_off[l] + obs_cap[l] <= num_entries */
+    const double* pos_w;     /* L x 3 */
+    const double* ref_trans_wc;     /* L x 3 */
+    const float* ref_scale_factor;  /* L */
+    const int32_t* obs_off;  /* L */
+    const int32_t* obs_cap;  /* L */
+    uint8_t* alive;          /* L */
+    uint8_t* descriptor;     /* L x 32 */
+    double* mean_normal;     /* L x 3 */
+    float* min_valid_dist;   /* L */
+    float* max_valid_dist;   /* L */
+    uint8_t* has_descriptor; /* L */
+    uint8_t* has_geometry;   /* L */
+    int32_t* obs_cnt;        /* L */
+    int32_t* obs_observer;   /* num_entries */
+    int32_t* obs_kp;         /* num_entries */
+    uint8_t* obs_desc;       /* num_entries x 32 */
+    int32_t* obs_weight;     /* num_entries */
+    int32_t* replaced_by;    /* L, out */
+} svgpu_fuse_table;
+int svgpu_fuse_landmarks_batch(svgpu_ctx* ctx, int num_targets, const svgpu_fuse_keyframe* keyframes, int num_observers,
+                               const int32_t* observer_rank, const double* observer_trans_wc, const svgpu_fuse_table* table, int n_fwd,
+                               const int32_t* fwd_list, int n_bwd, const int32_t* bwd_list, int num_levels, const float* scale_factors,
+                               const float* inv_level_sigma_sq, float log_scale_factor, float inv_scale_factor_last, float margin,
+                               int do_reprojection_matching, int32_t* best_idx, uint8_t* event, int32_t* num_fused, svgpu_call_stats* stats);
+
 /* Global BA core (optimize/global_bundle_adjuster.cc:26-192, 279-412): the same graph over ALL keyframes (spanning root
  * fixed), ONE Levenberg-Marquardt run of problem->num_first_iter iterations with the terminate rule, optional Huber
  * (obs_huber_delta), no outlier gate (num_second_iter is ignored).  The caller applies the reference's post-conditions

@@ -246,7 +246,7 @@ public:
     float get_max_valid_distance() const { return max_valid_dist_; }
     cv::Mat get_descriptor() const { return descriptor_; }
     observations_t get_observations() const { return observations_; }
-    unsigned int num_observations() const { return (unsigned)observations_.size(); }
+    unsigned int num_observations() const;  // defined behind keyframe: a keypoint with a stereo x_right counts twice (data/landmark.cc:116-121)
     bool has_observation() const { return !observations_.empty(); }
     bool will_be_erased() { return will_be_erased_; }
     int get_index_in_keyframe(const std::shared_ptr<keyframe>& keyfrm) const {
@@ -254,10 +254,17 @@ public:
         return it == observations_.end() ? -1 : (int)it->second;
     }
     bool is_observed_in_keyframe(const std::shared_ptr<keyframe>& keyfrm) const { return observations_.count(keyfrm) != 0; }
-    void add_observation(const std::shared_ptr<keyframe>& keyfrm, unsigned int idx) {
+    void add_observation(const std::shared_ptr<keyframe>& keyfrm, unsigned int idx) {  // data/landmark.cc:106-122
         observations_[keyfrm] = idx;
+        has_valid_prediction_parameters_ = false;
+        has_representative_descriptor_ = false;
         hip::map_mirror::set_has_observation(id_, true);
     }
+    bool has_representative_descriptor() const { return has_representative_descriptor_; }      // data/landmark.cc:188-191
+    bool has_valid_prediction_parameters() const { return has_valid_prediction_parameters_; }  // :319-322
+    void prepare_for_erasing(map_database* map_db);                                            // :355-370, defined behind keyframe
+    void connect_to_keyframe(const std::shared_ptr<keyframe>& keyfrm, unsigned int idx);       // :376-380
+    void replace(std::shared_ptr<landmark> lm, map_database* map_db);                          // :382-414
     void erase_observation(map_database* map_db, const std::shared_ptr<keyframe>& keyfrm) {  // data/landmark.cc:100-140
         observations_.erase(keyfrm);
         hip::map_mirror::set_has_observation(id_, !observations_.empty());
@@ -289,6 +296,7 @@ public:
         mean_normal_ = mean_normal;
         min_valid_dist_ = min_valid_dist;
         max_valid_dist_ = max_valid_dist;
+        has_valid_prediction_parameters_ = true;
         const double nv[3] = {mean_normal(0), mean_normal(1), mean_normal(2)};
         hip::map_mirror::set_geometry(id_, nv, min_valid_dist_, max_valid_dist_);
     }
@@ -296,6 +304,7 @@ public:
         ++num_descriptor_refreshes_;
         descriptor_.create(1, 32, CV_8U);
         std::memcpy(descriptor_.ptr(0), descriptor32, 32);
+        has_representative_descriptor_ = true;
         hip::map_mirror::set_descriptor(id_, descriptor_.ptr(0));
     }
     unsigned int id_;
@@ -309,6 +318,7 @@ public:
 private:
     observations_t observations_;
     std::atomic<bool> will_be_erased_{false};
+    bool has_representative_descriptor_ = false, has_valid_prediction_parameters_ = false;
 };
 
 class marker2d {  // data/marker2d.h: the undistorted image corners global BA reads
@@ -352,6 +362,7 @@ public:
         const int idx = lm->get_index_in_keyframe(shared_from_this());
         if (0 <= idx) landmarks_.at(idx) = nullptr;
     }
+    void erase_landmark_with_index(const unsigned int idx) { landmarks_.at(idx) = nullptr; }  // data/keyframe.cc
     std::vector<std::shared_ptr<landmark>> get_landmarks() const { return landmarks_; }
     std::shared_ptr<landmark>& get_landmark(const unsigned int idx) { return landmarks_.at(idx); }
     bool will_be_erased() { return will_be_erased_; }
@@ -410,7 +421,43 @@ inline std::vector<std::shared_ptr<keyframe>> graph_node::get_keyframes_from_roo
     return keyfrms;
 }
 
+inline unsigned int landmark::num_observations() const {
+    unsigned int n = 0;
+    for (const auto& obs : observations_) {
+        const auto kf = obs.first.lock();
+        n += (kf && !kf->frm_obs_.stereo_x_right_.empty() && 0 <= kf->frm_obs_.stereo_x_right_.at(obs.second)) ? 2 : 1;
+    }
+    return n;
+}
+inline void landmark::prepare_for_erasing(map_database* map_db) {
+    const observations_t observations = observations_;
+    observations_.clear();
+    will_be_erased_ = true;
+    for (const auto& keyfrm_and_idx : observations)
+        if (auto kf = keyfrm_and_idx.first.lock()) kf->erase_landmark_with_index(keyfrm_and_idx.second);
+    hip::map_mirror::set_has_observation(id_, false);
+    hip::map_mirror::landmark_erased(id_);
+    if (map_db) ++map_db->num_erased_landmarks_;
+}
+inline void landmark::connect_to_keyframe(const std::shared_ptr<keyframe>& keyfrm, unsigned int idx) {
+    keyfrm->add_landmark(shared_from_this(), idx);
+    add_observation(keyfrm, idx);
+}
+inline void landmark::replace(std::shared_ptr<landmark> lm, map_database* map_db) {
+    if (lm->id_ == id_) return;
+    const observations_t observations = observations_;
+    prepare_for_erasing(map_db);
+    const unsigned int num_observable = num_observable_, num_observed = num_observed_;
+    for (const auto& keyfrm_and_idx : observations) {
+        const auto keyfrm = keyfrm_and_idx.first.lock();
+        if (keyfrm && !lm->is_observed_in_keyframe(keyfrm)) lm->connect_to_keyframe(keyfrm, keyfrm_and_idx.second);
+    }
+    lm->increase_num_observed(num_observed);
+    lm->increase_num_observable(num_observable);
+}
+
 inline void landmark::compute_descriptor() {  // median-of-distances representative (data/landmark.cc:199-254)
+    has_representative_descriptor_ = true;
     std::vector<const uint8_t*> descs;
     for (const auto& obs : observations_)
         if (auto kf = obs.first.lock())
@@ -440,6 +487,7 @@ inline void landmark::compute_descriptor() {  // median-of-distances representat
 }
 
 inline void landmark::update_mean_normal_and_obs_scale_variance() {  // data/landmark.cc:256-318
+    has_valid_prediction_parameters_ = true;
     ++num_geometry_refreshes_;
     if (observations_.empty()) return;
     double m[3] = {0, 0, 0};

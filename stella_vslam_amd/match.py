@@ -489,3 +489,76 @@ def new_landmarks_batch(ctx, lowe_ratio, check_orientation, side1, view1, side2,
         _p(out["num_accepted"]), _p(out["created_by"]), C.byref(st)), "svgpu_new_landmarks_batch")
     out["stats"] = dict(launches=st.launches, copies=st.copies, synchronisations=st.synchronisations)
     return out
+
+
+FUSE_OVERFLOW = 100  # include/svgpu.h SVGPU_FUSE_OVERFLOW
+FUSE_NONE, FUSE_NEW_CONNECTION, FUSE_DUP_SURVIVED, FUSE_DUP_LOST, FUSE_SAME_ID, FUSE_SKIPPED = range(6)
+
+
+class svgpu_fuse_keyframe(C.Structure):
+    """include/svgpu.h svgpu_fuse_keyframe."""
+    _fields_ = [("cam", C.c_void_p), ("rot_cw", C.c_void_p), ("trans_cw", C.c_void_p), ("desc", C.c_void_p), ("xy", C.c_void_p), ("octave", C.c_void_p),
+                ("xright", C.c_void_p), ("kp_lm", C.c_void_p), ("n", C.c_int32), ("observer", C.c_int32), ("grid_cols", C.c_int32), ("grid_rows", C.c_int32)]
+
+
+class svgpu_fuse_table(C.Structure):
+    """include/svgpu.h svgpu_fuse_table."""
+    _fields_ = [("num_landmarks", C.c_int32), ("num_entries", C.c_int32)] + [(k, C.c_void_p) for k in (
+        "pos_w", "ref_trans_wc", "ref_scale_factor", "obs_off", "obs_cap", "alive", "descriptor", "mean_normal", "min_valid_dist", "max_valid_dist",
+        "has_descriptor", "has_geometry", "obs_cnt", "obs_observer", "obs_kp", "obs_desc", "obs_weight", "replaced_by")]
+
+
+_FUSE_TABLE_TYPES = dict(pos_w=np.float64, ref_trans_wc=np.float64, ref_scale_factor=np.float32, obs_off=np.int32, obs_cap=np.int32, alive=np.uint8,
+                         descriptor=np.uint8, mean_normal=np.float64, min_valid_dist=np.float32, max_valid_dist=np.float32, has_descriptor=np.uint8,
+                         has_geometry=np.uint8, obs_cnt=np.int32, obs_observer=np.int32, obs_kp=np.int32, obs_desc=np.uint8, obs_weight=np.int32)
+
+
+def fuse_landmarks_batch(ctx, keyframes, observer_rank, observer_trans_wc, table, fwd_list, bwd_list, scale_factors, inv_level_sigma_sq, log_scale_factor,
+                         inv_scale_factor_last, margin=3.0, do_reprojection_matching=True, check=True, sentinel=None):
+    """mapping_module::fuse_landmark_duplication for all fuse targets in ONE device call (svgpu_fuse_landmarks_batch): `keyframes[0]` is the
+    current keyframe, the others the targets in order; each a dict with cam (a camera object or its svgpu_camera), rot_cw, trans_cw, desc, xy,
+    octave, xright (optional), kp_lm, observer, grid_cols, grid_rows.  `table` is a dict of the svgpu_fuse_table arrays.  Nothing passed in is
+    modified.  Returns a dict: status (0, or FUSE_OVERFLOW: nothing else is meaningful then), the table's in/out arrays after the call,
+    replaced_by, kp_lm (a list per keyframe), best_idx / event (the forward rows, then the backward row), num_fused, stats.
+    check=False returns any status instead of raising; `sentinel` (an int below 128) fills every pure output before the call, so that what a
+    refused call left untouched can be seen."""
+    from .relocalizer import call_stats
+    keep = []
+    k = len(keyframes) - 1
+    recs = (svgpu_fuse_keyframe * (k + 1))()
+    kp_lm = []
+    for u, f in enumerate(keyframes):
+        cam = getattr(f["cam"], "c_", f["cam"])
+        a = dict(rot=_f64(f["rot_cw"]), trans=_f64(f["trans_cw"]), desc=np.ascontiguousarray(f["desc"], np.uint8).reshape(-1, 32), xy=_c(f["xy"], np.float32),
+                 octave=_c(f["octave"], np.int32), xright=_c(f.get("xright"), np.float32), kp_lm=np.array(f["kp_lm"], np.int32, copy=True), cam=cam)
+        keep.append(a)
+        kp_lm.append(a["kp_lm"])
+        r = recs[u]
+        r.cam, r.rot_cw, r.trans_cw = C.addressof(cam), a["rot"].ctypes.data, a["trans"].ctypes.data
+        r.desc, r.xy, r.octave, r.kp_lm = a["desc"].ctypes.data, a["xy"].ctypes.data, a["octave"].ctypes.data, a["kp_lm"].ctypes.data
+        r.xright = None if a["xright"] is None else a["xright"].ctypes.data
+        r.n, r.observer, r.grid_cols, r.grid_rows = len(a["octave"]), int(f["observer"]), int(f.get("grid_cols", 64)), int(f.get("grid_rows", 48))
+    t = {key: np.array(table[key], ty, copy=True) for key, ty in _FUSE_TABLE_TYPES.items()}
+    t["replaced_by"] = np.full(len(t["obs_off"]), -1, np.int32)
+    tab = svgpu_fuse_table()
+    tab.num_landmarks, tab.num_entries = len(t["obs_off"]), len(t["obs_observer"])
+    for key, arr in t.items():
+        setattr(tab, key, arr.ctypes.data)
+    rank, twc = _c(observer_rank, np.int32), _f64(observer_trans_wc)
+    fwd, bwd = _c(fwd_list, np.int32), _c(bwd_list, np.int32)
+    sf, ils = _c(scale_factors, np.float32), _c(inv_level_sigma_sq, np.float32)
+    n_out = k * len(fwd) + len(bwd)
+    best, event, num = np.full(max(n_out, 1), -1, np.int32), np.zeros(max(n_out, 1), np.uint8), np.zeros(k + 1, np.int32)
+    st = call_stats()
+    if sentinel is not None:
+        best[:], event[:], num[:], t["replaced_by"][:] = sentinel, sentinel, sentinel, sentinel
+        st.launches = st.copies = st.synchronisations = sentinel
+    rc = lib().svgpu_fuse_landmarks_batch(ctx.handle, k, recs, len(rank), _p(rank), _p(twc), C.byref(tab), len(fwd), _p(fwd), len(bwd), _p(bwd), len(sf),
+                                          _p(sf), _p(ils), log_scale_factor, inv_scale_factor_last, margin, int(do_reprojection_matching), _p(best), _p(event),
+                                          _p(num), C.byref(st))
+    if check and rc != FUSE_OVERFLOW:
+        ctx.check(rc, "svgpu_fuse_landmarks_batch")
+    out = {key: t[key] for key in t if key not in ("pos_w", "ref_trans_wc", "ref_scale_factor", "obs_off", "obs_cap")}
+    out.update(status=rc, kp_lm=kp_lm, best_idx=best[:n_out], event=event[:n_out], num_fused=num,
+               stats=dict(launches=st.launches, copies=st.copies, synchronisations=st.synchronisations))
+    return out
